@@ -13,16 +13,26 @@ Multi-GPU (--gpus N): launched by `python -m torch.distributed.run --nproc-per-n
 `python bench.py --gpus N`, which starts the N ranks itself as fresh child processes before any GPU call
 (graph_odenet_amd/launch.py).  Every rank owns an independent R-MAT graph (seed = rank), i.e. a batch of N graphs sharded
 one per GPU; the only exchange step is the RCCL all-reduce of the gradients per step.  scaling = "weak";
-value = N*K / max-over-ranks time.  Under N > 1 the line also carries the two other multi-GPU workloads of SURVEY 8(e),
+value = N*K / max-over-ranks time.  Under N > 1 and --full the line also carries the two other multi-GPU workloads of
+SURVEY 8(e),
 measured after (outside) the timed region: `secondary.qc_data_parallel` (C4: batches of 20 molecules per rank, the 57 MB
 bucketed gradient exchange, graphs/s; tools/qc_bench.py) and `secondary.strong_scaling` (the SAME C5 graph row-partitioned
 over the ranks, one all-gather per aggregation; tools/partition_bench.py), and `rccl_ranks` = the ranks that answered a
 checked all-reduce of 1.0.  With fewer GPUs than ranks (rehearsal on a one-GPU box) the ranks share the GPUs and exchange
 over gloo; `backend` says which.
 
-Prints ONE JSON line on rank 0 (contract in the task description) with `roofline` (SpMM main
-kernel, HIP events recorded around every launch of the timed region by libgraphode's profiler
-hook) and `cpu_baseline` (the oracle timed on the host cores, bounded sample, rank 0, N=1 only).
+Prints ONE JSON line on rank 0, the contract line.  A plain run does only what that line's headline figure
+needs: set-up, warm-up, the timed steps, the line.  Everything else is measured under `--full` only: `roofline` (SpMM
+main kernel, HIP events recorded around every launch of the timed region by libgraphode's profiler hook),
+`roofline_dense`, `cpu_baseline` (the oracle timed on the host cores, bounded sample, rank 0, N=1 only) and the
+`secondary` block (N = 1: the other BASELINE.json configurations and the extra step readings; N > 1: the two other
+multi-GPU workloads above).
+
+`--dump-outputs DIR` writes what the timed path computed in its last step, right after the timed region (rank 0):
+`loss.npy`, a fixed sample of the rows of the log-probabilities (`log_probs_sample.npy`, row ids in
+`log_probs_sample_rows.npy`), and every parameter after the Adam update and its gradient (`param.<name>.npy`,
+`grad.<name>.npy`), float32 (the row ids float64).  The inputs depend on the arguments alone, so two builds can be
+compared file by file.
 """
 import argparse
 import ctypes
@@ -56,6 +66,10 @@ def parse():
     ap.add_argument("--nfeat", type=int, default=128)
     ap.add_argument("--nclass", type=int, default=16)
     ap.add_argument("--ode-steps", type=int, default=16, help="rk4 steps on [0,1] (4 evals each)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline figure: rooflines, CPU baseline, secondary block")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32, rank 0)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-evals", type=int, default=4, help="f-evals in the CPU-baseline sample (median is used)")
     ap.add_argument("--force-dist", action="store_true",
@@ -243,96 +257,33 @@ def multi_gpu_secondary(args, dev, rank, world, backend):
     return out
 
 
-def main():
-    args = parse()
-    from graph_odenet_amd import launch
-    if launch.needs_self_launch(args.gpus):
-        # bare `python bench.py --gpus N`: start the N ranks as fresh children BEFORE this process touches the GPU, relay
-        # their output (rank 0 prints the JSON line) and leave with their exit code
-        sys.exit(launch.self_launch(__file__, sys.argv[1:], args.gpus))
-    other_configs = None
-    if int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.no_configs and not args.no_secondary:
-        # The other BASELINE.json configurations (parity-test cases) with their CPU legs, timed on this box by
-        # tools/config_bench.py in a CHILD process that runs to completion BEFORE this process makes its first GPU call
-        # (a process that has initialised the GPU starts no further programs on this pool).  A fresh process also keeps
-        # the C4 leg's HIP-graph captures of arbitrary autograd away from the process that prints the contract line.
-        import subprocess
-        try:
-            assert not torch.cuda.is_initialized()
-            cp = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "config_bench.py"), "--one-line"],
-                                capture_output=True, text=True, timeout=args.configs_timeout)
-            lines = [l for l in cp.stdout.splitlines() if l.startswith("{")]
-            if cp.returncode != 0 or not lines:
-                raise RuntimeError("config_bench.py rc %d: %s" % (cp.returncode, (cp.stderr or cp.stdout)[-400:]))
-            other_configs = json.loads(lines[-1])
-        except Exception as e:
-            other_configs = {"error": "%s: %s" % (type(e).__name__, e)}
-    import torch.distributed as dist
-    if args.force_dist and int(os.environ.get("WORLD_SIZE", "1")) == 1:
-        rank, local_rank, world, backend = 0, 0, 1, "nccl"
-        torch.cuda.set_device(0)
-        dev = torch.device("cuda", 0)
-        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-        os.environ.setdefault("MASTER_PORT", "29533")
-        dist.init_process_group("nccl", rank=0, world_size=1, device_id=dev)
-    else:
-        rank, local_rank, world, dev, backend = launch.init_ranks(args.backend)      # includes the checked all-reduce of 1.0
-    if world != args.gpus and rank == 0:
-        print("bench.py: --gpus %d but WORLD_SIZE=%d; reporting n_gpus=%d" % (args.gpus, world, world), file=sys.stderr)
-    use_dist = world > 1 or args.force_dist
+DUMP_SAMPLE_ROWS = 65536          # rows of the N x nclass log-probabilities written by --dump-outputs (4 MB at 16 classes)
+DUMP_SAMPLE_BYTES = 32 << 20      # ... and never more than this
 
-    from graph_odenet_amd import _lib, models, ops
-    from graph_odenet_amd import parallel
-    from graph_odenet_amd.parallel import GradBucket, broadcast_parameters
-    parallel.FORCE_COLLECTIVES = bool(args.force_dist)
-    from graph_odenet_amd.synth import rmat_graph
-    lib = _lib.load()
 
-    # ---- inputs: resident in HBM before the timed region ------------------------------------
-    g = rmat_graph(args.scale, args.edges, seed=rank, device=dev)
-    g.transpose()                                   # CSR-by-source for the backward pass, built once
-    n = g.n_rows
-    gen = torch.Generator(device=dev).manual_seed(1000 + rank)
-    x = torch.randn(n, args.nfeat, generator=gen, device=dev)
-    labels = torch.randint(0, args.nclass, (n,), generator=gen, device=dev)
-    idx_train = torch.randperm(n, generator=gen, device=dev)[: n // 10]
+def dump_outputs(out_dir, loss, log_probs, model):
+    """--dump-outputs: the last timed step's loss, a fixed sample of its output rows (the same rows for the same
+    arguments), and the parameters after the update with their gradients, as .npy files (float32; the row ids float64)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
 
-    torch.manual_seed(42)
-    model = models.ODEGCN3(nfeat=args.nfeat, nhid=args.hidden, nclass=args.nclass, dropout=0.5,
-                           method="rk4", step_size=1.0 / args.ode_steps).to(dev)
-    broadcast_parameters(model, 0)
-    from graph_odenet_amd.optim import Adam
-    opt = Adam(model.parameters(), lr=0.01, weight_decay=5e-4)        # torch.optim.Adam's update as one launch (csrc/mlp.hip)
-    bucket = GradBucket(model)
-    sd_cpu = {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}
+    def save(name, t, dtype=torch.float32):
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().to("cpu", dtype).numpy())
+    n, c = log_probs.shape
+    k = min(n, DUMP_SAMPLE_ROWS, max(1, DUMP_SAMPLE_BYTES // (4 * c)))
+    rows = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:k].sort().values
+    save("loss", loss.reshape(1))
+    save("log_probs_sample", log_probs[rows.to(log_probs.device)])
+    save("log_probs_sample_rows", rows, torch.float64)
+    for name, p in model.named_parameters():
+        save("param." + name, p)
+        if p.grad is not None:
+            save("grad." + name, p.grad)
 
-    def step():
-        model.train()
-        opt.zero_grad(set_to_none=False)
-        out = model(x, g)
-        loss = torch.nn.functional.nll_loss(out[idx_train], labels[idx_train])
-        loss.backward()
-        bucket.allreduce_mean()
-        opt.step()
-        return loss
 
-    def barrier():
-        if use_dist:
-            dist.barrier()
-        torch.cuda.synchronize()
-
-    for _ in range(args.warmup):
-        step()
-    model.nfe = 0
-    cap = args.steps * (8 * 4 * args.ode_steps + 32) + 64
-    prof = lib.gode_prof_create(cap)
-    lib.gode_prof_enable(prof)
-    # exactly `steps` steps between barrier + synchronize on both sides, MAX over ranks (parallel.run_timed: the same
-    # helper the world_size-2 gloo test drives)
-    elapsed, loss = parallel.run_timed(step, args.steps, 0, dev)
-    lib.gode_prof_enable(None)
-    nfe_per_step = model.nfe / max(args.steps, 1)
-
+def full_measurements(args, lib, prof, cap, g, n, world, model, x, step, barrier, other_configs):
+    """`--full` only, after the timed region: the rooflines from the profile of the timed steps, and (N = 1) the
+    secondary block - extra steps with other settings, the dense kernels alone, the other configurations."""
     # ---- roofline of the dominant kernel (SpMM main kernel at d = hidden) and of the dense kernels --------------
     ms = (ctypes.c_float * cap)()
     dd = (ctypes.c_int64 * cap)()
@@ -412,6 +363,108 @@ def main():
                 lib.gode_prof_destroy(prof2)
         if other_configs is not None:
             extras["other_configs"] = other_configs
+    return roof, dense, extras
+
+
+def main():
+    args = parse()
+    from graph_odenet_amd import launch
+    if launch.needs_self_launch(args.gpus):
+        # bare `python bench.py --gpus N`: start the N ranks as fresh children BEFORE this process touches the GPU, relay
+        # their output (rank 0 prints the JSON line) and leave with their exit code
+        sys.exit(launch.self_launch(__file__, sys.argv[1:], args.gpus))
+    other_configs = None
+    if args.full and int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.no_configs and not args.no_secondary:
+        # The other BASELINE.json configurations (parity-test cases) with their CPU legs, timed on this box by
+        # tools/config_bench.py in a CHILD process that runs to completion BEFORE this process makes its first GPU call
+        # (a process that has initialised the GPU starts no further programs on this pool).  A fresh process also keeps
+        # the C4 leg's HIP-graph captures of arbitrary autograd away from the process that prints the contract line.
+        import subprocess
+        try:
+            assert not torch.cuda.is_initialized()
+            cp = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "config_bench.py"), "--one-line"],
+                                capture_output=True, text=True, timeout=args.configs_timeout)
+            lines = [l for l in cp.stdout.splitlines() if l.startswith("{")]
+            if cp.returncode != 0 or not lines:
+                raise RuntimeError("config_bench.py rc %d: %s" % (cp.returncode, (cp.stderr or cp.stdout)[-400:]))
+            other_configs = json.loads(lines[-1])
+        except Exception as e:
+            other_configs = {"error": "%s: %s" % (type(e).__name__, e)}
+    import torch.distributed as dist
+    if args.force_dist and int(os.environ.get("WORLD_SIZE", "1")) == 1:
+        rank, local_rank, world, backend = 0, 0, 1, "nccl"
+        torch.cuda.set_device(0)
+        dev = torch.device("cuda", 0)
+        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+        os.environ.setdefault("MASTER_PORT", "29533")
+        dist.init_process_group("nccl", rank=0, world_size=1, device_id=dev)
+    else:
+        rank, local_rank, world, dev, backend = launch.init_ranks(args.backend)      # includes the checked all-reduce of 1.0
+    if world != args.gpus and rank == 0:
+        print("bench.py: --gpus %d but WORLD_SIZE=%d; reporting n_gpus=%d" % (args.gpus, world, world), file=sys.stderr)
+    use_dist = world > 1 or args.force_dist
+
+    from graph_odenet_amd import _lib, models, ops
+    from graph_odenet_amd import parallel
+    from graph_odenet_amd.parallel import GradBucket, broadcast_parameters
+    parallel.FORCE_COLLECTIVES = bool(args.force_dist)
+    from graph_odenet_amd.synth import rmat_graph
+    lib = _lib.load()
+
+    # ---- inputs: resident in HBM before the timed region ------------------------------------
+    g = rmat_graph(args.scale, args.edges, seed=rank, device=dev)
+    g.transpose()                                   # CSR-by-source for the backward pass, built once
+    n = g.n_rows
+    gen = torch.Generator(device=dev).manual_seed(1000 + rank)
+    x = torch.randn(n, args.nfeat, generator=gen, device=dev)
+    labels = torch.randint(0, args.nclass, (n,), generator=gen, device=dev)
+    idx_train = torch.randperm(n, generator=gen, device=dev)[: n // 10]
+
+    torch.manual_seed(42)
+    model = models.ODEGCN3(nfeat=args.nfeat, nhid=args.hidden, nclass=args.nclass, dropout=0.5,
+                           method="rk4", step_size=1.0 / args.ode_steps).to(dev)
+    broadcast_parameters(model, 0)
+    from graph_odenet_amd.optim import Adam
+    opt = Adam(model.parameters(), lr=0.01, weight_decay=5e-4)        # torch.optim.Adam's update as one launch (csrc/mlp.hip)
+    bucket = GradBucket(model)
+    sd_cpu = {k: v.detach().cpu().clone() for k, v in model.state_dict().items()} if args.full else None
+    last_out = [] if args.dump_outputs and rank == 0 else None
+
+    def step():
+        model.train()
+        opt.zero_grad(set_to_none=False)
+        out = model(x, g)
+        loss = torch.nn.functional.nll_loss(out[idx_train], labels[idx_train])
+        loss.backward()
+        bucket.allreduce_mean()
+        opt.step()
+        if last_out is not None:
+            last_out[:] = [out.detach()]
+        return loss
+
+    def barrier():
+        if use_dist:
+            dist.barrier()
+        torch.cuda.synchronize()
+
+    for _ in range(args.warmup):
+        step()
+    model.nfe = 0
+    if args.full:
+        cap = args.steps * (8 * 4 * args.ode_steps + 32) + 64
+        prof = lib.gode_prof_create(cap)
+        lib.gode_prof_enable(prof)
+    # exactly `steps` steps between barrier + synchronize on both sides, MAX over ranks (parallel.run_timed: the same
+    # helper the world_size-2 gloo test drives)
+    elapsed, loss = parallel.run_timed(step, args.steps, 0, dev)
+    if args.full:
+        lib.gode_prof_enable(None)
+    nfe_per_step = model.nfe / max(args.steps, 1)
+    if last_out is not None:
+        dump_outputs(args.dump_outputs, loss, last_out[0], model)
+    roof = dense = extras = None
+    if args.full:
+        roof, dense, extras = full_measurements(args, lib, prof, cap, g, n, world, model, x, step, barrier, other_configs)
 
     res = None
     if rank == 0:
@@ -429,9 +482,10 @@ def main():
                        "nclass": args.nclass, "nfe_per_step": nfe_per_step,
                        "parallelism": "dp%d (one graph per rank, 1 gradient all-reduce/step)" % world},
             "loss": round(float(loss.detach()), 5),
-            "roofline": roof,
-            "roofline_dense": dense,
         }
+        if args.full:
+            res["roofline"] = roof
+            res["roofline_dense"] = dense
         if use_dist:
             # ranks that answered the checked all-reduce of 1.0 at start-up (launch.init_ranks), and what carried it:
             # "nccl" = RCCL, one GPU per rank; "gloo" = rehearsal, the ranks share the GPUs of a smaller box
@@ -439,13 +493,13 @@ def main():
             res["backend"] = backend
         if extras is not None:
             res["secondary"] = extras
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             rp = g.rowptr.to(torch.int64)
             rows = torch.repeat_interleave(torch.arange(n, device=dev), rp[1:] - rp[:-1]).cpu()
             gc = {"n": n, "r": rows, "c": g.col.to(torch.int64).cpu(), "v": g.val.cpu()}
             res["cpu_baseline"] = cpu_baseline(args, gc, sd_cpu, x.cpu())
 
-    if world > 1 and not args.no_secondary:
+    if args.full and world > 1 and not args.no_secondary:
         # The two other multi-GPU workloads run AFTER the contract measurement is complete.  They are collective code
         # that may stall on a node this build has never seen: a watchdog prints the line without them (and ends the
         # process, on every rank) rather than let a secondary number take the contract line down.

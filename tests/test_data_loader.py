@@ -1,21 +1,24 @@
 """Own Planetoid reader vs the loader outputs captured from the reference (tests/golden/*_graph.npz).
-Needs the raw `ind.*` files, which exist only in the build container (skipped elsewhere)."""
-import os
-
+The raw `ind.*` files it reads are stored byte for byte in tests/golden/planetoid_raw.npz and written back to a
+temporary directory here."""
 import numpy as np
 import pytest
 import torch
 
 from graph_odenet_amd.data import load_captured, load_captured_gat, load_planetoid, load_planetoid_gat
 
-RAW = "/root/reference/data"
+
+@pytest.fixture(scope="module")
+def raw_dir(golden, tmp_path_factory):
+    d = tmp_path_factory.mktemp("planetoid")
+    for fn, data in golden("planetoid_raw.npz").items():
+        (d / fn).write_bytes(data.tobytes())
+    return str(d)
 
 
 @pytest.mark.parametrize("name", ["cora", "citeseer"])
-def test_own_reader_matches_reference_loader(name):
-    if not os.path.exists(os.path.join(RAW, "ind.%s.graph" % name)):
-        pytest.skip("raw Planetoid files not present on this machine")
-    adj, x, y, itr, iva, ite = load_planetoid(name, RAW)
+def test_own_reader_matches_reference_loader(name, raw_dir):
+    adj, x, y, itr, iva, ite = load_planetoid(name, raw_dir)
     radj, rx, ry, ritr, riva, rite = load_captured(name)
     assert adj.shape == radj.shape
     assert torch.allclose(adj.to_dense(), radj.to_dense(), atol=1e-7)
@@ -30,14 +33,12 @@ def test_captured_shapes():
 
 
 @pytest.mark.parametrize("name,n_edges", [("cora", 5278), ("citeseer", 4676)])
-def test_own_gat_edge_list_matches_reference_loader(name, n_edges):
+def test_own_gat_edge_list_matches_reference_loader(name, n_edges, raw_dir):
     """undirected_edge_list restates networkx's edge order (GAT/utils.py:187-189); compared with the edge lists captured
     from the reference's GAT loader."""
     src, tgt, Mtgt, x, y, itr, iva, ite = load_captured_gat(name)
     assert src.numel() == n_edges and Mtgt.shape == (x.shape[0], n_edges)
-    if not os.path.exists(os.path.join(RAW, "ind.%s.graph" % name)):
-        pytest.skip("raw Planetoid files not present on this machine")
-    s2, t2, M2, x2, y2, *_ = load_planetoid_gat(name, RAW)
+    s2, t2, M2, x2, y2, *_ = load_planetoid_gat(name, raw_dir)
     assert torch.equal(s2, src) and torch.equal(t2, tgt)
     assert torch.equal(M2.coalesce().indices(), Mtgt.coalesce().indices())
     assert torch.allclose(x2, x, atol=1e-7) and torch.equal(y2, y)

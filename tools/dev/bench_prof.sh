@@ -1,11 +1,11 @@
 #!/bin/bash
-# kernel-trace stats of `python bench.py` (the round's committed profile: profiles/rNN_bench_kernel_stats.txt)
+# kernel-trace stats of `python bench.py --full` (the round's committed profile: profiles/rNN_bench_kernel_stats.txt)
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/../.." && pwd)}
 OUT=$R/gpurun_out/prof_bench
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 echo "profiling bench.py ..."
-timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python $R/bench.py > $OUT/bench.log 2> $OUT/bench.err
+timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python $R/bench.py --full > $OUT/bench.log 2> $OUT/bench.err
 echo "rc=$?"
 f=$(find $OUT/stats -name "*kernel_stats.csv" | head -1)
 python - "$f" "$OUT/bench.log" > $R/gpurun_out/bench_kernel_stats.txt <<'PY'

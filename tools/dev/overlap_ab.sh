@@ -3,5 +3,5 @@
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/../.." && pwd)}
 for ov in 1 0 1 0; do
   echo "## GODE_OVERLAP=$ov"
-  GODE_OVERLAP=$ov python $R/bench.py --no-configs --no-cpu-baseline --no-secondary --steps 4 2>/dev/null
+  GODE_OVERLAP=$ov python $R/bench.py --full --no-configs --no-cpu-baseline --no-secondary --steps 4 2>/dev/null
 done | python $R/tools/dev/overlap_ab.py

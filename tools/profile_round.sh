@@ -1,5 +1,5 @@
 #!/bin/bash
-# Round profile: kernel-trace stats of the default bench + PMC traffic passes + FETCH_SIZE calibration.
+# Round profile: kernel-trace stats of the full bench (--full) + PMC traffic passes + FETCH_SIZE calibration.
 # usage (on the GPU box): tools/profile_round.sh r01
 set -u
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
@@ -7,7 +7,7 @@ TAG=$1
 OUT=$R/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python $R/bench.py > $OUT/bench_stats.log 2>&1
+timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python $R/bench.py --full > $OUT/bench_stats.log 2>&1
 echo "stats rc=$?"; tail -1 $OUT/bench_stats.log | cut -c1-400
 for c in FETCH_SIZE WRITE_SIZE "TCC_HIT_sum TCC_MISS_sum"; do
   n=$(echo $c | tr ' ' '_')

@@ -33,7 +33,7 @@ for f in sorted(glob.glob(out + "/stats/**/*kernel_stats.csv", recursive=True)):
     # bench.py runs tools/config_bench.py (the other BASELINE configurations) as a child process first: the profiler writes one
     # table per process - the one with the SpMM on top is the benchmark itself
     is_main = any("spmm_vec4_kernel" in r["Name"] for r in rows[:3])
-    lines.append("# rocprofv3 --kernel-trace --stats -- python bench.py   (round %s; %s)"
+    lines.append("# rocprofv3 --kernel-trace --stats -- python bench.py --full   (round %s; %s)"
                  % (tag, "the benchmark process: C5" if is_main else "its child process tools/config_bench.py: configurations C1-C4"))
     lines.append("# %-46s %7s %12s %12s %7s" % ("kernel", "calls", "avg_us", "total_ms", "pct"))
     for r in rows[:25]:
