@@ -105,6 +105,10 @@ SIGNATURES = {
     "gode_get_option": (c_i, [ctypes.c_char_p]),
     "gode_spmm_csr_f32": (c_i, [c_p, c_p, c_p, c_p, c_i64, c_p, c_i64, c_p, c_p, c_i64, c_p, c_i64,
                                 c_i64, c_i64, ctypes.POINTER(SpmmEpilogue), c_p]),
+    "gode_spmm_csr_save_f32": (c_i, [c_p, c_p, c_p, c_p, c_i64, c_p, c_i64, c_p, c_p, c_i64, c_p, c_i64,
+                                     c_i64, c_i64, ctypes.POINTER(SpmmEpilogue), c_p, c_p]),
+    "gode_masked_cot_parts": (c_i64, [c_i64, c_i64]),
+    "gode_masked_cot_f32": (c_i, [ctypes.POINTER(LinComb), c_p, c_p, c_i64, c_i64, c_p, c_p]),
     "gode_lincomb_f32": (c_i, [c_p, ctypes.POINTER(LinComb), c_i64, c_p]),
     "gode_lincomb_multi_f32": (c_i, [c_p, c_p, c_p, ctypes.c_int32, c_p]),
     "gode_rk_errnorm_multi_f32": (c_i, [c_p, c_p, c_p, c_p, c_p, ctypes.c_int32, c_f, c_f, c_p, c_p]),
@@ -164,6 +168,10 @@ SIGNATURES = {
                                             ctypes.POINTER(LinComb), c_p, c_p, ctypes.POINTER(LinComb), c_p, c_p]),
     "gode_gcn_vjp_small_f32": (c_i, [ctypes.POINTER(GcnOdeFunc), ctypes.POINTER(LinComb), c_p, c_f, ctypes.POINTER(LinComb),
                                      c_p, c_p, c_p]),
+    "gode_gcn_vjp_small_next_f32": (c_i, [ctypes.POINTER(GcnOdeFunc), ctypes.POINTER(LinComb), c_p, c_f, ctypes.POINTER(LinComb),
+                                          c_p, c_p, ctypes.POINTER(LinComb), c_p, c_p, c_p]),
+    "gode_gcn_feval_small_save_f32": (c_i, [ctypes.POINTER(GcnOdeFunc), ctypes.POINTER(LinComb), c_f, c_f,
+                                            ctypes.POINTER(LinComb), c_p, c_p, c_p]),
     "gode_gcn_small_finish_f32": (c_i, [ctypes.POINTER(GcnOdeFunc), c_p, c_p, c_f, c_p]),
     "gode_gcn_small_finish_multi_f32": (c_i, [ctypes.POINTER(GcnOdeFunc), c_p, ctypes.c_int32, ctypes.POINTER(c_p), ctypes.POINTER(c_f), c_p]),
     "gode_gcn_small_finish4_f32": (c_i, [ctypes.POINTER(GcnOdeFunc), c_p, c_p, c_p, c_p, c_p]),
@@ -216,6 +224,11 @@ SIGNATURES = {
                                        c_f, c_f, ctypes.c_int32, c_p]),
     "gode_gcn_ode_rk4_adjoint": (c_i, [ctypes.POINTER(GcnOdeFunc), c_p, c_p, c_p, ctypes.POINTER(c_p), ctypes.POINTER(c_p),
                                        ctypes.POINTER(Rk4Workspace), c_f, c_f, ctypes.c_int32, c_p]),
+    "gode_gcn_ode_rk4_forward_save": (c_i, [ctypes.POINTER(GcnOdeFunc), c_p, c_p, c_p, ctypes.POINTER(Rk4Workspace),
+                                            c_f, c_f, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, c_p]),
+    "gode_gcn_ode_rk4_backprop": (c_i, [ctypes.POINTER(GcnOdeFunc), c_p, c_p, c_p, ctypes.POINTER(c_p),
+                                        ctypes.POINTER(Rk4Workspace), c_p, c_f, c_f, ctypes.c_int32, ctypes.c_int32,
+                                        ctypes.c_int32, c_p]),
     "gode_gcn_ode_dopri5_step_forward": (c_i, [ctypes.POINTER(GcnOdeFunc), c_p, ctypes.POINTER(c_p), c_p,
                                                ctypes.POINTER(Rk4Workspace), ctypes.c_double, ctypes.c_double, c_f, c_f,
                                                c_p, c_p, c_p]),

@@ -505,3 +505,207 @@ extern "C" int gode_gcn_ode_dopri5_step_adjoint(const gode_gcn_odefunc_t* f, con
     const int64_t ens[4] = {nd, nd, 1, P - 1};
     return gode_rk_errnorm_multi_f32(sums, e0, e1, errs, ens, 4, rtol, atol, err_scratch, stream);
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// Backprop through a fixed-grid rk4 solve (odeint._OdeintBackprop): a forward solve that keeps every step's y_n and
+// k_1..k_4, and ONE call for the whole reverse sweep over them.  Record r of `save` (step step_begin + r) is
+// [ y_n | k_1 | k_2 | k_3 | k_4 ], five n x d arrays.  Per step, with cotangent abar = dL/dy_{n+1} (3/8 rule):
+//   kbar_4 = h/8 abar,  kbar_3 = 3h/8 abar + h Ybar_4,  kbar_2 = 3h/8 abar + h Ybar_3 - h Ybar_4,
+//   kbar_1 = h/8 abar + h/3 Ybar_2 - h/3 Ybar_3 + h Ybar_4;   Ybar_s = J_s^T kbar_s,  theta += (df/dtheta)_s^T kbar_s,
+//   abar_n = abar + sum_s Ybar_s
+// where J_s is the Jacobian of f at the stage input Y_s = y_n + h sum_j A38[s][j] k_j; f = relu(z), so the VJP's mask
+// [z_s > 0] is [k_s > 0] of the saved derivative.
+// ---------------------------------------------------------------------------------------------------------------
+namespace {
+
+int spmm_save(const gode_graph_t& g, const float* X, float* Y, int64_t d, const gode_spmm_epilogue_t* ep, float* K, void* s) {
+    return gode_spmm_csr_save_f32(g.rowptr, g.col, g.val, g.items, g.n_items, g.long_rows, g.n_long, g.partial,
+                                  X, d, Y, d, g.n_rows, d, ep, K, s);
+}
+
+// kbar_s: h b_s abar + h sum_{q > s} A38[q][s] Ybar_q
+gode_lincomb_t stage_cotangent(const float* abar, float* const* ybar, int s, double h) {
+    gode_lincomb_t lc;
+    lc.n = 0;
+    lc.coef[lc.n] = (float)(h * B38[s]); lc.ptr[lc.n] = abar; ++lc.n;
+    for (int q = s + 1; q < 4; ++q)
+        if (A38[q][s] != 0.0) { lc.coef[lc.n] = (float)(h * A38[q][s]); lc.ptr[lc.n] = ybar[q]; ++lc.n; }
+    return lc;
+}
+
+}  // namespace
+
+extern "C" int gode_gcn_ode_rk4_forward_save(const gode_gcn_odefunc_t* f, const float* y0, float* y_end, float* save,
+                                             const gode_rk4_workspace_t* ws, float t0, float t1, int32_t n_steps,
+                                             int32_t step_begin, int32_t step_end, void* stream)
+{
+    if (!f || !y0 || !y_end || !save || !ws) return GODE_E_NULLPTR;
+    if (n_steps <= 0 || f->n <= 0 || f->d <= 0) return GODE_E_SHAPE;
+    if (step_begin < 0 || step_end > n_steps || step_begin >= step_end) return GODE_E_SHAPE;
+    if (!ws->S) return GODE_E_NULLPTR;
+    const int64_t n = f->n, d = f->d, nd = n * d;
+    const double h = ((double)t1 - (double)t0) / n_steps;
+    const bool fused = fused_small(f);
+    if (y0 != save) {                                            // record 0 starts with a copy of y0
+        gode_lincomb_t c; c.n = 1; c.coef[0] = 1.f; c.ptr[0] = y0;
+        GODE_TRY(gode_lincomb_f32(save, &c, nd, stream));
+    }
+    for (int i = step_begin; i < step_end; ++i) {
+        float* rec = save + (int64_t)(i - step_begin) * 5 * nd;
+        const float* y = rec;
+        float* k[4] = {rec + nd, rec + 2 * nd, rec + 3 * nd, rec + 4 * nd};
+        float* ynext = (i + 1 < step_end) ? rec + 5 * nd : y_end;      // the next record's y_n, or the result
+        const double t = (double)t0 + i * h;
+        // the launches of gode_gcn_ode_rk4_forward; the folded last stage also stores k_4
+        for (int s = 0; s < 4; ++s) {
+            gode_lincomb_t xin = stage_terms(y, k, s, h);
+            const float ts = (float)(t + C38[s] * h);
+            if (fused) {
+                if (s < 3) {
+                    GODE_TRY(gode_gcn_feval_small_f32(f, &xin, ts, 1.f, nullptr, nullptr, nullptr, k[s], stream));
+                } else {
+                    gode_lincomb_t pre = combine_terms(y, k, h);
+                    GODE_TRY(gode_gcn_feval_small_save_f32(f, &xin, ts, (float)(h * B38[3]), &pre, ynext, k[3], stream));
+                }
+                continue;
+            }
+            GODE_TRY(gode_gn_time_gemm_f32(&xin, n, d, f->groups, f->eps, f->gamma, f->beta, f->W, d, 1, ts, ws->S, stream));
+            gode_spmm_epilogue_t ep = {};
+            ep.bias = f->b; ep.relu = 1; ep.alpha = 1.f;
+            if (s < 3) {
+                GODE_TRY(spmm(f->A, ws->S, k[s], d, &ep, stream));
+            } else {
+                ep.pre = combine_terms(y, k, h); ep.alpha = (float)(h * B38[3]);
+                GODE_TRY(spmm_save(f->A, ws->S, ynext, d, &ep, k[3], stream));
+            }
+        }
+    }
+    return 0;
+}
+
+extern "C" int gode_gcn_ode_rk4_backprop(const gode_gcn_odefunc_t* f, const float* save, float* a, float* theta,
+                                         float** a_result, const gode_rk4_workspace_t* ws, float* cot_colpart,
+                                         float t0, float t1, int32_t n_steps, int32_t step_begin, int32_t step_end,
+                                         void* stream)
+{
+    if (!f || !save || !a || !theta || !a_result || !ws) return GODE_E_NULLPTR;
+    if (n_steps <= 0 || f->n <= 0 || f->d <= 0) return GODE_E_SHAPE;
+    if (step_begin < 0 || step_end > n_steps || step_begin >= step_end) return GODE_E_SHAPE;
+    for (int s = 0; s < 4; ++s) if (!ws->ka[s] || !ws->ktheta[s]) return GODE_E_NULLPTR;
+    if (!ws->dZ || !ws->dS || !ws->wpart || !ws->colsum_scratch) return GODE_E_NULLPTR;
+    if (f->groups > 0 && (!ws->gpart || !ws->bpart)) return GODE_E_NULLPTR;
+    const int64_t n = f->n, d = f->d, nd = n * d;
+    const int64_t nW = (d + 1) * d, P = gode_gcn_ode_theta_len(d);
+    const double h = ((double)t1 - (double)t0) / n_steps;
+    float* acur = a;
+    float* yb[4] = {ws->ka[0], ws->ka[1], ws->ka[2], ws->ka[3]};   // yb[1..3]: Ybar_2..4; yb[0] receives abar_n
+    auto record = [&](int i) { return save + (int64_t)(i - step_begin) * 5 * nd; };
+    const bool fused = fused_small(f) && ws->small_part != nullptr;
+    if (fused) {
+        // launch-bound graphs: ONE launch per stage - the VJP of stage s (csrc/small.hip) also forms the masked cotangent
+        // of the stage after it in the sweep (s - 1, or stage 4 of the previous step); one launch per step closes theta
+        const int64_t slot = gode_gcn_small_parts(n) * gode_gcn_small_part_len(d);
+        float* dz[2] = {ws->dZ, ws->dS};
+        int cur = 0;
+        {
+            const float* r = record(step_end - 1);
+            const gode_lincomb_t c4 = stage_cotangent(acur, yb, 3, h);
+            GODE_TRY(gode_masked_cot_f32(&c4, r + 4 * nd, dz[0], n, d, nullptr, stream));
+        }
+        for (int i = step_end - 1; i >= step_begin; --i) {
+            const float* y = record(i);
+            float* k[4] = {(float*)y + nd, (float*)y + 2 * nd, (float*)y + 3 * nd, (float*)y + 4 * nd};
+            const double t = (double)t0 + i * h;
+            float stage_t[4];
+            for (int s = 3; s >= 0; --s) {
+                stage_t[s] = (float)(t + C38[s] * h);
+                const gode_lincomb_t yin = stage_terms(y, k, s, h);
+                gode_lincomb_t pre; pre.n = 0;
+                if (s == 0) {
+                    pre.n = 4;
+                    pre.coef[0] = 1.f; pre.ptr[0] = acur;
+                    for (int q = 1; q < 4; ++q) { pre.coef[q] = 1.f; pre.ptr[q] = yb[q]; }
+                }
+                gode_lincomb_t nxt; nxt.n = 0;
+                const float* knext = nullptr;
+                if (s > 0) {
+                    nxt = stage_cotangent(acur, yb, s - 1, h);               // names yb[s]: this launch's rows
+                    knext = k[s - 1];
+                } else if (i > step_begin) {
+                    nxt.n = 1; nxt.coef[0] = (float)(h * B38[3]); nxt.ptr[0] = yb[0];      // kbar_4 of step i - 1
+                    knext = record(i - 1) + 4 * nd;
+                }
+                float* part = ws->small_part + s * slot;
+                if (knext) {
+                    GODE_TRY(gode_gcn_vjp_small_next_f32(f, &yin, dz[cur], 1.f, s == 0 ? &pre : nullptr, yb[s], part,
+                                                         &nxt, knext, dz[cur ^ 1], stream));
+                    cur ^= 1;
+                } else {
+                    GODE_TRY(gode_gcn_vjp_small_f32(f, &yin, dz[cur], 1.f, s == 0 ? &pre : nullptr, yb[s], part, stream));
+                }
+            }
+            const float w1[4] = {1.f, 1.f, 1.f, 1.f};               // h is already inside kbar
+            GODE_TRY(gode_gcn_small_finish4_f32(f, ws->small_part, theta, w1, stage_t, stream));
+            float* tmp = acur; acur = yb[0]; yb[0] = tmp;
+        }
+        *a_result = acur;
+        return 0;
+    }
+    const bool small = n <= kMergedFinishMaxRows;
+    const int64_t wparts = gode_wgrad_parts(n), gparts = gode_gemm_bwd_parts(n);
+    const bool bw = !small && gode_bwd_wgrad_supported(n, d, d, f->groups) && gode_bwd_wgrad_parts(n) <= wparts;
+    const int64_t cparts = (!small && cot_colpart) ? gode_masked_cot_parts(n, d) : 0;
+    for (int i = step_end - 1; i >= step_begin; --i) {
+        const float* y = record(i);
+        float* k[4] = {(float*)y + nd, (float*)y + 2 * nd, (float*)y + 3 * nd, (float*)y + 4 * nd};
+        const double t = (double)t0 + i * h;
+        for (int s = 3; s >= 0; --s) {
+            const float ts = (float)(t + C38[s] * h);
+            const gode_lincomb_t cot = stage_cotangent(acur, yb, s, h);
+            GODE_TRY(gode_masked_cot_f32(&cot, k[s], ws->dZ, n, d, cparts > 0 ? cot_colpart : nullptr, stream));
+            GODE_TRY(spmm(f->AT, ws->dZ, ws->dS, d, nullptr, stream));                 // dS = A^T dZ
+            const gode_lincomb_t yin = stage_terms(y, k, s, h);
+            gode_lincomb_t pre; pre.n = 0;
+            if (s == 0) {
+                pre.n = 4;
+                pre.coef[0] = 1.f; pre.ptr[0] = acur;
+                for (int q = 1; q < 4; ++q) { pre.coef[q] = 1.f; pre.ptr[q] = yb[q]; }
+            }
+            float* kt = ws->ktheta[s];
+            if (bw) {
+                GODE_TRY(gode_gn_time_gemm_bwd_wgrad_f32(&yin, n, d, f->groups, f->eps, f->gamma, f->beta, f->W, d, 1, ws->dS,
+                                                         1.f, s == 0 ? &pre : nullptr, yb[s],
+                                                         f->groups > 0 ? ws->gpart : nullptr, f->groups > 0 ? ws->bpart : nullptr,
+                                                         ws->wpart, stream));
+                GODE_TRY(gode_reduce_parts_f32(kt, ws->wpart, gode_bwd_wgrad_parts(n), nW, 1.f, 0, stream));
+            } else {
+                GODE_TRY(gode_gn_time_gemm_bwd_f32(&yin, n, d, f->groups, f->eps, f->gamma, f->W, d, 1, ws->dS, 1.f,
+                                                   s == 0 ? &pre : nullptr, yb[s], f->groups > 0 ? ws->gpart : nullptr,
+                                                   f->groups > 0 ? ws->bpart : nullptr, stream));
+                GODE_TRY(gode_wgrad_f32(&yin, n, d, f->groups, f->eps, f->gamma, f->beta, ws->dS, d, 1, ws->wpart, stream));
+                if (small) {
+                    GODE_TRY(stage_finish_merged(f, ws, kt, ts, stream));
+                    continue;
+                }
+                GODE_TRY(gode_reduce_parts_f32(kt, ws->wpart, wparts, nW, 1.f, 0, stream));
+            }
+            hipLaunchKernelGGL(theta_fixup_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, kt, f->W, ts, (int)d, P - 1);
+            GODE_LAUNCH_CHECK();
+            if (cparts > 0) GODE_TRY(gode_colsum_f32(kt + nW, cot_colpart, cparts, d, 1.f, 0, ws->colsum_scratch, stream));
+            else GODE_TRY(gode_colsum_f32(kt + nW, ws->dZ, n, d, 1.f, 0, ws->colsum_scratch, stream));
+            if (f->groups > 0) {
+                GODE_TRY(gode_reduce_parts2_f32(kt + nW + d, ws->gpart, kt + nW + 2 * d, ws->bpart, gparts, d, 1.f, 0, stream));
+            } else {
+                GODE_TRY(gode_zero_f32(kt + nW + d, 2 * d, stream));
+            }
+        }
+        // theta += sum_s ktheta_s   (weights 1: h is already inside kbar)
+        gode_lincomb_t tc;
+        tc.n = 5; tc.coef[0] = 1.f; tc.ptr[0] = theta;
+        for (int q = 0; q < 4; ++q) { tc.coef[1 + q] = 1.f; tc.ptr[1 + q] = ws->ktheta[q]; }
+        GODE_TRY(gode_lincomb_f32(theta, &tc, P, stream));
+        float* tmp = acur; acur = yb[0]; yb[0] = tmp;
+    }
+    *a_result = acur;
+    return 0;
+}

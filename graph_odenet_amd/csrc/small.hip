@@ -69,17 +69,20 @@ __device__ __forceinline__ float4 lc_load4_self(const LinComb& lc, int64_t idx, 
 // 26.7 us per launch with a wave per row).
 // (the next-stage arguments travel only with the launches that use them: an rk4 evaluation on Cora is ~8 us of launch-bound
 // work, and 112 more bytes of kernel arguments in each of its 128 launches per step showed in the step time)
-template <bool NEXT> struct NextArgs { LinComb nxt; float* x_next; };
-template <> struct NextArgs<false> {};
+// NX = 0: nothing more; 1: the next stage's combined input; 2: relu(z) itself into k (gode_gcn_feval_small_save_f32: the
+// launch that folds the last RK stage into the solution leaves that stage's derivative for a backward sweep)
+template <int NX> struct NextArgs {};
+template <> struct NextArgs<1> { LinComb nxt; float* x_next; };
+template <> struct NextArgs<2> { float* k; };
 
-template <int D, int CG, int GW, bool NEXT>
+template <int D, int CG, int GW, int NX>
 __global__ __launch_bounds__(256) void gcn_feval_small_kernel(const int* __restrict__ rowptr, const int* __restrict__ col,
                                                              const float* __restrict__ val, LinComb xin, int n_rows,
                                                              float eps, const float* __restrict__ gamma,
                                                              const float* __restrict__ beta, const float* __restrict__ W,
                                                              const float* __restrict__ bias, float t, float alpha,
                                                              LinComb pre, LinComb cot, float* __restrict__ Y2,
-                                                             float* __restrict__ out, NextArgs<NEXT> nx)
+                                                             float* __restrict__ out, NextArgs<NX> nx)
 {
     constexpr int LPR = D / 4, SG = GW / LPR, RPW = 64 / GW, PU = 4;   // lanes per row, sub-groups per row, rows per wave, gathers in flight per lane
     __shared__ __attribute__((aligned(16))) float Ws[(D + 1) * D];
@@ -146,6 +149,7 @@ __global__ __launch_bounds__(256) void gcn_feval_small_kernel(const int* __restr
             z.x += bi.x; z.y += bi.y; z.z += bi.z; z.w += bi.w;
             float4 y = make_float4(fmaxf(z.x, 0.f), fmaxf(z.y, 0.f), fmaxf(z.z, 0.f), fmaxf(z.w, 0.f));
             const int64_t o = (int64_t)row * D + 4 * q;
+            if constexpr (NX == 2) *reinterpret_cast<float4*>(nx.k + o) = y;
             if (pre.n > 0) {
                 const float4 p = lc_load4(pre, o);
                 y.x = fmaf(alpha, y.x, p.x); y.y = fmaf(alpha, y.y, p.y); y.z = fmaf(alpha, y.z, p.z); y.w = fmaf(alpha, y.w, p.w);
@@ -161,7 +165,7 @@ __global__ __launch_bounds__(256) void gcn_feval_small_kernel(const int* __restr
             // the NEXT stage's combined input, row by row (a term that names `out` takes this row's value from the
             // register): the next evaluation then gathers ONE array per neighbour instead of one per term of its stage
             // input - 4.3 terms on average over the six stages of a dopri5 step, and the gather is what this kernel waits for
-            if constexpr (NEXT) *reinterpret_cast<float4*>(nx.x_next + o) = lc_load4_self(nx.nxt, o, out, y);
+            if constexpr (NX == 1) *reinterpret_cast<float4*>(nx.x_next + o) = lc_load4_self(nx.nxt, o, out, y);
         }
         __builtin_amdgcn_wave_barrier();                         // the next row's mrow stores follow these reads
     }
@@ -202,13 +206,18 @@ __device__ __forceinline__ float4 gn_backward4(const float4 x, const float4 dy, 
 // VJP: dS_i = sum_j aT_ij dZ_j;  ka_i = (sum pre)_i + out_scale * GN'(x_i)^T (dS_i W1^T);  block partial row
 // part[block] = [ sum_i [1|xn_i]^T dS_i  ((D+1) x D, row 0 = colsum(dS): the time row) | colsum(dZ) | dgamma | dbeta | a_t' share ]
 // ---------------------------------------------------------------------------------------------------------------
-template <int D, int CG, int GW>
+// NXT (gode_gcn_vjp_small_next_f32, the reverse sweep of a backprop solve): the launch also forms the NEXT stage's masked
+// cotangent dZn = (sum cot) * [k > 0] row by row; a term of cot that names `ka` takes this row's value from the register
+template <bool NXT> struct VjpNext { LinComb cot; const float* k; float* dZn; };
+template <> struct VjpNext<false> {};
+
+template <int D, int CG, int GW, bool NXT>
 __global__ __launch_bounds__(256) void gcn_vjp_small_kernel(const int* __restrict__ rowptrT, const int* __restrict__ colT,
                                                            const float* __restrict__ valT, LinComb xin, int n_rows,
                                                            float eps, const float* __restrict__ gamma,
                                                            const float* __restrict__ beta, const float* __restrict__ W,
                                                            const float* __restrict__ dZ, float out_scale, LinComb pre,
-                                                           float* __restrict__ ka, float* __restrict__ part)
+                                                           float* __restrict__ ka, float* __restrict__ part, VjpNext<NXT> vn)
 {
     constexpr int LPR = D / 4, SG = GW / LPR, RPW = 64 / GW, NS = D / SG, PU = 4;     // NS = columns of dW per lane
     constexpr int PLEN = (D + 1) * D + 3 * D + 1;                 // ... | the block's share of a_t' = colsum(dS) . W[0, :]
@@ -278,6 +287,12 @@ __global__ __launch_bounds__(256) void gcn_vjp_small_kernel(const int* __restric
             float4 out = make_float4(out_scale * dx.x, out_scale * dx.y, out_scale * dx.z, out_scale * dx.w);
             if (pre.n > 0) { const float4 p = lc_load4(pre, o); out.x += p.x; out.y += p.y; out.z += p.z; out.w += p.w; }
             *reinterpret_cast<float4*>(ka + o) = out;
+            if constexpr (NXT) {
+                float4 g = lc_load4_self(vn.cot, o, ka, out);
+                const float4 kk = ld4(vn.k + o);
+                g.x = kk.x > 0.f ? g.x : 0.f; g.y = kk.y > 0.f ? g.y : 0.f; g.z = kk.z > 0.f ? g.z : 0.f; g.w = kk.w > 0.f ? g.w : 0.f;
+                *reinterpret_cast<float4*>(vn.dZn + o) = g;
+            }
             dg.x += dy.x * xh.x; dg.y += dy.y * xh.y; dg.z += dy.z * xh.z; dg.w += dy.w * xh.w;
             db.x += dy.x; db.y += dy.y; db.z += dy.z; db.w += dy.w;
             cs.x += dS.x; cs.y += dS.y; cs.z += dS.z; cs.w += dS.w;
@@ -527,10 +542,10 @@ extern "C" int gode_gcn_feval_small_next_f32(const gode_gcn_odefunc_t* f, const 
     const int cg = small_cg(d, f->groups);
     const dim3 grid((unsigned)feval_blocks(f->n));
     const bool r4 = rows4(f->n);
-    NextArgs<true> nxa; nxa.nxt = lnext; nxa.x_next = x_next;
-    const NextArgs<false> nx0;
+    NextArgs<1> nxa; nxa.nxt = lnext; nxa.x_next = x_next;
+    const NextArgs<0> nx0;
 #define GODE_FEV(DV, CGV) if (r4) GODE_FEV_(DV, CGV, 16) else GODE_FEV_(DV, CGV, 64)
-#define GODE_FEV_(DV, CGV, GWV) if (x_next) GODE_FEV__(DV, CGV, GWV, true, nxa) else GODE_FEV__(DV, CGV, GWV, false, nx0)
+#define GODE_FEV_(DV, CGV, GWV) if (x_next) GODE_FEV__(DV, CGV, GWV, 1, nxa) else GODE_FEV__(DV, CGV, GWV, 0, nx0)
 #define GODE_FEV__(DV, CGV, GWV, NXV, NXA) hipLaunchKernelGGL((gcn_feval_small_kernel<DV, CGV, GWV, NXV>), grid, dim3(256), 0, (hipStream_t)stream, \
                                              f->A.rowptr, f->A.col, f->A.val, lx, (int)f->n, f->eps, f->gamma, f->beta, f->W,    \
                                              f->b, t, alpha, lp, lcot, Y2, out, NXA);
@@ -542,10 +557,19 @@ extern "C" int gode_gcn_feval_small_next_f32(const gode_gcn_odefunc_t* f, const 
     return 0;
 }
 
-extern "C" int gode_gcn_vjp_small_f32(const gode_gcn_odefunc_t* f, const gode_lincomb_t* xin, const float* dZ,
-                                      float out_scale, const gode_lincomb_t* pre, float* ka, float* part, void* stream)
+namespace {
+
+int vjp_small(const gode_gcn_odefunc_t* f, const gode_lincomb_t* xin, const float* dZ, float out_scale,
+              const gode_lincomb_t* pre, float* ka, float* part, const gode_lincomb_t* cot_next, const float* k_next,
+              float* dZ_next, void* stream)
 {
     if (!f || !xin || !dZ || !ka || !part) return GODE_E_NULLPTR;
+    if (dZ_next) {
+        if (!cot_next || !k_next) return GODE_E_NULLPTR;
+        int rcn = check_lincomb(cot_next, true); if (rcn) return rcn;
+        if (dZ_next == dZ || dZ_next == ka) return GODE_E_SHAPE;          // dZ is gathered by other blocks
+        if (!lincomb_aligned16(cot_next) || ((((uintptr_t)k_next) | ((uintptr_t)dZ_next)) & 15)) return GODE_E_ALIGN;
+    } else cot_next = nullptr;
     if (!gode_gcn_small_supported(f->n, f->d, f->groups)) return GODE_E_UNSUPPORTED;
     if (!f->AT.rowptr || !f->AT.col || !f->W) return GODE_E_NULLPTR;
     int rc = check_lincomb(xin, true); if (rc) return rc;
@@ -557,13 +581,63 @@ extern "C" int gode_gcn_vjp_small_f32(const gode_gcn_odefunc_t* f, const gode_li
     const int cg = small_cg(d, f->groups);
     const dim3 grid((unsigned)gode_gcn_small_parts(f->n));
     const bool r4 = rows4(f->n);
+    VjpNext<true> vna; vna.cot = make_lincomb(cot_next); vna.k = k_next; vna.dZn = dZ_next;
+    const VjpNext<false> vn0;
 #define GODE_VJS(DV, CGV) if (r4) GODE_VJS_(DV, CGV, 16) else GODE_VJS_(DV, CGV, 64)
-#define GODE_VJS_(DV, CGV, GWV) hipLaunchKernelGGL((gcn_vjp_small_kernel<DV, CGV, GWV>), grid, dim3(256), 0, (hipStream_t)stream,           \
+#define GODE_VJS_(DV, CGV, GWV) if (dZ_next) GODE_VJS__(DV, CGV, GWV, true, vna) else GODE_VJS__(DV, CGV, GWV, false, vn0)
+#define GODE_VJS__(DV, CGV, GWV, NV, VNA) hipLaunchKernelGGL((gcn_vjp_small_kernel<DV, CGV, GWV, NV>), grid, dim3(256), 0, (hipStream_t)stream, \
                                              f->AT.rowptr, f->AT.col, f->AT.val, lx, (int)f->n, f->eps, f->gamma, f->beta, f->W, \
-                                             dZ, out_scale, lp, ka, part);
+                                             dZ, out_scale, lp, ka, part, VNA);
     GODE_SMALL_DISPATCH(GODE_VJS)
 #undef GODE_VJS
 #undef GODE_VJS_
+#undef GODE_VJS__
+    GODE_LAUNCH_CHECK();
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int gode_gcn_vjp_small_f32(const gode_gcn_odefunc_t* f, const gode_lincomb_t* xin, const float* dZ,
+                                      float out_scale, const gode_lincomb_t* pre, float* ka, float* part, void* stream)
+{
+    return vjp_small(f, xin, dZ, out_scale, pre, ka, part, nullptr, nullptr, nullptr, stream);
+}
+
+// the same launch, which also writes the next stage's masked cotangent dZ_next = (sum cot_next) * [k_next > 0]
+extern "C" int gode_gcn_vjp_small_next_f32(const gode_gcn_odefunc_t* f, const gode_lincomb_t* xin, const float* dZ,
+                                           float out_scale, const gode_lincomb_t* pre, float* ka, float* part,
+                                           const gode_lincomb_t* cot_next, const float* k_next, float* dZ_next, void* stream)
+{
+    if (!dZ_next) return GODE_E_NULLPTR;
+    return vjp_small(f, xin, dZ, out_scale, pre, ka, part, cot_next, k_next, dZ_next, stream);
+}
+
+// forward evaluation that also stores relu(z) into k (before the combine with pre / alpha)
+extern "C" int gode_gcn_feval_small_save_f32(const gode_gcn_odefunc_t* f, const gode_lincomb_t* xin, float t, float alpha,
+                                             const gode_lincomb_t* pre, float* out, float* k, void* stream)
+{
+    if (!f || !xin || !out || !k) return GODE_E_NULLPTR;
+    if (k == out) return GODE_E_SHAPE;
+    if (!gode_gcn_small_supported(f->n, f->d, f->groups)) return GODE_E_UNSUPPORTED;
+    if (!f->A.rowptr || !f->A.col || !f->W) return GODE_E_NULLPTR;
+    int rc = check_lincomb(xin, true); if (rc) return rc;
+    if (pre && pre->n > 0) { rc = check_lincomb(pre, true); if (rc) return rc; } else pre = nullptr;
+    if (!lincomb_aligned16(xin) || !lincomb_aligned16(pre) ||
+        ((((uintptr_t)out) | ((uintptr_t)k) | ((uintptr_t)f->gamma) | ((uintptr_t)f->beta) | ((uintptr_t)f->b)) & 15)) return GODE_E_ALIGN;
+    const LinComb lx = make_lincomb(xin), lp = make_lincomb(pre), lcot = make_lincomb(nullptr);
+    const int64_t d = f->d;
+    const int cg = small_cg(d, f->groups);
+    const dim3 grid((unsigned)feval_blocks(f->n));
+    const bool r4 = rows4(f->n);
+    NextArgs<2> ks; ks.k = k;
+#define GODE_FSV(DV, CGV) if (r4) GODE_FSV_(DV, CGV, 16) else GODE_FSV_(DV, CGV, 64)
+#define GODE_FSV_(DV, CGV, GWV) hipLaunchKernelGGL((gcn_feval_small_kernel<DV, CGV, GWV, 2>), grid, dim3(256), 0, (hipStream_t)stream, \
+                                             f->A.rowptr, f->A.col, f->A.val, lx, (int)f->n, f->eps, f->gamma, f->beta, f->W,    \
+                                             f->b, t, alpha, lp, lcot, nullptr, out, ks);
+    GODE_SMALL_DISPATCH(GODE_FSV)
+#undef GODE_FSV
+#undef GODE_FSV_
     GODE_LAUNCH_CHECK();
     return 0;
 }

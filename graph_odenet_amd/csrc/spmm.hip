@@ -28,6 +28,7 @@ struct Epilogue {
     float* colpart;  // with Y2 (vec4 kernels, a thread group per record): block b writes the column sums of the Y2 rows it stored
                      // to colpart[b][d]; the finishing launch continues at row `colpart_row0`
     int64_t colpart_row0;
+    float* K;        // nullable (gode_spmm_csr_save_f32): K = act(Z + bias), ld = d, before the combine with pre / alpha
 };
 
 template <int LPR>
@@ -39,6 +40,7 @@ __device__ __forceinline__ float4 epilogue_store4(const Epilogue& ep, float4 z, 
     }
     float4 y = z;
     if (ep.relu) { y.x = fmaxf(z.x, 0.f); y.y = fmaxf(z.y, 0.f); y.z = fmaxf(z.z, 0.f); y.w = fmaxf(z.w, 0.f); }
+    if (ep.K) *reinterpret_cast<float4*>(ep.K + (int64_t)row * d + lane * 4) = y;
     if (ep.pre.n > 0) {          // fused RK solution combine: rows of the pre-terms have ld = d
         const float4 p = lc_load4(ep.pre, (int64_t)row * d + lane * 4);
         y.x = fmaf(ep.alpha, y.x, p.x); y.y = fmaf(ep.alpha, y.y, p.y);
@@ -237,6 +239,7 @@ __device__ __forceinline__ void epilogue_store1(const Epilogue& ep, float z, int
                                                 float* Y, int64_t ldy) {
     if (ep.bias) z += ep.bias[c];
     float y = ep.relu ? fmaxf(z, 0.f) : z;
+    if (ep.K) ep.K[(int64_t)row * d + c] = y;
     if (ep.pre.n > 0) y = fmaf(ep.alpha, y, lc_load1(ep.pre, (int64_t)row * d + c));
     else y *= ep.alpha;
     Y[(int64_t)row * ldy + c] = y;
@@ -370,12 +373,14 @@ extern "C" int64_t gode_spmm_y2_colsum_rows(int64_t n_items, int64_t n_long, int
     return (n_items * lpr + 255) / 256 + (n_long * lpr + 255) / 256;
 }
 
-extern "C" int gode_spmm_csr_f32(const int32_t* rowptr, const int32_t* col, const float* val,
-                                 const int32_t* items, int64_t n_items,
-                                 const int32_t* long_rows, int64_t n_long, float* partial,
-                                 const float* X, int64_t ldx, float* Y, int64_t ldy,
-                                 int64_t n_rows, int64_t d,
-                                 const gode_spmm_epilogue_t* epi, void* stream)
+namespace {
+
+int spmm_csr_impl(const int32_t* rowptr, const int32_t* col, const float* val,
+                  const int32_t* items, int64_t n_items,
+                  const int32_t* long_rows, int64_t n_long, float* partial,
+                  const float* X, int64_t ldx, float* Y, int64_t ldy,
+                  int64_t n_rows, int64_t d,
+                  const gode_spmm_epilogue_t* epi, float* K, void* stream)
 {
     if (n_rows < 0 || d <= 0 || ldx < d || ldy < d) return GODE_E_SHAPE;
     if (n_rows == 0) return 0;
@@ -397,11 +402,13 @@ extern "C" int gode_spmm_csr_f32(const int32_t* rowptr, const int32_t* col, cons
     ep.bias = bias; ep.relu = epi ? epi->relu : 0; ep.alpha = epi ? epi->alpha : 1.f;
     ep.pre = make_lincomb(pre); ep.cot = make_lincomb(cot); ep.Y2 = Y2;
     ep.colpart = (epi && Y2) ? epi->Y2_colsum : nullptr; ep.colpart_row0 = 0;
+    ep.K = K;
     if (ep.colpart && ((((uintptr_t)ep.colpart) & 15) || gode_spmm_y2_colsum_rows(n_items, n_long, d) == 0)) return GODE_E_UNSUPPORTED;
 
     const bool al = !(((uintptr_t)X) & 15) && !(((uintptr_t)Y) & 15) && (ldx % 4 == 0) && (ldy % 4 == 0) &&
                     (!bias || !(((uintptr_t)bias) & 15)) && (!partial || !(((uintptr_t)partial) & 15)) &&
-                    (!Y2 || (!(((uintptr_t)Y2) & 15) && lincomb_aligned16(cot))) && lincomb_aligned16(pre);
+                    (!Y2 || (!(((uintptr_t)Y2) & 15) && lincomb_aligned16(cot))) && lincomb_aligned16(pre) &&
+                    !(((uintptr_t)K) & 15);
     const int4* it4 = reinterpret_cast<const int4*>(items);
     const int4* lr4 = reinterpret_cast<const int4*>(long_rows);
     if (al && d % 4 == 0) {
@@ -434,4 +441,32 @@ extern "C" int gode_spmm_csr_f32(const int32_t* rowptr, const int32_t* col, cons
         GODE_LAUNCH_CHECK();
     }
     return 0;
+}
+
+}  // namespace
+
+extern "C" int gode_spmm_csr_f32(const int32_t* rowptr, const int32_t* col, const float* val,
+                                 const int32_t* items, int64_t n_items,
+                                 const int32_t* long_rows, int64_t n_long, float* partial,
+                                 const float* X, int64_t ldx, float* Y, int64_t ldy,
+                                 int64_t n_rows, int64_t d,
+                                 const gode_spmm_epilogue_t* epi, void* stream)
+{
+    return spmm_csr_impl(rowptr, col, val, items, n_items, long_rows, n_long, partial, X, ldx, Y, ldy, n_rows, d, epi,
+                         nullptr, stream);
+}
+
+// the same product, which also stores the activated aggregate K = act(Z + bias) (ld = d) before the combine with the
+// pre-terms: the launch that folds the last RK stage into the solution leaves that stage's derivative for a backward sweep
+extern "C" int gode_spmm_csr_save_f32(const int32_t* rowptr, const int32_t* col, const float* val,
+                                      const int32_t* items, int64_t n_items,
+                                      const int32_t* long_rows, int64_t n_long, float* partial,
+                                      const float* X, int64_t ldx, float* Y, int64_t ldy,
+                                      int64_t n_rows, int64_t d,
+                                      const gode_spmm_epilogue_t* epi, float* K, void* stream)
+{
+    if (n_rows < 0 || d <= 0 || ldx < d || ldy < d) return GODE_E_SHAPE;
+    if (n_rows > 0 && !K) return GODE_E_NULLPTR;
+    return spmm_csr_impl(rowptr, col, val, items, n_items, long_rows, n_long, partial, X, ldx, Y, ldy, n_rows, d, epi,
+                         K, stream);
 }

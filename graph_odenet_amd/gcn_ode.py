@@ -106,6 +106,16 @@ class _Shared:
                 ws.y2_colsum = self._y2_colsum.data_ptr()
         return ws
 
+    def cot_colpart(self):
+        """Per-block column sums of the masked cotangent of a backprop sweep (csrc/backprop.hip); None when the width has
+        no 16-byte kernel."""
+        rows = _lib.load().gode_masked_cot_parts(self.n, self.d)
+        if rows <= 0:
+            return None
+        if getattr(self, "_cot_colpart", None) is None:
+            self._cot_colpart = torch.empty(rows, self.d, dtype=torch.float32, device=self.device)
+        return self._cot_colpart
+
     def small_part(self, groups):
         """Block partials of the fused launch-bound VJP (csrc/small.hip); None when the shape is outside that path."""
         lib = _lib.load()
@@ -276,6 +286,32 @@ class GcnOdeField(Field):
             comps[0].copy_(out)
         return 4 * n_steps
 
+    # ---- backprop through a fixed-grid solve (odeint._OdeintBackprop; csrc/ode_driver.hip) ----------------------
+    def rk4_forward_save(self, y0, y_end, save, t0, t1, n_steps, i0, i1):
+        """Steps i0 .. i1-1 of the n_steps-step rk4 solve from t0 to t1, bit for bit rk4_native's launches; save[r] =
+        [y_n, k_1, k_2, k_3, k_4] of step i0 + r (y0 is copied into save[0][0] unless it is that slice)."""
+        lib = _lib.load()
+        s, w = self.s, self.w
+        fs, ws = _func_struct(s), w.workspace_struct(False, s.groups)
+        _lib.check(lib.gode_gcn_ode_rk4_forward_save(ctypes.byref(fs), _lib.ptr(y0), _lib.ptr(y_end), _lib.ptr(save),
+                                                     ctypes.byref(ws), float(t0), float(t1), int(n_steps), int(i0), int(i1),
+                                                     _lib.stream_ptr()), "gode_gcn_ode_rk4_forward_save")
+
+    def rk4_backprop(self, save, a, theta, t0, t1, n_steps, i0, i1):
+        """Reverse sweep over the records of rk4_forward_save: `a` (dL/dy after step i1-1) is overwritten; returns the
+        tensor holding dL/dy before step i0 (`a` or a workspace buffer); theta (packed [W | b | gamma | beta | .]) is
+        incremented by the parameter gradients."""
+        lib = _lib.load()
+        s, w = self.s, self.w
+        ka = w.stage_buffers(True)[1]
+        fs, ws = _func_struct(s), w.workspace_struct(True, s.groups)
+        res = ctypes.c_void_p()
+        _lib.check(lib.gode_gcn_ode_rk4_backprop(ctypes.byref(fs), _lib.ptr(save), _lib.ptr(a), _lib.ptr(theta),
+                                                 ctypes.byref(res), ctypes.byref(ws), _lib.ptr(w.cot_colpart()),
+                                                 float(t0), float(t1), int(n_steps), int(i0), int(i1), _lib.stream_ptr()),
+                   "gode_gcn_ode_rk4_backprop")
+        return _by_ptr(res.value, [a] + ka)
+
     def eval_combine(self, t, terms, pre, coef, out):
         """Last RK stage: out[0] = (sum pre[0]) + coef * f(t, sum terms[0]) without materialising f."""
         s, w = self.s, self.w
@@ -338,6 +374,8 @@ class GcnOdePartField(_PartMixin, GcnOdeField):
     """The same field on a row-partitioned graph (partition.py): ops.spmm gathers the operand rows between the two
     launches of an f-eval, so the whole-solve C drivers are not offered and the solver takes the per-stage path."""
     big_components = (0,)
+    rk4_forward_save = None
+    rk4_backprop = None
 
     def __init__(self, spec, shared):
         GcnOdeField.__init__(self, spec, shared)

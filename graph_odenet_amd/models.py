@@ -28,6 +28,7 @@ from .gcn_ode import (GcnOdeAdjointField, GcnOdeField, GcnOdePartAdjointField, G
                       odefunc_apply, tuned_graph)
 from .graph import as_graph
 from .layers import FixedGraphConvolution, GraphConvolution
+from .odeint import odeint as odeint_plain
 from .odeint import odeint_adjoint as odeint
 
 
@@ -185,9 +186,12 @@ class ODEfunc2(nn.Module):
 class ODEBlock(nn.Module):
     """y(1) of y' = odefunc(t, y), y(0) = x (reference: GCN/models.py:181-201)."""
 
-    def __init__(self, odefunc, tol=1e-5, method=None, step_size=None, node_order=None):
+    def __init__(self, odefunc, tol=1e-5, method=None, step_size=None, node_order=None, adjoint=True):
         super(ODEBlock, self).__init__()
         self.odefunc = odefunc
+        # True (the reference): odeint_adjoint.  False: odeint, differentiable by backprop through the solve under rk4
+        # (odeint._OdeintBackprop); under dopri5 that solve is forward-only
+        self.adjoint = bool(adjoint)
         if node_order is not None:            # extension: "auto" (default rule) | "given" | "degree" (gcn_ode.tuned_graph)
             from .gcn_ode import NODE_ORDERS
             if node_order not in NODE_ORDERS:
@@ -202,6 +206,9 @@ class ODEBlock(nn.Module):
         self.integration_time = self.integration_time.type_as(x)
         self.odefunc.set_adj(*graph)
         options = None if self.step_size is None else {"step_size": self.step_size}
+        if not self.adjoint:
+            return odeint_plain(self.odefunc, x, self.integration_time, rtol=self.tol, atol=self.tol,
+                                method=self.method, options=options)[1]
         # the reference keeps `out[1]` of the stack over integration_time (GCN/models.py:200); asking for that state alone
         # saves three passes over it here and in the backward pass (odeint._OdeintAdjoint, last_only)
         if self.integration_time.numel() == 2:

@@ -8,6 +8,11 @@ GCN/models.py:5,192, GAT/models.py:5,192 in the reference):
 `gode_fields(y0)` (our ODEfunc does) the whole f-eval and its VJP run as fused HIP kernels
 and stage inputs are never materialised; any other module runs through autograd with the
 RK arithmetic still in the HIP kernels.
+
+`odeint` is differentiable under method="rk4" as torchdiffeq's is (backprop through the solver's operations, not the
+adjoint): with grad mode on and y0 or a parameter of func requiring grad it returns a tensor with a grad_fn whose
+gradient is the exact derivative of the computed discrete solution w.r.t. y0 and func's parameters (t gets None).
+Adaptive dopri5 under `odeint` stays forward-only (a follow-up), and so do row-partitioned fields.
 """
 import weakref
 
@@ -28,6 +33,10 @@ GRAPH_CAPTURE_MAX_ELEMS = 1 << 21
 # evaluations exactly as with torchdiffeq (asserted against the oracle's own count in tests/test_gpu_gcn.py).  Off:
 # nfe counts the evaluations actually launched (64).  Adaptive dopri5 executes and counts the evaluation either way.
 NFE_COUNTS_SKIPPED_DLDT_EVAL = True
+# Backprop through a fused rk4 solve keeps y_n and k_1..k_4 of every step (5 n d floats per step) when they fit in this many
+# bytes (2^20 x 128 state, 16 steps: 40 GiB); above it only y_n is kept and each step is re-run into a one-step record just
+# before its reverse sweep (the same launches: gradients bit for bit those of the save-everything mode).
+BACKPROP_SAVE_MAX_BYTES = 48 << 30
 
 
 def _materialise(terms):
@@ -262,12 +271,152 @@ def _bump_nfe(func, n):
         func.nfe += n
 
 
+def _rk4_torch(func, y, t0, t1, n):
+    """n 3/8-rule steps from t0 to t1 as differentiable torch ops through func (torchdiffeq's rk4 step)."""
+    h = (t1 - t0) / n
+    tt = lambda v: torch.tensor(v, dtype=y.dtype, device=y.device)      # noqa: E731
+    for i in range(n):
+        t = t0 + i * h
+        k1 = func(tt(t), y)
+        k2 = func(tt(t + h / 3.0), y + h * k1 / 3.0)
+        k3 = func(tt(t + 2.0 * h / 3.0), y + h * (k2 - k1 / 3.0))
+        k4 = func(tt(t + h), y + h * (k1 - k2 + k3))
+        y = y + (k1 + 3.0 * (k2 + k3) + k4) * (h * 0.125)
+    return y
+
+
+class _OdeintBackprop(torch.autograd.Function):
+    """odeint under rk4 with gradients: the forward is odeint's own (bit for bit), the backward the exact derivative of
+    the discrete solution.  Fused fields offering rk4_forward_save / rk4_backprop (GcnOdeField) keep the stage
+    derivatives of every step and run the reverse sweep as one C call per interval (csrc/ode_driver.hip); any other field
+    re-runs each interval as torch ops through func under autograd from its saved start state (what torchdiffeq does)."""
+
+    @staticmethod
+    def forward(ctx, func, fields, tl, rtol, atol, options, y0, *params):
+        fwd = fields[0]
+        order, inverse = _rows(fwd)
+        step_size = (options or {}).get("step_size")
+        steps = [uniform_grid(tl[i - 1], tl[i], step_size) for i in range(1, len(tl))]
+        fused = getattr(fwd, "rk4_forward_save", None) is not None and NATIVE_RK4
+        y0c = y0.detach().contiguous()
+        outs = [y0c.clone()]
+        ctx.saved = None
+        with torch.no_grad():
+            if fused:
+                prep = getattr(fwd, "prepare", None)
+                if prep is not None:
+                    prep()
+                shape = tuple(y0c.shape)
+                save_all = 5 * sum(steps) * y0c.numel() * 4 <= BACKPROP_SAVE_MAX_BYTES
+                cur = y0c.clone() if order is None else y0c.index_select(0, order)
+                saved = []
+                for i in range(1, len(tl)):
+                    n = steps[i - 1]
+                    y_end = torch.empty_like(cur)
+                    if save_all:
+                        rec = torch.empty((n, 5) + shape, dtype=y0c.dtype, device=y0c.device)
+                        rec[0, 0].copy_(cur)
+                        fwd.rk4_forward_save(rec[0, 0], y_end, rec, tl[i - 1], tl[i], n, 0, n)
+                        saved.append(rec)
+                    else:
+                        ys = torch.empty((n,) + shape, dtype=y0c.dtype, device=y0c.device)
+                        ys[0].copy_(cur)
+                        rec = torch.empty((1, 5) + shape, dtype=y0c.dtype, device=y0c.device)
+                        for j in range(n):
+                            fwd.rk4_forward_save(ys[j], ys[j + 1] if j + 1 < n else y_end, rec, tl[i - 1], tl[i], n, j, j + 1)
+                        saved.append(ys)
+                    cur = y_end
+                    outs.append(cur.clone() if order is None else cur.index_select(0, inverse))
+                ctx.saved, ctx.save_all = saved, save_all
+                _bump_nfe(func, 4 * sum(steps))
+            else:
+                stats = Dopri5Stats()
+                ys = [y0c.clone() if order is None else y0c.index_select(0, order)]
+                for i in range(1, len(tl)):
+                    _integrate(fwd, ys, tl[i - 1], tl[i], rtol, atol, "rk4", options, stats)
+                    outs.append(ys[0].clone() if order is None else ys[0].index_select(0, inverse))
+                _bump_nfe(func, stats.nfe if getattr(fwd, "fused", False) else 0)
+        ans = torch.stack(outs)
+        ctx.func, ctx.fields, ctx.tl, ctx.steps, ctx.fused = func, fields, tl, steps, fused
+        ctx.outs = None if fused else outs
+        ctx.n_params = len(params)
+        return ans
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        grad_out = grad_out.contiguous()
+        tl, steps = ctx.tl, ctx.steps
+        params = ctx.fields[2] if ctx.fused else tuple(p for p in ctx.func.parameters() if p.requires_grad) \
+            if isinstance(ctx.func, torch.nn.Module) else ()
+        if ctx.fused:
+            fwd = ctx.fields[0]
+            order, inverse = _rows(fwd)
+            gather = (lambda g: g.clone()) if order is None else (lambda g: g.index_select(0, order))
+            a = gather(grad_out[-1])
+            s = fwd.s
+            d = s.d
+            nW = (d + 1) * d
+            theta = torch.zeros((nW + 3 * d + 1,), dtype=torch.float32, device=a.device)
+            scratch = rec1 = None
+            with torch.no_grad():
+                for i in range(len(tl) - 1, 0, -1):
+                    n, sv = steps[i - 1], ctx.saved[i - 1]
+                    if ctx.save_all:
+                        res = fwd.rk4_backprop(sv, a, theta, tl[i - 1], tl[i], n, 0, n)
+                        if res is not a:
+                            a.copy_(res)
+                    else:
+                        if rec1 is None:
+                            rec1 = torch.empty((1, 5) + tuple(a.shape), dtype=a.dtype, device=a.device)
+                            scratch = torch.empty_like(a)
+                        for j in range(n - 1, -1, -1):          # re-run the step into a one-step record, then sweep it
+                            fwd.rk4_forward_save(sv[j], scratch, rec1, tl[i - 1], tl[i], n, j, j + 1)
+                            res = fwd.rk4_backprop(rec1, a, theta, tl[i - 1], tl[i], n, j, j + 1)
+                            if res is not a:
+                                a.copy_(res)
+                    if i > 1:
+                        a.add_(gather(grad_out[i - 1]))
+                gy0 = (a if order is None else a.index_select(0, inverse)).add_(grad_out[0])
+            comps = [None, None, None, theta[:nW].view(d + 1, d), theta[nW:nW + d], theta[nW + d:nW + 2 * d],
+                     theta[nW + 2 * d:nW + 3 * d]]
+            pg = ctx.fields[1]().param_grads(comps)
+        else:
+            func = ctx.func
+            nfe0 = getattr(func, "nfe", None)
+            a = grad_out[-1]
+            pg = [None] * len(params)
+            for i in range(len(tl) - 1, 0, -1):
+                with torch.enable_grad():
+                    y = ctx.outs[i - 1].detach().requires_grad_(True)
+                    yt = _rk4_torch(func, y, tl[i - 1], tl[i], steps[i - 1])
+                    g = torch.autograd.grad(yt, (y,) + tuple(params), a, allow_unused=True)
+                a = g[0] + grad_out[i - 1] if g[0] is not None else grad_out[i - 1].clone()
+                for q, gq in enumerate(g[1:]):
+                    if gq is not None:
+                        pg[q] = gq if pg[q] is None else pg[q] + gq
+            gy0 = a
+            if nfe0 is not None:
+                func.nfe = nfe0                   # evaluations re-run by the backward pass are not counted (torchdiffeq's
+                                                  # odeint counts none in its backward)
+        return (None, None, None, None, None, None, gy0, *pg)
+
+
 def odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None):
-    """Forward solve without gradient support through the solver (use odeint_adjoint to train)."""
+    """torchdiffeq's odeint.  Under method="rk4" with grad mode on and y0 or a parameter of func requiring grad the
+    result is differentiable (backprop through the solve: _OdeintBackprop; t gets no gradient); otherwise - and always
+    under dopri5 or on row-partitioned fields - a forward solve without gradient support (use odeint_adjoint to train)."""
     _check_state(y0)
     tl = _times(t)
     method = _method(method)
-    fwd, _, _ = _fields(func, y0)
+    fields = _fields(func, y0)
+    fwd = fields[0]
+    if method == "rk4" and torch.is_grad_enabled() and getattr(fwd, "big_components", None) is None:
+        params = tuple(p for p in func.parameters() if p.requires_grad) if isinstance(func, torch.nn.Module) else ()
+        if y0.requires_grad or params:
+            same = len(fields[2]) == len(params) and all(p is q for p, q in zip(fields[2], params))
+            if getattr(fwd, "rk4_forward_save", None) is not None and not same:
+                fields = (AutogradField(func, y0), None, params)      # the fused field does not cover these parameters
+            return _OdeintBackprop.apply(func, fields, tl, float(rtol), float(atol), options, y0, *params)
     stats = Dopri5Stats()
     order, inverse = _rows(fwd)
     ys = [y0.detach().contiguous().clone() if order is None else y0.detach().index_select(0, order)]

@@ -64,6 +64,9 @@ def build_parser():
     p.add_argument('--heads', type=int, default=1,
                    help="gat variant: H reference attention heads side by side in every layer whose width H divides "
                         "(gat_heads.py; --hidden must be a multiple of H)")
+    p.add_argument('--adjoint', type=int, choices=[0, 1], default=1,
+                   help="1: every ODE block trains through odeint_adjoint (the reference); 0: through odeint, "
+                        "differentiated by backprop through the rk4 solve (forward-only under dopri5)")
     p.add_argument('--variant', choices=sorted(VARIANTS), default="gcn",
                    help="gcn: models over a normalised adjacency (GCN/train_res.py); gat: edge attention over "
                         "(src, tgt, Mtgt) (GAT/train_res.py)")
@@ -89,6 +92,9 @@ class Trainer:
             from . import gat_heads
             table = _model_dict(gat_heads.zoo(a.heads))
         model = table[a.model](**kw).to(self.device)
+        for m in model.modules():
+            if isinstance(m, models.ODEBlock):
+                m.adjoint = bool(getattr(a, "adjoint", 1))
         opt = Adam(model.parameters(), lr=a.lr, weight_decay=a.weight_decay)       # optim.py: torch.optim.Adam's update, one launch
         return model, opt
 

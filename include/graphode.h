@@ -116,6 +116,23 @@ int gode_spmm_csr_f32(const int32_t* rowptr, const int32_t* col, const float* va
                       int64_t n_rows, int64_t d,
                       const gode_spmm_epilogue_t* epi /* host, nullable */,
                       void* stream);
+/* the same product, which also stores K = act(Z + bias) (n_rows x d, ld = d) before the combine with the pre-terms: the
+ * launch that folds the last RK stage into the solution keeps that stage's derivative for a backward sweep */
+int gode_spmm_csr_save_f32(const int32_t* rowptr, const int32_t* col, const float* val,
+                           const int32_t* items, int64_t n_items,
+                           const int32_t* long_rows, int64_t n_long, float* partial,
+                           const float* X, int64_t ldx, float* Y, int64_t ldy,
+                           int64_t n_rows, int64_t d,
+                           const gode_spmm_epilogue_t* epi /* host, nullable */, float* K,
+                           void* stream);
+
+/* masked cotangent of a relu layer: dZ = (sum_j cot.coef[j] * cot.ptr[j]) * [k > 0], n_rows x d (one pass, 16-byte
+ * accesses where d = 4 * 2^j <= 256 and every operand is 16-byte aligned).  colpart (nullable; 16-byte kernel only, else
+ * GODE_E_UNSUPPORTED): gode_masked_cot_parts(n_rows, d) rows of d floats, the column sums of the rows each block stored -
+ * their sum (gode_colsum_f32) is colsum(dZ).  dZ must not be a term of cot. */
+int64_t gode_masked_cot_parts(int64_t n_rows, int64_t d);
+int gode_masked_cot_f32(const gode_lincomb_t* cot /* host */, const float* k, float* dZ, int64_t n_rows, int64_t d,
+                        float* colpart /* nullable */, void* stream);
 
 /* ---- Runge-Kutta elementwise steps -------------------------------------- */
 /* out[i] = sum_j lc.coef[j]*lc.ptr[j][i],  i < n.  out may alias any ptr[j]. */
@@ -540,6 +557,16 @@ int gode_gcn_feval_small_next_f32(const gode_gcn_odefunc_t* f, const gode_lincom
 int gode_gcn_vjp_small_f32(const gode_gcn_odefunc_t* f, const gode_lincomb_t* xin /* host */, const float* dZ,
                            float out_scale, const gode_lincomb_t* pre /* host, nullable */, float* ka, float* part,
                            void* stream);
+/* the VJP launch which also writes the masked cotangent of the next stage of a backward sweep,
+ * dZ_next = (sum cot_next) * [k_next > 0] (a term of cot_next that names `ka` is this launch's result).  dZ_next must
+ * not be dZ or ka. */
+int gode_gcn_vjp_small_next_f32(const gode_gcn_odefunc_t* f, const gode_lincomb_t* xin /* host */, const float* dZ,
+                                float out_scale, const gode_lincomb_t* pre /* host, nullable */, float* ka, float* part,
+                                const gode_lincomb_t* cot_next /* host */, const float* k_next, float* dZ_next,
+                                void* stream);
+/* the forward evaluation which also stores relu(z) in k (before the combine with pre / alpha); k must not be out */
+int gode_gcn_feval_small_save_f32(const gode_gcn_odefunc_t* f, const gode_lincomb_t* xin /* host */, float t, float alpha,
+                                  const gode_lincomb_t* pre /* host, nullable */, float* out, float* k, void* stream);
 int gode_gcn_small_finish_f32(const gode_gcn_odefunc_t* f, const float* part, float* ktheta, float t, void* stream);
 /* n_stages <= 8 stages in one launch: stage s reads part + s * parts * part_len, writes ktheta[s] (time ts[s]); each result is
  * bit for bit gode_gcn_small_finish_f32's (the dopri5 step driver closes its six stages at the end of the step) */
@@ -557,6 +584,23 @@ int gode_gcn_ode_rk4_forward(const gode_gcn_odefunc_t* f, float* y, float** resu
 int gode_gcn_ode_rk4_adjoint(const gode_gcn_odefunc_t* f, float* y, float* a, float* theta,
                              float** y_result, float** a_result,
                              const gode_rk4_workspace_t* ws, float t0, float t1, int32_t n_steps, void* stream);
+
+/* Backprop through a fixed-grid rk4 solve (the discrete gradient of the computed solution, as autograd through the
+ * solver's operations gives it).  Steps step_begin .. step_end - 1 of the n_steps-step grid from t0 to t1; `save` holds
+ * one record per step, [ y_n | k_1 | k_2 | k_3 | k_4 ] (5 n x d floats each).
+ * forward_save: the launch sequence of gode_gcn_ode_rk4_forward (bit for bit the same values), filling the records; y0
+ *   is copied into record 0 unless it is record 0 itself; y_end receives the state after step step_end - 1.
+ * backprop: the reverse sweep over the records.  a = dL/dy after step step_end - 1 on entry (overwritten: work buffer);
+ *   *a_result (a or ws->ka[0]) = dL/dy before step step_begin; theta (packed as for the adjoint, a_t slot unspecified)
+ *   is INCREMENTED by dL/d[W | b | gamma | beta].  ws as for the adjoint driver (ka, ktheta, dZ, dS, partial buffers;
+ *   small_part enables the one-launch-per-stage path of launch-bound graphs); cot_colpart (nullable):
+ *   gode_masked_cot_parts(n, d) * d floats for the bias gradient of large graphs. */
+int gode_gcn_ode_rk4_forward_save(const gode_gcn_odefunc_t* f, const float* y0, float* y_end, float* save,
+                                  const gode_rk4_workspace_t* ws, float t0, float t1, int32_t n_steps,
+                                  int32_t step_begin, int32_t step_end, void* stream);
+int gode_gcn_ode_rk4_backprop(const gode_gcn_odefunc_t* f, const float* save, float* a, float* theta, float** a_result,
+                              const gode_rk4_workspace_t* ws, float* cot_colpart /* nullable */, float t0, float t1,
+                              int32_t n_steps, int32_t step_begin, int32_t step_end, void* stream);
 
 /* One Dormand-Prince 5(4) step of the same ODE function per call (adaptive solves on launch-bound sizes; the controller
  * - step-size selection, accept / reject, interpolation - stays with the caller, as in torchdiffeq).
