@@ -4,7 +4,8 @@
 // The adaptive controller (step-size choice, accept / reject, interpolation) stays with the caller, as for the GCN
 // function in ode_driver.hip; this file only sequences the launches of six stage evaluations, the solution combine
 // and the error-ratio sums, so that an adaptive step on a citation-size graph is one call instead of ~200.
-// The launch sequence of one evaluation is graph_odenet_amd/gat_ode.py (GatOdeField / GatOdeAdjointField).
+// The launch sequence of one evaluation is graph_odenet_amd/gat_ode.py (GatOdeField / GatOdeAdjointField), which
+// branches on the head count where this file does.
 #include "common.h"
 #include "options.h"
 
@@ -63,7 +64,7 @@ inline bool small_dense(const gode_gat_odefunc_t* f) {
     return gode_opt_small_fused() && gode_gat_small_supported(f->n, f->d, f->groups, n_heads(f));
 }
 
-// the same condition as gat_heads.GatHeadsField.raw_logits (the Python and the C driver issue the same launches)
+// the same condition as gat_ode.GatOdeField.raw_logits (the Python and the C driver issue the same launches)
 inline bool raw_logits(const gode_gat_odefunc_t* f) {
     return f->n * n_heads(f) <= 65536 && f->n_edges > 8192 && small_dense(f);
 }
@@ -159,7 +160,7 @@ int eval_adjoint(const gode_gat_odefunc_t* f, const gode_gat_workspace_t* w, god
     const float* Wj[3] = {f->Wsrc, f->Wtgt, f->Wlog};
     const float* dPj[3] = {w->dPs, w->dPt, w->dA2};
     const int64_t dout[3] = {d, d, 2 * H};
-    // launch-bound graphs: ONE reduction launch closes the stage (the same launch sequence as gat_ode.py / gat_heads.py)
+    // launch-bound graphs: ONE reduction launch closes the stage (the same launch sequence as gat_ode.py)
     const bool merged = n <= kMergedFinishMaxRows && affine && w->colsum_scratch2 != nullptr;
     int64_t n_a = 0, n_b = 0;
     if (merged) {

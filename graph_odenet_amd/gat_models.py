@@ -40,8 +40,15 @@ class ODEfunc(nn.Module):
 
     def gode_fields(self, y0):
         """Hook for graph_odenet_amd.odeint: fused forward / adjoint kernel sequences (gat_ode.py)."""
+        from .gat_layers import edge_graph
         from .gat_ode import gat_fields
-        return gat_fields(self, y0)
+        layer, norm = self.gc1, self.norm1
+        if not torch.is_tensor(layer.src) or layer.src.dim() != 1:
+            return None
+        names = {id(norm.weight): "gamma", id(norm.bias): "beta", id(layer.f.weight): "Wf", id(layer.f.bias): "bf",
+                 id(layer.w.weight): "ww", id(layer.w.bias): "bw"}
+        eg = edge_graph(layer.src, layer.tgt, layer.Mtgt)
+        return gat_fields(self, layer, eg, eg.n, names, y0)
 
 
 class ODEfunc2(nn.Module):

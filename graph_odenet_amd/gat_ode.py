@@ -15,6 +15,10 @@ MFMA kernels and only the two logit columns take the generic path:
             gode_gat_scatter_f32 (all four incidence sums in one launch), 3 x gode_gn_time_gemm_bwd_f32 (accumulating
             into k_a), 3 x gode_wgrad_f32 + reductions, gode_time_row_fixup_f32, column sums for the biases.
 
+H heads (gat_heads.py) run the same sequence on the H-fold graph, with d = H * o: Wlog has 2H columns, bw H entries, the
+message biases bf are folded into Pt and the logits are shifted by their head's maximum (gode_gat_logits_heads_f32),
+so that the aggregation runs with zero bias and amax = 0.  The branches on H are those of csrc/gat_driver.hip.
+
 The adjoint integrates [y, a, a_t, theta] with theta = [Wsrc | Wtgt | Wlog | bf | bw | gamma | beta] packed in ONE
 buffer (one RK combine launch for all parameters); the gradient is converted back to the parameters' layout once,
 at the end of the solve.
@@ -22,135 +26,163 @@ at the end of the solve.
 import ctypes
 
 import torch
+import torch.nn.functional as F
 
 from . import _lib, ops
-from .gat_layers import edge_graph
 from .solver import Field
 
 
 # launch-bound graphs: the reduction launches that close an adjoint stage run as one (ops.reduce_segments_); larger graphs
 # keep the separate launches (the weight-gradient reduction has a 16-byte form that matters there)
 MERGED_FINISH_MAX_ROWS = 1 << 16
-
-
-def _repack(spec, heads):
-    """Keep spec.Wpacked (csrc/gat_small.hip: gode_gat_small_pack_f32) in step with the weights.  Worth a launch per solve
-    from d = 32 on (at d = 16 the blocks are 2.4 KB and the kernels lay them out themselves)."""
-    if spec.d < 32 or not spec.Wsrc.is_cuda:
-        return
-    lib = _lib.load()
-    # spec.n is the BASE node count (what _HeadsWork and the fields' small() test): with heads spec.eg is the H-fold graph
-    if not lib.gode_gat_small_supported(spec.n, spec.d, int(spec.groups), heads):
-        return
-    spec.Wpacked = ops.gat_small_pack(spec.Wsrc, spec.Wtgt, spec.Wlog, heads, out=spec.Wpacked)
+# H heads on at least this many nodes: the 2H logit columns ride the square MFMA kernels as a zero-padded (d+1) x d block
+# (0.4-0.5 ms per product at 2^20 x 128 against 2.2 / 5.5 / 3.8 ms for the generic kernels on a (d+1) x 16 block);
+# smaller graphs are launch-bound and keep the compact product
+PAD_LOGITS_MIN_ROWS = 4096
 
 
 class GatOdeSpec:
-    def __init__(self, eg, layer, norm):
-        self.eg, self.layer, self.norm = eg, layer, norm
-        self.d = layer.out_features
-        self.i = layer.in_features                    # d + 1 (time column first)
-        if self.i != self.d + 1:
+    """Packed description of relu(layer([t | norm(x)])) on n nodes: theta = [Wsrc | Wtgt | Wlog | bf | bw | gamma | beta]
+    with Wsrc, Wtgt (d+1) x d (head h in columns h*o..), Wlog (d+1) x 2H, bf d, bw H.  eg is the graph the kernels see
+    (the H-fold graph with H > 1 heads); layer is the reference's layer, or a MultiHeadGraphConvolution."""
+
+    def __init__(self, eg, n, layer, norm):
+        self.eg, self.n, self.layer, self.norm = eg, n, layer, norm
+        self.heads = H = getattr(layer, "n_heads", 1)
+        self.d, self.i = d, i = layer.out_features, layer.in_features
+        if i != d + 1:
             raise ValueError("GatOdeSpec: the ODE layer maps d+1 -> d features")
-        self.groups, self.eps_gn = int(norm.num_groups), float(norm.eps)
-        self.eps = float(layer.eps)
-        dev = layer.f.weight.device
-        self.Wsrc = torch.empty(self.i, self.d, dtype=torch.float32, device=dev)
-        self.Wtgt = torch.empty(self.i, self.d, dtype=torch.float32, device=dev)
-        self.Wlog = torch.empty(self.i, 2, dtype=torch.float32, device=dev)
+        self.o = d // H
+        self.groups, self.eps_gn, self.eps = int(norm.num_groups), float(norm.eps), float(layer.eps)
+        f = dict(dtype=torch.float32, device=norm.weight.device)
+        self.Wsrc, self.Wtgt, self.Wlog = torch.empty(i, d, **f), torch.empty(i, d, **f), torch.empty(i, 2 * H, **f)
+        self.pad_logits = n >= PAD_LOGITS_MIN_ROWS and d in (16, 32, 64, 128) and 4 < 2 * H <= d
+        self.Wlog_pad = torch.zeros(i, d, **f) if self.pad_logits else None
         self.Wpacked = None                           # LDS images of the three blocks for the one-launch kernels (d >= 32)
-        self.n = eg.n
-        self.refresh()
-        self.bf, self.bw = layer.f.bias.detach(), layer.w.bias.detach()
+        if H == 1:
+            self.bf, self.bw = layer.f.bias.detach(), layer.w.bias.detach()
+        else:
+            self.bf, self.bw = torch.empty(d, **f), torch.empty(H, **f)
         self.gamma, self.beta = norm.weight.detach(), norm.bias.detach()
-        self.n = eg.n
-        i, o, d = self.i, self.d, self.d
+        self.refresh()
         # offsets inside the packed parameter-gradient buffer
-        self.off = {}
-        p = 0
-        for name, ln in (("Wsrc", i * o), ("Wtgt", i * o), ("Wlog", i * 2), ("bf", o), ("bw", 1), ("gamma", d), ("beta", d)):
+        self.off, p = {}, 0
+        for name, ln in (("Wsrc", i * d), ("Wtgt", i * d), ("Wlog", i * 2 * H), ("bf", d), ("bw", H), ("gamma", d), ("beta", d)):
             self.off[name] = (p, p + ln)
             p += ln
         self.n_theta = p
 
     def refresh(self):
-        """Re-pack the two Linear weights by role, in place (at the start of every solve: the parameters move between
-        solves, the buffers - and a HIP graph captured over them - do not)."""
-        Wf, ww = self.layer.f.weight.detach(), self.layer.w.weight.detach()
-        i = self.i
-        self.Wsrc.copy_(Wf[:, :i].t())
-        self.Wtgt.copy_(Wf[:, i:].t())
-        self.Wlog[:, 0].copy_(ww[0, :i])
-        self.Wlog[:, 1].copy_(ww[0, i:])
-        _repack(self, 1)
-
+        """Re-pack the weights by role, in place (at the start of every solve: the parameters move between solves, the
+        buffers - and a HIP graph captured over them - do not)."""
+        if self.heads == 1:
+            Wf, ww = self.layer.f.weight.detach(), self.layer.w.weight.detach()
+            i = self.i
+            self.Wsrc.copy_(Wf[:, :i].t())
+            self.Wtgt.copy_(Wf[:, i:].t())
+            self.Wlog[:, 0].copy_(ww[0, :i])
+            self.Wlog[:, 1].copy_(ww[0, i:])
+        else:
+            with torch.no_grad():
+                Wsrc, Wtgt, Wlog, bf, ba = self.layer.packed()
+                self.Wsrc.copy_(Wsrc); self.Wtgt.copy_(Wtgt); self.Wlog.copy_(Wlog); self.bf.copy_(bf); self.bw.copy_(ba[1::2])
+                if self.pad_logits:
+                    self.Wlog_pad[:, :2 * self.heads].copy_(Wlog)
+        # Wpacked (csrc/gat_small.hip: gode_gat_small_pack_f32) follows the weights.  Worth a launch per solve from d = 32
+        # on (at d = 16 the blocks are 2.4 KB and the kernels lay them out themselves).
+        if not self.pad_logits and self.d >= 32 and self.Wsrc.is_cuda and \
+                _lib.load().gode_gat_small_supported(self.n, self.d, self.groups, self.heads):
+            self.Wpacked = ops.gat_small_pack(self.Wsrc, self.Wtgt, self.Wlog, self.heads, out=self.Wpacked)
 
     def views(self, theta):
-        o, i = self.d, self.i
         v = {k: theta[a:b] for k, (a, b) in self.off.items()}
-        v["Wsrc"], v["Wtgt"], v["Wlog"] = v["Wsrc"].view(i, o), v["Wtgt"].view(i, o), v["Wlog"].view(i, 2)
+        v["Wsrc"], v["Wtgt"] = v["Wsrc"].view(self.i, self.d), v["Wtgt"].view(self.i, self.d)
+        v["Wlog"] = v["Wlog"].view(self.i, 2 * self.heads)
         return v
 
 
 class _Work:
-    """Buffers of one (graph, d): allocated once, so that neither the eager path nor a captured graph allocates."""
+    """Buffers of one (graph, d, H): allocated once, so that neither the eager path nor a captured graph allocates."""
 
     def __init__(self, spec, device):
-        n, o, E = spec.n, spec.d, spec.eg.E
+        n, d, o, H, E = spec.n, spec.d, spec.o, spec.heads, spec.eg.E
+        nv = n * H
         lib = _lib.load()
         f = dict(dtype=torch.float32, device=device)
-        self.X = torch.empty(n, o, **f)
-        self.Ps, self.Pt, self.A2 = torch.empty(n, o, **f), torch.empty(n, o, **f), torch.empty(n, 2, **f)
-        self.dPs, self.dPt, self.dA2 = torch.empty(n, o, **f), torch.empty(n, o, **f), torch.empty(n, 2, **f)
-        self.a, self.amax = torch.empty(max(E, 1), **f)[:E], torch.empty(1, **f)
-        self.wgt, self.den = torch.zeros(max(E, 1), **f)[:E], torch.empty(n, **f)
-        self.dz, self.da = torch.zeros(max(E, 1), o, **f)[:E], torch.zeros(max(E, 1), **f)[:E]
-        self.proj = ops.gat_proj(self.Ps, self.Pt, self.A2)
-        self.np_b = lib.gode_gemm_bwd_parts(n)
-        self.gp, self.bp = torch.empty(3 * self.np_b, o, **f), torch.empty(3 * self.np_b, o, **f)
-        npw = lib.gode_wgrad_parts(n)
-        self.wp = [torch.empty(npw, spec.i * o, **f), torch.empty(npw, spec.i * o, **f), torch.empty(npw, spec.i * 2, **f)]
-        # extras of the C-level dopri5 step (csrc/gat_driver.hip)
-        self.pair = torch.empty(2, **f)
         u8 = dict(dtype=torch.uint8, device=device)
-        self.logits_scratch = torch.empty(max(lib.gode_gat_logits_scratch_bytes(E), 16), **u8)
-        self.colsum_scratch = torch.empty(max(lib.gode_colsum_scratch_bytes(n, o), 16), **u8)
-        self.colsum_scratch2 = torch.empty(max(lib.gode_colsum_scratch_bytes(n, 2), 16), **u8)
+        self.X = torch.empty(n, d, **f)
+        self.Ps, self.Pt, self.A2 = torch.empty(n, d, **f), torch.empty(n, d, **f), torch.empty(n, 2 * H, **f)
+        self.dPs, self.dPt, self.dA2 = torch.empty(n, d, **f), torch.empty(n, d, **f), torch.empty(n, 2 * H, **f)
+        self.a = torch.empty(max(E, 1), **f)[:E]
+        self.wgt, self.den = torch.zeros(max(E, 1), **f)[:E], torch.empty(nv, **f)
+        self.dz, self.da = torch.zeros(max(E, 1), o, **f)[:E], torch.zeros(max(E, 1), **f)[:E]
+        # with H heads the n x (H*o) projections ARE the (n*H) x o projections of the virtual nodes
+        self.proj = ops.gat_proj(self.Ps.view(nv, o), self.Pt.view(nv, o), self.A2.view(nv, 2))
+        self.np_b = lib.gode_gemm_bwd_parts(n)
+        self.gp, self.bp = torch.empty(3 * self.np_b, d, **f), torch.empty(3 * self.np_b, d, **f)
+        npw = lib.gode_wgrad_parts(n)
+        nl = spec.i * (d if spec.pad_logits else 2 * H)
+        self.wp = [torch.empty(npw, spec.i * d, **f), torch.empty(npw, spec.i * d, **f), torch.empty(npw, nl, **f)]
+        if H == 1:
+            self.amax = torch.empty(1, **f)
+            self.logits_scratch = torch.empty(max(lib.gode_gat_logits_scratch_bytes(E), 16), **u8)
+        else:
+            # zero message bias and maximum of the edge kernels (the biases ride Pt and the logits kernel)
+            self.zero, self.bf0, self.zeros = torch.zeros(1, **f), torch.zeros(o, **f), torch.zeros(max(o, 1), **f)
+            self.heads_scratch = torch.empty(max(lib.gode_gat_heads_scratch_bytes(E, H), 16), **u8)
+            self.ba_grad = torch.empty(2 * H, **f)
+        if spec.pad_logits:
+            self.A2pad, self.dA2pad = torch.empty(n, d, **f), torch.zeros(n, d, **f)     # columns >= 2H of dA2pad stay 0
+            self.gWlog_pad = torch.empty(spec.i, d, **f)
+        # extras of the C-level dopri5 step (csrc/gat_driver.hip)
+        self.pair = torch.empty(2 * H, **f)
+        self.colsum_scratch = torch.empty(max(lib.gode_colsum_scratch_bytes(n, d), 16), **u8)
+        self.colsum_scratch2 = torch.empty(max(lib.gode_colsum_scratch_bytes(n, 2 * H), 16), **u8)
         self.err_scratch = torch.empty(lib.gode_rk_errnorm_scratch_bytes(), **u8)
         # launch-bound graphs: block partials of the one-launch dense VJP (csrc/gat_small.hip)
-        self.small_part = ops.gat_small_part(n, o, 1, device) if lib.gode_gat_small_supported(n, o, spec.groups, 1) else None
+        small = not spec.pad_logits and lib.gode_gat_small_supported(n, d, spec.groups, H)
+        self.small_part = ops.gat_small_part(n, d, H, device) if small else None
         self.step_parts = None                 # four such buffers, one per stage of a fixed-grid step (allocated on first use)
 
 
 class GatOdeField(Field):
+    """f(t, x) = relu(layer([t | GroupNorm(x)])) as a kernel sequence.  Adaptive steps run as one C call
+    (csrc/gat_driver.hip) except with padded logit columns (H heads above PAD_LOGITS_MIN_ROWS nodes), where the solver
+    takes the per-stage path."""
     n_components = 1
     fused = True
 
     def __init__(self, spec, work):
         self.s, self.w = spec, work
-        self.token = ("gat", id(spec.eg))
-
-    heads = 1
+        self.token = ("gat-heads" if spec.heads > 1 else "gat", id(spec.eg))
+        if spec.pad_logits:
+            self.dopri5_step_native = None
 
     def prepare(self):
         self.s.refresh()
 
     def small(self):
         """The dense half runs on the one-launch kernels of csrc/gat_small.hip (launch-bound graphs; option small_fused)."""
-        return self.w.small_part is not None and ops.gat_small_supported(self.s.n, self.s.d, self.s.groups, self.heads)
+        return self.w.small_part is not None and ops.gat_small_supported(self.s.n, self.s.d, self.s.groups, self.s.heads)
+
+    def raw_logits(self):
+        """H heads on launch-bound graphs: no launch that shifts the logits - the aggregation reduces its head's partial
+        maxima."""
+        s = self.s
+        return s.heads > 1 and s.n * s.heads <= 65536 and s.eg.E > 8192 and self.small()
 
     # ---- one adaptive step per C call (csrc/gat_driver.hip) -------------------------------------------------------
     def _structs(self, adjoint):
         s, w, eg = self.s, self.w, self.s.eg
         fs = _lib.GatOdeFunc()
-        fs.mt = ops._edge_csr(eg, s.d + 4)
+        fs.mt = ops._edge_csr(eg, s.o + 4)
         for name, gph in (("ms_inc", eg.Ms_inc), ("mt_inc", eg.Mt_inc)):
             gs = _lib.Graph()
             gs.rowptr, gs.col, gs.val = gph.rowptr.data_ptr(), gph.col.data_ptr(), None
             gs.items, gs.n_items = (gph.items.data_ptr() if gph.items is not None else None), gph.n_items
             gs.long_rows = gph.long_rows.data_ptr() if gph.long_rows is not None else None
             gs.n_long = gph.n_long
-            part = gph.partial(s.d) if adjoint else None
+            part = gph.partial(s.o) if adjoint else None
             gs.partial = part.data_ptr() if part is not None else None
             gs.n_rows, gs.nnz = gph.n_rows, gph.nnz
             setattr(fs, name, gs)
@@ -161,14 +193,20 @@ class GatOdeField(Field):
         fs.bf, fs.bw, fs.gamma, fs.beta = s.bf.data_ptr(), s.bw.data_ptr(), s.gamma.data_ptr(), s.beta.data_ptr()
         fs.Wpacked = s.Wpacked.data_ptr() if s.Wpacked is not None else None
         ws = _lib.GatWorkspace()
-        for k in ("X", "Ps", "Pt", "A2", "a", "amax", "wgt", "den", "logits_scratch"):
+        for k in ("X", "Ps", "Pt", "A2", "a", "wgt", "den"):
             setattr(ws, k, p(getattr(w, k)))
+        if s.heads > 1:
+            fs.heads = s.heads
+            ws.zeros, ws.heads_scratch = p(w.zeros), p(w.heads_scratch)
+            ws.amax, ws.logits_scratch = p(w.zero), p(w.heads_scratch)          # unused by the heads sequence, must be set
+        else:
+            ws.amax, ws.logits_scratch = p(w.amax), p(w.logits_scratch)
         if adjoint:
             for k in ("dz", "da", "dPs", "dPt", "dA2", "pair", "gp", "bp", "colsum_scratch", "colsum_scratch2"):
                 setattr(ws, k, p(getattr(w, k)))
             for j in range(3):
                 ws.wp[j] = w.wp[j].data_ptr()
-            ws.maxpath_scratch = p(eg.maxpath_scratch())
+            ws.maxpath_scratch = p(w.heads_scratch if s.heads > 1 else eg.maxpath_scratch())
             ws.small_part = p(w.small_part)
         return fs, ws
 
@@ -189,19 +227,33 @@ class GatOdeField(Field):
         x_out = w.X if len(y_terms) > 1 else None
         terms = [(1.0, w.X)] if x_out is not None else y_terms
         if self.small():
-            ops.gat_project_small(y_terms, s.n, s.d, s.groups, s.eps_gn, s.gamma, s.beta, s.Wsrc, s.Wtgt, s.Wlog, 1, None, t,
-                                  w.Ps, w.Pt, w.A2, x_out=x_out, packed=s.Wpacked)
+            ops.gat_project_small(y_terms, s.n, s.d, s.groups, s.eps_gn, s.gamma, s.beta, s.Wsrc, s.Wtgt, s.Wlog, s.heads,
+                                  s.bf if s.heads > 1 else None, t, w.Ps, w.Pt, w.A2, x_out=x_out, packed=s.Wpacked)
             return terms
         ops.gn_time_gemm_pair(y_terms, s.n, s.d, s.groups, s.eps_gn, s.gamma, s.beta, s.Wsrc, s.Wtgt, True, t, w.Ps, w.Pt,
                               x_out=x_out)
-        ops.gn_time_gemm(terms, s.n, s.d, s.groups, s.eps_gn, s.gamma, s.beta, s.Wlog, True, t, out=w.A2)
+        if s.pad_logits:
+            ops.gn_time_gemm(terms, s.n, s.d, s.groups, s.eps_gn, s.gamma, s.beta, s.Wlog_pad, True, t, out=w.A2pad)
+            w.A2.copy_(w.A2pad[:, :2 * s.heads])
+        else:
+            ops.gn_time_gemm(terms, s.n, s.d, s.groups, s.eps_gn, s.gamma, s.beta, s.Wlog, True, t, out=w.A2)
+        if s.heads > 1:
+            w.Pt.add_(s.bf)                              # per-head message biases, folded into the target-side part
         return terms
 
     def _forward(self, t, y_terms, out):
         s, w, eg = self.s, self.w, self.s.eg
         terms = self._project(t, y_terms)
-        ops.gat_logits(w.proj, s.bw, eg.src, eg.tgt, w.a, w.amax)
-        ops.gat_agg_fwd(eg, w.proj, s.d, s.bf, w.a, w.amax, s.eps, out, w.wgt, w.den)
+        if s.heads == 1:
+            ops.gat_logits(w.proj, s.bw, eg.src, eg.tgt, w.a, w.amax)
+            ops.gat_agg_fwd(eg, w.proj, s.d, s.bf, w.a, w.amax, s.eps, out, w.wgt, w.den)
+        elif self.raw_logits():
+            ops.gat_logits_heads_raw(w.proj, eg.src, eg.tgt, s.heads, w.a, w.heads_scratch, bw=s.bw)
+            ops.gat_agg_heads_fwd(eg, w.proj, s.o, w.bf0, w.a, w.heads_scratch, s.heads, s.eps, out.view(s.n * s.heads, s.o),
+                                  w.wgt, w.den)
+        else:
+            ops.gat_logits_heads(w.proj, eg.src, eg.tgt, s.heads, w.a, bw=s.bw)
+            ops.gat_agg_fwd(eg, w.proj, s.o, w.bf0, w.a, w.zero, s.eps, out.view(s.n * s.heads, s.o), w.wgt, w.den)
         return terms                 # the outer relu of ODEfunc is the identity on a weighted mean of relu's
 
     def eval(self, t, terms, out):
@@ -209,7 +261,7 @@ class GatOdeField(Field):
 
 
 class GatOdeAdjointField(GatOdeField):
-    """Components: [y, a, a_t, theta] with theta = [Wsrc | Wtgt | Wlog | bf | bw | gamma | beta]."""
+    """Components: [y, a, a_t, theta], theta laid out as GatOdeSpec.off."""
 
     def __init__(self, spec, work, order):
         super().__init__(spec, work)
@@ -224,12 +276,21 @@ class GatOdeAdjointField(GatOdeField):
 
     def param_grads(self, comps):
         s = self.s
-        i = s.i
-        v = s.views(comps[3])
-        gWf = torch.cat([v["Wsrc"].t(), v["Wtgt"].t()], 1).contiguous()                          # o x 2i
-        gww = torch.cat([v["Wlog"][:, 0], v["Wlog"][:, 1]]).view(1, 2 * i).contiguous()           # 1 x 2i
-        m = {"gamma": v["gamma"].clone(), "beta": v["beta"].clone(), "Wf": gWf, "bf": v["bf"].clone(),
-             "ww": gww, "bw": v["bw"].clone()}
+        i, o, H = s.i, s.o, s.heads
+        if H == 1:
+            v = s.views(comps[3])
+            gWf = torch.cat([v["Wsrc"].t(), v["Wtgt"].t()], 1).contiguous()                          # o x 2i
+            gww = torch.cat([v["Wlog"][:, 0], v["Wlog"][:, 1]]).view(1, 2 * i).contiguous()           # 1 x 2i
+            m = {"gamma": v["gamma"].clone(), "beta": v["beta"].clone(), "Wf": gWf, "bf": v["bf"].clone(),
+                 "ww": gww, "bw": v["bw"].clone()}
+            return [m[k] for k in self.order]
+        v = s.views(comps[3].clone())                    # one copy; everything below is a view of it or one permuted copy
+        m = {"gamma": v["gamma"], "beta": v["beta"]}
+        gWf = torch.cat([v["Wsrc"].view(i, H, o).permute(1, 2, 0), v["Wtgt"].view(i, H, o).permute(1, 2, 0)], 2)    # H x o x 2i
+        gww = v["Wlog"].view(i, H, 2).permute(1, 2, 0).reshape(H, 1, 2 * i)                                         # H x 1 x 2i
+        gbf, gbw = v["bf"].view(H, o), v["bw"].view(H, 1)
+        for h in range(H):
+            m["Wf%d" % h], m["bf%d" % h], m["ww%d" % h], m["bw%d" % h] = gWf[h], gbf[h], gww[h], gbw[h]
         return [m[k] for k in self.order]
 
     def dopri5_step_native(self, y, kk, y1, t, h, rtol, atol):
@@ -261,7 +322,7 @@ class GatOdeAdjointField(GatOdeField):
     def finish_rk4_step(self, weights, y):
         s, ts = self.s, self._slots
         self._slots = None
-        ops.gat_small_finish_step(self.w.step_parts, s.n, s.d, self.heads, ts, weights[:len(ts)], y[3], y[2])
+        ops.gat_small_finish_step(self.w.step_parts, s.n, s.d, s.heads, ts, weights[:len(ts)], y[3], y[2])
         return self.deferred_components
 
     def _stage_part(self, t):
@@ -276,76 +337,94 @@ class GatOdeAdjointField(GatOdeField):
 
     def eval(self, t, terms, out):
         s, w = self.s, self.w
-        eg, n, o = s.eg, s.n, s.d
+        eg, n, d, o, H = s.eg, s.n, s.d, s.o, s.heads
         xt = self._forward(t, terms[0], out[0])
         g = s.views(out[3])
+        raw = self.raw_logits()
         # cotangent -a of the VJP, masked by the outer relu, is formed inside the kernel
-        ops.gat_vjp(eg, w.proj, o, s.bf, w.a, w.amax, w.wgt, w.den, out[0], w.dz, w.da, w.dPs, w.dPt, w.dA2,
-                    cot_terms=terms[1], cot_scale=-1.0)
+        if H == 1:
+            ops.gat_vjp(eg, w.proj, o, s.bf, w.a, w.amax, w.wgt, w.den, out[0], w.dz, w.da, w.dPs, w.dPt, w.dA2,
+                        cot_terms=terms[1], cot_scale=-1.0)
+        else:
+            nv = n * H
+            ops.gat_vjp(eg, w.proj, o, w.bf0, w.a, w.zero, w.wgt, w.den, out[0].view(nv, o), w.dz, w.da, w.dPs.view(nv, o),
+                        w.dPt.view(nv, o), w.dA2.view(nv, 2), cot_terms=terms[1], cot_scale=-1.0, heads=H,
+                        raw_scratch=w.heads_scratch if raw else None, defer_maxpath=raw)
         if self.small():
-            # launch-bound graphs: k_a and the partials of every parameter gradient in one launch, one more to close
+            # launch-bound graphs: k_a and the partials of every parameter gradient in one launch, one more to close (on the
+            # raw-logit route the per-head max-path sums are taken off dA2 inside the first)
             part, deferred = self._stage_part(t)
-            ops.gat_dense_vjp_small(xt, n, o, s.groups, s.eps_gn, s.gamma, s.beta, s.Wsrc, s.Wtgt, s.Wlog, 1, w.dPs, w.dPt, w.dA2,
-                                    out[1], part, packed=s.Wpacked)
+            ops.gat_dense_vjp_small(xt, n, d, s.groups, s.eps_gn, s.gamma, s.beta, s.Wsrc, s.Wtgt, s.Wlog, H, w.dPs, w.dPt, w.dA2,
+                                    out[1], part, maxfix=(w.heads_scratch, eg.src, eg.tgt) if raw and eg.E > 0 else None,
+                                    packed=s.Wpacked)
             if not deferred:
-                ops.gat_small_finish(part, n, o, 1, t, out[3], out[2])
+                ops.gat_small_finish(part, n, d, H, t, out[3], out[2])
             return
         # bias gradients: sum over edges of dz / da = sum over nodes of the per-target sums just formed (every edge has
         # exactly one target) - N rows instead of E
-        merged = n <= MERGED_FINISH_MAX_ROWS and s.groups > 0        # launch-bound: ONE reduction launch closes the stage
+        merged = n <= MERGED_FINISH_MAX_ROWS and s.groups > 0 and not s.pad_logits     # ONE reduction launch closes the stage
         if merged:
             n_a = ops.colsum_parts(w.dPt, w.colsum_scratch)
             n_b = ops.colsum_parts(w.dA2, w.colsum_scratch2)
         else:
             ops.colsum_(g["bf"], w.dPt)
-            ops.colsum_(g["bw"], w.dA2[:, 1:2].contiguous())
+            if H == 1:
+                ops.colsum_(g["bw"], w.dA2[:, 1:2].contiguous())
+            else:
+                ops.colsum_(w.ba_grad, w.dA2)
+                g["bw"].copy_(w.ba_grad[1::2])
         nb = w.np_b
         affine = s.groups > 0
-        for j, (Wj, dPj) in enumerate(((s.Wsrc, w.dPs), (s.Wtgt, w.dPt), (s.Wlog, w.dA2))):
-            ops.gn_time_gemm_bwd(xt, n, o, s.groups, s.eps_gn, s.gamma, Wj, True, dPj, out=out[1],
+        Wl, dAl = s.Wlog, w.dA2
+        if s.pad_logits:
+            w.dA2pad[:, :2 * H].copy_(w.dA2)
+            Wl, dAl = s.Wlog_pad, w.dA2pad
+        for j, (Wj, dPj) in enumerate(((s.Wsrc, w.dPs), (s.Wtgt, w.dPt), (Wl, dAl))):
+            ops.gn_time_gemm_bwd(xt, n, d, s.groups, s.eps_gn, s.gamma, Wj, True, dPj, out=out[1],
                                  pre_terms=[(1.0, out[1])] if j else None,
                                  parts=(w.gp[j * nb:(j + 1) * nb], w.bp[j * nb:(j + 1) * nb]) if affine else None)
         if affine and not merged:
             ops.reduce_parts2_(g["gamma"], w.gp, g["beta"], w.bp)
         elif not affine:
             g["gamma"].zero_(); g["beta"].zero_()
-        for j, dPj in enumerate((w.dPs, w.dPt, w.dA2)):
-            ops.wgrad(xt, n, o, s.groups, s.eps_gn, s.gamma, s.beta, dPj, True, part=w.wp[j])
+        for j, dPj in enumerate((w.dPs, w.dPt, dAl)):
+            ops.wgrad(xt, n, d, s.groups, s.eps_gn, s.gamma, s.beta, dPj, True, part=w.wp[j])
         if merged:
             i, npw = s.i, w.wp[0].shape[0]
             ops.reduce_segments_([
-                (g["Wsrc"], w.wp[0], npw, i * o, 0, 1, i * o, s.Wsrc[0], o),          # row 0 of each block = its time row
-                (g["Wtgt"], w.wp[1], npw, i * o, 0, 1, i * o, s.Wtgt[0], o),
-                (g["Wlog"], w.wp[2], npw, i * 2, 0, 1, i * 2, s.Wlog[0], 2),
-                (g["bf"], w.colsum_scratch, n_a, o, 0, 1, o, None, 0),
-                (g["bw"], w.colsum_scratch2, n_b, 2, 1, 2, 1, None, 0),               # column 1 of the n x 2 sums
-                (g["gamma"], w.gp, 3 * nb, o, 0, 1, o, None, 0),
-                (g["beta"], w.bp, 3 * nb, o, 0, 1, o, None, 0)], t, out[2])
+                (g["Wsrc"], w.wp[0], npw, i * d, 0, 1, i * d, s.Wsrc[0], d),          # row 0 of each block = its time row
+                (g["Wtgt"], w.wp[1], npw, i * d, 0, 1, i * d, s.Wtgt[0], d),
+                (g["Wlog"], w.wp[2], npw, i * 2 * H, 0, 1, i * 2 * H, s.Wlog[0], 2 * H),
+                (g["bf"], w.colsum_scratch, n_a, d, 0, 1, d, None, 0),
+                (g["bw"], w.colsum_scratch2, n_b, 2 * H, 1, 2, H, None, 0),           # the odd columns of the n x 2H sums
+                (g["gamma"], w.gp, 3 * nb, d, 0, 1, d, None, 0),
+                (g["beta"], w.bp, 3 * nb, d, 0, 1, d, None, 0)], t, out[2])
             return
         ops.reduce_parts2_(g["Wsrc"].view(-1), w.wp[0], g["Wtgt"].view(-1), w.wp[1])
-        ops.reduce_parts_(g["Wlog"].view(-1), w.wp[2])
+        if s.pad_logits:
+            ops.reduce_parts_(w.gWlog_pad.view(-1), w.wp[2])
+            g["Wlog"].copy_(w.gWlog_pad[:, :2 * H])
+        else:
+            ops.reduce_parts_(g["Wlog"].view(-1), w.wp[2])
         # a_t' = -a^T df/dt over the three time rows; each row 0 *= t
         ops.time_row_fixup3_([g["Wsrc"][0], g["Wtgt"][0], g["Wlog"][0]], [s.Wsrc[0], s.Wtgt[0], s.Wlog[0]], t, out[2])
 
 
-def gat_fields(odefunc, y0):
-    """Hook body for gat_models.ODEfunc.gode_fields."""
-    layer, norm = odefunc.gc1, odefunc.norm1
-    import torch.nn.functional as F
-    if layer.act is not F.relu or y0.dim() != 2 or not torch.is_tensor(layer.src) or layer.src.dim() != 1:
+def gat_fields(odefunc, layer, eg, n, names, y0):
+    """Hook body of gat_models.ODEfunc.gode_fields and gat_heads.ODEfunc.gode_fields, after their own checks of the
+    graph: the fused fields of relu(layer([t | odefunc.norm1(x)])) on n nodes, or None.  eg is the graph the kernels see
+    (the H-fold graph with H heads); names maps id(parameter) -> its name in param_grads."""
+    if layer.act is not F.relu or y0.dim() != 2 or n != y0.shape[0]:
         return None
     plist = [p for p in odefunc.parameters() if p.requires_grad]
-    names = {id(norm.weight): "gamma", id(norm.bias): "beta", id(layer.f.weight): "Wf", id(layer.f.bias): "bf",
-             id(layer.w.weight): "ww", id(layer.w.bias): "bw"}
-    if len(plist) != 6 or any(id(p) not in names for p in plist):
+    if len(plist) != len(names) or any(id(p) not in names for p in plist):
         return None
-    eg = edge_graph(layer.src, layer.tgt, layer.Mtgt)
-    if eg.n != y0.shape[0]:
-        return None
-    spec = GatOdeSpec(eg, layer, norm)
-    work = getattr(eg, "_ode_work", {}).get((spec.d, y0.device))
+    spec = GatOdeSpec(eg, n, layer, odefunc.norm1)
+    # a one-head and an H-head function on the same edge list keep their own buffers
+    key = ("heads", spec.d, y0.device) if spec.heads > 1 else (spec.d, y0.device)
+    cache = eg.__dict__.setdefault("_ode_work", {})
+    work = cache.get(key)
     if work is None:
-        work = _Work(spec, y0.device)
-        eg.__dict__.setdefault("_ode_work", {})[(spec.d, y0.device)] = work
+        work = cache[key] = _Work(spec, y0.device)
     order = [names[id(p)] for p in plist]
     return GatOdeField(spec, work), (lambda: GatOdeAdjointField(spec, work, order)), tuple(plist)

@@ -104,7 +104,7 @@ def integrate_rk4(field, y, t0, t1, n_steps, work=None):
     fused = getattr(field, "eval_combine", None)
     # a field may keep the stage derivatives of its SMALL components (a_t, parameter gradients: the adjoint ODE is linear
     # in them and no stage input reads them) as block partials and close the four stages of a step with ONE launch that
-    # adds h * sum_s b_s k_s to the solution (gat_ode / gat_heads on launch-bound graphs): begin_rk4_step() before the
+    # adds h * sum_s b_s k_s to the solution (gat_ode, one head or H, on launch-bound graphs): begin_rk4_step() before the
     # stages, finish_rk4_step(weights, y) after them returns the components it has advanced
     begin, finish = getattr(field, "begin_rk4_step", None), getattr(field, "finish_rk4_step", None)
     for i in range(n_steps):

@@ -630,7 +630,7 @@ typedef struct gode_gat_odefunc {
     int64_t n, d; int32_t groups; float eps_gn; float eps;
     const float* Wsrc; const float* Wtgt; const float* Wlog;
     const float* bf; const float* bw; const float* gamma; const float* beta;
-    /* H heads side by side (graph_odenet_amd/gat_heads.py; 0 or 1: one head).  With heads = H > 1 the graphs, src, tgt
+    /* H heads side by side (the layer of graph_odenet_amd/gat_heads.py, run by gat_ode.py; 0 or 1: one head).  With heads = H > 1 the graphs, src, tgt
      * and n_edges above are those of the H-fold graph (virtual node v*H + h = head h of node v; n stays the number of
      * real nodes, d = H * o), Wlog is (d+1) x 2H, bw holds H logit biases, bf (d) is added to the target-side
      * projection, and theta = [Wsrc | Wtgt | Wlog | bf | bw (H) | gamma | beta] (gode_gat_ode_theta_len_heads). */
