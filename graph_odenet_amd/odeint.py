@@ -250,13 +250,27 @@ def _run_rk4(field, comps, t0, t1, n):
     return integrate_rk4(field, comps, t0, t1, n)
 
 
+def _extra_inputs(func):
+    """Differentiable inputs of func that are not its parameters (private hook `gode_extra_inputs`, e.g. the edge
+    matrices of qc_ode.EdgeODEfunc: the output of a trainable encoder).  Their gradients are returned after the
+    parameters'; a func without the hook has none."""
+    hook = getattr(func, "gode_extra_inputs", None)
+    return tuple(hook()) if hook is not None else ()
+
+
+def _params(func):
+    """What a solve differentiates with respect to besides y0: func's trainable parameters, then its extra inputs."""
+    params = tuple(p for p in func.parameters() if p.requires_grad) if isinstance(func, torch.nn.Module) else ()
+    return params + _extra_inputs(func)
+
+
 def _fields(func, y0):
     mk = getattr(func, "gode_fields", None)
     if mk is not None:
         pair = mk(y0)
         if pair is not None:
             return pair
-    params = tuple(p for p in func.parameters() if p.requires_grad) if isinstance(func, torch.nn.Module) else ()
+    params = _params(func)
     return AutogradField(func, y0), (lambda: AutogradAdjointField(func, params, y0)), params
 
 
@@ -346,8 +360,7 @@ class _OdeintBackprop(torch.autograd.Function):
     def backward(ctx, grad_out):
         grad_out = grad_out.contiguous()
         tl, steps = ctx.tl, ctx.steps
-        params = ctx.fields[2] if ctx.fused else tuple(p for p in ctx.func.parameters() if p.requires_grad) \
-            if isinstance(ctx.func, torch.nn.Module) else ()
+        params = ctx.fields[2] if ctx.fused else _params(ctx.func)
         if ctx.fused:
             fwd = ctx.fields[0]
             order, inverse = _rows(fwd)
@@ -411,7 +424,7 @@ def odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None):
     fields = _fields(func, y0)
     fwd = fields[0]
     if method == "rk4" and torch.is_grad_enabled() and getattr(fwd, "big_components", None) is None:
-        params = tuple(p for p in func.parameters() if p.requires_grad) if isinstance(func, torch.nn.Module) else ()
+        params = _params(func)
         if y0.requires_grad or params:
             same = len(fields[2]) == len(params) and all(p is q for p, q in zip(fields[2], params))
             if getattr(fwd, "rk4_forward_save", None) is not None and not same:
@@ -565,5 +578,5 @@ def odeint_adjoint(func, y0, t, rtol=1e-6, atol=1e-12, method=None, options=None
     method = _method(method)
     if not isinstance(func, torch.nn.Module):
         raise ValueError("odeint_adjoint: func must be an nn.Module")
-    params = tuple(p for p in func.parameters() if p.requires_grad)
+    params = _params(func)
     return _OdeintAdjoint.apply(func, tl, float(rtol), float(atol), method, options, bool(_last_only), y0, *params)

@@ -892,6 +892,98 @@ def edge_outer_sum(edge_row, edge_val, src, pairs, like):
 
 
 # ---- QC node update: fused GRU cell ---------------------------------------------------------------
+
+# ---- the edge-conditioned ODE function (csrc/edge_ode.hip; qc_ode.py) -----------------------------------------------
+# below this many edges an evaluation is one launch over the targets (messages never written) and its VJP one launch over the
+# sources; from it on, a workgroup per edge (gode_edge_matvec_msg_f32 + SpMM forward, per-edge dxe + SpMM backward)
+EDGE_ODE_FUSED_MAX_EDGES = 4096
+# kinds of the launches above in a gode_prof_* profile (include/graphode.h)
+PROF_EDGE_FEVAL, PROF_EDGE_VJP, PROF_EDGE_OUTER_STEP, PROF_EDGE_OUTER_STAGE = 5, 6, 7, 8
+
+
+def edge_ode_supported(h):
+    return bool(_lib.load().gode_edge_ode_supported(int(h)))
+
+
+def _need_edge_matrices(A, E, h):
+    _need(A, "edge_data")
+    if A.dim() != 3 or tuple(A.shape) != (E, h, h):
+        raise ValueError("edge_ode: edge_data must be E x h x h = (%d, %d, %d), got %s" % (E, h, h, tuple(A.shape)))
+
+
+def edge_ode_feval(Mt, src, A, S, bias, out, pre_terms=None, alpha=1.0):
+    """out = (sum pre_terms) + alpha * relu(Mt . bmm(A, S[src]) + bias) in one launch; Mt: CSR of Etgt (N x E)."""
+    lib = _lib.load()
+    _need(S, "S"); _need(bias, "bias"); _need(out, "out"); _need(src, "Esrc", torch.int32)
+    if S.dim() != 2 or S.shape[0] != Mt.n_rows:
+        raise ValueError("edge_ode_feval: S has shape %s, the batch has %d atoms" % (tuple(S.shape), Mt.n_rows))
+    n, h = S.shape
+    _need_edge_matrices(A, src.numel(), h)
+    if Mt.n_cols != src.numel() or bias.numel() != h or out.numel() != n * h:
+        raise ValueError("edge_ode_feval: Etgt is %d x %d, Esrc has %d entries, bias %d, out %d elements"
+                         % (Mt.n_rows, Mt.n_cols, src.numel(), bias.numel(), out.numel()))
+    pre = None
+    if pre_terms is not None:
+        if _need_terms(pre_terms, "pre") != n * h:
+            raise ValueError("edge_ode_feval: pre terms have wrong size")
+        if any(t.data_ptr() == out.data_ptr() for _, t in pre_terms):
+            raise ValueError("edge_ode_feval: out must not be a pre term")
+        pre = lincomb(pre_terms)
+    check(lib.gode_edge_ode_feval_f32(ptr(Mt.rowptr), ptr(Mt.col), ptr(Mt.val), ptr(src), ptr(A), ptr(S), h, n, ptr(bias),
+                                      ctypes.byref(pre) if pre is not None else None, float(alpha), ptr(out), stream_ptr()),
+          "gode_edge_ode_feval_f32")
+    return out
+
+
+def edge_ode_vjp(Ms_inc, edge_row, edge_val, A, cot_terms, cot_scale, fout, dM, dS=None, dxe=None):
+    """dM = cot_scale * (sum cot_terms) * [fout > 0] and, by source (dS given; Ms_inc: N x E source incidence) dS = Ms_inc .
+    (A_e^T (val_e dM[tgt_e])), or per edge (dxe given) dxe[e] = A_e^T (val_e dM[tgt_e])."""
+    lib = _lib.load()
+    _need(fout, "fout"); _need(dM, "dM"); _need(dS, "dS"); _need(dxe, "dxe")
+    _need(edge_row, "edge_row", torch.int32); _need(edge_val, "edge_val")
+    if (dS is None) == (dxe is None):
+        raise ValueError("edge_ode_vjp: exactly one of dS (by source) and dxe (by edge)")
+    n, h = fout.shape
+    E = edge_row.numel()
+    _need_edge_matrices(A, E, h)
+    if _need_terms(cot_terms, "cot") != n * h or dM.numel() != n * h:
+        raise ValueError("edge_ode_vjp: cotangent terms and dM must be n x h")
+    if any(t.data_ptr() == dM.data_ptr() for _, t in cot_terms):
+        raise ValueError("edge_ode_vjp: dM must not be a cotangent term")
+    rp = eid = None
+    if dS is not None:
+        if Ms_inc.n_rows != n or Ms_inc.n_cols != E or dS.numel() != n * h:
+            raise ValueError("edge_ode_vjp: the source incidence must be n x E and dS n x h")
+        rp, eid = Ms_inc.rowptr, Ms_inc.col
+    elif dxe.numel() != E * h:
+        raise ValueError("edge_ode_vjp: dxe must be E x h")
+    lc = lincomb(cot_terms)
+    check(lib.gode_edge_ode_vjp_f32(ptr(rp), ptr(eid), ptr(edge_row), ptr(edge_val), ptr(A), ctypes.byref(lc), float(cot_scale),
+                                    ptr(fout), h, n, E, ptr(dM), ptr(dS), ptr(dxe), stream_ptr()), "gode_edge_ode_vjp_f32")
+
+
+def edge_outer_sum_acc(edge_row, edge_val, src, pairs, weights, dA, accumulate):
+    """dA (+)= sum_s weights[s] * (val dM_s[tgt]) (x) X_s[src] over pairs = [(dM_s, X_s), ...] in one pass."""
+    lib = _lib.load()
+    k = len(pairs)
+    if not 1 <= k <= EDGE_OUTER_MAX_TERMS or len(weights) != k:
+        raise ValueError("edge_outer_sum_acc: 1 .. %d terms, one weight each" % EDGE_OUTER_MAX_TERMS)
+    E, h = src.numel(), pairs[0][1].shape[1]
+    _need_edge_matrices(dA, E, h)
+    _need(edge_row, "edge_row", torch.int32); _need(edge_val, "edge_val"); _need(src, "Esrc", torch.int32)
+    if edge_row.numel() != E:
+        raise ValueError("edge_outer_sum_acc: one target per edge")
+    dms, xs, ws = (ctypes.c_void_p * k)(), (ctypes.c_void_p * k)(), (ctypes.c_float * k)(*[float(w) for w in weights])
+    for t, (dM, x) in enumerate(pairs):
+        _need(dM, "dM"); _need(x, "x")
+        if dM.dim() != 2 or tuple(dM.shape) != tuple(x.shape) or x.shape[1] != h:
+            raise ValueError("edge_outer_sum_acc: every term is a pair of n x %d arrays" % h)
+        dms[t], xs[t] = dM.data_ptr(), x.data_ptr()
+    check(lib.gode_edge_outer_sum_acc_f32(ptr(edge_row), ptr(edge_val), ptr(src), k, dms, xs, ws, h, E, 1 if accumulate else 0,
+                                          ptr(dA), stream_ptr()), "gode_edge_outer_sum_acc_f32")
+    return dA
+
+
 def lstm_cell_supported(B, I, H):
     return bool(_lib.load().gode_lstm_cell_supported(B, I, H))
 

@@ -46,12 +46,13 @@ def pad_batch(x, edge_feat, Esrc, Etgt, batch, node_multiple=64, edge_multiple=1
     return x2, ef2, src2, Etgt2, batch2, n_graphs
 
 
-def prepare(Esrc, etgt, batch, n_nodes, n_graphs):
+def prepare(Esrc, etgt, batch, n_nodes, n_graphs, values=None):
     """Loader-side preparation of a batch for the QC models: returns (edges, batch) to be passed in place of
     (Etgt, batch).  `etgt` is the per-edge target index (the loader has it before it builds the reference's dense
     N x E matrix); nothing here synchronises with the host, so a training loop that prepares its batches this way keeps
     the GPU queue full (the dense-matrix route costs a column arg-max over N x E, a validity check and a second
-    synchronisation for the number of graphs - DESIGN.md section 5)."""
+    synchronisation for the number of graphs - DESIGN.md section 5).  `values`: the entries of Etgt per edge (default: 1,
+    the collate's incidence)."""
     from .qc_layers import prepared_edges
     batch._gode_n_graphs = int(n_graphs)
-    return prepared_edges(Esrc, etgt, n_nodes), batch
+    return prepared_edges(Esrc, etgt, n_nodes, values), batch

@@ -424,6 +424,65 @@ class EdgeRES1_K_Set2Set(_QCBase):
         return self.output_function(self.mlpout(x))
 
 
+# ---- continuous-depth models: the reference's "eodesum" / "eodes2s" (QC/train_egcn.py:93-94 binds them to
+# UnimplementedModel; the shape is ODEGCN3, GCN/models.py:204-222, on the QC layers) -------------------------------------
+class _EdgeODE1(_QCBase):
+    def _init_ode(self, node_features, edge_features, target_features, hidden_features, dropout, kwargs):
+        from .qc_ode import EdgeODEBlock, EdgeODEfunc
+        self.mlpin = TransitionMLP(node_features, hidden_features)
+        self.gcin = EdgeGraphConvolution(hidden_features, hidden_features)
+        self.ode = EdgeODEBlock(EdgeODEfunc(hidden_features), tol=kwargs.get("tol", 1e-5), method=kwargs.get("method"),
+                                step_size=kwargs.get("step_size"), adjoint=kwargs.get("adjoint", True))
+        self.gcout = EdgeGraphConvolution(hidden_features, hidden_features)
+        self.mlpout = TransitionMLP(hidden_features, target_features)
+        self.dropout = dropout
+        self.ee = EdgeEncoderMLP(edge_features, hidden_features)
+
+    def _body(self, x, Esrc, Etgt, ef):
+        with shared_edge_data(ef):       # gcin and gcout share the edge matrices with the block: one encoder, one gradient
+            x = F.dropout(F.relu(self.gcin(x, Esrc, Etgt, ef)), self.dropout, training=self.training)
+            x = self.ode(x, Esrc, Etgt, ef)
+            return self.gcout(x, Esrc, Etgt, ef)
+
+
+class EdgeODE1_K_Sum(_EdgeODE1):
+    """mlpin -> gcin + relu + dropout -> EdgeODEBlock -> gcout -> per-graph sum (readout of EdgeGCN_K_Sum).
+    **kwargs: method=None, step_size=None, tol=1e-5, adjoint=True of the block."""
+
+    def __init__(self, node_features=None, edge_features=None, target_features=1, hidden_features=73, num_layers=3,
+                 s2s_processing_steps=12, type="regression", dropout=0.5, **kwargs):
+        super().__init__()
+        self._init_ode(node_features, edge_features, target_features, hidden_features, dropout, kwargs)
+        self._finish(type, target_features)
+
+    def forward(self, node_features, edge_features, Esrc, Etgt, batch):
+        x = self._body(self.mlpin(node_features), Esrc, Etgt, self.ee(edge_features))
+        return self.output_function(segment_sum(self.mlpout(x), batch))
+
+
+class EdgeODE1_K_Set2Set(_EdgeODE1):
+    """The same with the Set2Set readout of EdgeGCN_K_Set2Set."""
+
+    def __init__(self, node_features=None, edge_features=None, target_features=1, hidden_features=73, num_layers=3,
+                 s2s_processing_steps=12, type="regression", dropout=0.5, **kwargs):
+        super().__init__()
+        self._init_ode(node_features, edge_features, target_features, hidden_features, dropout, kwargs)
+        self.s2s = Set2Set(hidden_features, s2s_processing_steps, num_layers=1)
+        self._finish(type, target_features)
+
+    def forward(self, node_features, edge_features, Esrc, Etgt, batch):
+        x = self._body(self.mlpin(node_features), Esrc, Etgt, self.ee(edge_features))
+        x = self.s2s(x, batch)[:, :x.size(1)]
+        return self.output_function(self.mlpout(x))
+
+
+def __getattr__(name):
+    if name in ("EdgeODEfunc", "EdgeODEBlock"):          # re-exported from qc_ode (imported late: qc_ode imports the layers)
+        from . import qc_ode
+        return getattr(qc_ode, name)
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))
+
+
 # ---- the fixed-depth models of QC/models.py (used by QC/train_egcn_multitask.py) ------------------------------------
 class _Fixed(nn.Module):
     """`type` decides between raw outputs and log_softmax (QC/models.py:36,64; the two EdgeGCN3 classes read

@@ -49,6 +49,11 @@ class CapturedQCStep:
 
     def __init__(self, model, optimizer, loss_fn, exchange=None, warmup=2):
         self.model, self.opt, self.loss_fn, self.exchange, self.warmup = model, optimizer, loss_fn, exchange, warmup
+        if any(type(m).__name__ == "EdgeODEBlock" for m in model.modules()):
+            # an ODE solve makes host decisions inside the step (dopri5 accepts / rejects on a value read back) and builds
+            # its fields per batch; the continuous-depth QC models run in TrainStep's "eager" / "prepared" modes
+            raise NotImplementedError("CapturedQCStep: models with an EdgeODEBlock cannot run as a captured step; "
+                                      "use qc_train.TrainStep(mode='prepared')")
         self.buckets = {}
         self.capture_optimizer = exchange is None
         self.capture_disabled_reason = None

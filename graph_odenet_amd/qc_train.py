@@ -81,9 +81,12 @@ class TrainStep:
                 self._captured = CapturedQCStep(self.model, self.opt, self.criterion, exchange=self.exchange)
             return self._captured(x, edge_feat, Esrc, Etgt, batch, target, n_graphs=n_graphs + 1)
         if self.mode == "prepared":
+            values = None
             if not by_index:
-                Etgt = _target_index(Etgt)                           # one entry per edge column (the collate's layout)
-            Etgt, batch = prepare(Esrc, Etgt, batch, x.shape[0], n_graphs)
+                dense = Etgt
+                Etgt = _target_index(dense)                          # one entry per edge column (the collate's layout)
+                values = dense.gather(0, Etgt.unsqueeze(0)).squeeze(0)      # its value: a weighted Etgt means what it means in "eager"
+            Etgt, batch = prepare(Esrc, Etgt, batch, x.shape[0], n_graphs, values)
         # Without an exchange the gradients are DROPPED, not zeroed: autograd then hands every parameter its gradient
         # tensor as it is (no fill launch before the step, no `grad += new` launch after it - ~2 x 25 launches of a
         # ~300-launch step); optim.Adam takes the new addresses by value in its kernel arguments.  With an exchange the

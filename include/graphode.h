@@ -748,6 +748,29 @@ int gode_gru_cell_f32_bwd(const float* x, const float* m, const float* w_ih, con
 int gode_gru_wreduce_f32(const float* part, int64_t n_part, int64_t h, float* dw_ih, float* dw_hh, float* db_ih,
                          float* db_hh, void* stream);
 
+/* ---- the edge-conditioned ODE function of the QM9 models (csrc/edge_ode.hip; qc_ode.py) ----------
+ *   S = [t | GN(X)] W   (gode_gn_time_gemm_f32),   f = relu(Etgt . bmm(A, S[Esrc]) + b),   h <= 112 (gode_edge_ode_supported).
+ * feval: out = (sum pre) + alpha * f in ONE launch over the CSR of Etgt (rowptr / eid / val as for gode_edge_matvec_f32_fwd);
+ *   the E x h messages are never written.  pre NULL or empty: out = alpha * f.  out must not be a term of pre.
+ * vjp: dM = cot_scale * (sum cot) * [fout > 0] (n_rows x h, the masked stage cotangent) and
+ *   with ms_rowptr / ms_eid (CSR of the source incidence, eid nullable = identity): dS[u] = sum_{e: src_e = u} A_e^T (val_e dM[tgt_e]);
+ *   with ms_rowptr NULL: dxe[e] = A_e^T (val_e dM[tgt_e]) per edge (its per-source sum is an SpMM).  edge_row[e] < 0: no target.
+ *   The rows of dM are the block partials of the bias gradient (colsum).  The edge-matrix gradient is NOT formed here.
+ * outer_sum_acc: dA[e] (+)= sum_s w[s] (val_e dM_s[tgt_e]) (x) X_s[src_e], s < n_terms <= 8 (accumulate != 0: added to dA):
+ *   the stages of one RK step that share A, closed in one pass with the RK weights applied. */
+int gode_edge_ode_supported(int64_t h);
+int gode_edge_ode_feval_f32(const int32_t* rowptr, const int32_t* eid, const float* val, const int32_t* src,
+                            const float* A, const float* S, int64_t h, int64_t n_rows, const float* bias,
+                            const gode_lincomb_t* pre /* host, nullable */, float alpha, float* out, void* stream);
+int gode_edge_ode_vjp_f32(const int32_t* ms_rowptr, const int32_t* ms_eid, const int32_t* edge_row,
+                          const float* edge_val, const float* A, const gode_lincomb_t* cot /* host */, float cot_scale,
+                          const float* fout, int64_t h, int64_t n_rows, int64_t n_edges, float* dM, float* dS,
+                          float* dxe, void* stream);
+int gode_edge_outer_sum_acc_f32(const int32_t* edge_row, const float* edge_val, const int32_t* src, int32_t n_terms,
+                                const float* const* dM /* host[n_terms] */, const float* const* X /* host[n_terms] */,
+                                const float* w /* host[n_terms] */, int64_t h, int64_t n_edges, int accumulate, float* dA,
+                                void* stream);
+
 /* ---- measurement aid (bench.py): HIP-event brackets around the dominant kernels ----------
  * While a profiler is enabled (process-wide; one measuring client at a time), every gode_spmm_csr_f32 main-kernel launch
  * and every MFMA-path launch of the dense kernels (gn_gemm_fwd / gn_gemm_bwd / wgrad) records a start/stop event pair
@@ -762,6 +785,11 @@ int gode_gru_wreduce_f32(const float* part, int64_t n_part, int64_t h, float* dw
 #define GODE_PROF_GEMM_BWD 2
 #define GODE_PROF_WGRAD    3
 #define GODE_PROF_BWD_WGRAD 4      /* VJP + weight gradient in one pass (gode_gn_time_gemm_bwd_wgrad_f32): 2 x 2 N d^2 flop */
+/* csrc/edge_ode.hip (d = h, rows = launched blocks, extra = pre / cotangent / outer-sum terms) */
+#define GODE_PROF_EDGE_FEVAL 5
+#define GODE_PROF_EDGE_VJP   6
+#define GODE_PROF_EDGE_OUTER_STEP  7   /* gode_edge_outer_sum_acc_f32 accumulating: one pass per RK step */
+#define GODE_PROF_EDGE_OUTER_STAGE 8   /* the same kernel overwriting: one stage's own dA */
 /* which kernel of the family ran, OR-ed into the kind of a dense launch (kind & 0xff = family, kind >> 8 = form):
  * exact-fp32 MFMA kernel; bf16-piece kernel, every wave loading + cutting + multiplying; bf16-piece kernel in
  * producer / consumer form (wgrad_split_kernel, gemm_pc.hip) */

@@ -32,13 +32,18 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
+ODE_KW = {"method": "rk4", "step_size": 0.25}      # solver of the EdgeODE1_* models (--method / --step-size)
+
+
 def build(dev, model_name, seed, n_batches, batch_size, bucket=False, by_index=False):
     from graph_odenet_amd import qc_models
     from graph_odenet_amd.qc_batch import pad_batch
     from graph_odenet_amd.synth import qm9_like_batch
     torch.manual_seed(0)
-    net = getattr(qc_models, model_name)(node_features=13, edge_features=5, target_features=12,
-                                         hidden_features=73, num_layers=3).to(dev)
+    kw = dict(hidden_features=73, num_layers=3)
+    if model_name.startswith("EdgeODE"):      # GroupNorm(32, .) of the ODE function refuses the reference's 73: 64 channels
+        kw = dict(hidden_features=64, **ODE_KW)
+    net = getattr(qc_models, model_name)(node_features=13, edge_features=5, target_features=12, **kw).to(dev)
     batches = []
     for b in range(n_batches):
         x, ef, Esrc, Etgt, batch = qm9_like_batch(batch_size, seed=seed * 1000 + b, device=dev)
@@ -154,7 +159,15 @@ def main():
     ap.add_argument("--bucket", action="store_true",
                     help="pad every batch to its shape bucket (multiples of 64 atoms / 128 edges, one dummy graph)")
     ap.add_argument("--backend", choices=["auto", "nccl", "gloo"], default="auto")
+    ap.add_argument("--method", choices=["rk4", "dopri5"], default="rk4", help="EdgeODE1_* models: solver of the ODE block")
+    ap.add_argument("--step-size", type=float, default=0.25, help="EdgeODE1_* models under rk4: step size (4 steps)")
+    ap.add_argument("--generic-fields", action="store_true",
+                    help="EdgeODE1_* models: switch the fused fields off (generic autograd fields: the baseline they must beat)")
     args = ap.parse_args()
+    if args.generic_fields:
+        from graph_odenet_amd import qc_ode
+        qc_ode.EdgeODEfunc.FUSED = False
+    ODE_KW.update(method=args.method, step_size=args.step_size if args.method == "rk4" else None)
     from graph_odenet_amd import launch
     if launch.needs_self_launch(args.gpus):
         sys.exit(launch.self_launch(__file__, sys.argv[1:], args.gpus))
