@@ -24,7 +24,8 @@ class LinComb(ctypes.Structure):
 class SpmmEpilogue(ctypes.Structure):
     """Mirror of gode_spmm_epilogue_t."""
     _fields_ = [("bias", ctypes.c_void_p), ("relu", ctypes.c_int32), ("alpha", ctypes.c_float),
-                ("pre", LinComb), ("cot", LinComb), ("Y2", ctypes.c_void_p), ("Y2_colsum", ctypes.c_void_p)]
+                ("pre", LinComb), ("cot", LinComb), ("Y2", ctypes.c_void_p), ("Y2_colsum", ctypes.c_void_p),
+                ("cot_out", ctypes.c_void_p), ("cot_out_coef", ctypes.c_float * GODE_MAX_TERMS)]
 
 
 class Graph(ctypes.Structure):
@@ -119,6 +120,8 @@ SIGNATURES = {
                                     c_p, c_i64, c_i, c_f, c_p, c_p]),
     "gode_gn_time_gemm_xout_f32": (c_i, [ctypes.POINTER(LinComb), c_i64, c_i64, ctypes.c_int32, c_f, c_p, c_p,
                                          c_p, c_i64, c_i, c_f, c_p, c_p, c_p]),
+    "gode_gn_time_gemm_xout_aux_f32": (c_i, [ctypes.POINTER(LinComb), c_i64, c_i64, ctypes.c_int32, c_f, c_p, c_p,
+                                             c_p, c_i64, c_i, c_f, c_p, c_p, c_p, c_p, c_p]),
     "gode_gn_time_gemm_pair_f32": (c_i, [ctypes.POINTER(LinComb), c_i64, c_i64, ctypes.c_int32, c_f, c_p, c_p, c_p, c_p,
                                          c_i, c_f, c_p, c_p, c_p, c_p]),
     "gode_gemm_bwd_parts": (c_i64, [c_i64]),

@@ -69,6 +69,42 @@ __device__ __forceinline__ float4 lc_load4(const LinComb& lc, int64_t idx) {
     }
 }
 
+// Two combinations of the SAME terms from one set of loads: r with lc.coef, r2 with coef2, each the multiply-add chain
+// of lc_load4_n (so r is bit for bit lc_load4's value and r2 that of a combination with coef2 in a launch of its own).
+template <int NT>
+__device__ __forceinline__ void lc_load4_pair_n(const LinComb& lc, const float* coef2, int64_t idx, float4& r, float4& r2) {
+    float4 v[NT];
+#pragma unroll
+    for (int j = 0; j < NT; ++j) v[j] = *reinterpret_cast<const float4*>(lc.ptr[j] + idx);
+    r = make_float4(0.f, 0.f, 0.f, 0.f);
+    r2 = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+        const float c = lc.coef[j], c2 = coef2[j];
+        r.x = fmaf(c, v[j].x, r.x); r.y = fmaf(c, v[j].y, r.y);
+        r.z = fmaf(c, v[j].z, r.z); r.w = fmaf(c, v[j].w, r.w);
+        r2.x = fmaf(c2, v[j].x, r2.x); r2.y = fmaf(c2, v[j].y, r2.y);
+        r2.z = fmaf(c2, v[j].z, r2.z); r2.w = fmaf(c2, v[j].w, r2.w);
+    }
+}
+
+__device__ __forceinline__ void lc_load4_pair(const LinComb& lc, const float* coef2, int64_t idx, float4& r, float4& r2) {
+    switch (lc.n) {          // wave-uniform
+        case 1: lc_load4_pair_n<1>(lc, coef2, idx, r, r2); break;
+        case 2: lc_load4_pair_n<2>(lc, coef2, idx, r, r2); break;
+        case 3: lc_load4_pair_n<3>(lc, coef2, idx, r, r2); break;
+        case 4: lc_load4_pair_n<4>(lc, coef2, idx, r, r2); break;
+        case 5: lc_load4_pair_n<5>(lc, coef2, idx, r, r2); break;
+        case 6: lc_load4_pair_n<6>(lc, coef2, idx, r, r2); break;
+        case 7: lc_load4_pair_n<7>(lc, coef2, idx, r, r2); break;
+        case 8: lc_load4_pair_n<8>(lc, coef2, idx, r, r2); break;
+        default: r = make_float4(0.f, 0.f, 0.f, 0.f); r2 = r; break;
+    }
+}
+
+// Second coefficient vector over the terms of a LinComb (kernel argument, by value)
+struct AuxCoef { float c[GODE_MAX_TERMS]; };
+
 __device__ __forceinline__ float lc_load1(const LinComb& lc, int64_t idx) {
     float r = 0.f;
 #pragma unroll

@@ -5,7 +5,8 @@
 #include "common.h"
 
 int gode_pc_fwd_launch(const LinComb& lc, int64_t n_rows, float eps, const float* gamma, const float* beta,
-                       const float* W, int has_time, float t, float* S, float* xout, int cg, hipStream_t s);
+                       const float* W, int has_time, float t, float* S, float* xout, const float* aux_coef, float* aux,
+                       int cg, hipStream_t s);   // aux (nullable): second combination of the terms, 4 terms only
 int gode_pc_bwd_launch(const LinComb& lc, int64_t n_rows, float eps, const float* gamma, const float* W, int has_time,
                        const float* dS, float out_scale, const LinComb& pre, float* dx, float* dgamma_part,
                        float* dbeta_part, int64_t n_part, int cg, hipStream_t s);

@@ -221,13 +221,15 @@ __device__ __forceinline__ float4 acc_to_mem_layout(const f32x4 a, int src_f_lan
                        __int_as_float(__builtin_amdgcn_ds_bpermute(src_f_lane_x4, __float_as_int(a[3]))));
 }
 
-template <int NJ, int CG>   // d = 16*NJ
+// AUX: aux[row, :] = sum_j acoef.c[j] x_j[row, :], a second combination of the terms from the same loads (same chain).
+template <int NJ, int CG, bool AUX = false>   // d = 16*NJ
 __global__ __launch_bounds__(256, 2) void gn_gemm_fwd_kernel(LinComb xin, int n_rows, float eps,
                                                              const float* __restrict__ gamma,
                                                              const float* __restrict__ beta,
                                                              const float* __restrict__ W, int has_time, float t,
                                                              float* __restrict__ S, float* __restrict__ xout,
-                                                             const float* __restrict__ W2, float* __restrict__ S2)
+                                                             const float* __restrict__ W2, float* __restrict__ S2,
+                                                             AuxCoef acoef, float* __restrict__ aux)
 {
     constexpr int D = 16 * NJ;
     constexpr int LDW = D + 4;
@@ -255,7 +257,27 @@ __global__ __launch_bounds__(256, 2) void gn_gemm_fwd_kernel(LinComb xin, int n_
     // solvers only - are completed after the panel).  With two waves per SIMD (LDS-bound occupancy) the loads of a
     // 3- or 4-term stage input are otherwise exposed.
     float4 nx[NJ];
-    load_tile<NJ, 2>(xin, (int64_t)(tile * 16 + mr) * D + 4 * mg, tile * 16 + mr < n_rows, nx);
+    LinComb xa = xin;                             // AUX: the same terms under the second coefficient vector
+    float4 na[NJ];                                // (dead code unless AUX)
+    if (AUX) {
+#pragma unroll
+        for (int j = 0; j < GODE_MAX_TERMS; ++j) xa.coef[j] = acoef.c[j];
+        // first tile: the pairwise issue / fold sequence (= the chain of load_tile_n) so that both sums come from one load
+        const int64_t base0 = (int64_t)(tile * 16 + mr) * D + 4 * mg;
+        const bool valid0 = tile * 16 + mr < n_rows;
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) { nx[j] = make_float4(0.f, 0.f, 0.f, 0.f); na[j] = nx[j]; }
+        float4 v0[2][NJ];
+#pragma unroll
+        for (int t0 = 0; t0 < GODE_MAX_TERMS; t0 += 2)
+            if (t0 < xin.n) {
+                issue_terms2<NJ>(xin, t0, base0, valid0, v0);
+                fold_terms2<NJ>(xin, t0, valid0, v0, nx);
+                fold_terms2<NJ>(xa, t0, valid0, v0, na);
+            }
+    } else {
+        load_tile<NJ, 2>(xin, (int64_t)(tile * 16 + mr) * D + 4 * mg, tile * 16 + mr < n_rows, nx);
+    }
     for (; tile < n_tiles; tile += stride) {
         const int row = tile * 16 + mr;
         const bool valid = row < n_rows;
@@ -266,6 +288,10 @@ __global__ __launch_bounds__(256, 2) void gn_gemm_fwd_kernel(LinComb xin, int n_
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
             if (xout != nullptr && valid) *reinterpret_cast<float4*>(xout + (int64_t)row * D + 16 * j + 4 * mg) = nx[j];
+            if (AUX) {
+                if (valid) *reinterpret_cast<float4*>(aux + (int64_t)row * D + 16 * j + 4 * mg) = na[j];
+                na[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+            }
             xv[j] = gn_forward_v<CG>(nx[j], eps, ld4(Gs + 16 * j + 4 * mg), ld4(Bs + 16 * j + 4 * mg));
             xv[j] = to_mfma_layout(xv[j], to_f);
             nx[j] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -280,11 +306,13 @@ __global__ __launch_bounds__(256, 2) void gn_gemm_fwd_kernel(LinComb xin, int n_
         issue_terms2<NJ>(xin, 0, nbase, nvalid, v);
         mfma_panel_part<NJ, 0, 2 * NJ>(Ws + 4 * g * LDW + r, xv, acc);
         fold_terms2<NJ>(xin, 0, nvalid, v, nx);
+        if (AUX) fold_terms2<NJ>(xa, 0, nvalid, v, na);
         issue_terms2<NJ>(xin, 2, nbase, nvalid, v);
         mfma_panel_part<NJ, 2 * NJ, 4 * NJ>(Ws + 4 * g * LDW + r, xv, acc);
         fold_terms2<NJ>(xin, 2, nvalid, v, nx);
-        if (xin.n > 4) { issue_terms2<NJ>(xin, 4, nbase, nvalid, v); fold_terms2<NJ>(xin, 4, nvalid, v, nx); }
-        if (xin.n > 6) { issue_terms2<NJ>(xin, 6, nbase, nvalid, v); fold_terms2<NJ>(xin, 6, nvalid, v, nx); }
+        if (AUX) fold_terms2<NJ>(xa, 2, nvalid, v, na);
+        if (xin.n > 4) { issue_terms2<NJ>(xin, 4, nbase, nvalid, v); fold_terms2<NJ>(xin, 4, nvalid, v, nx); if (AUX) fold_terms2<NJ>(xa, 4, nvalid, v, na); }
+        if (xin.n > 6) { issue_terms2<NJ>(xin, 6, nbase, nvalid, v); fold_terms2<NJ>(xin, 6, nvalid, v, nx); if (AUX) fold_terms2<NJ>(xa, 6, nvalid, v, na); }
 #pragma unroll
         for (int tt = 0; tt < NJ; ++tt) {
             const float4 o = acc_to_mem_layout(acc[tt], to_m);
@@ -1411,24 +1439,47 @@ extern "C" int gode_gn_time_gemm_xout_f32(const gode_lincomb_t* xin, int64_t n_r
                                           float eps, const float* gamma, const float* beta, const float* W,
                                           int64_t d_out, int has_time, float t, float* S, float* x_out, void* stream)
 {
+    return gode_gn_time_gemm_xout_aux_f32(xin, n_rows, d_in, groups, eps, gamma, beta, W, d_out, has_time, t, S, x_out,
+                                          nullptr, nullptr, stream);
+}
+
+// aux_out == nullptr: the plain launch.  With aux_out every branch below either launches a kernel that forms it or
+// returns GODE_E_UNSUPPORTED before anything is launched; the kernel taken is the one the plain launch would take.
+extern "C" int gode_gn_time_gemm_xout_aux_f32(const gode_lincomb_t* xin, int64_t n_rows, int64_t d_in, int32_t groups,
+                                              float eps, const float* gamma, const float* beta, const float* W,
+                                              int64_t d_out, int has_time, float t, float* S, float* x_out,
+                                              const float* aux_coef, float* aux_out, void* stream)
+{
     int rc = check_common(xin, n_rows, d_in, groups, d_out); if (rc) return rc;
+    if (aux_out && !aux_coef) return GODE_E_NULLPTR;
     if (n_rows == 0) return 0;
     if (!W || !S) return GODE_E_NULLPTR;
     if (x_out && (((uintptr_t)x_out) & 15)) return GODE_E_ALIGN;
+    if (aux_out && (((uintptr_t)aux_out) & 15)) return GODE_E_ALIGN;
+    if (aux_out) {
+        if (aux_out == S || aux_out == x_out) return GODE_E_RANGE;
+        for (int j = 0; j < xin->n; ++j) if (aux_out == xin->ptr[j]) return GODE_E_RANGE;
+    }
     has_time = has_time ? 1 : 0;
     hipStream_t s = (hipStream_t)stream;
     LinComb lc = make_lincomb(xin);
+    AuxCoef ac;
+    for (int j = 0; j < GODE_MAX_TERMS; ++j) ac.c[j] = (aux_out && j < lc.n) ? aux_coef[j] : 0.f;
     const int cg = fast_cg(d_in, d_out, groups);
     const bool al = lincomb_aligned16(xin) && !(((uintptr_t)S) & 15) && !(((uintptr_t)W) & 15) &&
                     (!gamma || !(((uintptr_t)gamma) & 15)) && (!beta || !(((uintptr_t)beta) & 15));
+    if (aux_out && !(cg >= 0 && al && d_in == 128)) return GODE_E_UNSUPPORTED;
     // producer / consumer form on the bf16 matrix cores (gemm_pc.hip): fwd_pc bit 0 = launches of <= 2 terms, bit 1 = 3
     // and more terms (with or without x_out)
     if (cg >= 0 && al && d_in == 128 && (n_rows >= kWgradSplitMinRows || gode_opt_wgrad_split_small()) &&
         ((lc.n <= 2 && !x_out) ? (gode_opt_fwd_pc() & 1) : (gode_opt_fwd_pc() & 2))) {
-        rc = gode_pc_fwd_launch(lc, n_rows, eps, gamma, beta, W, has_time, t, S, x_out, cg, s);
+        rc = gode_pc_fwd_launch(lc, n_rows, eps, gamma, beta, W, has_time, t, S, x_out, aux_coef, aux_out, cg, s);
         if (rc != GODE_E_UNSUPPORTED) return rc;
+        // with aux_out: no producer / consumer kernel for this term count, although the plain launch has one
+        if (aux_out && (cg == 0 || cg == 1 || cg == 2 || cg == 4)) return GODE_E_UNSUPPORTED;
     }
     if (cg >= 0 && al && d_in == 128 && !x_out && (gode_opt_gemm_split() == 1 || (gode_opt_gemm_split() == 2 && lc.n <= 2 && n_rows >= 65536))) {
+        if (aux_out) return GODE_E_UNSUPPORTED;                   // the split-bf16 kernel keeps no raw terms
         const size_t lds = (size_t)3 * 128 * (128 + 8) * sizeof(unsigned short) + 3 * 128 * sizeof(float);
         int64_t blocks = ((n_rows + 15) / 16 + 7) / 8; if (blocks < 1) blocks = 1; if (blocks > 256) blocks = 256;
 #define GODE_FWDS2(CGV, NXV) { rc = set_lds(gn_gemm_fwd_split_kernel<CGV, NXV>, lds); if (rc) return rc;    \
@@ -1451,10 +1502,24 @@ extern "C" int gode_gn_time_gemm_xout_f32(const gode_lincomb_t* xin, int64_t n_r
           const int slot = gode_prof_begin(s, d_in, n_rows, (int64_t)lc.n - 1 + (x_out ? 1 : 0), GODE_PROF_GEMM_FWD); \
           hipLaunchKernelGGL((gn_gemm_fwd_kernel<NJV, CGV>), dim3((unsigned)blocks), dim3(256), lds, s, \
                              lc, (int)n_rows, eps, gamma, beta, W, has_time, t, S, x_out,           \
-                             (const float*)nullptr, (float*)nullptr);                               \
+                             (const float*)nullptr, (float*)nullptr, ac, (float*)nullptr);          \
           gode_prof_end(s, slot);                                                                   \
           GODE_LAUNCH_CHECK(); return 0; }
+#define GODE_FWDA(NJV, CGV)                                                                         \
+        { rc = set_lds(gn_gemm_fwd_kernel<NJV, CGV, true>, lds); if (rc) return rc;                 \
+          const int slot = gode_prof_begin(s, d_in, n_rows, (int64_t)lc.n - 1 + (x_out ? 1 : 0) + 1, GODE_PROF_GEMM_FWD); \
+          hipLaunchKernelGGL((gn_gemm_fwd_kernel<NJV, CGV, true>), dim3((unsigned)blocks), dim3(256), lds, s, \
+                             lc, (int)n_rows, eps, gamma, beta, W, has_time, t, S, x_out,           \
+                             (const float*)nullptr, (float*)nullptr, ac, aux_out);                  \
+          gode_prof_end(s, slot);                                                                   \
+          GODE_LAUNCH_CHECK(); return 0; }
+        if (aux_out) {                                            // d_in == 128 (checked above): nj == 8
+            GODE_DISPATCH_NJ_CG(8, 0, GODE_FWDA) GODE_DISPATCH_NJ_CG(8, 1, GODE_FWDA)
+            GODE_DISPATCH_NJ_CG(8, 2, GODE_FWDA) GODE_DISPATCH_NJ_CG(8, 4, GODE_FWDA)
+            return GODE_E_UNSUPPORTED;
+        }
         GODE_DISPATCH_ALL(GODE_FWD)
+#undef GODE_FWDA
 #undef GODE_FWD
     }
     {
@@ -1503,7 +1568,7 @@ extern "C" int gode_gn_time_gemm_pair_f32(const gode_lincomb_t* xin, int64_t n_r
 #define GODE_FWDP(NJV, CGV)                                                                         \
         { rc = set_lds(gn_gemm_fwd_kernel<NJV, CGV>, lds); if (rc) return rc;                       \
           hipLaunchKernelGGL((gn_gemm_fwd_kernel<NJV, CGV>), dim3((unsigned)blocks, 2), dim3(256), lds, s, \
-                             lc, (int)n_rows, eps, gamma, beta, Wa, has_time, t, Sa, x_out, Wb, Sb);  \
+                             lc, (int)n_rows, eps, gamma, beta, Wa, has_time, t, Sa, x_out, Wb, Sb, AuxCoef(), (float*)nullptr);  \
           GODE_LAUNCH_CHECK(); return 0; }
         GODE_DISPATCH_ALL(GODE_FWDP)
 #undef GODE_FWDP

@@ -121,14 +121,18 @@ struct TileWalk {
 // NX = number of terms held raw in the producers' prefetch registers (1..4); 0 = any count, combined at load.
 // R  = rows per tile: 32.  (64-row tiles - twice the bytes in flight per producer group - were measured and are
 //      slower: two terms 0.326 against 0.282 ms, one term equal; tools/dev/pc_ab.py, same process, interleaved.)
+// AUX (NX > 0 only): aux[row, :] = sum_j acoef.c[j] x_j[row, :], a second combination of the raw terms the producers hold
+//      (the closing combination of an rk4 step beside the last stage's product), same multiply-add chain as the first.
 // ---------------------------------------------------------------------------------------------------------------
-template <int CG, int NX, bool XOUT, int R>
+template <int CG, int NX, bool XOUT, int R, bool AUX = false>
 __global__ __launch_bounds__(1024, 1) void gn_gemm_fwd_pc_kernel(LinComb xin, int n_rows, float eps,
                                                                 const float* __restrict__ gamma,
                                                                 const float* __restrict__ beta,
                                                                 const float* __restrict__ W, int has_time, float t,
-                                                                float* __restrict__ S, float* __restrict__ xout)
+                                                                float* __restrict__ S, float* __restrict__ xout,
+                                                                AuxCoef acoef, float* __restrict__ aux)
 {
+    static_assert(!AUX || NX > 0, "the second combination needs the raw terms");
     constexpr int PIECE_B = Img<R>::PIECE_B, BUF_B = Img<R>::BUF_B;
     constexpr int RPT = R / 8;                    // rows per staging thread
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -173,6 +177,16 @@ __global__ __launch_bounds__(1024, 1) void gn_gemm_fwd_pc_kernel(LinComb xin, in
                     }
                 }
                 if (XOUT && row < n_rows) *reinterpret_cast<float4*>(xout + (int64_t)row * D + tcol) = x;
+                if (AUX) {
+                    float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+                    for (int j = 0; j < NXR; ++j) {
+                        const float c = acoef.c[j];
+                        a.x = fmaf(c, xr[j][p].x, a.x); a.y = fmaf(c, xr[j][p].y, a.y);
+                        a.z = fmaf(c, xr[j][p].z, a.z); a.w = fmaf(c, xr[j][p].w, a.w);
+                    }
+                    if (row < n_rows) *reinterpret_cast<float4*>(aux + (int64_t)row * D + tcol) = a;
+                }
                 float4 xn = gn_forward_v<CG>(x, eps, gmv, btv);
                 if (row >= n_rows) xn = make_float4(0.f, 0.f, 0.f, 0.f);
                 stage_row4<PIECE_B>(img + p * LDK * 2, xn);
@@ -640,25 +654,36 @@ int set_lds_pc(K kernel, size_t bytes) { return gode_set_lds_once(reinterpret_ca
 }  // namespace
 
 int gode_pc_fwd_launch(const LinComb& lc, int64_t n_rows, float eps, const float* gamma, const float* beta,
-                       const float* W, int has_time, float t, float* S, float* xout, int cg, hipStream_t s)
+                       const float* W, int has_time, float t, float* S, float* xout, const float* aux_coef, float* aux,
+                       int cg, hipStream_t s)
 {
     int rc = 0;
-#define GODE_FPC4(CGV, NXV, XO, RV)                                                                               \
+    AuxCoef ac;
+    for (int j = 0; j < GODE_MAX_TERMS; ++j) ac.c[j] = (aux && j < lc.n) ? aux_coef[j] : 0.f;
+#define GODE_FPC5(CGV, NXV, XO, RV, AX)                                                                           \
     { const size_t lds = 2 * (size_t)Img<RV>::BUF_B;                                                               \
       const int64_t blocks = pc_blocks(n_rows, RV);                                                                \
-      rc = set_lds_pc(gn_gemm_fwd_pc_kernel<CGV, NXV, XO, RV>, lds); if (rc) return rc;                            \
-      const int slot = gode_prof_begin(s, D, n_rows, (int64_t)lc.n - 1 + (XO ? 1 : 0), GODE_PROF_GEMM_FWD | GODE_PROF_FORM_PC); \
-      hipLaunchKernelGGL((gn_gemm_fwd_pc_kernel<CGV, NXV, XO, RV>), dim3((unsigned)blocks), dim3(1024), lds, s,    \
-                         lc, (int)n_rows, eps, gamma, beta, W, has_time, t, S, xout);                             \
+      rc = set_lds_pc(gn_gemm_fwd_pc_kernel<CGV, NXV, XO, RV, AX>, lds); if (rc) return rc;                        \
+      const int slot = gode_prof_begin(s, D, n_rows, (int64_t)lc.n - 1 + (XO ? 1 : 0) + (AX ? 1 : 0), GODE_PROF_GEMM_FWD | GODE_PROF_FORM_PC); \
+      hipLaunchKernelGGL((gn_gemm_fwd_pc_kernel<CGV, NXV, XO, RV, AX>), dim3((unsigned)blocks), dim3(1024), lds, s, \
+                         lc, (int)n_rows, eps, gamma, beta, W, has_time, t, S, xout, ac, aux);                    \
       gode_prof_end(s, slot);                                                                                      \
       GODE_LAUNCH_CHECK(); return 0; }
-#define GODE_FPC2(CGV, NXV, RV) { if (xout) GODE_FPC4(CGV, NXV, true, RV) else GODE_FPC4(CGV, NXV, false, RV) }
+#define GODE_FPC2(CGV, NXV, RV) { if (xout) GODE_FPC5(CGV, NXV, true, RV, false) else GODE_FPC5(CGV, NXV, false, RV, false) }
 #define GODE_FPC(CGV) { switch (lc.n) { case 1: GODE_FPC2(CGV, 1, 32) case 2: GODE_FPC2(CGV, 2, 32) case 3: GODE_FPC2(CGV, 3, 32) \
                                         case 4: GODE_FPC2(CGV, 4, 32) default: GODE_FPC2(CGV, 0, 32) } }
+    // the second combination: four terms (the last stage of the 3/8 rule), the only count a driver asks it for
+#define GODE_FPCA(CGV) { if (xout) GODE_FPC5(CGV, 4, true, 32, true) else GODE_FPC5(CGV, 4, false, 32, true) }
+    if (aux) {
+        if (lc.n != 4) return GODE_E_UNSUPPORTED;
+        if (cg == 0) GODE_FPCA(0) else if (cg == 1) GODE_FPCA(1) else if (cg == 2) GODE_FPCA(2) else if (cg == 4) GODE_FPCA(4)
+        return GODE_E_UNSUPPORTED;
+    }
     if (cg == 0) GODE_FPC(0) else if (cg == 1) GODE_FPC(1) else if (cg == 2) GODE_FPC(2) else if (cg == 4) GODE_FPC(4)
+#undef GODE_FPCA
 #undef GODE_FPC
 #undef GODE_FPC2
-#undef GODE_FPC4
+#undef GODE_FPC5
     return GODE_E_UNSUPPORTED;
 }
 

@@ -86,6 +86,33 @@ bool fused_small(const gode_gcn_odefunc_t* f) {
 }
 gode_lincomb_t negated(gode_lincomb_t lc) { for (int j = 0; j < lc.n; ++j) lc.coef[j] = -lc.coef[j]; return lc; }
 
+// Closing combination of a step formed ONCE (option rk_close_once; large route: no fused launch, > 65 536 rows, d = 128).
+// The last stage's input  y + h (k0 - k1 + k2)  and the closing combination  P = y + h/8 k0 + 3h/8 k1 + 3h/8 k2  are
+// combinations of the same four arrays in the same order, so the launch that loads them for the one also stores the
+// other (dense product: aux output; SpMM: third output) and the closing launch reads {1.0, P} - one array instead of
+// four.  P is formed with the multiply-add chain every kernel forms a combination with (lc_load4_n), and a one-term
+// {1.0, P} reproduces P exactly, so every result keeps its bits.
+bool close_once_route(const gode_gcn_odefunc_t* f) {
+    return gode_opt_rk_close_once() && !fused_small(f) && f->n > kMergedFinishMaxRows && f->d == 128;
+}
+gode_lincomb_t one_term(const float* p) { gode_lincomb_t lc; lc.n = 1; lc.coef[0] = 1.f; lc.ptr[0] = p; return lc; }
+
+// Gf of a last stage that also leaves P in `p_out`.  *formed = false (and the plain launch issued) where the kernel the
+// options select cannot: the caller then closes the step from the four terms as before.
+int gf_last_stage(const gode_gcn_odefunc_t* f, const float* y, float* const* k, double h, float t, float* S, float* x_out,
+                  float* p_out, bool* formed, void* stream) {
+    const gode_lincomb_t xin = stage_terms(y, k, 3, h), pre = combine_terms(y, k, h);
+    *formed = false;
+    bool distinct = p_out != S && p_out != x_out;
+    for (int j = 0; j < xin.n; ++j) distinct = distinct && p_out != xin.ptr[j];
+    if (distinct && xin.n == pre.n) {       // same arrays in the same order (every A38[3][j] is non-zero)
+        const int rc = gode_gn_time_gemm_xout_aux_f32(&xin, f->n, f->d, f->groups, f->eps, f->gamma, f->beta, f->W, f->d, 1, t, S,
+                                                      x_out, pre.coef, p_out, stream);
+        if (rc != GODE_E_UNSUPPORTED) { *formed = rc == 0; return rc; }
+    }
+    return gode_gn_time_gemm_xout_f32(&xin, f->n, f->d, f->groups, f->eps, f->gamma, f->beta, f->W, f->d, 1, t, S, x_out, stream);
+}
+
 }  // namespace
 
 extern "C" int64_t gode_gcn_ode_theta_len(int64_t d) { return (d + 1) * d + 3 * d + 1; }
@@ -102,6 +129,7 @@ extern "C" int gode_gcn_ode_rk4_forward(const gode_gcn_odefunc_t* f, float* y, f
     float* cur = y;
     float* k[4] = {ws->ky[0], ws->ky[1], ws->ky[2], ws->ky[3]};
     const bool fused = fused_small(f);
+    const bool close_once = close_once_route(f);
     for (int i = 0; i < n_steps; ++i) {
         const double t = (double)t0 + i * h;
         for (int s = 0; s < 4; ++s) {
@@ -112,11 +140,16 @@ extern "C" int gode_gcn_ode_rk4_forward(const gode_gcn_odefunc_t* f, float* y, f
                                                   s == 3 ? &pre : nullptr, nullptr, nullptr, k[s], stream));
                 continue;
             }
-            GODE_TRY(gode_gn_time_gemm_f32(&xin, n, d, f->groups, f->eps, f->gamma, f->beta, f->W, d, 1,
-                                           (float)(t + C38[s] * h), ws->S, stream));
+            bool p_formed = false;                 // Gf(3) left the closing combination in k[3]: Sp(3) reads and overwrites it
+            if (s == 3 && close_once) {
+                GODE_TRY(gf_last_stage(f, cur, k, h, (float)(t + C38[s] * h), ws->S, nullptr, k[3], &p_formed, stream));
+            } else {
+                GODE_TRY(gode_gn_time_gemm_f32(&xin, n, d, f->groups, f->eps, f->gamma, f->beta, f->W, d, 1,
+                                               (float)(t + C38[s] * h), ws->S, stream));
+            }
             gode_spmm_epilogue_t ep = {};
             ep.bias = f->b; ep.relu = 1; ep.alpha = 1.f;
-            if (s == 3) { ep.pre = combine_terms(cur, k, h); ep.alpha = (float)(h * B38[3]); }
+            if (s == 3) { ep.pre = p_formed ? one_term(k[3]) : combine_terms(cur, k, h); ep.alpha = (float)(h * B38[3]); }
             GODE_TRY(spmm(f->A, ws->S, k[s], d, &ep, stream));
         }
         float* tmp = cur; cur = k[3]; k[3] = tmp;      // k[3] holds the new solution
@@ -206,6 +239,13 @@ extern "C" int gode_gcn_ode_rk4_adjoint(const gode_gcn_odefunc_t* f, float* y, f
         GODE_TRY(gode_gn_time_gemm_xout_f32(&yin0, n, d, f->groups, f->eps, f->gamma, f->beta, f->W, d, 1,
                                             (float)((double)t0), Sbuf[0], x_out_of(0), stream));
     }
+    // the closing combinations of a step formed once (bw branch): P_y by Gf of the last stage into ky[3], P_a by Sp(3) into
+    // ka[3]; Sp(3) and the stage-3 dense launch read and overwrite them in place, row by row (the SpMM's lane group and
+    // its finishing launch load the pre-terms of the row they then store; the consumer lane of the dense launch loads
+    // pre[row, c0..c0+3] and stores dx[row, c0..c0+3]).  ky[3] / ka[3] hold the state two steps back: their last readers
+    // are launches of the previous step on the caller's stream, ahead of these in stream order.
+    const bool close_once = bw && close_once_route(f);
+    bool py_formed = false;
     bool wg_pending = false;
     float stage_t[4] = {0.f, 0.f, 0.f, 0.f};
     for (int g = 0; g < total; ++g) {
@@ -245,7 +285,17 @@ extern "C" int gode_gcn_ode_rk4_adjoint(const gode_gcn_odefunc_t* f, float* y, f
             ? gode_spmm_y2_colsum_rows(f->A.items ? f->A.n_items : f->A.n_rows, f->A.items ? f->A.n_long : 0, d) : 0;
         if (y2rows > 0) ep.Y2_colsum = ws->y2_colsum;
         gode_lincomb_t apre; apre.n = 0;
-        if (s == 3) { ep.pre = combine_terms(ycur, ky, h); ep.alpha = (float)(h * B38[3]); apre = combine_terms(acur, ka, h); }
+        if (s == 3) {
+            ep.pre = py_formed ? one_term(ky[3]) : combine_terms(ycur, ky, h);
+            ep.alpha = (float)(h * B38[3]);
+            apre = combine_terms(acur, ka, h);
+            if (close_once && ain.n == apre.n) {              // the cotangent terms are a, ka0, ka1, ka2 in this order
+                ep.cot_out = ka[3];
+                for (int j = 0; j < apre.n; ++j) ep.cot_out_coef[j] = apre.coef[j];
+                apre = one_term(ka[3]);
+            }
+            py_formed = false;
+        }
         if (two && g > 0) GODE_HIP(hipStreamWaitEvent(hs, ov->gf, 0));          // S of this stage was produced on the side stream
         GODE_TRY(spmm(f->A, Sbuf[g & 1], ky[s], d, &ep, stream));               // Sp(g): k_y (or new y) and dZ
         // pointers as the NEXT stage will see them (the y-chain swaps buffers after stage 3)
@@ -285,9 +335,14 @@ extern "C" int gode_gcn_ode_rk4_adjoint(const gode_gcn_odefunc_t* f, float* y, f
             if (g + 1 < total) {                                                    // Gf(g+1), same stream as Sp(g+1)
                 const int i2 = (g + 1) / 4, s2 = (g + 1) % 4;
                 gode_lincomb_t yin2 = stage_terms(ycur_n, ky_n, s2, h);
-                GODE_TRY(gode_gn_time_gemm_xout_f32(&yin2, n, d, f->groups, f->eps, f->gamma, f->beta, f->W, d, 1,
-                                                    (float)((double)t0 + i2 * h + C38[s2] * h), Sbuf[(g + 1) & 1],
-                                                    x_out_of(g + 1), stream));
+                if (s2 == 3 && close_once) {
+                    GODE_TRY(gf_last_stage(f, ycur_n, ky_n, h, (float)((double)t0 + i2 * h + C38[s2] * h), Sbuf[(g + 1) & 1],
+                                           x_out_of(g + 1), ky_n[3], &py_formed, stream));
+                } else {
+                    GODE_TRY(gode_gn_time_gemm_xout_f32(&yin2, n, d, f->groups, f->eps, f->gamma, f->beta, f->W, d, 1,
+                                                        (float)((double)t0 + i2 * h + C38[s2] * h), Sbuf[(g + 1) & 1],
+                                                        x_out_of(g + 1), stream));
+                }
                 if (two) GODE_HIP(hipEventRecord(ov->gf, hs));      // the wait at the top of the next stage finds it done
             }
             // the side chain still reads dZ and the partial buffers, which Sp(g+1) and the next dense launch overwrite
@@ -546,6 +601,7 @@ extern "C" int gode_gcn_ode_rk4_forward_save(const gode_gcn_odefunc_t* f, const 
     const int64_t n = f->n, d = f->d, nd = n * d;
     const double h = ((double)t1 - (double)t0) / n_steps;
     const bool fused = fused_small(f);
+    const bool close_once = close_once_route(f);
     if (y0 != save) {                                            // record 0 starts with a copy of y0
         gode_lincomb_t c; c.n = 1; c.coef[0] = 1.f; c.ptr[0] = y0;
         GODE_TRY(gode_lincomb_f32(save, &c, nd, stream));
@@ -569,13 +625,18 @@ extern "C" int gode_gcn_ode_rk4_forward_save(const gode_gcn_odefunc_t* f, const 
                 }
                 continue;
             }
-            GODE_TRY(gode_gn_time_gemm_f32(&xin, n, d, f->groups, f->eps, f->gamma, f->beta, f->W, d, 1, ts, ws->S, stream));
+            bool p_formed = false;                 // as in gode_gcn_ode_rk4_forward; the combination goes where y_{n+1} will
+            if (s == 3 && close_once) {
+                GODE_TRY(gf_last_stage(f, y, k, h, ts, ws->S, nullptr, ynext, &p_formed, stream));
+            } else {
+                GODE_TRY(gode_gn_time_gemm_f32(&xin, n, d, f->groups, f->eps, f->gamma, f->beta, f->W, d, 1, ts, ws->S, stream));
+            }
             gode_spmm_epilogue_t ep = {};
             ep.bias = f->b; ep.relu = 1; ep.alpha = 1.f;
             if (s < 3) {
                 GODE_TRY(spmm(f->A, ws->S, k[s], d, &ep, stream));
             } else {
-                ep.pre = combine_terms(y, k, h); ep.alpha = (float)(h * B38[3]);
+                ep.pre = p_formed ? one_term(ynext) : combine_terms(y, k, h); ep.alpha = (float)(h * B38[3]);
                 GODE_TRY(spmm_save(f->A, ws->S, ynext, d, &ep, k[3], stream));
             }
         }

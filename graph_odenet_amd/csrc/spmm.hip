@@ -29,9 +29,13 @@ struct Epilogue {
                      // to colpart[b][d]; the finishing launch continues at row `colpart_row0`
     int64_t colpart_row0;
     float* K;        // nullable (gode_spmm_csr_save_f32): K = act(Z + bias), ld = d, before the combine with pre / alpha
+    float* Y3;       // nullable, with Y2: Y3 = sum_j c3[j] * cot.ptr[j] (unmasked), from the values loaded for Y2
+    float c3[GODE_MAX_TERMS];
 };
 
-template <int LPR>
+// OUT3: the launch has a third output (ep.Y3) - a variant of its own, so that the kernels every other product runs keep
+// their registers
+template <int LPR, bool OUT3 = false>
 __device__ __forceinline__ float4 epilogue_store4(const Epilogue& ep, float4 z, int row, int lane,
                                                   int64_t d, float* Y, int64_t ldy) {
     if (ep.bias) {
@@ -51,7 +55,14 @@ __device__ __forceinline__ float4 epilogue_store4(const Epilogue& ep, float4 z, 
     *reinterpret_cast<float4*>(Y + (int64_t)row * ldy + lane * 4) = y;
     if (ep.Y2) {
         const int64_t o = (int64_t)row * d + lane * 4;
-        float4 g = lc_load4(ep.cot, o);
+        float4 g;
+        if (OUT3) {              // a second combination of the cotangent terms, row by row beside Y2
+            float4 g3;
+            lc_load4_pair(ep.cot, ep.c3, o, g, g3);
+            *reinterpret_cast<float4*>(ep.Y3 + o) = g3;
+        } else {
+            g = lc_load4(ep.cot, o);
+        }
         g.x = z.x > 0.f ? g.x : 0.f; g.y = z.y > 0.f ? g.y : 0.f;
         g.z = z.z > 0.f ? g.z : 0.f; g.w = z.w > 0.f ? g.w : 0.f;
         *reinterpret_cast<float4*>(ep.Y2 + o) = g;
@@ -80,7 +91,7 @@ __device__ __forceinline__ void block_colsum_store(const float4 g, float* __rest
 }
 
 // d == 4*LPR, X/Y rows 16-byte aligned.
-template <int LPR>
+template <int LPR, bool OUT3 = false>
 __global__ __launch_bounds__(256) void spmm_vec4_kernel(
     const int* __restrict__ rowptr, const int* __restrict__ col, const float* __restrict__ val,
     const int4* __restrict__ items, int n_items, float* __restrict__ partial,
@@ -131,14 +142,14 @@ __global__ __launch_bounds__(256) void spmm_vec4_kernel(
     if (ep.colpart) {                                  // (block-uniform) nobody leaves before the block's column sums
         float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
         if (active) {
-            if (slot < 0) g = epilogue_store4<LPR>(ep, acc, row, lane, (int64_t)LPR * 4, Y, ldy);
+            if (slot < 0) g = epilogue_store4<LPR, OUT3>(ep, acc, row, lane, (int64_t)LPR * 4, Y, ldy);
             else *reinterpret_cast<float4*>(partial + (int64_t)slot * (LPR * 4) + lane * 4) = acc;
         }
         block_colsum_store<LPR>(g, ep.colpart + (int64_t)blockIdx.x * (LPR * 4));
         return;
     }
     if (!active) return;
-    if (slot < 0) epilogue_store4<LPR>(ep, acc, row, lane, (int64_t)LPR * 4, Y, ldy);
+    if (slot < 0) epilogue_store4<LPR, OUT3>(ep, acc, row, lane, (int64_t)LPR * 4, Y, ldy);
     else *reinterpret_cast<float4*>(partial + (int64_t)slot * (LPR * 4) + lane * 4) = acc;
 }
 
@@ -147,7 +158,7 @@ __global__ __launch_bounds__(256) void spmm_vec4_kernel(
 // long row costs len/(64/LPR) dependent gathers instead of len (on Cora at d=16 one 169-neighbour row was the whole
 // 34 us of the launch) and no row needs the split / finish pass.  Used when there are too few records to fill the
 // chip anyway (launch_vec4).
-template <int LPR>
+template <int LPR, bool OUT3 = false>
 __global__ __launch_bounds__(256) void spmm_vec4_wave_kernel(
     const int* __restrict__ rowptr, const int* __restrict__ col, const float* __restrict__ val,
     const int4* __restrict__ items, int n_items, float* __restrict__ partial,
@@ -194,11 +205,11 @@ __global__ __launch_bounds__(256) void spmm_vec4_wave_kernel(
         acc.z += __shfl_xor(acc.z, off, 64); acc.w += __shfl_xor(acc.w, off, 64);
     }
     if (sub != 0) return;
-    if (slot < 0) epilogue_store4<LPR>(ep, acc, row, lane, (int64_t)LPR * 4, Y, ldy);
+    if (slot < 0) epilogue_store4<LPR, OUT3>(ep, acc, row, lane, (int64_t)LPR * 4, Y, ldy);
     else *reinterpret_cast<float4*>(partial + (int64_t)slot * (LPR * 4) + lane * 4) = acc;
 }
 
-template <int LPR>
+template <int LPR, bool OUT3 = false>
 __global__ __launch_bounds__(256) void spmm_finish_vec4_kernel(
     const int4* __restrict__ long_rows, int n_long, const float* __restrict__ partial,
     float* __restrict__ Y, int64_t ldy, Epilogue ep)
@@ -227,11 +238,11 @@ __global__ __launch_bounds__(256) void spmm_finish_vec4_kernel(
     }
     if (ep.colpart) {
         float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (active) g = epilogue_store4<LPR>(ep, acc, lr.x, lane, (int64_t)LPR * 4, Y, ldy);
+        if (active) g = epilogue_store4<LPR, OUT3>(ep, acc, lr.x, lane, (int64_t)LPR * 4, Y, ldy);
         block_colsum_store<LPR>(g, ep.colpart + (ep.colpart_row0 + blockIdx.x) * (LPR * 4));
         return;
     }
-    epilogue_store4<LPR>(ep, acc, lr.x, lane, (int64_t)LPR * 4, Y, ldy);
+    epilogue_store4<LPR, OUT3>(ep, acc, lr.x, lane, (int64_t)LPR * 4, Y, ldy);
 }
 
 // Generic path: any d, any alignment.  A group of G lanes (power of two <= 64) owns a record.
@@ -247,6 +258,13 @@ __device__ __forceinline__ void epilogue_store1(const Epilogue& ep, float z, int
         const int64_t o = (int64_t)row * d + c;
         const float g = lc_load1(ep.cot, o);
         ep.Y2[o] = z > 0.f ? g : 0.f;
+        if (ep.Y3) {
+            float g3 = 0.f;
+#pragma unroll
+            for (int j = 0; j < GODE_MAX_TERMS; ++j)
+                if (j < ep.cot.n) g3 = fmaf(ep.c3[j], ep.cot.ptr[j][o], g3);
+            ep.Y3[o] = g3;
+        }
     }
 }
 
@@ -322,21 +340,21 @@ __global__ __launch_bounds__(256) void spmm_finish_generic_kernel(
     }
 }
 
-template <int LPR>
+template <int LPR, bool OUT3>
 int launch_vec4(const int* rowptr, const int* col, const float* val, const int4* items, int n_items,
                 const int4* long_rows, int n_long, float* partial, const float* X, int64_t ldx,
                 float* Y, int64_t ldy, const Epilogue& ep, hipStream_t s) {
     if (LPR < 64 && n_items > 0 && n_items <= 65536) {         // too few records to fill the chip: a wave per record
         if (ep.colpart) return GODE_E_UNSUPPORTED;             // (gode_spmm_y2_colsum_rows is 0 for such a graph)
         const int64_t wb = ((int64_t)n_items * 64 + 255) / 256;
-        const int slot = gode_prof_begin(s, (int64_t)LPR * 4, n_items, (int64_t)ep.pre.n + ep.cot.n + (ep.Y2 ? 1 : 0));
-        hipLaunchKernelGGL(spmm_vec4_wave_kernel<LPR>, dim3((unsigned)wb), dim3(256), 0, s,
+        const int slot = gode_prof_begin(s, (int64_t)LPR * 4, n_items, (int64_t)ep.pre.n + ep.cot.n + (ep.Y2 ? 1 : 0) + (ep.Y3 ? 1 : 0));
+        hipLaunchKernelGGL((spmm_vec4_wave_kernel<LPR, OUT3>), dim3((unsigned)wb), dim3(256), 0, s,
                            rowptr, col, val, items, n_items, partial, X, ldx, Y, ldy, ep);
         gode_prof_end(s, slot);
         GODE_LAUNCH_CHECK();
         if (n_long > 0) {
             const int64_t b2 = ((int64_t)n_long * LPR + 255) / 256;
-            hipLaunchKernelGGL(spmm_finish_vec4_kernel<LPR>, dim3((unsigned)b2), dim3(256), 0, s,
+            hipLaunchKernelGGL((spmm_finish_vec4_kernel<LPR, OUT3>), dim3((unsigned)b2), dim3(256), 0, s,
                                long_rows, n_long, partial, Y, ldy, ep);
             GODE_LAUNCH_CHECK();
         }
@@ -345,8 +363,8 @@ int launch_vec4(const int* rowptr, const int* col, const float* val, const int4*
     const int64_t threads = (int64_t)n_items * LPR;
     const int64_t blocks = (threads + 255) / 256;
     if (blocks > 0) {
-        const int slot = gode_prof_begin(s, (int64_t)LPR * 4, n_items, (int64_t)ep.pre.n + ep.cot.n + (ep.Y2 ? 1 : 0));
-        hipLaunchKernelGGL(spmm_vec4_kernel<LPR>, dim3((unsigned)blocks), dim3(256), 0, s,
+        const int slot = gode_prof_begin(s, (int64_t)LPR * 4, n_items, (int64_t)ep.pre.n + ep.cot.n + (ep.Y2 ? 1 : 0) + (ep.Y3 ? 1 : 0));
+        hipLaunchKernelGGL((spmm_vec4_kernel<LPR, OUT3>), dim3((unsigned)blocks), dim3(256), 0, s,
                            rowptr, col, val, items, n_items, partial, X, ldx, Y, ldy, ep);
         gode_prof_end(s, slot);
         GODE_LAUNCH_CHECK();
@@ -355,7 +373,7 @@ int launch_vec4(const int* rowptr, const int* col, const float* val, const int4*
         const int64_t b2 = ((int64_t)n_long * LPR + 255) / 256;
         Epilogue ep2 = ep;
         ep2.colpart_row0 = blocks;                             // its partial rows follow the main launch's
-        hipLaunchKernelGGL(spmm_finish_vec4_kernel<LPR>, dim3((unsigned)b2), dim3(256), 0, s,
+        hipLaunchKernelGGL((spmm_finish_vec4_kernel<LPR, OUT3>), dim3((unsigned)b2), dim3(256), 0, s,
                            long_rows, n_long, partial, Y, ldy, ep2);
         GODE_LAUNCH_CHECK();
     }
@@ -403,17 +421,24 @@ int spmm_csr_impl(const int32_t* rowptr, const int32_t* col, const float* val,
     ep.pre = make_lincomb(pre); ep.cot = make_lincomb(cot); ep.Y2 = Y2;
     ep.colpart = (epi && Y2) ? epi->Y2_colsum : nullptr; ep.colpart_row0 = 0;
     ep.K = K;
+    ep.Y3 = (epi && Y2) ? epi->cot_out : nullptr;
+    for (int j = 0; j < GODE_MAX_TERMS; ++j) ep.c3[j] = (ep.Y3 && j < ep.cot.n) ? epi->cot_out_coef[j] : 0.f;
+    if (ep.Y3) {
+        if (ep.Y3 == Y || ep.Y3 == Y2 || ep.Y3 == K) return GODE_E_RANGE;
+        for (int j = 0; j < ep.cot.n; ++j) if (ep.Y3 == ep.cot.ptr[j]) return GODE_E_RANGE;
+    }
     if (ep.colpart && ((((uintptr_t)ep.colpart) & 15) || gode_spmm_y2_colsum_rows(n_items, n_long, d) == 0)) return GODE_E_UNSUPPORTED;
 
     const bool al = !(((uintptr_t)X) & 15) && !(((uintptr_t)Y) & 15) && (ldx % 4 == 0) && (ldy % 4 == 0) &&
                     (!bias || !(((uintptr_t)bias) & 15)) && (!partial || !(((uintptr_t)partial) & 15)) &&
                     (!Y2 || (!(((uintptr_t)Y2) & 15) && lincomb_aligned16(cot))) && lincomb_aligned16(pre) &&
-                    !(((uintptr_t)K) & 15);
+                    !(((uintptr_t)K) & 15) && !(((uintptr_t)ep.Y3) & 15);
     const int4* it4 = reinterpret_cast<const int4*>(items);
     const int4* lr4 = reinterpret_cast<const int4*>(long_rows);
     if (al && d % 4 == 0) {
         switch (d / 4) {
-#define GODE_CASE(L) case L: return launch_vec4<L>(rowptr, col, val, it4, (int)n_items, lr4, (int)n_long, partial, X, ldx, Y, ldy, ep, s);
+#define GODE_CASE(L) case L: return ep.Y3 ? launch_vec4<L, true>(rowptr, col, val, it4, (int)n_items, lr4, (int)n_long, partial, X, ldx, Y, ldy, ep, s) \
+                                        : launch_vec4<L, false>(rowptr, col, val, it4, (int)n_items, lr4, (int)n_long, partial, X, ldx, Y, ldy, ep, s);
             GODE_CASE(1) GODE_CASE(2) GODE_CASE(4) GODE_CASE(8) GODE_CASE(16) GODE_CASE(32) GODE_CASE(64)
 #undef GODE_CASE
             default: break;
@@ -423,7 +448,7 @@ int spmm_csr_impl(const int32_t* rowptr, const int32_t* col, const float* val,
     int G = 1; while (G < d && G < 64) G <<= 1;
     if (d == 1 && it4 != nullptr) {                    // record lists only: whole short rows are cheaper one thread each
         const int64_t blocks = ((int64_t)n_items * 64 + 255) / 256;
-        const int slot = gode_prof_begin(s, 1, n_items, (int64_t)ep.pre.n + ep.cot.n + (ep.Y2 ? 1 : 0));
+        const int slot = gode_prof_begin(s, 1, n_items, (int64_t)ep.pre.n + ep.cot.n + (ep.Y2 ? 1 : 0) + (ep.Y3 ? 1 : 0));
         hipLaunchKernelGGL(spmv_wave_kernel, dim3((unsigned)blocks), dim3(256), 0, s,
                            rowptr, col, val, it4, (int)n_items, partial, X, ldx, Y, ldy, ep);
         gode_prof_end(s, slot);

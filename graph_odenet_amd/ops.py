@@ -34,10 +34,12 @@ def _need_terms(terms, name):
     return n
 
 
-def spmm(graph, X, bias=None, relu=False, out=None, cot_terms=None, out2=None, pre_terms=None, alpha=1.0, out2_colsum=None):
+def spmm(graph, X, bias=None, relu=False, out=None, cot_terms=None, out2=None, pre_terms=None, alpha=1.0, out2_colsum=None,
+         cot_out=None, cot_out_coefs=None):
     """Y = (sum pre_terms) + alpha * relu?(A @ X + bias); optionally out2 = (sum cot_terms) * (A@X+bias > 0).
     out2_colsum ([spmm_y2_colsum_rows(graph, d), d], with cot_terms): the launch also leaves per-block column sums of out2
-    there - their sum over the rows is out2.sum(0)."""
+    there - their sum over the rows is out2.sum(0).
+    cot_out / cot_out_coefs (with cot_terms): third output, sum_j cot_out_coefs[j] * cot tensor j (unmasked)."""
     lib = _lib.load()
     _need(X, "X")
     _need(bias, "bias")
@@ -86,6 +88,15 @@ def spmm(graph, X, bias=None, relu=False, out=None, cot_terms=None, out2=None, p
                 if out2_colsum.numel() != spmm_y2_colsum_rows(graph, d) * d or out2_colsum.numel() == 0:
                     raise ValueError("spmm: out2_colsum must be spmm_y2_colsum_rows(graph, d) x d (and the shape must support it)")
                 ep.Y2_colsum = out2_colsum.data_ptr()
+            if cot_out is not None:
+                _need(cot_out, "cot_out")
+                if cot_out.numel() != graph.n_rows * d or cot_out_coefs is None or len(cot_out_coefs) != len(cot_terms):
+                    raise ValueError("spmm: cot_out must be n_rows x d with one coefficient per cotangent term")
+                ep.cot_out = cot_out.data_ptr()
+                for j, cj in enumerate(cot_out_coefs):
+                    ep.cot_out_coef[j] = float(cj)
+        elif cot_out is not None:
+            raise ValueError("spmm: cot_out needs cot_terms")
     partial = graph.partial(d)
     rc = lib.gode_spmm_csr_f32(ptr(graph.rowptr), ptr(graph.col), ptr(graph.val),
                                ptr(graph.items), graph.n_items,
@@ -181,8 +192,11 @@ def rk_scaled_sumsq(terms, y, rtol, atol, out=None):
     return out
 
 
-def gn_time_gemm(x_terms, n_rows, d_in, groups, eps, gamma, beta, W, has_time, t, out=None, x_out=None):
-    """S = [t | GroupNorm(sum x_terms)] @ W   (W is (d_in+has_time) x d_out); x_out (optional) receives sum x_terms."""
+def gn_time_gemm(x_terms, n_rows, d_in, groups, eps, gamma, beta, W, has_time, t, out=None, x_out=None, aux_coefs=None,
+                 aux_out=None):
+    """S = [t | GroupNorm(sum x_terms)] @ W   (W is (d_in+has_time) x d_out); x_out (optional) receives sum x_terms.
+    aux_out / aux_coefs (optional): aux_out = sum_j aux_coefs[j] * x tensor j, a second combination of the same terms from
+    the same loads; raises where the kernel selected for the shape cannot form it."""
     lib = _lib.load()
     _need(W, "W"); _need(gamma, "gamma"); _need(beta, "beta")
     if _need_terms(x_terms, "x") != n_rows * d_in:
@@ -198,6 +212,15 @@ def gn_time_gemm(x_terms, n_rows, d_in, groups, eps, gamma, beta, W, has_time, t
         _need(x_out, "x_out")
         if x_out.numel() != n_rows * d_in:
             raise ValueError("gn_time_gemm: x_out has wrong size")
+    if aux_out is not None:
+        _need(aux_out, "aux_out")
+        if aux_out.numel() != n_rows * d_in or aux_coefs is None or len(aux_coefs) != len(x_terms):
+            raise ValueError("gn_time_gemm: aux_out must be n_rows x d_in with one coefficient per term")
+        ac = (ctypes.c_float * len(aux_coefs))(*[float(c) for c in aux_coefs])
+        check(lib.gode_gn_time_gemm_xout_aux_f32(ctypes.byref(lc), n_rows, d_in, groups, float(eps), ptr(gamma), ptr(beta),
+                                                 ptr(W), d_out, 1 if has_time else 0, float(t), ptr(out), ptr(x_out),
+                                                 ac, ptr(aux_out), stream_ptr()), "gode_gn_time_gemm_xout_aux_f32")
+        return out
     check(lib.gode_gn_time_gemm_xout_f32(ctypes.byref(lc), n_rows, d_in, groups, float(eps), ptr(gamma), ptr(beta),
                                          ptr(W), d_out, 1 if has_time else 0, float(t), ptr(out), ptr(x_out),
                                          stream_ptr()), "gode_gn_time_gemm_xout_f32")

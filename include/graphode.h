@@ -69,7 +69,9 @@ int         gode_abi_version(void);
  * the bf16-piece kernels below 65 536 rows too), "bwd_pc" (1 default / 0: the VJP at d = 128 and >= 65 536 rows in the
  * same exact bf16-piece arithmetic, producer / consumer form, csrc/gemm_pc.hip; 0: fp32-MFMA kernel), "fwd_pc" (3
  * default: the forward product likewise - bit 0: launches of <= 2 terms, bit 1: launches of >= 3 terms or with x_out;
- * 0: the round-2 selection by "gemm_split").  Initial values come from GODE_GEMM_SPLIT / GODE_OVERLAP /
+ * 0: the round-2 selection by "gemm_split"), "rk_close_once" (1 default / 0: above 65 536 rows at d = 128 the rk4
+ * drivers form the closing combination of a step once, in the launch that already holds its terms, instead of loading
+ * the four arrays again in the closing launch; same bits either way).  Initial values come from GODE_GEMM_SPLIT / GODE_OVERLAP /
  * GODE_WGRAD_SPLIT / GODE_BWD_PC / GODE_FWD_PC.
  * Returns 0 or GODE_E_UNSUPPORTED. */
 int         gode_set_option(const char* name, int value);
@@ -103,6 +105,10 @@ typedef struct gode_spmm_epilogue {
     float*         Y2_colsum; /* nullable, with Y2: per-block column sums of the rows of Y2 - gode_spmm_y2_colsum_rows(n_items,
                                n_long, d) rows of d floats (16-byte aligned); their sum over the rows (gode_colsum_f32 on this
                                array) is colsum(Y2), the bias gradient of the layer, without reading Y2 again */
+    float*         cot_out;   /* nullable, with Y2: third output  cot_out = sum_j cot_out_coef[j]*cot.ptr[j]  (n_rows x d, ld = d;
+                               unmasked) - a second combination of the cotangent terms, formed from the values the launch has
+                               loaded for Y2 with the multiply-add chain of gode_lincomb_f32.  Must not be one of the terms */
+    float          cot_out_coef[GODE_MAX_TERMS];
 } gode_spmm_epilogue_t;
 
 /* rows of the Y2_colsum array for a graph's record lists (0: the shape runs on kernels without it - small graphs,
@@ -176,6 +182,18 @@ int gode_gn_time_gemm_xout_f32(const gode_lincomb_t* xin /* host */, int64_t n_r
                                int32_t groups, float eps, const float* gamma, const float* beta,
                                const float* W, int64_t d_out, int has_time, float t,
                                float* S, float* x_out, void* stream);
+/* Same, and additionally aux_out[i,:] = sum_j aux_coef[j]*xin.ptr[j][i,:]: a second combination of the SAME terms (host
+ * aux_coef[xin.n]), formed from the term values the launch has loaded anyway with the multiply-add chain of
+ * gode_lincomb_f32 (bit for bit that launch's result).  aux_out: n_rows x d_in contiguous, 16-byte aligned, none of the
+ * terms.  The rk4 drivers use it to leave the closing combination y + h sum b_j k_j of a step beside the last stage's
+ * product.  GODE_E_UNSUPPORTED - and nothing launched - where the kernel the options select for the shape cannot form it
+ * (it can at d_in = d_out = 128 with 16-byte aligned operands: the producer / consumer kernels with 4 terms, the
+ * fp32-MFMA kernel with any count); S and x_out are bit for bit those of gode_gn_time_gemm_xout_f32. */
+int gode_gn_time_gemm_xout_aux_f32(const gode_lincomb_t* xin /* host */, int64_t n_rows, int64_t d_in,
+                                   int32_t groups, float eps, const float* gamma, const float* beta,
+                                   const float* W, int64_t d_out, int has_time, float t,
+                                   float* S, float* x_out /* nullable */, const float* aux_coef /* host */,
+                                   float* aux_out, void* stream);
 
 /* Two square products (d_out = d_in = d) over the same input in one launch: Sa = [t | xn] Wa, Sb = [t | xn] Wb
  * (the two message projections of the GAT ODE function); x_out as above. */
