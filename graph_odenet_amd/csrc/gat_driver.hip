@@ -6,39 +6,12 @@
 // and the error-ratio sums, so that an adaptive step on a citation-size graph is one call instead of ~200.
 // The launch sequence of one evaluation is graph_odenet_amd/gat_ode.py (GatOdeField / GatOdeAdjointField), which
 // branches on the head count where this file does.
-#include "common.h"
+#include "rk_driver.h"
 #include "options.h"
 
 namespace {
 
-#define GODE_TRY(expr) do { int rc__ = (expr); if (rc__) return rc__; } while (0)
-#define GODE_HIP(expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) return (int)e__; } while (0)
-
-const double DPC[7] = {0.0, 1.0 / 5, 3.0 / 10, 4.0 / 5, 8.0 / 9, 1.0, 1.0};
-const double DPA[7][6] = {
-    {0, 0, 0, 0, 0, 0},
-    {1.0 / 5, 0, 0, 0, 0, 0},
-    {3.0 / 40, 9.0 / 40, 0, 0, 0, 0},
-    {44.0 / 45, -56.0 / 15, 32.0 / 9, 0, 0, 0},
-    {19372.0 / 6561, -25360.0 / 2187, 64448.0 / 6561, -212.0 / 729, 0, 0},
-    {9017.0 / 3168, -355.0 / 33, 46732.0 / 5247, 49.0 / 176, -5103.0 / 18656, 0},
-    {35.0 / 384, 0, 500.0 / 1113, 125.0 / 192, -2187.0 / 6784, 11.0 / 84},
-};
-const double DPB[7] = {35.0 / 384, 0, 500.0 / 1113, 125.0 / 192, -2187.0 / 6784, 11.0 / 84, 0};
-const double DPE[7] = {35.0 / 384 - 1951.0 / 21600, 0, 500.0 / 1113 - 22642.0 / 50085, 125.0 / 192 - 451.0 / 720,
-                       -2187.0 / 6784 - -12231.0 / 42400, 11.0 / 84 - 649.0 / 6300, -1.0 / 60.0};
-
-gode_lincomb_t dp_terms(const float* y, float* const* k, const double* coef, int count, double h, bool with_y, int64_t off = 0) {
-    gode_lincomb_t lc;
-    lc.n = 0;
-    if (with_y) { lc.coef[0] = 1.f; lc.ptr[0] = y + off; lc.n = 1; }
-    for (int j = 0; j < count; ++j)
-        if (coef[j] != 0.0) { lc.coef[lc.n] = (float)(h * coef[j]); lc.ptr[lc.n] = k[j] + off; ++lc.n; }
-    return lc;
-}
-
 inline int64_t n_heads(const gode_gat_odefunc_t* f) { return f->heads > 1 ? f->heads : 1; }
-constexpr int64_t kMergedFinishMaxRows = 1 << 16;      // as graph_odenet_amd/gat_ode.py: MERGED_FINISH_MAX_ROWS
 
 // projections as the edge kernels see them: with H heads the n x (H*o) matrices ARE the (n*H) x o matrices of the
 // virtual nodes (row stride o), and A2 (n x 2H) is (n*H) x 2

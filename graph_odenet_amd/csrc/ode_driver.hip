@@ -6,41 +6,36 @@
 // sequence of an rk4 (3/8 rule) forward solve or adjoint solve from C with no allocation and no
 // synchronisation, which also makes the call capturable into a HIP graph by the caller.
 // Launch sequence per stage = graph_odenet_amd/gcn_ode.py (GcnOdeField / GcnOdeAdjointField).
+//
+// Every launch sequence is stated once (tables and term lists: rk_driver.h):
+//   feval_large         Gf then Sp of one evaluation on the large route (optionally closing a step, optionally keeping k_4)
+//   rk4_forward_step    one step of the forward solve, fused or large route
+//   close_bias / close_weight / close_affine    the reductions that close a stage's parameter derivative, large route
+//   stage_finish_merged the same as ONE launch, launch-bound sizes
+//   rk4_adjoint_small   the fused launch-bound schedule of the adjoint solve
+//   sweep_pre           the four terms a backprop step's last launch adds up to abar_n
+// and the entry points compose them:
+//   gode_gcn_ode_rk4_forward, gode_gcn_ode_rk4_forward_save   rk4_forward_step per step (swapping buffers / into records)
+//   gode_gcn_ode_rk4_adjoint     rk4_adjoint_small, or the two-chain loop: Gf (one lambda), Sp, SpT, dense VJP, close_*
+//   gode_gcn_ode_dopri5_step_*   dp_eval_forward (feval_large) / dp_eval_adjoint (close_*) per stage
+//   gode_gcn_ode_rk4_backprop    the fused sweep, or per stage masked cotangent, SpT, dense VJP, close_*
 #include <map>
 #include <mutex>
 #include <utility>
-#include "common.h"
+#include "rk_driver.h"
 #include "options.h"
 
 namespace {
 
-// step size, stage times and h*coefficient products are formed in double and rounded once, exactly as the
-// Python driver (solver.py) does, so both drivers feed identical fp32 coefficients to the kernels
-const double C38[4] = {0.0, 1.0 / 3.0, 2.0 / 3.0, 1.0};
-const double A38[4][3] = {{0.0, 0.0, 0.0}, {1.0 / 3.0, 0.0, 0.0}, {-1.0 / 3.0, 1.0, 0.0}, {1.0, -1.0, 1.0}};
-const double B38[4] = {1.0 / 8.0, 3.0 / 8.0, 3.0 / 8.0, 1.0 / 8.0};
-
-// terms of  y + h * sum_{j<s} A38[s][j] * k[j]
-gode_lincomb_t stage_terms(const float* y, float* const* k, int s, double h) {
-    gode_lincomb_t lc;
-    lc.n = 0;
-    lc.coef[lc.n] = 1.f; lc.ptr[lc.n] = y; ++lc.n;
-    for (int j = 0; j < s; ++j)
-        if (A38[s][j] != 0.0) { lc.coef[lc.n] = (float)(h * A38[s][j]); lc.ptr[lc.n] = k[j]; ++lc.n; }
-    return lc;
-}
-// terms of  y + h * sum_{j<3} B38[j] * k[j]   (the last stage is folded into the producing launch)
-gode_lincomb_t combine_terms(const float* y, float* const* k, double h) {
-    gode_lincomb_t lc;
-    lc.n = 0;
-    lc.coef[lc.n] = 1.f; lc.ptr[lc.n] = y; ++lc.n;
-    for (int j = 0; j < 3; ++j) { lc.coef[lc.n] = (float)(h * B38[j]); lc.ptr[lc.n] = k[j]; ++lc.n; }
-    return lc;
-}
-
 int spmm(const gode_graph_t& g, const float* X, float* Y, int64_t d, const gode_spmm_epilogue_t* ep, void* s) {
     return gode_spmm_csr_f32(g.rowptr, g.col, g.val, g.items, g.n_items, g.long_rows, g.n_long, g.partial,
                              X, d, Y, d, g.n_rows, d, ep, s);
+}
+// relu(. + b): the epilogue of every Sp
+gode_spmm_epilogue_t relu_bias_epilogue(const gode_gcn_odefunc_t* f) {
+    gode_spmm_epilogue_t ep = {};
+    ep.bias = f->b; ep.relu = 1; ep.alpha = 1.f;
+    return ep;
 }
 
 // theta-k layout: [ W ((d+1)*d) | b (d) | gamma (d) | beta (d) | a_t (1) ]
@@ -57,13 +52,34 @@ __global__ void theta_fixup_kernel(float* ktheta, const float* W, float t, int d
     for (int c = threadIdx.x; c < d; c += blockDim.x) ktheta[c] *= t;
 }
 
-#define GODE_TRY(expr) do { int rc__ = (expr); if (rc__) return rc__; } while (0)
+// Closing a stage's parameter derivative kt on the large route, slot by slot (the schedules place the three on different
+// streams, with launches and event waits between them).
+// b: column sums of `src` - dZ itself (n rows), or the per-block column sums an earlier launch of the stage left
+int close_bias(const gode_gcn_odefunc_t* f, const gode_rk4_workspace_t* ws, float* kt, const float* src, int64_t rows,
+               void* stream) {
+    return gode_colsum_f32(kt + (f->d + 1) * f->d, src, rows, f->d, 1.f, 0, ws->colsum_scratch, stream);
+}
+// W from the `parts` block partials in ws->wpart, then the time-row bookkeeping (a_t; row 0 *= ts)
+int close_weight(const gode_gcn_odefunc_t* f, const gode_rk4_workspace_t* ws, float* kt, int64_t parts, float ts,
+                 void* stream) {
+    const int64_t d = f->d;
+    GODE_TRY(gode_reduce_parts_f32(kt, ws->wpart, parts, (d + 1) * d, 1.f, 0, stream));
+    hipLaunchKernelGGL(theta_fixup_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, kt, f->W, ts, (int)d,
+                       gode_gcn_ode_theta_len(d) - 1);
+    GODE_LAUNCH_CHECK();
+    return 0;
+}
+// gamma, beta from the dense VJP's block partials (zeros without GroupNorm)
+int close_affine(const gode_gcn_odefunc_t* f, const gode_rk4_workspace_t* ws, float* kt, void* stream) {
+    const int64_t d = f->d;
+    float* kg = kt + (d + 1) * d + d;
+    if (f->groups <= 0) return gode_zero_f32(kg, 2 * d, stream);
+    return gode_reduce_parts2_f32(kg, ws->gpart, kg + d, ws->bpart, gode_gemm_bwd_parts(f->n), d, 1.f, 0, stream);
+}
 
 // Launch-bound graphs: the four reduction launches that close an adjoint stage (weight-gradient partials, time-row
-// bookkeeping, bias column sums, GroupNorm affine partials) as ONE launch (rk.hip: reduce_segments_kernel).  Above this
-// many rows the separate launches are kept: the weight-gradient reduction has a 16-byte form that matters there.
-constexpr int64_t kMergedFinishMaxRows = 1 << 16;
-
+// bookkeeping, bias column sums, GroupNorm affine partials) as ONE launch (rk.hip: reduce_segments_kernel), up to
+// kMergedFinishMaxRows rows.
 // kt = [W | b | gamma | beta | a_t] from ws->wpart, colsum partials of dZ, ws->gpart / ws->bpart
 int stage_finish_merged(const gode_gcn_odefunc_t* f, const gode_rk4_workspace_t* ws, float* kt, float ts, void* stream) {
     const int64_t n = f->n, d = f->d, nW = (d + 1) * d, P = gode_gcn_ode_theta_len(d);
@@ -84,7 +100,6 @@ int stage_finish_merged(const gode_gcn_odefunc_t* f, const gode_rk4_workspace_t*
 bool fused_small(const gode_gcn_odefunc_t* f) {
     return gode_opt_small_fused() && gode_gcn_small_supported(f->n, f->d, f->groups);
 }
-gode_lincomb_t negated(gode_lincomb_t lc) { for (int j = 0; j < lc.n; ++j) lc.coef[j] = -lc.coef[j]; return lc; }
 
 // Closing combination of a step formed ONCE (option rk_close_once; large route: no fused launch, > 65 536 rows, d = 128).
 // The last stage's input  y + h (k0 - k1 + k2)  and the closing combination  P = y + h/8 k0 + 3h/8 k1 + 3h/8 k2  are
@@ -95,13 +110,11 @@ gode_lincomb_t negated(gode_lincomb_t lc) { for (int j = 0; j < lc.n; ++j) lc.co
 bool close_once_route(const gode_gcn_odefunc_t* f) {
     return gode_opt_rk_close_once() && !fused_small(f) && f->n > kMergedFinishMaxRows && f->d == 128;
 }
-gode_lincomb_t one_term(const float* p) { gode_lincomb_t lc; lc.n = 1; lc.coef[0] = 1.f; lc.ptr[0] = p; return lc; }
 
-// Gf of a last stage that also leaves P in `p_out`.  *formed = false (and the plain launch issued) where the kernel the
-// options select cannot: the caller then closes the step from the four terms as before.
-int gf_last_stage(const gode_gcn_odefunc_t* f, const float* y, float* const* k, double h, float t, float* S, float* x_out,
-                  float* p_out, bool* formed, void* stream) {
-    const gode_lincomb_t xin = stage_terms(y, k, 3, h), pre = combine_terms(y, k, h);
+// Gf of a last stage (input terms xin) that also leaves P (terms pre) in `p_out`.  *formed = false (and the plain launch
+// issued) where the kernel the options select cannot: the caller then closes the step from the four terms as before.
+int gf_last_stage(const gode_gcn_odefunc_t* f, const gode_lincomb_t& xin, const gode_lincomb_t& pre, float t, float* S,
+                  float* x_out, float* p_out, bool* formed, void* stream) {
     *formed = false;
     bool distinct = p_out != S && p_out != x_out;
     for (int j = 0; j < xin.n; ++j) distinct = distinct && p_out != xin.ptr[j];
@@ -111,6 +124,49 @@ int gf_last_stage(const gode_gcn_odefunc_t* f, const float* y, float* const* k, 
         if (rc != GODE_E_UNSUPPORTED) { *formed = rc == 0; return rc; }
     }
     return gode_gn_time_gemm_xout_f32(&xin, f->n, f->d, f->groups, f->eps, f->gamma, f->beta, f->W, f->d, 1, t, S, x_out, stream);
+}
+
+// How an evaluation closes a step:  out = sum pre + alpha * f(t, x);  once: the closing-combination-once route
+struct StepClose { gode_lincomb_t pre; float alpha; bool once; };
+
+// Gf then Sp of one evaluation on the large route: out = f(t, sum xin) through S, or the closed step (`close`).  On the
+// once route Gf leaves the closing combination in `out`, which Sp then reads and overwrites.  k_save: Sp also stores the
+// plain derivative there (the k_4 a backprop record keeps).
+int feval_large(const gode_gcn_odefunc_t* f, const gode_lincomb_t& xin, float t, float* S, float* out,
+                const StepClose* close, float* k_save, void* stream) {
+    const int64_t d = f->d;
+    bool p_formed = false;
+    if (close && close->once) {
+        GODE_TRY(gf_last_stage(f, xin, close->pre, t, S, nullptr, out, &p_formed, stream));
+    } else {
+        GODE_TRY(gode_gn_time_gemm_f32(&xin, f->n, d, f->groups, f->eps, f->gamma, f->beta, f->W, d, 1, t, S, stream));
+    }
+    gode_spmm_epilogue_t ep = relu_bias_epilogue(f);
+    if (close) { ep.pre = p_formed ? one_term(out) : close->pre; ep.alpha = close->alpha; }
+    if (!k_save) return spmm(f->A, S, out, d, &ep, stream);
+    const gode_graph_t& g = f->A;
+    return gode_spmm_csr_save_f32(g.rowptr, g.col, g.val, g.items, g.n_items, g.long_rows, g.n_long, g.partial,
+                                  S, d, out, d, g.n_rows, d, &ep, k_save, stream);
+}
+
+// One step of the forward solve from y at time t: k_1..k_3 into k[0..2], y_{n+1} into ynext (which may be k[3]: the
+// folded last stage never materialises k_4) - or, keep_k4, k_4 into k[3] as well (ynext is then another array).
+int rk4_forward_step(const gode_gcn_odefunc_t* f, const gode_rk4_workspace_t* ws, const float* y, float* const* k,
+                     float* ynext, bool keep_k4, double t, double h, bool fused, bool close_once, void* stream) {
+    for (int s = 0; s < 4; ++s) {
+        const gode_lincomb_t xin = stage_terms(y, k, s, h);
+        const float ts = (float)(t + C38[s] * h);
+        if (s < 3) {
+            if (fused) GODE_TRY(gode_gcn_feval_small_f32(f, &xin, ts, 1.f, nullptr, nullptr, nullptr, k[s], stream));
+            else GODE_TRY(feval_large(f, xin, ts, ws->S, k[s], nullptr, nullptr, stream));
+            continue;
+        }
+        const StepClose close = {combine_terms(y, k, h), (float)(h * B38[3]), close_once};
+        if (!fused) GODE_TRY(feval_large(f, xin, ts, ws->S, ynext, &close, keep_k4 ? k[3] : nullptr, stream));
+        else if (keep_k4) GODE_TRY(gode_gcn_feval_small_save_f32(f, &xin, ts, close.alpha, &close.pre, ynext, k[3], stream));
+        else GODE_TRY(gode_gcn_feval_small_f32(f, &xin, ts, close.alpha, &close.pre, nullptr, nullptr, ynext, stream));
+    }
+    return 0;
 }
 
 }  // namespace
@@ -124,34 +180,13 @@ extern "C" int gode_gcn_ode_rk4_forward(const gode_gcn_odefunc_t* f, float* y, f
     if (!f || !y || !ws || !result) return GODE_E_NULLPTR;
     if (n_steps <= 0 || f->n <= 0 || f->d <= 0) return GODE_E_SHAPE;
     if (!ws->S || !ws->ky[0] || !ws->ky[1] || !ws->ky[2] || !ws->ky[3]) return GODE_E_NULLPTR;
-    const int64_t n = f->n, d = f->d;
     const double h = ((double)t1 - (double)t0) / n_steps;
     float* cur = y;
     float* k[4] = {ws->ky[0], ws->ky[1], ws->ky[2], ws->ky[3]};
     const bool fused = fused_small(f);
     const bool close_once = close_once_route(f);
     for (int i = 0; i < n_steps; ++i) {
-        const double t = (double)t0 + i * h;
-        for (int s = 0; s < 4; ++s) {
-            gode_lincomb_t xin = stage_terms(cur, k, s, h);
-            if (fused) {
-                gode_lincomb_t pre = combine_terms(cur, k, h);
-                GODE_TRY(gode_gcn_feval_small_f32(f, &xin, (float)(t + C38[s] * h), s == 3 ? (float)(h * B38[3]) : 1.f,
-                                                  s == 3 ? &pre : nullptr, nullptr, nullptr, k[s], stream));
-                continue;
-            }
-            bool p_formed = false;                 // Gf(3) left the closing combination in k[3]: Sp(3) reads and overwrites it
-            if (s == 3 && close_once) {
-                GODE_TRY(gf_last_stage(f, cur, k, h, (float)(t + C38[s] * h), ws->S, nullptr, k[3], &p_formed, stream));
-            } else {
-                GODE_TRY(gode_gn_time_gemm_f32(&xin, n, d, f->groups, f->eps, f->gamma, f->beta, f->W, d, 1,
-                                               (float)(t + C38[s] * h), ws->S, stream));
-            }
-            gode_spmm_epilogue_t ep = {};
-            ep.bias = f->b; ep.relu = 1; ep.alpha = 1.f;
-            if (s == 3) { ep.pre = p_formed ? one_term(k[3]) : combine_terms(cur, k, h); ep.alpha = (float)(h * B38[3]); }
-            GODE_TRY(spmm(f->A, ws->S, k[s], d, &ep, stream));
-        }
+        GODE_TRY(rk4_forward_step(f, ws, cur, k, k[3], false, (double)t0 + i * h, h, fused, close_once, stream));
         float* tmp = cur; cur = k[3]; k[3] = tmp;      // k[3] holds the new solution
     }
     *result = cur;
@@ -187,7 +222,38 @@ Overlap* overlap_ctx(hipStream_t caller) {
     ctxs[key] = c;
     return c;
 }
-#define GODE_HIP(expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) return (int)e__; } while (0)
+
+// Launch-bound graphs, fused launches: two per stage - f-eval (+ masked cotangent dZ), VJP (+ block partials) - and one
+// more per step; a single stream.
+int rk4_adjoint_small(const gode_gcn_odefunc_t* f, const gode_rk4_workspace_t* ws, float* y, float* a, float* theta,
+                      float** y_result, float** a_result, float t0, double h, int32_t n_steps, void* stream) {
+    float* ycur = y; float* acur = a;
+    float* ky[4] = {ws->ky[0], ws->ky[1], ws->ky[2], ws->ky[3]};
+    float* ka[4] = {ws->ka[0], ws->ka[1], ws->ka[2], ws->ka[3]};
+    const int64_t slot = gode_gcn_small_parts(f->n) * gode_gcn_small_part_len(f->d);
+    const float hb3 = (float)(h * B38[3]);
+    for (int i = 0; i < n_steps; ++i) {
+        float stage_t[4];
+        const gode_lincomb_t ypre = combine_terms(ycur, ky, h), apre = combine_terms(acur, ka, h);
+        for (int s = 0; s < 4; ++s) {
+            stage_t[s] = (float)((double)t0 + i * h + C38[s] * h);
+            const gode_lincomb_t yin = stage_terms(ycur, ky, s, h);
+            const gode_lincomb_t cot = negated(stage_terms(acur, ka, s, h));          // cotangent of the VJP is -a
+            GODE_TRY(gode_gcn_feval_small_f32(f, &yin, stage_t[s], s == 3 ? hb3 : 1.f, s == 3 ? &ypre : nullptr,
+                                              &cot, ws->dZ, ky[s], stream));
+            GODE_TRY(gode_gcn_vjp_small_f32(f, &yin, ws->dZ, s == 3 ? hb3 : 1.f, s == 3 ? &apre : nullptr,
+                                            ka[s], ws->small_part + s * slot, stream));
+        }
+        // theta <- theta + h * sum_s b_s ktheta_s straight from the four stages' block partials: one launch per step
+        const float wb[4] = {(float)(h * B38[0]), (float)(h * B38[1]), (float)(h * B38[2]), hb3};
+        GODE_TRY(gode_gcn_small_finish4_f32(f, ws->small_part, theta, wb, stage_t, stream));
+        float* tmp = ycur; ycur = ky[3]; ky[3] = tmp;
+        tmp = acur; acur = ka[3]; ka[3] = tmp;
+    }
+    *y_result = ycur;
+    *a_result = acur;
+    return 0;
+}
 
 }  // namespace
 
@@ -208,8 +274,9 @@ extern "C" int gode_gcn_ode_rk4_adjoint(const gode_gcn_odefunc_t* f, float* y, f
     if (!ws->S || !ws->dZ || !ws->dS || !ws->wpart || !ws->colsum_scratch) return GODE_E_NULLPTR;
     if (f->groups > 0 && (!ws->gpart || !ws->bpart)) return GODE_E_NULLPTR;
     const int64_t n = f->n, d = f->d;
-    const int64_t nW = (d + 1) * d, P = gode_gcn_ode_theta_len(d);
     const double h = ((double)t1 - (double)t0) / n_steps;   // negative: the adjoint runs from t0 (later) to t1 (earlier)
+    if (fused_small(f) && ws->small_part != nullptr)
+        return rk4_adjoint_small(f, ws, y, a, theta, y_result, a_result, t0, h, n_steps, stream);
     hipStream_t hs = (hipStream_t)stream;
     // the side stream exists only for callers that ask for the two-chain schedule (never created inside a capture:
     // odeint turns the option off around its HIP-graph captures)
@@ -222,23 +289,22 @@ extern "C" int gode_gcn_ode_rk4_adjoint(const gode_gcn_odefunc_t* f, float* y, f
     float* ycur = y; float* acur = a;
     float* ky[4] = {ws->ky[0], ws->ky[1], ws->ky[2], ws->ky[3]};
     float* ka[4] = {ws->ka[0], ws->ka[1], ws->ka[2], ws->ka[3]};
-    const int64_t wparts = gode_wgrad_parts(n), gparts = gode_gemm_bwd_parts(n);
+    const int64_t wparts = gode_wgrad_parts(n);
     const int total = 4 * n_steps;
     // d = 128 on large graphs: Gb(s) and Wg(s) as ONE pass over x and dS (gemm_pc.hip: gn_gemm_bwd_wgrad_pc_kernel)
     const bool bw = !small && gode_bwd_wgrad_supported(n, d, d, f->groups) && gode_bwd_wgrad_parts(n) <= wparts;
+    // colsum(dZ), the bias gradient of a stage: from the per-block column sums Sp(g) leaves in ws->y2_colsum (1/8 of
+    // dZ's bytes) when the workspace has them and the graph runs on the kernels that form them
+    const int64_t y2rows = (bw && ws->y2_colsum && gode_opt_y2_colsum())
+        ? gode_spmm_y2_colsum_rows(f->A.items ? f->A.n_items : f->A.n_rows, f->A.items ? f->A.n_long : 0, d) : 0;
 
     // Stage inputs with 3 or 4 terms (stages 2 and 3 of the 3/8 rule) are written out by their Gf launch so that
     // Gb and Wg read ONE n x d array instead of the term list (measured at C5: Gb 0.78 -> 0.42 ms, Wg 0.56 -> 0.43 ms
     // for +0.10 ms in Gf).  X[g&1]: Gf(g+2) is ordered after Gb(g) and Wg(g) by the spt event / side-stream order.
     const bool mat = ws->X[0] != nullptr && ws->X[1] != nullptr;
     auto x_out_of = [&](int g) -> float* { return (mat && (g % 4) >= 2) ? ws->X[g & 1] : nullptr; };
+    auto stage_time = [&](int g) { return (float)((double)t0 + (g / 4) * h + C38[g % 4] * h); };
 
-    const bool fused = fused_small(f) && ws->small_part != nullptr;
-    if (!fused) {
-        gode_lincomb_t yin0 = stage_terms(ycur, ky, 0, h);
-        GODE_TRY(gode_gn_time_gemm_xout_f32(&yin0, n, d, f->groups, f->eps, f->gamma, f->beta, f->W, d, 1,
-                                            (float)((double)t0), Sbuf[0], x_out_of(0), stream));
-    }
     // the closing combinations of a step formed once (bw branch): P_y by Gf of the last stage into ky[3], P_a by Sp(3) into
     // ka[3]; Sp(3) and the stage-3 dense launch read and overwrite them in place, row by row (the SpMM's lane group and
     // its finishing launch load the pre-terms of the row they then store; the consumer lane of the dense launch loads
@@ -246,43 +312,25 @@ extern "C" int gode_gcn_ode_rk4_adjoint(const gode_gcn_odefunc_t* f, float* y, f
     // are launches of the previous step on the caller's stream, ahead of these in stream order.
     const bool close_once = bw && close_once_route(f);
     bool py_formed = false;
+    // Gf(g) from the y-chain as it stands (stage g's step must be the current one: Sp of a last stage swaps the chain)
+    auto gf = [&](int g, void* st) -> int {
+        const gode_lincomb_t yin = stage_terms(ycur, ky, g % 4, h);
+        if (g % 4 == 3 && close_once)
+            return gf_last_stage(f, yin, combine_terms(ycur, ky, h), stage_time(g), Sbuf[g & 1], x_out_of(g), ky[3], &py_formed, st);
+        return gode_gn_time_gemm_xout_f32(&yin, n, d, f->groups, f->eps, f->gamma, f->beta, f->W, d, 1, stage_time(g),
+                                          Sbuf[g & 1], x_out_of(g), st);
+    };
+    GODE_TRY(gf(0, stream));
     bool wg_pending = false;
-    float stage_t[4] = {0.f, 0.f, 0.f, 0.f};
     for (int g = 0; g < total; ++g) {
-        const int i = g / 4, s = g % 4;
-        const float ts = (float)((double)t0 + i * h + C38[s] * h);
-        if (fused) {
-            // two launches per stage: f-eval (+ masked cotangent dZ), VJP (+ block partials); one more per step
-            const gode_lincomb_t yin = stage_terms(ycur, ky, s, h);
-            const gode_lincomb_t cot = negated(stage_terms(acur, ka, s, h));          // cotangent of the VJP is -a
-            const gode_lincomb_t ypre = combine_terms(ycur, ky, h), apre = combine_terms(acur, ka, h);
-            GODE_TRY(gode_gcn_feval_small_f32(f, &yin, ts, s == 3 ? (float)(h * B38[3]) : 1.f, s == 3 ? &ypre : nullptr,
-                                              &cot, ws->dZ, ky[s], stream));
-            const int64_t slot = gode_gcn_small_parts(n) * gode_gcn_small_part_len(d);
-            GODE_TRY(gode_gcn_vjp_small_f32(f, &yin, ws->dZ, s == 3 ? (float)(h * B38[3]) : 1.f, s == 3 ? &apre : nullptr,
-                                            ka[s], ws->small_part + s * slot, stream));
-            stage_t[s] = ts;
-            if (s == 3) {
-                // theta <- theta + h * sum_s b_s ktheta_s straight from the four stages' block partials: one launch per step
-                const float wb[4] = {(float)(h * B38[0]), (float)(h * B38[1]), (float)(h * B38[2]), (float)(h * B38[3])};
-                GODE_TRY(gode_gcn_small_finish4_f32(f, ws->small_part, theta, wb, stage_t, stream));
-                float* tmp = ycur; ycur = ky[3]; ky[3] = tmp;
-                tmp = acur; acur = ka[3]; ka[3] = tmp;
-            }
-            continue;
-        }
-        gode_lincomb_t yin = stage_terms(ycur, ky, s, h);     // terms of THIS stage (used by Gb / Wg below)
-        if (x_out_of(g)) { yin.n = 1; yin.coef[0] = 1.f; yin.ptr[0] = x_out_of(g); }
-        gode_lincomb_t ain = stage_terms(acur, ka, s, h);
-        gode_spmm_epilogue_t ep = {};
-        ep.bias = f->b; ep.relu = 1; ep.alpha = 1.f;
-        ep.cot = ain;
-        for (int j = 0; j < ep.cot.n; ++j) ep.cot.coef[j] = -ep.cot.coef[j];     // cotangent of the VJP is -a
+        const int s = g % 4;
+        const float ts = stage_time(g);
+        // terms of THIS stage (used by Gb / Wg below)
+        const gode_lincomb_t yin = x_out_of(g) ? one_term(x_out_of(g)) : stage_terms(ycur, ky, s, h);
+        const gode_lincomb_t ain = stage_terms(acur, ka, s, h);
+        gode_spmm_epilogue_t ep = relu_bias_epilogue(f);
+        ep.cot = negated(ain);                                // cotangent of the VJP is -a
         ep.Y2 = ws->dZ;
-        // colsum(dZ), the bias gradient of the stage: from the per-block column sums Sp(g) leaves in ws->y2_colsum (1/8 of
-        // dZ's bytes) when the workspace has them and the graph runs on the kernels that form them
-        const int64_t y2rows = (bw && ws->y2_colsum && gode_opt_y2_colsum())
-            ? gode_spmm_y2_colsum_rows(f->A.items ? f->A.n_items : f->A.n_rows, f->A.items ? f->A.n_long : 0, d) : 0;
         if (y2rows > 0) ep.Y2_colsum = ws->y2_colsum;
         gode_lincomb_t apre; apre.n = 0;
         if (s == 3) {
@@ -298,9 +346,7 @@ extern "C" int gode_gcn_ode_rk4_adjoint(const gode_gcn_odefunc_t* f, float* y, f
         }
         if (two && g > 0) GODE_HIP(hipStreamWaitEvent(hs, ov->gf, 0));          // S of this stage was produced on the side stream
         GODE_TRY(spmm(f->A, Sbuf[g & 1], ky[s], d, &ep, stream));               // Sp(g): k_y (or new y) and dZ
-        // pointers as the NEXT stage will see them (the y-chain swaps buffers after stage 3)
-        float* ycur_n = ycur; float* ky_n[4] = {ky[0], ky[1], ky[2], ky[3]};
-        if (s == 3) { ycur_n = ky[3]; ky_n[3] = ycur; }
+        if (s == 3) { float* tmp = ycur; ycur = ky[3]; ky[3] = tmp; }           // the y-chain as Gf(g+1) will see it
         if (two && wg_pending) GODE_HIP(hipStreamWaitEvent(hs, ov->wg, 0));     // previous Wg still reads dS
         GODE_TRY(spmm(f->AT, ws->dZ, ws->dS, d, nullptr, stream));              // SpT(g): alone on the chip
         if (two) {
@@ -308,86 +354,56 @@ extern "C" int gode_gcn_ode_rk4_adjoint(const gode_gcn_odefunc_t* f, float* y, f
             GODE_HIP(hipStreamWaitEvent(ov->side, ov->spt, 0));
         }
         float* kt = ws->ktheta[s];
+        const float out_scale = s == 3 ? (float)(h * B38[3]) : 1.f;
+        float* gpart = f->groups > 0 ? ws->gpart : nullptr;
+        float* bpart = f->groups > 0 ? ws->bpart : nullptr;
         if (bw) {
             // Gb(g) + Wg(g) in one launch on the caller's stream, then Gf(g+1) behind it (a 138 KB-LDS block and a
             // forward block do not share a CU anyway); the small reductions of the stage run on the side stream beside
             // them: colsum(dZ) as soon as SpT(g) is done, the partial sums once the dense launch is
             if (two) GODE_HIP(hipStreamWaitEvent(ov->side, ov->spt, 0));
-            if (y2rows > 0) GODE_TRY(gode_colsum_f32(kt + nW, ws->y2_colsum, y2rows, d, 1.f, 0, ws->colsum_scratch, side));
-            else GODE_TRY(gode_colsum_f32(kt + nW, ws->dZ, n, d, 1.f, 0, ws->colsum_scratch, side));
+            GODE_TRY(close_bias(f, ws, kt, y2rows > 0 ? ws->y2_colsum : ws->dZ, y2rows > 0 ? y2rows : n, side));
             GODE_TRY(gode_gn_time_gemm_bwd_wgrad_f32(&yin, n, d, f->groups, f->eps, f->gamma, f->beta, f->W, d, 1, ws->dS,
-                                                     s == 3 ? (float)(h * B38[3]) : 1.f, s == 3 ? &apre : nullptr, ka[s],
-                                                     f->groups > 0 ? ws->gpart : nullptr, f->groups > 0 ? ws->bpart : nullptr,
-                                                     ws->wpart, stream));
+                                                     out_scale, s == 3 ? &apre : nullptr, ka[s], gpart, bpart, ws->wpart, stream));
             if (two) {
                 GODE_HIP(hipEventRecord(ov->sp, hs));
                 GODE_HIP(hipStreamWaitEvent(ov->side, ov->sp, 0));
             }
-            GODE_TRY(gode_reduce_parts_f32(kt, ws->wpart, gode_bwd_wgrad_parts(n), nW, 1.f, 0, side));
-            hipLaunchKernelGGL(theta_fixup_kernel, dim3(1), dim3(256), 0, (hipStream_t)side, kt, f->W, ts, (int)d, P - 1);
-            GODE_LAUNCH_CHECK();
-            if (f->groups > 0) {
-                GODE_TRY(gode_reduce_parts2_f32(kt + nW + d, ws->gpart, kt + nW + 2 * d, ws->bpart, gparts, d, 1.f, 0, side));
-            } else {
-                GODE_TRY(gode_zero_f32(kt + nW + d, 2 * d, side));
-            }
+            GODE_TRY(close_weight(f, ws, kt, gode_bwd_wgrad_parts(n), ts, side));
+            GODE_TRY(close_affine(f, ws, kt, side));
             if (two) { GODE_HIP(hipEventRecord(ov->wg, ov->side)); wg_pending = true; }
             if (g + 1 < total) {                                                    // Gf(g+1), same stream as Sp(g+1)
-                const int i2 = (g + 1) / 4, s2 = (g + 1) % 4;
-                gode_lincomb_t yin2 = stage_terms(ycur_n, ky_n, s2, h);
-                if (s2 == 3 && close_once) {
-                    GODE_TRY(gf_last_stage(f, ycur_n, ky_n, h, (float)((double)t0 + i2 * h + C38[s2] * h), Sbuf[(g + 1) & 1],
-                                           x_out_of(g + 1), ky_n[3], &py_formed, stream));
-                } else {
-                    GODE_TRY(gode_gn_time_gemm_xout_f32(&yin2, n, d, f->groups, f->eps, f->gamma, f->beta, f->W, d, 1,
-                                                        (float)((double)t0 + i2 * h + C38[s2] * h), Sbuf[(g + 1) & 1],
-                                                        x_out_of(g + 1), stream));
-                }
+                GODE_TRY(gf(g + 1, stream));
                 if (two) GODE_HIP(hipEventRecord(ov->gf, hs));      // the wait at the top of the next stage finds it done
             }
             // the side chain still reads dZ and the partial buffers, which Sp(g+1) and the next dense launch overwrite
             if (two) { GODE_HIP(hipStreamWaitEvent(hs, ov->wg, 0)); wg_pending = false; }
         } else {
-        // side stream, beside Gb(g) on the main stream: Wg(g), then the dense part of the NEXT stage
-        const bool merged = small;                                    // launch-bound: one finishing launch per stage
-        GODE_TRY(gode_wgrad_f32(&yin, n, d, f->groups, f->eps, f->gamma, f->beta, ws->dS, d, 1, ws->wpart, side));   // Wg(g)
-        if (!merged) {
-            GODE_TRY(gode_reduce_parts_f32(kt, ws->wpart, wparts, nW, 1.f, 0, side));
-            hipLaunchKernelGGL(theta_fixup_kernel, dim3(1), dim3(256), 0, (hipStream_t)side, kt, f->W, ts, (int)d, P - 1);
-            GODE_LAUNCH_CHECK();
-        }
-        if (two) { GODE_HIP(hipEventRecord(ov->wg, ov->side)); wg_pending = true; }
-        if (g + 1 < total) {                                                    // Gf(g+1)
-            const int i2 = (g + 1) / 4, s2 = (g + 1) % 4;
-            gode_lincomb_t yin2 = stage_terms(ycur_n, ky_n, s2, h);
-            GODE_TRY(gode_gn_time_gemm_xout_f32(&yin2, n, d, f->groups, f->eps, f->gamma, f->beta, f->W, d, 1,
-                                                (float)((double)t0 + i2 * h + C38[s2] * h), Sbuf[(g + 1) & 1],
-                                                x_out_of(g + 1), side));
-            if (two) GODE_HIP(hipEventRecord(ov->gf, ov->side));
-        }
-        GODE_TRY(gode_gn_time_gemm_bwd_f32(&yin, n, d, f->groups, f->eps, f->gamma, f->W, d, 1, ws->dS,
-                                           s == 3 ? (float)(h * B38[3]) : 1.f, s == 3 ? &apre : nullptr, ka[s],
-                                           f->groups > 0 ? ws->gpart : nullptr, f->groups > 0 ? ws->bpart : nullptr, stream));   // Gb(g)
-        if (merged) {
-            GODE_TRY(stage_finish_merged(f, ws, kt, ts, stream));
-        } else {
-            GODE_TRY(gode_colsum_f32(kt + nW, ws->dZ, n, d, 1.f, 0, ws->colsum_scratch, stream));
-            if (f->groups > 0) {
-                GODE_TRY(gode_reduce_parts2_f32(kt + nW + d, ws->gpart, kt + nW + 2 * d, ws->bpart, gparts, d, 1.f, 0, stream));
-            } else {
-                GODE_TRY(gode_zero_f32(kt + nW + d, 2 * d, stream));
+            // side stream, beside Gb(g) on the main stream: Wg(g), then the dense part of the NEXT stage
+            GODE_TRY(gode_wgrad_f32(&yin, n, d, f->groups, f->eps, f->gamma, f->beta, ws->dS, d, 1, ws->wpart, side));   // Wg(g)
+            if (!small) GODE_TRY(close_weight(f, ws, kt, wparts, ts, side));
+            if (two) { GODE_HIP(hipEventRecord(ov->wg, ov->side)); wg_pending = true; }
+            if (g + 1 < total) {                                                    // Gf(g+1)
+                GODE_TRY(gf(g + 1, side));
+                if (two) GODE_HIP(hipEventRecord(ov->gf, ov->side));
             }
-        }
+            GODE_TRY(gode_gn_time_gemm_bwd_f32(&yin, n, d, f->groups, f->eps, f->gamma, f->W, d, 1, ws->dS, out_scale,
+                                               s == 3 ? &apre : nullptr, ka[s], gpart, bpart, stream));               // Gb(g)
+            if (small) {                                                            // launch-bound: one finishing launch per stage
+                GODE_TRY(stage_finish_merged(f, ws, kt, ts, stream));
+            } else {
+                GODE_TRY(close_bias(f, ws, kt, ws->dZ, n, stream));
+                GODE_TRY(close_affine(f, ws, kt, stream));
+            }
         }
         if (s == 3) {
             // theta <- theta + h * sum b_s ktheta_s   (packed small components, one launch)
             if (two) { GODE_HIP(hipStreamWaitEvent(hs, ov->wg, 0)); wg_pending = false; }
-            gode_lincomb_t tc;
-            tc.n = 5; tc.coef[0] = 1.f; tc.ptr[0] = theta;
+            gode_lincomb_t tc = one_term(theta);
+            tc.n = 5;
             for (int q = 0; q < 4; ++q) { tc.coef[1 + q] = (float)(h * B38[q]); tc.ptr[1 + q] = ws->ktheta[q]; }
-            GODE_TRY(gode_lincomb_f32(theta, &tc, P, stream));
-            float* tmp = ycur; ycur = ky[3]; ky[3] = tmp;
-            tmp = acur; acur = ka[3]; ka[3] = tmp;
+            GODE_TRY(gode_lincomb_f32(theta, &tc, gode_gcn_ode_theta_len(d), stream));
+            float* tmp = acur; acur = ka[3]; ka[3] = tmp;
         }
     }
     if (two) {                      // join: nothing of this call is left running on the side stream
@@ -407,38 +423,11 @@ extern "C" int gode_gcn_ode_rk4_adjoint(const gode_gcn_odefunc_t* f, float* y, f
 // ---------------------------------------------------------------------------------------------------------------
 namespace {
 
-const double DPC[7] = {0.0, 1.0 / 5, 3.0 / 10, 4.0 / 5, 8.0 / 9, 1.0, 1.0};
-const double DPA[7][6] = {
-    {0, 0, 0, 0, 0, 0},
-    {1.0 / 5, 0, 0, 0, 0, 0},
-    {3.0 / 40, 9.0 / 40, 0, 0, 0, 0},
-    {44.0 / 45, -56.0 / 15, 32.0 / 9, 0, 0, 0},
-    {19372.0 / 6561, -25360.0 / 2187, 64448.0 / 6561, -212.0 / 729, 0, 0},
-    {9017.0 / 3168, -355.0 / 33, 46732.0 / 5247, 49.0 / 176, -5103.0 / 18656, 0},
-    {35.0 / 384, 0, 500.0 / 1113, 125.0 / 192, -2187.0 / 6784, 11.0 / 84},
-};
-const double DPB[7] = {35.0 / 384, 0, 500.0 / 1113, 125.0 / 192, -2187.0 / 6784, 11.0 / 84, 0};
-const double DPE[7] = {35.0 / 384 - 1951.0 / 21600, 0, 500.0 / 1113 - 22642.0 / 50085, 125.0 / 192 - 451.0 / 720,
-                       -2187.0 / 6784 - -12231.0 / 42400, 11.0 / 84 - 649.0 / 6300, -1.0 / 60.0};
-
-// terms of  y + h * sum_j coef[j] * k[j]  (zero coefficients dropped; first = number of leading k's considered)
-gode_lincomb_t dp_terms(const float* y, float* const* k, const double* coef, int count, double h, bool with_y) {
-    gode_lincomb_t lc;
-    lc.n = 0;
-    if (with_y) { lc.coef[0] = 1.f; lc.ptr[0] = y; lc.n = 1; }
-    for (int j = 0; j < count; ++j)
-        if (coef[j] != 0.0) { lc.coef[lc.n] = (float)(h * coef[j]); lc.ptr[lc.n] = k[j]; ++lc.n; }
-    return lc;
-}
-
 // next / x_next (fused launch-bound path only): the stage's launch also writes the next stage's combined input
 int dp_eval_forward(const gode_gcn_odefunc_t* f, const gode_rk4_workspace_t* ws, const gode_lincomb_t* yin, float t,
                     float* k_out, const gode_lincomb_t* next, float* x_next, void* stream) {
     if (fused_small(f)) return gode_gcn_feval_small_next_f32(f, yin, t, 1.f, nullptr, nullptr, nullptr, k_out, next, x_next, stream);
-    GODE_TRY(gode_gn_time_gemm_f32(yin, f->n, f->d, f->groups, f->eps, f->gamma, f->beta, f->W, f->d, 1, t, ws->S, stream));
-    gode_spmm_epilogue_t ep = {};
-    ep.bias = f->b; ep.relu = 1; ep.alpha = 1.f;
-    return spmm(f->A, ws->S, k_out, f->d, &ep, stream);
+    return feval_large(f, *yin, t, ws->S, k_out, nullptr, nullptr, stream);
 }
 
 // One evaluation of the augmented adjoint field: k_y = f(t, y), k_a = -a^T df/dy, k_theta = [-a^T df/dW | .. b | .. gamma |
@@ -448,7 +437,7 @@ int dp_eval_forward(const gode_gcn_odefunc_t* f, const gode_rk4_workspace_t* ws,
 int dp_eval_adjoint(const gode_gcn_odefunc_t* f, const gode_rk4_workspace_t* ws, gode_lincomb_t yin,
                     const gode_lincomb_t& ain, float t, float* ky, float* ka, float* kth, const gode_lincomb_t* next,
                     float* x_next, int part_slot, void* stream) {
-    const int64_t n = f->n, d = f->d, nW = (d + 1) * d, P = gode_gcn_ode_theta_len(d);
+    const int64_t n = f->n, d = f->d;
     if (fused_small(f) && ws->small_part) {
         const gode_lincomb_t cot = negated(ain);
         GODE_TRY(gode_gcn_feval_small_next_f32(f, &yin, t, 1.f, nullptr, &cot, ws->dZ, ky, next, x_next, stream));
@@ -459,11 +448,9 @@ int dp_eval_adjoint(const gode_gcn_odefunc_t* f, const gode_rk4_workspace_t* ws,
     }
     float* xo = (yin.n >= 3 && ws->X[0]) ? ws->X[0] : nullptr;
     GODE_TRY(gode_gn_time_gemm_xout_f32(&yin, n, d, f->groups, f->eps, f->gamma, f->beta, f->W, d, 1, t, ws->S, xo, stream));
-    if (xo) { yin.n = 1; yin.coef[0] = 1.f; yin.ptr[0] = xo; }
-    gode_spmm_epilogue_t ep = {};
-    ep.bias = f->b; ep.relu = 1; ep.alpha = 1.f;
-    ep.cot = ain;
-    for (int j = 0; j < ep.cot.n; ++j) ep.cot.coef[j] = -ep.cot.coef[j];
+    if (xo) yin = one_term(xo);
+    gode_spmm_epilogue_t ep = relu_bias_epilogue(f);
+    ep.cot = negated(ain);
     ep.Y2 = ws->dZ;
     GODE_TRY(spmm(f->A, ws->S, ky, d, &ep, stream));
     GODE_TRY(spmm(f->AT, ws->dZ, ws->dS, d, nullptr, stream));
@@ -471,17 +458,9 @@ int dp_eval_adjoint(const gode_gcn_odefunc_t* f, const gode_rk4_workspace_t* ws,
                                        f->groups > 0 ? ws->gpart : nullptr, f->groups > 0 ? ws->bpart : nullptr, stream));
     GODE_TRY(gode_wgrad_f32(&yin, n, d, f->groups, f->eps, f->gamma, f->beta, ws->dS, d, 1, ws->wpart, stream));
     if (n <= kMergedFinishMaxRows) return stage_finish_merged(f, ws, kth, t, stream);
-    GODE_TRY(gode_reduce_parts_f32(kth, ws->wpart, gode_wgrad_parts(n), nW, 1.f, 0, stream));
-    hipLaunchKernelGGL(theta_fixup_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, kth, f->W, t, (int)d, P - 1);
-    GODE_LAUNCH_CHECK();
-    GODE_TRY(gode_colsum_f32(kth + nW, ws->dZ, n, d, 1.f, 0, ws->colsum_scratch, stream));
-    if (f->groups > 0) {
-        const int64_t gparts = gode_gemm_bwd_parts(n);
-        GODE_TRY(gode_reduce_parts2_f32(kth + nW + d, ws->gpart, kth + nW + 2 * d, ws->bpart, gparts, d, 1.f, 0, stream));
-    } else {
-        GODE_TRY(gode_zero_f32(kth + nW + d, 2 * d, stream));
-    }
-    return 0;
+    GODE_TRY(close_weight(f, ws, kth, gode_wgrad_parts(n), t, stream));
+    GODE_TRY(close_bias(f, ws, kth, ws->dZ, n, stream));
+    return close_affine(f, ws, kth, stream);
 }
 
 }  // namespace
@@ -500,7 +479,7 @@ extern "C" int gode_gcn_ode_dopri5_step_forward(const gode_gcn_odefunc_t* f, con
     const bool chain = fused_small(f) && ws->X[0] && ws->X[1];
     for (int s = 1; s < 7; ++s) {
         gode_lincomb_t yin = dp_terms(y, k, DPA[s], s, h, true);
-        if (chain && s >= 2) { yin.n = 1; yin.coef[0] = 1.f; yin.ptr[0] = ws->X[s & 1]; }
+        if (chain && s >= 2) yin = one_term(ws->X[s & 1]);
         gode_lincomb_t nxt; nxt.n = 0;
         if (chain && s < 6) nxt = dp_terms(y, k, DPA[s + 1], s + 1, h, true);
         GODE_TRY(dp_eval_forward(f, ws, &yin, (float)(t + DPC[s] * h), k[s], nxt.n > 0 ? &nxt : nullptr,
@@ -529,7 +508,7 @@ extern "C" int gode_gcn_ode_dopri5_step_adjoint(const gode_gcn_odefunc_t* f, con
     const bool chain = fused && ws->X[0] && ws->X[1];                                   // as in the forward step
     for (int s = 1; s < 7; ++s) {
         gode_lincomb_t yin = dp_terms(y, ky, DPA[s], s, h, true);
-        if (chain && s >= 2) { yin.n = 1; yin.coef[0] = 1.f; yin.ptr[0] = ws->X[s & 1]; }
+        if (chain && s >= 2) yin = one_term(ws->X[s & 1]);
         gode_lincomb_t ain = dp_terms(a, ka, DPA[s], s, h, true);
         gode_lincomb_t nxt; nxt.n = 0;
         if (chain && s < 6) nxt = dp_terms(y, ky, DPA[s + 1], s + 1, h, true);
@@ -549,14 +528,11 @@ extern "C" int gode_gcn_ode_dopri5_step_adjoint(const gode_gcn_odefunc_t* f, con
         const int64_t lens[3] = {nd, nd, P};
         GODE_TRY(gode_lincomb_multi_f32(outs, sols, lens, 3, stream));
     }
-    gode_lincomb_t ey = dp_terms(nullptr, ky, DPE, 7, h, false), ea = dp_terms(nullptr, ka, DPE, 7, h, false),
-                   et = dp_terms(nullptr, kth, DPE, 7, h, false);
     // a_t is the last entry of the packed vector, the flattened parameters the P-1 before it
-    gode_lincomb_t et_at = et;
-    for (int j = 0; j < et_at.n; ++j) et_at.ptr[j] = et.ptr[j] + (P - 1);
+    const gode_lincomb_t errs[4] = {dp_terms(nullptr, ky, DPE, 7, h, false), dp_terms(nullptr, ka, DPE, 7, h, false),
+                                    dp_terms(nullptr, kth, DPE, 7, h, false, P - 1), dp_terms(nullptr, kth, DPE, 7, h, false)};
     const float* e0[4] = {y, a, theta + (P - 1), theta};
     const float* e1[4] = {y1, a1, theta1 + (P - 1), theta1};
-    const gode_lincomb_t errs[4] = {ey, ea, et_at, et};
     const int64_t ens[4] = {nd, nd, 1, P - 1};
     return gode_rk_errnorm_multi_f32(sums, e0, e1, errs, ens, 4, rtol, atol, err_scratch, stream);
 }
@@ -569,23 +545,16 @@ extern "C" int gode_gcn_ode_dopri5_step_adjoint(const gode_gcn_odefunc_t* f, con
 //   kbar_1 = h/8 abar + h/3 Ybar_2 - h/3 Ybar_3 + h Ybar_4;   Ybar_s = J_s^T kbar_s,  theta += (df/dtheta)_s^T kbar_s,
 //   abar_n = abar + sum_s Ybar_s
 // where J_s is the Jacobian of f at the stage input Y_s = y_n + h sum_j A38[s][j] k_j; f = relu(z), so the VJP's mask
-// [z_s > 0] is [k_s > 0] of the saved derivative.
+// [z_s > 0] is [k_s > 0] of the saved derivative  (kbar_s: rk_driver.h, stage_cotangent).
 // ---------------------------------------------------------------------------------------------------------------
 namespace {
 
-int spmm_save(const gode_graph_t& g, const float* X, float* Y, int64_t d, const gode_spmm_epilogue_t* ep, float* K, void* s) {
-    return gode_spmm_csr_save_f32(g.rowptr, g.col, g.val, g.items, g.n_items, g.long_rows, g.n_long, g.partial,
-                                  X, d, Y, d, g.n_rows, d, ep, K, s);
-}
-
-// kbar_s: h b_s abar + h sum_{q > s} A38[q][s] Ybar_q
-gode_lincomb_t stage_cotangent(const float* abar, float* const* ybar, int s, double h) {
-    gode_lincomb_t lc;
-    lc.n = 0;
-    lc.coef[lc.n] = (float)(h * B38[s]); lc.ptr[lc.n] = abar; ++lc.n;
-    for (int q = s + 1; q < 4; ++q)
-        if (A38[q][s] != 0.0) { lc.coef[lc.n] = (float)(h * A38[q][s]); lc.ptr[lc.n] = ybar[q]; ++lc.n; }
-    return lc;
+// abar + Ybar_2 + Ybar_3 + Ybar_4: what the launch that forms Ybar_1 adds to it, leaving abar_n
+gode_lincomb_t sweep_pre(const float* abar, float* const* yb) {
+    gode_lincomb_t pre = one_term(abar);
+    for (int q = 1; q < 4; ++q) { pre.coef[q] = 1.f; pre.ptr[q] = yb[q]; }
+    pre.n = 4;
+    return pre;
 }
 
 }  // namespace
@@ -598,48 +567,20 @@ extern "C" int gode_gcn_ode_rk4_forward_save(const gode_gcn_odefunc_t* f, const 
     if (n_steps <= 0 || f->n <= 0 || f->d <= 0) return GODE_E_SHAPE;
     if (step_begin < 0 || step_end > n_steps || step_begin >= step_end) return GODE_E_SHAPE;
     if (!ws->S) return GODE_E_NULLPTR;
-    const int64_t n = f->n, d = f->d, nd = n * d;
+    const int64_t nd = f->n * f->d;
     const double h = ((double)t1 - (double)t0) / n_steps;
     const bool fused = fused_small(f);
     const bool close_once = close_once_route(f);
     if (y0 != save) {                                            // record 0 starts with a copy of y0
-        gode_lincomb_t c; c.n = 1; c.coef[0] = 1.f; c.ptr[0] = y0;
+        const gode_lincomb_t c = one_term(y0);
         GODE_TRY(gode_lincomb_f32(save, &c, nd, stream));
     }
     for (int i = step_begin; i < step_end; ++i) {
         float* rec = save + (int64_t)(i - step_begin) * 5 * nd;
-        const float* y = rec;
         float* k[4] = {rec + nd, rec + 2 * nd, rec + 3 * nd, rec + 4 * nd};
         float* ynext = (i + 1 < step_end) ? rec + 5 * nd : y_end;      // the next record's y_n, or the result
-        const double t = (double)t0 + i * h;
         // the launches of gode_gcn_ode_rk4_forward; the folded last stage also stores k_4
-        for (int s = 0; s < 4; ++s) {
-            gode_lincomb_t xin = stage_terms(y, k, s, h);
-            const float ts = (float)(t + C38[s] * h);
-            if (fused) {
-                if (s < 3) {
-                    GODE_TRY(gode_gcn_feval_small_f32(f, &xin, ts, 1.f, nullptr, nullptr, nullptr, k[s], stream));
-                } else {
-                    gode_lincomb_t pre = combine_terms(y, k, h);
-                    GODE_TRY(gode_gcn_feval_small_save_f32(f, &xin, ts, (float)(h * B38[3]), &pre, ynext, k[3], stream));
-                }
-                continue;
-            }
-            bool p_formed = false;                 // as in gode_gcn_ode_rk4_forward; the combination goes where y_{n+1} will
-            if (s == 3 && close_once) {
-                GODE_TRY(gf_last_stage(f, y, k, h, ts, ws->S, nullptr, ynext, &p_formed, stream));
-            } else {
-                GODE_TRY(gode_gn_time_gemm_f32(&xin, n, d, f->groups, f->eps, f->gamma, f->beta, f->W, d, 1, ts, ws->S, stream));
-            }
-            gode_spmm_epilogue_t ep = {};
-            ep.bias = f->b; ep.relu = 1; ep.alpha = 1.f;
-            if (s < 3) {
-                GODE_TRY(spmm(f->A, ws->S, k[s], d, &ep, stream));
-            } else {
-                ep.pre = p_formed ? one_term(ynext) : combine_terms(y, k, h); ep.alpha = (float)(h * B38[3]);
-                GODE_TRY(spmm_save(f->A, ws->S, ynext, d, &ep, k[3], stream));
-            }
-        }
+        GODE_TRY(rk4_forward_step(f, ws, rec, k, ynext, true, (double)t0 + i * h, h, fused, close_once, stream));
     }
     return 0;
 }
@@ -656,7 +597,6 @@ extern "C" int gode_gcn_ode_rk4_backprop(const gode_gcn_odefunc_t* f, const floa
     if (!ws->dZ || !ws->dS || !ws->wpart || !ws->colsum_scratch) return GODE_E_NULLPTR;
     if (f->groups > 0 && (!ws->gpart || !ws->bpart)) return GODE_E_NULLPTR;
     const int64_t n = f->n, d = f->d, nd = n * d;
-    const int64_t nW = (d + 1) * d, P = gode_gcn_ode_theta_len(d);
     const double h = ((double)t1 - (double)t0) / n_steps;
     float* acur = a;
     float* yb[4] = {ws->ka[0], ws->ka[1], ws->ka[2], ws->ka[3]};   // yb[1..3]: Ybar_2..4; yb[0] receives abar_n
@@ -677,23 +617,18 @@ extern "C" int gode_gcn_ode_rk4_backprop(const gode_gcn_odefunc_t* f, const floa
             const float* y = record(i);
             float* k[4] = {(float*)y + nd, (float*)y + 2 * nd, (float*)y + 3 * nd, (float*)y + 4 * nd};
             const double t = (double)t0 + i * h;
+            const gode_lincomb_t pre = sweep_pre(acur, yb);
             float stage_t[4];
             for (int s = 3; s >= 0; --s) {
                 stage_t[s] = (float)(t + C38[s] * h);
                 const gode_lincomb_t yin = stage_terms(y, k, s, h);
-                gode_lincomb_t pre; pre.n = 0;
-                if (s == 0) {
-                    pre.n = 4;
-                    pre.coef[0] = 1.f; pre.ptr[0] = acur;
-                    for (int q = 1; q < 4; ++q) { pre.coef[q] = 1.f; pre.ptr[q] = yb[q]; }
-                }
                 gode_lincomb_t nxt; nxt.n = 0;
                 const float* knext = nullptr;
                 if (s > 0) {
                     nxt = stage_cotangent(acur, yb, s - 1, h);               // names yb[s]: this launch's rows
                     knext = k[s - 1];
                 } else if (i > step_begin) {
-                    nxt.n = 1; nxt.coef[0] = (float)(h * B38[3]); nxt.ptr[0] = yb[0];      // kbar_4 of step i - 1
+                    nxt = one_term(yb[0]); nxt.coef[0] = (float)(h * B38[3]);              // kbar_4 of step i - 1
                     knext = record(i - 1) + 4 * nd;
                 }
                 float* part = ws->small_part + s * slot;
@@ -713,58 +648,44 @@ extern "C" int gode_gcn_ode_rk4_backprop(const gode_gcn_odefunc_t* f, const floa
         return 0;
     }
     const bool small = n <= kMergedFinishMaxRows;
-    const int64_t wparts = gode_wgrad_parts(n), gparts = gode_gemm_bwd_parts(n);
+    const int64_t wparts = gode_wgrad_parts(n);
     const bool bw = !small && gode_bwd_wgrad_supported(n, d, d, f->groups) && gode_bwd_wgrad_parts(n) <= wparts;
     const int64_t cparts = (!small && cot_colpart) ? gode_masked_cot_parts(n, d) : 0;
+    float* gpart = f->groups > 0 ? ws->gpart : nullptr;
+    float* bpart = f->groups > 0 ? ws->bpart : nullptr;
     for (int i = step_end - 1; i >= step_begin; --i) {
         const float* y = record(i);
         float* k[4] = {(float*)y + nd, (float*)y + 2 * nd, (float*)y + 3 * nd, (float*)y + 4 * nd};
         const double t = (double)t0 + i * h;
+        const gode_lincomb_t pre = sweep_pre(acur, yb);
         for (int s = 3; s >= 0; --s) {
             const float ts = (float)(t + C38[s] * h);
             const gode_lincomb_t cot = stage_cotangent(acur, yb, s, h);
             GODE_TRY(gode_masked_cot_f32(&cot, k[s], ws->dZ, n, d, cparts > 0 ? cot_colpart : nullptr, stream));
             GODE_TRY(spmm(f->AT, ws->dZ, ws->dS, d, nullptr, stream));                 // dS = A^T dZ
             const gode_lincomb_t yin = stage_terms(y, k, s, h);
-            gode_lincomb_t pre; pre.n = 0;
-            if (s == 0) {
-                pre.n = 4;
-                pre.coef[0] = 1.f; pre.ptr[0] = acur;
-                for (int q = 1; q < 4; ++q) { pre.coef[q] = 1.f; pre.ptr[q] = yb[q]; }
-            }
             float* kt = ws->ktheta[s];
             if (bw) {
                 GODE_TRY(gode_gn_time_gemm_bwd_wgrad_f32(&yin, n, d, f->groups, f->eps, f->gamma, f->beta, f->W, d, 1, ws->dS,
-                                                         1.f, s == 0 ? &pre : nullptr, yb[s],
-                                                         f->groups > 0 ? ws->gpart : nullptr, f->groups > 0 ? ws->bpart : nullptr,
-                                                         ws->wpart, stream));
-                GODE_TRY(gode_reduce_parts_f32(kt, ws->wpart, gode_bwd_wgrad_parts(n), nW, 1.f, 0, stream));
+                                                         1.f, s == 0 ? &pre : nullptr, yb[s], gpart, bpart, ws->wpart, stream));
             } else {
                 GODE_TRY(gode_gn_time_gemm_bwd_f32(&yin, n, d, f->groups, f->eps, f->gamma, f->W, d, 1, ws->dS, 1.f,
-                                                   s == 0 ? &pre : nullptr, yb[s], f->groups > 0 ? ws->gpart : nullptr,
-                                                   f->groups > 0 ? ws->bpart : nullptr, stream));
+                                                   s == 0 ? &pre : nullptr, yb[s], gpart, bpart, stream));
                 GODE_TRY(gode_wgrad_f32(&yin, n, d, f->groups, f->eps, f->gamma, f->beta, ws->dS, d, 1, ws->wpart, stream));
                 if (small) {
                     GODE_TRY(stage_finish_merged(f, ws, kt, ts, stream));
                     continue;
                 }
-                GODE_TRY(gode_reduce_parts_f32(kt, ws->wpart, wparts, nW, 1.f, 0, stream));
             }
-            hipLaunchKernelGGL(theta_fixup_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, kt, f->W, ts, (int)d, P - 1);
-            GODE_LAUNCH_CHECK();
-            if (cparts > 0) GODE_TRY(gode_colsum_f32(kt + nW, cot_colpart, cparts, d, 1.f, 0, ws->colsum_scratch, stream));
-            else GODE_TRY(gode_colsum_f32(kt + nW, ws->dZ, n, d, 1.f, 0, ws->colsum_scratch, stream));
-            if (f->groups > 0) {
-                GODE_TRY(gode_reduce_parts2_f32(kt + nW + d, ws->gpart, kt + nW + 2 * d, ws->bpart, gparts, d, 1.f, 0, stream));
-            } else {
-                GODE_TRY(gode_zero_f32(kt + nW + d, 2 * d, stream));
-            }
+            GODE_TRY(close_weight(f, ws, kt, bw ? gode_bwd_wgrad_parts(n) : wparts, ts, stream));
+            GODE_TRY(close_bias(f, ws, kt, cparts > 0 ? cot_colpart : ws->dZ, cparts > 0 ? cparts : n, stream));
+            GODE_TRY(close_affine(f, ws, kt, stream));
         }
         // theta += sum_s ktheta_s   (weights 1: h is already inside kbar)
-        gode_lincomb_t tc;
-        tc.n = 5; tc.coef[0] = 1.f; tc.ptr[0] = theta;
+        gode_lincomb_t tc = one_term(theta);
+        tc.n = 5;
         for (int q = 0; q < 4; ++q) { tc.coef[1 + q] = 1.f; tc.ptr[1 + q] = ws->ktheta[q]; }
-        GODE_TRY(gode_lincomb_f32(theta, &tc, P, stream));
+        GODE_TRY(gode_lincomb_f32(theta, &tc, gode_gcn_ode_theta_len(d), stream));
         float* tmp = acur; acur = yb[0]; yb[0] = tmp;
     }
     *a_result = acur;

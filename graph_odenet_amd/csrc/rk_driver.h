@@ -1,0 +1,73 @@
+// rk_driver.h — what the C-level Runge-Kutta drivers (ode_driver.hip, gat_driver.hip) share: the error-propagation macros,
+// the coefficient tables of the two methods and the term lists built from them.  Private to csrc/; everything here has
+// internal linkage, so the header adds nothing to the library's exports.
+#pragma once
+#include "common.h"
+
+#define GODE_TRY(expr) do { int rc__ = (expr); if (rc__) return rc__; } while (0)
+#define GODE_HIP(expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) return (int)e__; } while (0)
+
+namespace {
+
+// Launch-bound graphs close an adjoint stage's parameter derivative with ONE reduction launch (rk.hip:
+// reduce_segments_kernel); above this many rows the separate launches are kept: the weight-gradient reduction has a
+// 16-byte form that matters there.  The same bound as graph_odenet_amd/gat_ode.py: MERGED_FINISH_MAX_ROWS.
+constexpr int64_t kMergedFinishMaxRows = 1 << 16;
+
+// step size, stage times and h*coefficient products are formed in double and rounded once, exactly as the
+// Python driver (solver.py) does, so both drivers feed identical fp32 coefficients to the kernels
+// rk4, 3/8 rule
+const double C38[4] = {0.0, 1.0 / 3.0, 2.0 / 3.0, 1.0};
+const double A38[4][3] = {{0.0, 0.0, 0.0}, {1.0 / 3.0, 0.0, 0.0}, {-1.0 / 3.0, 1.0, 0.0}, {1.0, -1.0, 1.0}};
+const double B38[4] = {1.0 / 8.0, 3.0 / 8.0, 3.0 / 8.0, 1.0 / 8.0};
+// Dormand-Prince 5(4)
+const double DPC[7] = {0.0, 1.0 / 5, 3.0 / 10, 4.0 / 5, 8.0 / 9, 1.0, 1.0};
+const double DPA[7][6] = {
+    {0, 0, 0, 0, 0, 0},
+    {1.0 / 5, 0, 0, 0, 0, 0},
+    {3.0 / 40, 9.0 / 40, 0, 0, 0, 0},
+    {44.0 / 45, -56.0 / 15, 32.0 / 9, 0, 0, 0},
+    {19372.0 / 6561, -25360.0 / 2187, 64448.0 / 6561, -212.0 / 729, 0, 0},
+    {9017.0 / 3168, -355.0 / 33, 46732.0 / 5247, 49.0 / 176, -5103.0 / 18656, 0},
+    {35.0 / 384, 0, 500.0 / 1113, 125.0 / 192, -2187.0 / 6784, 11.0 / 84},
+};
+const double DPB[7] = {35.0 / 384, 0, 500.0 / 1113, 125.0 / 192, -2187.0 / 6784, 11.0 / 84, 0};
+const double DPE[7] = {35.0 / 384 - 1951.0 / 21600, 0, 500.0 / 1113 - 22642.0 / 50085, 125.0 / 192 - 451.0 / 720,
+                       -2187.0 / 6784 - -12231.0 / 42400, 11.0 / 84 - 649.0 / 6300, -1.0 / 60.0};
+
+inline gode_lincomb_t one_term(const float* p) { gode_lincomb_t lc; lc.n = 1; lc.coef[0] = 1.f; lc.ptr[0] = p; return lc; }
+inline gode_lincomb_t negated(gode_lincomb_t lc) { for (int j = 0; j < lc.n; ++j) lc.coef[j] = -lc.coef[j]; return lc; }
+
+// terms of  y + h * sum_{j<s} A38[s][j] * k[j]
+inline gode_lincomb_t stage_terms(const float* y, float* const* k, int s, double h) {
+    gode_lincomb_t lc = one_term(y);
+    for (int j = 0; j < s; ++j)
+        if (A38[s][j] != 0.0) { lc.coef[lc.n] = (float)(h * A38[s][j]); lc.ptr[lc.n] = k[j]; ++lc.n; }
+    return lc;
+}
+// terms of  y + h * sum_{j<3} B38[j] * k[j]   (the last stage is folded into the producing launch)
+inline gode_lincomb_t combine_terms(const float* y, float* const* k, double h) {
+    gode_lincomb_t lc = one_term(y);
+    for (int j = 0; j < 3; ++j) { lc.coef[lc.n] = (float)(h * B38[j]); lc.ptr[lc.n] = k[j]; ++lc.n; }
+    return lc;
+}
+// kbar_s of a backprop sweep: h b_s abar + h sum_{q > s} A38[q][s] Ybar_q
+inline gode_lincomb_t stage_cotangent(const float* abar, float* const* ybar, int s, double h) {
+    gode_lincomb_t lc = one_term(abar);
+    lc.coef[0] = (float)(h * B38[s]);
+    for (int q = s + 1; q < 4; ++q)
+        if (A38[q][s] != 0.0) { lc.coef[lc.n] = (float)(h * A38[q][s]); lc.ptr[lc.n] = ybar[q]; ++lc.n; }
+    return lc;
+}
+// terms of  y + h * sum_{j<count} coef[j] * k[j], every array `off` elements in  (zero coefficients dropped)
+inline gode_lincomb_t dp_terms(const float* y, float* const* k, const double* coef, int count, double h, bool with_y,
+                               int64_t off = 0) {
+    gode_lincomb_t lc;
+    lc.n = 0;
+    if (with_y) { lc.coef[0] = 1.f; lc.ptr[0] = y + off; lc.n = 1; }
+    for (int j = 0; j < count; ++j)
+        if (coef[j] != 0.0) { lc.coef[lc.n] = (float)(h * coef[j]); lc.ptr[lc.n] = k[j] + off; ++lc.n; }
+    return lc;
+}
+
+}  // namespace

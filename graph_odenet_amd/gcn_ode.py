@@ -50,6 +50,14 @@ class _Shared:
         if not getattr(graph, "is_partitioned", False) and hasattr(graph, "n_items"):
             self.y2_rows = _lib.load().gode_spmm_y2_colsum_rows(graph.n_items if graph.items is not None else n, graph.n_long, d)
         self._y2_colsum = None
+        self._X2 = None
+
+    @property
+    def X2(self):
+        """Pair of n x d arrays the C drivers write combined stage inputs to (csrc/ode_driver.hip)."""
+        if self._X2 is None:
+            self._X2 = [torch.empty_like(self.S), torch.empty_like(self.S)]
+        return self._X2
 
     def bwd(self):
         if self.dZ is None:
@@ -82,8 +90,6 @@ class _Shared:
             ws.ky[i] = ky[i].data_ptr()
         if not adjoint and _lib.load().gode_gcn_small_supported(self.n, self.d, int(groups)):
             # launch-bound graphs: the dopri5 step driver chains the stage inputs through this pair (csrc/ode_driver.hip)
-            if getattr(self, "X2", None) is None:
-                self.X2 = [torch.empty_like(self.S), torch.empty_like(self.S)]
             ws.X[0], ws.X[1] = self.X2[0].data_ptr(), self.X2[1].data_ptr()
         if adjoint:
             dZ, dS = self.bwd()
@@ -95,8 +101,6 @@ class _Shared:
                 ws.ka[i] = ka[i].data_ptr()
                 ws.ktheta[i] = kt[i].data_ptr()
             ws.wpart, ws.gpart, ws.bpart, ws.colsum_scratch = (p.data_ptr() for p in parts)
-            if getattr(self, "X2", None) is None:
-                self.X2 = [torch.empty_like(self.S), torch.empty_like(self.S)]
             ws.X[0], ws.X[1] = self.X2[0].data_ptr(), self.X2[1].data_ptr()
             sp = self.small_part(groups)
             ws.small_part = sp.data_ptr() if sp is not None else None
@@ -395,14 +399,19 @@ class GcnOdeAdjointField(Field):
     def new_state(self, y_end):
         """[y, a, a_t, W, b, gamma, beta]; the small components are views of ONE packed buffer laid out as the
         C driver expects: [W | b | gamma | beta | a_t]."""
-        s = self.s
-        d = s.d
+        self.theta = torch.zeros(self._theta_len(), dtype=torch.float32, device=y_end.device)
+        return self._packed_state(self.theta, y_end.clone(), torch.zeros_like(y_end))
+
+    def _theta_len(self):
+        return (self.s.d + 1) * self.s.d + 3 * self.s.d + 1
+
+    def _packed_state(self, th, y, a):
+        """[y, a, a_t, W, b, gamma, beta] with the small components as views of the packed buffer th."""
+        d = self.s.d
         nW = (d + 1) * d
-        self.theta = torch.zeros(nW + 3 * d + 1, dtype=torch.float32, device=y_end.device)
-        th = self.theta
-        comps = [y_end.clone(), torch.zeros_like(y_end), th[nW + 3 * d:], th[:nW].view(d + 1, d), th[nW:nW + d],
-                 th[nW + d:nW + 2 * d], th[nW + 2 * d:nW + 3 * d]]
-        comps[2]._gode_packed = th
+        comps = [y, a, th[nW + 3 * d:], th[:nW].view(d + 1, d), th[nW:nW + d], th[nW + d:nW + 2 * d],
+                 th[nW + 2 * d:nW + 3 * d]]
+        comps[2]._gode_packed = th            # keeps the base alive and lets the native step find it
         return comps
 
     def rk4_native(self, comps, t0, t1, n_steps):
@@ -429,13 +438,8 @@ class GcnOdeAdjointField(Field):
 
     def _packed_like(self, y):
         """A work copy of the state with the small components as views of ONE packed buffer, as new_state lays it out."""
-        d = self.s.d
-        nW = (d + 1) * d
-        th = torch.empty(nW + 3 * d + 1, dtype=torch.float32, device=y[0].device)
-        comps = [torch.empty_like(y[0]), torch.empty_like(y[1]), th[nW + 3 * d:], th[:nW].view(d + 1, d), th[nW:nW + d],
-                 th[nW + d:nW + 2 * d], th[nW + 2 * d:nW + 3 * d]]
-        comps[2]._gode_packed = th            # keeps the base alive and lets the native step find it
-        return comps
+        th = torch.empty(self._theta_len(), dtype=torch.float32, device=y[0].device)
+        return self._packed_state(th, torch.empty_like(y[0]), torch.empty_like(y[1]))
 
     def alloc_like(self, y, n):
         return [self._packed_like(y) for _ in range(n)]
