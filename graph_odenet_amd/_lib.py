@@ -245,6 +245,10 @@ SIGNATURES = {
                                                ctypes.POINTER(c_p), ctypes.POINTER(c_p), c_p, c_p, c_p,
                                                ctypes.POINTER(Rk4Workspace), ctypes.c_double, ctypes.c_double, c_f, c_f,
                                                c_p, c_p, c_p]),
+    "gode_gcn_ode_dopri5_step_backprop": (c_i, [ctypes.POINTER(GcnOdeFunc), c_p, ctypes.POINTER(c_p), c_p, c_p,
+                                                ctypes.c_double, ctypes.POINTER(ctypes.c_double), ctypes.c_double,
+                                                ctypes.c_double, ctypes.c_int32, ctypes.POINTER(c_p), c_p, c_p, c_p,
+                                                ctypes.POINTER(c_p), ctypes.POINTER(Rk4Workspace), c_p, c_p]),
     "gode_gat_ode_theta_len": (c_i64, [c_i64]),
     "gode_gat_ode_theta_len_heads": (c_i64, [c_i64, c_i64]),
     "gode_gat_ode_dopri5_step_forward": (c_i, [ctypes.POINTER(GatOdeFunc), c_p, ctypes.POINTER(c_p), c_p,

@@ -549,12 +549,53 @@ extern "C" int gode_gcn_ode_dopri5_step_adjoint(const gode_gcn_odefunc_t* f, con
 // ---------------------------------------------------------------------------------------------------------------
 namespace {
 
-// abar + Ybar_2 + Ybar_3 + Ybar_4: what the launch that forms Ybar_1 adds to it, leaving abar_n
-gode_lincomb_t sweep_pre(const float* abar, float* const* yb) {
-    gode_lincomb_t pre = one_term(abar);
-    for (int q = 1; q < 4; ++q) { pre.coef[q] = 1.f; pre.ptr[q] = yb[q]; }
-    pre.n = 4;
-    return pre;
+// Which launches a reverse sweep's stage takes where the fused launch does not apply
+struct SweepRoute {
+    bool small;             // launch-bound: one merged finishing launch per stage
+    bool bw;                // large graphs at d = 128: dense VJP and weight-gradient partials from one pass
+    int64_t wparts, cparts; // weight-gradient partial rows; column-sum rows of the masked cotangent (0: none)
+    float* cot_colpart;
+    float* gpart; float* bpart;
+};
+SweepRoute sweep_route(const gode_gcn_odefunc_t* f, const gode_rk4_workspace_t* ws, float* cot_colpart) {
+    SweepRoute r;
+    r.small = f->n <= kMergedFinishMaxRows;
+    r.wparts = gode_wgrad_parts(f->n);
+    r.bw = !r.small && gode_bwd_wgrad_supported(f->n, f->d, f->d, f->groups) && gode_bwd_wgrad_parts(f->n) <= r.wparts;
+    r.cparts = (!r.small && cot_colpart) ? gode_masked_cot_parts(f->n, f->d) : 0;
+    r.cot_colpart = cot_colpart;
+    r.gpart = f->groups > 0 ? ws->gpart : nullptr;
+    r.bpart = f->groups > 0 ? ws->bpart : nullptr;
+    return r;
+}
+
+// One stage of a reverse sweep, multi-launch routes: masked cotangent kbar * [k > 0], SpT, the dense VJP at the stage
+// input yin into ybar (pre, nullable: added to it), the weight gradient, and the stage's parameter part closed into kt
+int sweep_stage(const gode_gcn_odefunc_t* f, const gode_rk4_workspace_t* ws, const SweepRoute& r, const gode_lincomb_t& cot,
+                const float* k, const gode_lincomb_t& yin, const gode_lincomb_t* pre, float* ybar, float* kt, float ts,
+                void* stream) {
+    const int64_t n = f->n, d = f->d;
+    GODE_TRY(gode_masked_cot_f32(&cot, k, ws->dZ, n, d, r.cparts > 0 ? r.cot_colpart : nullptr, stream));
+    GODE_TRY(spmm(f->AT, ws->dZ, ws->dS, d, nullptr, stream));                 // dS = A^T dZ
+    if (r.bw) {
+        GODE_TRY(gode_gn_time_gemm_bwd_wgrad_f32(&yin, n, d, f->groups, f->eps, f->gamma, f->beta, f->W, d, 1, ws->dS,
+                                                 1.f, pre, ybar, r.gpart, r.bpart, ws->wpart, stream));
+    } else {
+        GODE_TRY(gode_gn_time_gemm_bwd_f32(&yin, n, d, f->groups, f->eps, f->gamma, f->W, d, 1, ws->dS, 1.f,
+                                           pre, ybar, r.gpart, r.bpart, stream));
+        GODE_TRY(gode_wgrad_f32(&yin, n, d, f->groups, f->eps, f->gamma, f->beta, ws->dS, d, 1, ws->wpart, stream));
+        if (r.small) return stage_finish_merged(f, ws, kt, ts, stream);
+    }
+    GODE_TRY(close_weight(f, ws, kt, r.bw ? gode_bwd_wgrad_parts(n) : r.wparts, ts, stream));
+    GODE_TRY(close_bias(f, ws, kt, r.cparts > 0 ? r.cot_colpart : ws->dZ, r.cparts > 0 ? r.cparts : n, stream));
+    return close_affine(f, ws, kt, stream);
+}
+
+// theta += sum of `count` closed stage parts   (weights 1: h is already inside kbar)
+int add_stage_parts(float* theta, float* const* kt, int count, int64_t len, void* stream) {
+    gode_lincomb_t tc = one_term(theta);
+    for (int q = 0; q < count; ++q) { tc.coef[tc.n] = 1.f; tc.ptr[tc.n] = kt[q]; ++tc.n; }
+    return gode_lincomb_f32(theta, &tc, len, stream);
 }
 
 }  // namespace
@@ -610,14 +651,14 @@ extern "C" int gode_gcn_ode_rk4_backprop(const gode_gcn_odefunc_t* f, const floa
         int cur = 0;
         {
             const float* r = record(step_end - 1);
-            const gode_lincomb_t c4 = stage_cotangent(acur, yb, 3, h);
+            const gode_lincomb_t c4 = stage_cotangent(TAB38, acur, (float)(h * B38[3]), yb, 3, h);
             GODE_TRY(gode_masked_cot_f32(&c4, r + 4 * nd, dz[0], n, d, nullptr, stream));
         }
         for (int i = step_end - 1; i >= step_begin; --i) {
             const float* y = record(i);
             float* k[4] = {(float*)y + nd, (float*)y + 2 * nd, (float*)y + 3 * nd, (float*)y + 4 * nd};
             const double t = (double)t0 + i * h;
-            const gode_lincomb_t pre = sweep_pre(acur, yb);
+            const gode_lincomb_t pre = sweep_pre(TAB38, acur, 1.f, yb, 1);
             float stage_t[4];
             for (int s = 3; s >= 0; --s) {
                 stage_t[s] = (float)(t + C38[s] * h);
@@ -625,7 +666,7 @@ extern "C" int gode_gcn_ode_rk4_backprop(const gode_gcn_odefunc_t* f, const floa
                 gode_lincomb_t nxt; nxt.n = 0;
                 const float* knext = nullptr;
                 if (s > 0) {
-                    nxt = stage_cotangent(acur, yb, s - 1, h);               // names yb[s]: this launch's rows
+                    nxt = stage_cotangent(TAB38, acur, (float)(h * B38[s - 1]), yb, s - 1, h);    // names yb[s]: this launch's rows
                     knext = k[s - 1];
                 } else if (i > step_begin) {
                     nxt = one_term(yb[0]); nxt.coef[0] = (float)(h * B38[3]);              // kbar_4 of step i - 1
@@ -647,47 +688,97 @@ extern "C" int gode_gcn_ode_rk4_backprop(const gode_gcn_odefunc_t* f, const floa
         *a_result = acur;
         return 0;
     }
-    const bool small = n <= kMergedFinishMaxRows;
-    const int64_t wparts = gode_wgrad_parts(n);
-    const bool bw = !small && gode_bwd_wgrad_supported(n, d, d, f->groups) && gode_bwd_wgrad_parts(n) <= wparts;
-    const int64_t cparts = (!small && cot_colpart) ? gode_masked_cot_parts(n, d) : 0;
-    float* gpart = f->groups > 0 ? ws->gpart : nullptr;
-    float* bpart = f->groups > 0 ? ws->bpart : nullptr;
+    const SweepRoute route = sweep_route(f, ws, cot_colpart);
     for (int i = step_end - 1; i >= step_begin; --i) {
         const float* y = record(i);
         float* k[4] = {(float*)y + nd, (float*)y + 2 * nd, (float*)y + 3 * nd, (float*)y + 4 * nd};
         const double t = (double)t0 + i * h;
-        const gode_lincomb_t pre = sweep_pre(acur, yb);
+        const gode_lincomb_t pre = sweep_pre(TAB38, acur, 1.f, yb, 1);
         for (int s = 3; s >= 0; --s) {
-            const float ts = (float)(t + C38[s] * h);
-            const gode_lincomb_t cot = stage_cotangent(acur, yb, s, h);
-            GODE_TRY(gode_masked_cot_f32(&cot, k[s], ws->dZ, n, d, cparts > 0 ? cot_colpart : nullptr, stream));
-            GODE_TRY(spmm(f->AT, ws->dZ, ws->dS, d, nullptr, stream));                 // dS = A^T dZ
-            const gode_lincomb_t yin = stage_terms(y, k, s, h);
-            float* kt = ws->ktheta[s];
-            if (bw) {
-                GODE_TRY(gode_gn_time_gemm_bwd_wgrad_f32(&yin, n, d, f->groups, f->eps, f->gamma, f->beta, f->W, d, 1, ws->dS,
-                                                         1.f, s == 0 ? &pre : nullptr, yb[s], gpart, bpart, ws->wpart, stream));
-            } else {
-                GODE_TRY(gode_gn_time_gemm_bwd_f32(&yin, n, d, f->groups, f->eps, f->gamma, f->W, d, 1, ws->dS, 1.f,
-                                                   s == 0 ? &pre : nullptr, yb[s], gpart, bpart, stream));
-                GODE_TRY(gode_wgrad_f32(&yin, n, d, f->groups, f->eps, f->gamma, f->beta, ws->dS, d, 1, ws->wpart, stream));
-                if (small) {
-                    GODE_TRY(stage_finish_merged(f, ws, kt, ts, stream));
-                    continue;
-                }
-            }
-            GODE_TRY(close_weight(f, ws, kt, bw ? gode_bwd_wgrad_parts(n) : wparts, ts, stream));
-            GODE_TRY(close_bias(f, ws, kt, cparts > 0 ? cot_colpart : ws->dZ, cparts > 0 ? cparts : n, stream));
-            GODE_TRY(close_affine(f, ws, kt, stream));
+            const gode_lincomb_t cot = stage_cotangent(TAB38, acur, (float)(h * B38[s]), yb, s, h);
+            GODE_TRY(sweep_stage(f, ws, route, cot, k[s], stage_terms(y, k, s, h), s == 0 ? &pre : nullptr, yb[s],
+                                 ws->ktheta[s], (float)(t + C38[s] * h), stream));
         }
-        // theta += sum_s ktheta_s   (weights 1: h is already inside kbar)
-        gode_lincomb_t tc = one_term(theta);
-        tc.n = 5;
-        for (int q = 0; q < 4; ++q) { tc.coef[1 + q] = 1.f; tc.ptr[1 + q] = ws->ktheta[q]; }
-        GODE_TRY(gode_lincomb_f32(theta, &tc, gode_gcn_ode_theta_len(d), stream));
+        GODE_TRY(add_stage_parts(theta, ws->ktheta, 4, gode_gcn_ode_theta_len(d), stream));
         float* tmp = acur; acur = yb[0]; yb[0] = tmp;
     }
     *a_result = acur;
     return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Backprop through an adaptive dopri5 solve (odeint._OdeintBackpropDopri5): the reverse sweep over ONE accepted step per
+// call - the controller's record (which steps were accepted, their sizes, the interpolation that ends an interval) stays
+// with the caller, as the controller itself does.  The step went from y_n at t_n with step h through the saved stage
+// derivatives k_1..k_7 (k_1 = f(t_n, y_n) is the step before's k_7, or the interval's opening evaluation); with one
+// cotangent array g and host weights wy, wk[1..7] (stages numbered from 1 in this comment, from 0 in the code):
+//   kbar_s = wk[s] g + h sum_{q > s} DPA[q][s] Ybar_q  (+ kbar7 when s = 7),
+//   Ybar_s = J_s^T kbar_s,  theta += (df/dtheta)_s^T kbar_s   for s = 7..2 (and s = 1 when `first`),
+//   ybar_n = wy g + sum_s Ybar_s
+// kbar_1 leaves the call as the kbar7 of the step before, unless `first`: then it is pushed through f at (t_n, y_n) here.
+// An ordinary step has g = ybar_{n+1}, wy = 1, wk[s] = h b_s; the interpolated last step of an interval folds the
+// interpolation's coefficients into wy and wk.  A stage whose cotangent has no term is skipped.
+// The launches of a stage are the rk4 sweep's (sweep_stage; fused: masked cotangent + one VJP launch); the stages'
+// parameter parts are added to theta by one launch per step.
+// ---------------------------------------------------------------------------------------------------------------
+extern "C" int gode_gcn_ode_dopri5_step_backprop(const gode_gcn_odefunc_t* f, const float* y, float* const* k,
+                                                 const float* g, const float* kbar7, double wy, const double* wk,
+                                                 double t, double h, int32_t first, float* const* ybar, float* ybar_n,
+                                                 float* kbar1, float* theta, float* const* ktheta,
+                                                 const gode_rk4_workspace_t* ws, float* cot_colpart, void* stream)
+{
+    if (!f || !y || !k || !g || !wk || !ybar || !ybar_n || !theta || !ktheta || !ws) return GODE_E_NULLPTR;
+    if (f->n <= 0 || f->d <= 0) return GODE_E_SHAPE;
+    if (!first && !kbar1) return GODE_E_NULLPTR;
+    for (int s = 0; s < 7; ++s) if (!k[s] || !ktheta[s]) return GODE_E_NULLPTR;
+    for (int s = 1; s < 7; ++s) if (!ybar[s]) return GODE_E_NULLPTR;
+    if (first && !ybar[0]) return GODE_E_NULLPTR;
+    if (ybar_n == g || ybar_n == kbar7 || (kbar1 && (kbar1 == g || kbar1 == kbar7 || kbar1 == ybar_n))) return GODE_E_SHAPE;
+    for (int s = 0; s < 7; ++s)
+        if (ybar[s] && (ybar[s] == g || ybar[s] == kbar7 || ybar[s] == ybar_n || ybar[s] == kbar1)) return GODE_E_SHAPE;
+    if (!ws->dZ || !ws->dS || !ws->wpart || !ws->colsum_scratch) return GODE_E_NULLPTR;
+    if (f->groups > 0 && (!ws->gpart || !ws->bpart)) return GODE_E_NULLPTR;
+    const int64_t n = f->n, d = f->d, nd = n * d, P = gode_gcn_ode_theta_len(d);
+    const bool fused = fused_small(f) && ws->small_part != nullptr;
+    const SweepRoute route = sweep_route(f, ws, cot_colpart);
+    const int64_t slot = fused ? gode_gcn_small_parts(n) * gode_gcn_small_part_len(d) : 0;
+    const int last = first ? 0 : 1;                // the last stage the sweep pushes through f
+    bool dead[7] = {};
+    float* kt[7]; float kt_time[7];
+    int live = 0;
+    auto cotangent = [&](int s) {
+        gode_lincomb_t c = stage_cotangent(TABDP, g, (float)wk[s], ybar, s, h, dead);
+        if (s == 6 && kbar7) { c.coef[c.n] = 1.f; c.ptr[c.n] = kbar7; ++c.n; }
+        return c;
+    };
+    for (int s = 6; s >= last; --s) {
+        const gode_lincomb_t cot = cotangent(s);
+        if (cot.n == 0) { dead[s] = true; continue; }
+        const float ts = (float)(t + DPC[s] * h);
+        const gode_lincomb_t yin = dp_terms(y, k, DPA[s], s, h, true);
+        // `first`: the launch that forms Ybar_1 adds the rest of ybar_n to it (every later stage is settled by then)
+        const bool closes = first && s == 0;
+        const gode_lincomb_t pre = sweep_pre(TABDP, g, (float)wy, ybar, 1, dead);
+        float* out = closes ? ybar_n : ybar[s];
+        if (fused) {
+            GODE_TRY(gode_masked_cot_f32(&cot, k[s], ws->dZ, n, d, nullptr, stream));
+            GODE_TRY(gode_gcn_vjp_small_f32(f, &yin, ws->dZ, 1.f, closes ? &pre : nullptr, out, ws->small_part + live * slot, stream));
+        } else {
+            GODE_TRY(sweep_stage(f, ws, route, cot, k[s], yin, closes ? &pre : nullptr, out, ktheta[live], ts, stream));
+        }
+        kt[live] = ktheta[live]; kt_time[live] = ts;
+        ++live;
+    }
+    if (!first || dead[0]) {
+        // ybar_n = wy g + sum Ybar_s, and (not first) kbar_1 for the step before: one launch
+        float* outs[2] = {ybar_n, kbar1};
+        gode_lincomb_t lcs[2] = {sweep_pre(TABDP, g, (float)wy, ybar, 1, dead), cotangent(0)};
+        int64_t lens[2] = {nd, nd};
+        int count = first ? 1 : 2;
+        if (count == 2 && lcs[1].n == 0) { GODE_TRY(gode_zero_f32(kbar1, nd, stream)); count = 1; }
+        GODE_TRY(gode_lincomb_multi_f32(outs, lcs, lens, count, stream));
+    }
+    if (live == 0) return 0;
+    if (fused) GODE_TRY(gode_gcn_small_finish_multi_f32(f, ws->small_part, live, kt, kt_time, stream));
+    return add_stage_parts(theta, kt, live, P, stream);
 }

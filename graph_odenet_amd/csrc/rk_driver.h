@@ -51,12 +51,32 @@ inline gode_lincomb_t combine_terms(const float* y, float* const* k, double h) {
     for (int j = 0; j < 3; ++j) { lc.coef[lc.n] = (float)(h * B38[j]); lc.ptr[lc.n] = k[j]; ++lc.n; }
     return lc;
 }
-// kbar_s of a backprop sweep: h b_s abar + h sum_{q > s} A38[q][s] Ybar_q
-inline gode_lincomb_t stage_cotangent(const float* abar, float* const* ybar, int s, double h) {
+// A Butcher matrix as the sweeps read it: a[q * lda + s] = A[q][s] of a method with `stages` stages
+struct Tableau { const double* a; int lda; int stages; };
+const Tableau TAB38 = {&A38[0][0], 3, 4};
+const Tableau TABDP = {&DPA[0][0], 6, 7};
+
+// kbar_s of a backprop sweep: w abar + h sum_{q > s} A[q][s] Ybar_q  (w = h b_s in a plain step; a zero w, a zero
+// A[q][s] and a stage q with dead[q] set - its cotangent was identically zero, so it has no Ybar_q - add no term:
+// the result may have none)
+inline gode_lincomb_t stage_cotangent(const Tableau& tab, const float* abar, float w, float* const* ybar, int s, double h,
+                                      const bool* dead = nullptr) {
+    gode_lincomb_t lc;
+    lc.n = 0;
+    if (w != 0.f) { lc.coef[0] = w; lc.ptr[0] = abar; lc.n = 1; }
+    for (int q = s + 1; q < tab.stages; ++q) {
+        const double a = tab.a[q * tab.lda + s];
+        if (a != 0.0 && !(dead && dead[q])) { lc.coef[lc.n] = (float)(h * a); lc.ptr[lc.n] = ybar[q]; ++lc.n; }
+    }
+    return lc;
+}
+// w abar + sum_{from <= q < stages} Ybar_q: what a sweep adds up to the cotangent of the step's start state
+inline gode_lincomb_t sweep_pre(const Tableau& tab, const float* abar, float w, float* const* ybar, int from,
+                                const bool* dead = nullptr) {
     gode_lincomb_t lc = one_term(abar);
-    lc.coef[0] = (float)(h * B38[s]);
-    for (int q = s + 1; q < 4; ++q)
-        if (A38[q][s] != 0.0) { lc.coef[lc.n] = (float)(h * A38[q][s]); lc.ptr[lc.n] = ybar[q]; ++lc.n; }
+    lc.coef[0] = w;
+    for (int q = from; q < tab.stages; ++q)
+        if (!(dead && dead[q])) { lc.coef[lc.n] = 1.f; lc.ptr[lc.n] = ybar[q]; ++lc.n; }
     return lc;
 }
 // terms of  y + h * sum_{j<count} coef[j] * k[j], every array `off` elements in  (zero coefficients dropped)

@@ -126,7 +126,8 @@ class _Shared:
         if not lib.gode_gcn_small_supported(self.n, self.d, int(groups)):
             return None                       # e.g. 2^20 x 128: 277 MB that nothing would ever read
         if getattr(self, "_small_part", None) is None:
-            self._small_part = torch.empty(6 * lib.gode_gcn_small_parts(self.n) * lib.gode_gcn_small_part_len(self.d),
+            # 7 slots: a dopri5 backprop step that opens an interval closes seven stages at once
+            self._small_part = torch.empty(7 * lib.gode_gcn_small_parts(self.n) * lib.gode_gcn_small_part_len(self.d),
                                            dtype=torch.float32, device=self.device)
         return self._small_part
 
@@ -340,6 +341,33 @@ class GcnOdeField(Field):
                    "gode_gcn_ode_dopri5_step_forward")
         return sums
 
+    # ---- backprop through an adaptive solve (odeint._OdeintBackpropDopri5; csrc/ode_driver.hip) -----------------
+    def dopri5_backprop_work(self, like):
+        """Work arrays of dopri5_step_backprop for a state like `like`: 7 Ybar, two (ybar_n, kbar_1) pairs that take
+        turns from step to step, 7 packed parameter parts."""
+        lib = _lib.load()
+        P = lib.gode_gcn_ode_theta_len(self.s.d)
+        return {"ybar": [torch.empty_like(like) for _ in range(7)],
+                "pairs": [(torch.empty_like(like), torch.empty_like(like)) for _ in range(2)],
+                "ktheta": [torch.empty(P, dtype=torch.float32, device=like.device) for _ in range(7)]}
+
+    def dopri5_step_backprop(self, y, k, g, kbar7, wy, wk, t, h, first, work, turn, theta):
+        """Reverse sweep over one accepted step (y_n, k_1..k_7, t_n, h) with cotangent g, weights wy / wk[7] and the
+        cotangent kbar7 arriving on k_7 (None: none); theta (packed [W | b | gamma | beta | .]) is incremented.
+        Returns (ybar_n, kbar_1) in work["pairs"][turn]; kbar_1 is None when `first` (it went through f here)."""
+        lib = _lib.load()
+        s, w = self.s, self.w
+        w.stage_buffers(True)
+        fs, ws = _func_struct(s), w.workspace_struct(True, s.groups)
+        arr = lambda ts: (ctypes.c_void_p * 7)(*[x.data_ptr() for x in ts])      # noqa: E731
+        ybar_n, kbar1 = work["pairs"][turn]
+        _lib.check(lib.gode_gcn_ode_dopri5_step_backprop(
+            ctypes.byref(fs), _lib.ptr(y), arr(k), _lib.ptr(g), _lib.ptr(kbar7), float(wy),
+            (ctypes.c_double * 7)(*[float(v) for v in wk]), float(t), float(h), int(bool(first)), arr(work["ybar"]),
+            _lib.ptr(ybar_n), _lib.ptr(kbar1), _lib.ptr(theta), arr(work["ktheta"]), ctypes.byref(ws),
+            _lib.ptr(w.cot_colpart()), _lib.stream_ptr()), "gode_gcn_ode_dopri5_step_backprop")
+        return ybar_n, (None if first else kbar1)
+
 
 class _PartMixin:
     """Row-partitioned state (partition.py): hooks the adaptive solver uses to see global error norms."""
@@ -380,6 +408,7 @@ class GcnOdePartField(_PartMixin, GcnOdeField):
     big_components = (0,)
     rk4_forward_save = None
     rk4_backprop = None
+    dopri5_step_backprop = None
 
     def __init__(self, spec, shared):
         GcnOdeField.__init__(self, spec, shared)

@@ -190,7 +190,7 @@ class ODEBlock(nn.Module):
         super(ODEBlock, self).__init__()
         self.odefunc = odefunc
         # True (the reference): odeint_adjoint.  False: odeint, differentiable by backprop through the solve under rk4
-        # (odeint._OdeintBackprop); under dopri5 that solve is forward-only
+        # (odeint._OdeintBackprop) and under the adaptive default (odeint._OdeintBackpropDopri5)
         self.adjoint = bool(adjoint)
         if node_order is not None:            # extension: "auto" (default rule) | "given" | "degree" (gcn_ode.tuned_graph)
             from .gcn_ode import NODE_ORDERS

@@ -9,17 +9,21 @@ GCN/models.py:5,192, GAT/models.py:5,192 in the reference):
 and stage inputs are never materialised; any other module runs through autograd with the
 RK arithmetic still in the HIP kernels.
 
-`odeint` is differentiable under method="rk4" as torchdiffeq's is (backprop through the solver's operations, not the
-adjoint): with grad mode on and y0 or a parameter of func requiring grad it returns a tensor with a grad_fn whose
-gradient is the exact derivative of the computed discrete solution w.r.t. y0 and func's parameters (t gets None).
-Adaptive dopri5 under `odeint` stays forward-only (a follow-up), and so do row-partitioned fields.
+`odeint` is differentiable as torchdiffeq's is (backprop through the solver's operations, not the adjoint): with grad
+mode on and y0 or a parameter of func requiring grad it returns a tensor with a grad_fn whose gradient is the exact
+derivative of the computed discrete solution w.r.t. y0 and func's parameters (t gets None).  Under adaptive dopri5 the
+accepted step sizes are constants of that derivative: rejected attempts, the initial-step heuristic and the controller
+contribute nothing (what autograd through a solver whose step sizes are Python floats gives).  Row-partitioned fields
+stay forward-only.
 """
 import weakref
 
 import torch
 
 from . import ops
-from .solver import (Dopri5Stats, Field, integrate_dopri5_inplace, integrate_rk4, uniform_grid)
+from . import solver
+from .solver import (DP_A, DP_B, DP_C, DP_MID, Dopri5Record, Dopri5Stats, Field, integrate_dopri5,
+                     integrate_dopri5_inplace, integrate_rk4, uniform_grid)
 
 
 NATIVE_RK4 = True      # fused fields: issue a whole rk4 solve from one C-ABI call (False: per-stage Python driver)
@@ -36,6 +40,8 @@ NFE_COUNTS_SKIPPED_DLDT_EVAL = True
 # Backprop through a fused rk4 solve keeps y_n and k_1..k_4 of every step (5 n d floats per step) when they fit in this many
 # bytes (2^20 x 128 state, 16 steps: 40 GiB); above it only y_n is kept and each step is re-run into a one-step record just
 # before its reverse sweep (the same launches: gradients bit for bit those of the save-everything mode).
+# Backprop through a fused dopri5 solve keeps y_n and k_1..k_7 of every accepted step (8 n d floats per step) under the same
+# bound; a solve that outgrows it keeps y_n and k_1 and re-runs each step (one native step call) before its sweep.
 BACKPROP_SAVE_MAX_BYTES = 48 << 30
 
 
@@ -414,21 +420,151 @@ class _OdeintBackprop(torch.autograd.Function):
         return (None, None, None, None, None, None, gy0, *pg)
 
 
+def _interp_weights(x):
+    """(cy0, cy1, kc[7]): the 4th-order interpolation at abscissa x of a step as cy0 y_n + cy1 y_{n+1} + h sum kc_s k_s
+    (solver.integrate_dopri5 forms the same numbers)."""
+    x2, x3, x4 = x * x, x * x * x, x * x * x * x
+    wm = 16 * x4 - 32 * x3 + 16 * x2
+    cy0 = -8 * x4 + 18 * x3 - 11 * x2 + 1 + wm
+    cy1 = -8 * x4 + 14 * x3 - 5 * x2
+    kc = [wm * m for m in DP_MID]
+    kc[0] += -2 * x4 + 5 * x3 - 4 * x2 + x
+    kc[6] += 2 * x4 - 3 * x3 + x2
+    return cy0, cy1, kc
+
+
+def _dopri5_step_torch(func, y, t, h, x):
+    """One Dormand-Prince step from y at t as differentiable torch ops through func; x: the interpolation abscissa of a
+    last step that overshot the end time (None: the step's own end state is returned)."""
+    tt = lambda v: torch.tensor(v, dtype=y.dtype, device=y.device)      # noqa: E731
+    ks = [func(tt(t), y)]
+    for s in range(1, 7 if x is not None else 6):       # k_7 enters the result through the interpolation only
+        ks.append(func(tt(t + DP_C[s] * h), y + sum((h * a) * k for a, k in zip(DP_A[s], ks) if a != 0.0)))
+    y1 = y + sum((h * b) * k for b, k in zip(DP_B, ks) if b != 0.0)
+    if x is None:
+        return y1
+    cy0, cy1, kc = _interp_weights(x)
+    return cy0 * y + cy1 * y1 + sum((h * c) * k for c, k in zip(kc, ks) if c != 0.0)
+
+
+class _OdeintBackpropDopri5(torch.autograd.Function):
+    """odeint under adaptive dopri5 with gradients: the forward is odeint's own (bit for bit, the same launches on buffers
+    a solver.Dopri5Record keeps), the backward the exact derivative of the discrete solution with the accepted step
+    sizes as constants.  A fused field offering dopri5_step_backprop (GcnOdeField) keeps y_n and k_1..k_7 of every
+    accepted step - or y_n and k_1 past BACKPROP_SAVE_MAX_BYTES, each step then re-run by one native step call before
+    its sweep - and sweeps them in reverse, one C call per step (csrc/ode_driver.hip).  Any other field keeps y_n and
+    re-runs each accepted step as torch ops through func under autograd, k_1 = func(t_n, y_n) recomputed: the same
+    function of y_n as the derivative FSAL hands over, since Y_7 and y_{n+1} are the same combination."""
+
+    @staticmethod
+    def forward(ctx, func, fields, tl, rtol, atol, y0, *params):
+        fwd = fields[0]
+        order, inverse = _rows(fwd)
+        fused = getattr(fwd, "dopri5_step_backprop", None) is not None and solver.DOPRI5_NATIVE
+        if getattr(fwd, "fixed_grid_only", False):
+            raise NotImplementedError("odeint: this field supports the fixed-grid method only (method='rk4')")
+        y0c = y0.detach().contiguous()
+        outs = [y0c.clone()]
+        stats = Dopri5Stats()
+        records = []
+        with torch.no_grad():
+            prep = getattr(fwd, "prepare", None)
+            if prep is not None:
+                prep()
+            cur = y0c.clone() if order is None else y0c.index_select(0, order)
+            left = BACKPROP_SAVE_MAX_BYTES
+            for i in range(1, len(tl)):
+                rec = Dopri5Record(7, left) if fused and left is not None else Dopri5Record(1 if fused else 0)
+                (cur,), _ = integrate_dopri5(fwd, [cur], tl[i - 1], tl[i], rtol, atol, stats, record=rec)
+                if fused and left is not None:
+                    left = left - rec.bytes if rec.keep == 7 else None      # past the bound: the later intervals keep k_1 only
+                records.append(rec)
+                outs.append(cur.clone() if order is None else cur.index_select(0, inverse))
+        _bump_nfe(func, stats.nfe if getattr(fwd, "fused", False) else 0)
+        ctx.func, ctx.fields, ctx.tl, ctx.tols, ctx.fused, ctx.records = func, fields, tl, (rtol, atol), fused, records
+        return torch.stack(outs)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        grad_out = grad_out.contiguous()
+        tl, records = ctx.tl, ctx.records
+        fwd = ctx.fields[0]
+        order, inverse = _rows(fwd)
+        if ctx.fused:
+            gather = (lambda g: g.clone()) if order is None else (lambda g: g.index_select(0, order))
+            a = gather(grad_out[-1])
+            d = fwd.s.d
+            nW = (d + 1) * d
+            theta = torch.zeros((nW + 3 * d + 1,), dtype=torch.float32, device=a.device)
+            work = fwd.dopri5_backprop_work(a)
+            rerun = None
+            turn = 0                                    # which (ybar_n, kbar_1) pair the next call writes: never the one it reads
+            with torch.no_grad():
+                for i in range(len(tl) - 1, 0, -1):
+                    steps = records[i - 1].steps
+                    kbar7 = None
+                    for j in range(len(steps) - 1, -1, -1):
+                        t, h, x, y, ks = steps[j]
+                        ks = [k[0] for k in ks]
+                        if len(ks) < 7:                 # re-run the step into a one-step record (the forward's launches)
+                            if rerun is None:
+                                rerun = [torch.empty_like(a) for _ in range(7)]
+                            fwd.dopri5_step_native(y, [[ks[0]]] + [[b] for b in rerun[:6]], [rerun[6]], t, h, *ctx.tols)
+                            ks = [ks[0]] + rerun[:6]
+                        if x is None:
+                            wy, wk = 1.0, [h * b for b in DP_B]
+                        else:
+                            cy0, cy1, kc = _interp_weights(x)
+                            wy, wk = cy0 + cy1, [h * (cy1 * b + c) for b, c in zip(DP_B, kc)]
+                        a, kbar7 = fwd.dopri5_step_backprop(y[0], ks, a, kbar7, wy, wk, t, h, j == 0, work, turn, theta)
+                        turn ^= 1
+                    if i > 1:
+                        a = a.add_(gather(grad_out[i - 1]))
+                gy0 = (a.clone() if order is None else a.index_select(0, inverse)).add_(grad_out[0])
+            comps = [None, None, None, theta[:nW].view(d + 1, d), theta[nW:nW + d], theta[nW + d:nW + 2 * d],
+                     theta[nW + 2 * d:nW + 3 * d]]
+            pg = ctx.fields[1]().param_grads(comps)
+        else:
+            func = ctx.func
+            params = _params(func)
+            nfe0 = getattr(func, "nfe", None)
+            a = grad_out[-1]
+            pg = [None] * len(params)
+            for i in range(len(tl) - 1, 0, -1):
+                for (t, h, x, y, _) in reversed(records[i - 1].steps):
+                    with torch.enable_grad():
+                        yn = (y[0] if order is None else y[0].index_select(0, inverse)).detach().requires_grad_(True)
+                        g = torch.autograd.grad(_dopri5_step_torch(func, yn, t, h, x), (yn,) + tuple(params), a,
+                                                allow_unused=True)
+                    a = g[0] if g[0] is not None else torch.zeros_like(a)
+                    for q, gq in enumerate(g[1:]):
+                        if gq is not None:
+                            pg[q] = gq if pg[q] is None else pg[q] + gq
+                a = a + grad_out[i - 1]
+            gy0 = a
+            if nfe0 is not None:
+                func.nfe = nfe0                   # evaluations re-run by the backward pass are not counted
+        return (None, None, None, None, None, gy0, *pg)
+
+
 def odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None):
-    """torchdiffeq's odeint.  Under method="rk4" with grad mode on and y0 or a parameter of func requiring grad the
-    result is differentiable (backprop through the solve: _OdeintBackprop; t gets no gradient); otherwise - and always
-    under dopri5 or on row-partitioned fields - a forward solve without gradient support (use odeint_adjoint to train)."""
+    """torchdiffeq's odeint.  With grad mode on and y0 or a parameter of func requiring grad the result is differentiable
+    (backprop through the solve: _OdeintBackprop under rk4, _OdeintBackpropDopri5 under dopri5; t gets no gradient);
+    otherwise - and always on row-partitioned fields - a forward solve without gradient support."""
     _check_state(y0)
     tl = _times(t)
     method = _method(method)
     fields = _fields(func, y0)
     fwd = fields[0]
-    if method == "rk4" and torch.is_grad_enabled() and getattr(fwd, "big_components", None) is None:
+    if torch.is_grad_enabled() and getattr(fwd, "big_components", None) is None:
         params = _params(func)
         if y0.requires_grad or params:
             same = len(fields[2]) == len(params) and all(p is q for p, q in zip(fields[2], params))
-            if getattr(fwd, "rk4_forward_save", None) is not None and not same:
+            hook = "rk4_forward_save" if method == "rk4" else "dopri5_step_backprop"
+            if getattr(fwd, hook, None) is not None and not same:
                 fields = (AutogradField(func, y0), None, params)      # the fused field does not cover these parameters
+            if method != "rk4":
+                return _OdeintBackpropDopri5.apply(func, fields, tl, float(rtol), float(atol), y0, *params)
             return _OdeintBackprop.apply(func, fields, tl, float(rtol), float(atol), options, y0, *params)
     stats = Dopri5Stats()
     order, inverse = _rows(fwd)

@@ -278,7 +278,7 @@ class EdgeODEBlock(nn.Module):
     def __init__(self, odefunc, tol=1e-5, method=None, step_size=None, adjoint=True):
         super().__init__()
         self.odefunc = odefunc
-        self.adjoint = bool(adjoint)       # False: odeint, differentiable by backprop through the solve under rk4
+        self.adjoint = bool(adjoint)       # False: odeint, differentiable by backprop through the solve (rk4 and dopri5)
         self.integration_time = torch.tensor([0, 1]).float()
         self.tol, self.method, self.step_size = tol, method, step_size
 

@@ -229,8 +229,32 @@ def _optimal_step(last, ratio, safety=0.9, ifactor=10.0, dfactor=0.2, order=5):
     return last / factor
 
 
-def integrate_dopri5(field, y, t0, t1, rtol, atol, stats=None, max_steps=100000):
-    """In-place adaptive integration of the component list y from t0 to t1 (either direction)."""
+class Dopri5Record:
+    """What backprop through an adaptive solve keeps of it (odeint._OdeintBackpropDopri5): one entry per accepted step,
+    (t_n, h_n, x, y_n, [k_1..k_keep]) with x the interpolation abscissa of a last step that overshot the end time, else
+    None.  keep = 7: all stage derivatives; 1: k_1 only; 0: the state alone.  The entries hold the solve's own buffers,
+    which the solve then leaves alone; with max_bytes given, a record of 7 that outgrows it drops to 1."""
+
+    def __init__(self, keep, max_bytes=None):
+        self.keep, self.max_bytes = keep, max_bytes
+        self.steps = []
+        self.bytes = 0
+
+    def accepted(self, t, h, x, y, kk):
+        """-> how many of the leading stage buffers kk[0..] the record has kept."""
+        self.steps.append((t, h, x, y, list(kk[:self.keep])))
+        self.bytes += sum(c.numel() * c.element_size() for c in y) * (1 + self.keep)
+        if self.keep == 7 and self.max_bytes is not None and self.bytes > self.max_bytes:
+            self.keep = 1
+            self.steps = [(t_, h_, x_, y_, k_[:1]) for (t_, h_, x_, y_, k_) in self.steps]
+        return self.keep
+
+
+def integrate_dopri5(field, y, t0, t1, rtol, atol, stats=None, max_steps=100000, record=None):
+    """In-place adaptive integration of the component list y from t0 to t1 (either direction).  record (a
+    Dopri5Record): every accepted step is entered there with the buffers that hold its y_n and stage derivatives, and the
+    solve continues in fresh ones (a rejected attempt's are reused) - the same launches on other addresses, so the
+    values are bit for bit those of the plain solve; the result is then returned in a buffer of its own."""
     stats = stats if stats is not None else Dopri5Stats()
     nc = len(y)
     sgn = 1.0 if t1 >= t0 else -1.0
@@ -287,9 +311,14 @@ def integrate_dopri5(field, y, t0, t1, rtol, atol, stats=None, max_steps=100000)
             if tau + dt >= span:
                 # interpolate back to the end time with the 4th-order fit through (y0, y_mid, y1, f0, f1)
                 x = (span - tau) / dt
+                res = y                                   # the result overwrites y_n, unless a record keeps that
+                if record is not None:
+                    record.accepted(t, h, x if x < 1.0 else None, y, kk)
+                    res = y1 if x >= 1.0 else alloc(y, 1)[0]
                 if x >= 1.0:
                     for c in range(nc):
-                        y[c].copy_(y1[c])
+                        if res[c] is not y1[c]:
+                            res[c].copy_(y1[c])
                 else:
                     x2, x3, x4 = x * x, x * x * x, x * x * x * x
                     wm = 16 * x4 - 32 * x3 + 16 * x2
@@ -301,10 +330,16 @@ def integrate_dopri5(field, y, t0, t1, rtol, atol, stats=None, max_steps=100000)
                     kc[0] += cf0
                     kc[6] += cf1
                     for c in range(nc):
-                        ops.lincomb_(y[c], [(cy0, y[c]), (cy1, y1[c])] +
+                        ops.lincomb_(res[c], [(cy0, y[c]), (cy1, y1[c])] +
                                      [(h * kc[s], kk[s][c]) for s in range(7) if kc[s] != 0.0])
+                y = res
                 tau = span
                 break
+            if record is not None:
+                kept = record.accepted(t, h, None, y, kk)
+                for j in range(min(kept, 6)):             # kk[6] goes on as the next step's k_1 and is read only
+                    ks[order[j]] = alloc(y, 1)[0]
+                y = alloc(y, 1)[0]                        # takes y1's place below
             y, y1 = y1, y
             last = y1
             tau += dt

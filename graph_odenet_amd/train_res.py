@@ -66,7 +66,7 @@ def build_parser():
                         "(gat_heads.py; --hidden must be a multiple of H)")
     p.add_argument('--adjoint', type=int, choices=[0, 1], default=1,
                    help="1: every ODE block trains through odeint_adjoint (the reference); 0: through odeint, "
-                        "differentiated by backprop through the rk4 solve (forward-only under dopri5)")
+                        "differentiated by backprop through the solve (rk4 or dopri5)")
     p.add_argument('--variant', choices=sorted(VARIANTS), default="gcn",
                    help="gcn: models over a normalised adjacency (GCN/train_res.py); gat: edge attention over "
                         "(src, tgt, Mtgt) (GAT/train_res.py)")

@@ -544,7 +544,7 @@ typedef struct gode_rk4_workspace {
                                            3 or 4 terms is written once by its forward launch and read as one array by
                                            the VJP and weight-gradient launches */
     float* small_part;                  /* nullable: 6 * gode_gcn_small_parts(n) * gode_gcn_small_part_len(d) floats (rk4 uses 4 of
-                                           the 6 slots, a dopri5 step all of them) - enables
+                                           the 6 slots, a dopri5 step all of them; gode_gcn_ode_dopri5_step_backprop wants 7) - enables
                                            the fused launch-bound path of the adjoint drivers (csrc/small.hip) */
     float* y2_colsum;                   /* nullable: gode_spmm_y2_colsum_rows(A.n_items, A.n_long, d) * d floats - the bias
                                            gradient of an adjoint stage is reduced from the per-block column sums the
@@ -636,6 +636,29 @@ int gode_gcn_ode_dopri5_step_adjoint(const gode_gcn_odefunc_t* f, const float* y
                                      float* y1, float* a1, float* theta1, const gode_rk4_workspace_t* ws,
                                      double t, double h, float rtol, float atol, double* sums /* 4 */,
                                      void* err_scratch, void* stream);
+
+/* Backprop through an adaptive dopri5 solve, one accepted step per call (the discrete gradient of the computed solution
+ * with the accepted step sizes as constants; which steps were accepted, and the interpolation that ends an interval, are
+ * the caller's record).  y = y_n, k[0..6] = the step's saved stage derivatives k_1..k_7, t = t_n, h its signed size.
+ * With stages numbered from 1:
+ *   kbar_s = wk[s-1] g + h sum_{q > s} A[q][s] Ybar_q (+ kbar7 when s = 7; nullable: none arrives),
+ *   Ybar_s = J_s^T kbar_s and theta += (df/dtheta)_s^T kbar_s for s = 7..2,  ybar_n = wy g + sum_s Ybar_s,
+ * and kbar1 receives kbar_1: the kbar7 of the step before.  first != 0 (first step of an interval): kbar_1 is pushed
+ * through f at (t_n, y_n) here as well (Ybar_1 into ybar_n, its parameter part into theta) and kbar1 is not written
+ * (nullable then).  An ordinary step passes g = dL/dy_{n+1}, wy = 1, wk[s] = h b_s; a last step cut by the 4th-order
+ * interpolation passes g = dL/dy_end with the interpolation's coefficients folded into wy and wk.  wy, wk: fp64 on the
+ * host, rounded once here.  A stage whose cotangent has no term (wk = 0, no kbar7) is skipped.
+ * ybar[1..6] (and ybar[0] when first != 0): n x d work arrays for Ybar_2..Ybar_7; ybar_n, kbar1: n x d results - none of
+ * them may be g or kbar7.  theta (packed as for the adjoint, a_t slot unspecified) is INCREMENTED once per call; ktheta:
+ * 7 work vectors of gode_gcn_ode_theta_len(d) floats.  ws: dZ, dS, wpart, gpart, bpart, colsum_scratch as for
+ * gode_gcn_ode_rk4_backprop (ka / ktheta of ws are not used); small_part, when given, must hold 7 slots.  cot_colpart
+ * as there.  One stream. */
+int gode_gcn_ode_dopri5_step_backprop(const gode_gcn_odefunc_t* f, const float* y, float* const* k /* 7 */,
+                                      const float* g, const float* kbar7 /* nullable */, double wy,
+                                      const double* wk /* host, 7 */, double t, double h, int32_t first,
+                                      float* const* ybar /* 7 */, float* ybar_n, float* kbar1, float* theta,
+                                      float* const* ktheta /* 7 */, const gode_rk4_workspace_t* ws,
+                                      float* cot_colpart /* nullable */, void* stream);
 
 /* The same for the GAT ODE function  f(t, x) = relu(EdgeAttention([t | GroupNorm(x)]))  (GAT/models.py:172-179 ->
  * GAT/layers.py:95-122), with the two Linear layers packed by role: Wsrc, Wtgt ((d+1) x d: message parts by source /

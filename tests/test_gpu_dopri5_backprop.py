@@ -1,0 +1,342 @@
+"""Backprop through odeint under adaptive dopri5 (odeint._OdeintBackpropDopri5): the gradient of the computed discrete
+solution w.r.t. y0 and the ODE function's parameters with the accepted step sizes as constants, against autograd through
+the oracle solver (solver_ref.odeint dopri5 + the reference layer math, whose step sizes are Python floats) replaying
+the product's own attempt sequence - on the three kernel routes of the fused GCN field and on the generic path."""
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+
+def dev():
+    assert torch.cuda.is_available()
+    return torch.device("cuda:0")
+
+
+def T(a):
+    return torch.from_numpy(np.asarray(a))
+
+
+def cora_adj(golden):
+    gr = golden("cora_graph.npz")
+    n = int(gr["n"])
+    return torch.sparse_coo_tensor(torch.stack([T(gr["rows"].astype(np.int64)), T(gr["cols"].astype(np.int64))]),
+                                   T(gr["vals"]), (n, n))
+
+
+def noise_floor_check(got, ref32, ref64, what, slack=4.0, floor=1e-5):
+    """|got - exact| must stay within `slack` x the fp32 oracle's own distance to the fp64 ground truth
+    (plus 1e-5 of the magnitude): parity to the noise floor of the fp32 computation itself."""
+    got = got.detach().cpu().double()
+    e_ref = (ref32.double() - ref64).abs().max().item()
+    e_got = (got - ref64).abs().max().item()
+    scale = max(1.0, ref64.abs().max().item())
+    print("%-22s err %.3e  fp32-oracle err %.3e  scale %.2e" % (what, e_got, e_ref, scale))
+    assert e_got <= slack * e_ref + floor * scale, "%s: err %.3e vs fp32-oracle err %.3e (scale %.2e)" % (what, e_got, e_ref, scale)
+
+
+def make_func(d, adj_dev, seed=0, node_order=None):
+    from graph_odenet_amd import models
+    torch.manual_seed(seed)
+    f = models.ODEfunc(d)
+    if node_order is not None:
+        f.node_order = node_order
+    with torch.no_grad():
+        f.norm1.weight.uniform_(0.5, 1.5)
+        f.norm1.bias.uniform_(-0.5, 0.5)
+    f = f.to(dev())
+    f.set_adj(adj_dev)
+    return f
+
+
+PNAMES = ("norm1.weight", "norm1.bias", "gc1.weight", "gc1.bias")
+
+
+def oracle_grads(f, adj, x0, t, R, tol, dtype, trace):
+    """Autograd through the oracle's dopri5 solves of the reference ODEfunc on the attempt sequences `trace` (one per
+    interval of t; the oracle restarts at every output time as the product does): (outputs, dL/dx0, {name: dL/dparam})
+    with L = sum_i <y(t_i), R_i>."""
+    from oracle import layers_ref as L, solver_ref as S
+    ps = {k: torch.nn.Parameter(v.detach().cpu().to(dtype).clone()) for k, v in f.named_parameters()}
+    adj = adj.to(dtype)
+
+    def func(tt, x):
+        return L.odefunc(tt.to(dtype), x, adj, *[ps[k] for k in PNAMES])
+    x = x0.detach().cpu().to(dtype).requires_grad_(True)
+    assert len(trace) == len(t) - 1
+    outs = [x]
+    S.REPLAY = [list(seq) for seq in trace]
+    try:
+        for i in range(1, len(t)):
+            outs.append(S.odeint(func, outs[-1], torch.tensor(t[i - 1:i + 1], dtype=dtype), rtol=tol, atol=tol,
+                                 method="dopri5")[1])
+        assert S.REPLAY == []
+    finally:
+        S.REPLAY = None
+    out = torch.stack(outs)
+    (out * R.to(dtype)).sum().backward()
+    return out.detach(), x.grad, {k: ps[k].grad for k in PNAMES}
+
+
+def product_grads(f, x0, t, R, tol, replay=None):
+    """-> (outputs, dL/dx0, {name: dL/dparam}, attempt sequences of the forward solves)"""
+    from graph_odenet_amd import odeint as OI, solver
+    f.zero_grad()
+    x = x0.detach().clone().requires_grad_(True)
+    solver.TRACE = []
+    solver.REPLAY = [list(seq) for seq in replay] if replay is not None else None
+    try:
+        out = OI.odeint(f, x, torch.tensor(t, device=dev()), rtol=tol, atol=tol)
+        trace = solver.TRACE
+    finally:
+        solver.TRACE = solver.REPLAY = None
+    assert out.grad_fn is not None, "odeint under dopri5 must be differentiable"
+    (out * R.to(dev())).sum().backward()
+    torch.cuda.synchronize()
+    return out.detach(), x.grad.clone(), {k: p.grad.clone() for k, p in f.named_parameters()}, trace
+
+
+def check_against_oracle(f, adj, x0, t, R, tol, got):
+    out, gx, gp, trace = got
+    o32, gx32, gp32 = oracle_grads(f, adj, x0, t, R, tol, torch.float32, trace)
+    o64, gx64, gp64 = oracle_grads(f, adj, x0, t, R, tol, torch.float64, trace)
+    noise_floor_check(out, o32, o64, "y(t)")
+    noise_floor_check(gx, gx32, gx64, "dL/dx0")
+    for k in PNAMES:
+        noise_floor_check(gp[k], gp32[k], gp64[k], "dL/d" + k)
+
+
+def check_forward_bit_identical(f, x0, t, tol, out):
+    from graph_odenet_amd import odeint as OI
+    with torch.no_grad():
+        ref = OI.odeint(f, x0, torch.tensor(t, device=dev()), rtol=tol, atol=tol)
+    assert ref.grad_fn is None
+    assert torch.equal(out, ref), "forward differs from odeint under no_grad"
+
+
+def accepted_steps(seq):
+    return [a[0] for a in seq if a[1]]
+
+
+def last_abscissa(seq, span=1.0):
+    acc = accepted_steps(seq)
+    return (span - sum(acc[:-1])) / acc[-1]
+
+
+@pytest.mark.parametrize("d,small_fused", [(16, 1), (16, 0), (64, 1)])
+def test_cora_backprop_vs_oracle(golden, d, small_fused):
+    """Cora, t = [0, 1], rtol = atol = 1e-3, loss <y(1), R>: a grad_fn, forward bit for bit odeint's no-grad result,
+    at least two accepted steps the last of which is cut by the interpolation, y(1) and the gradients of x, W, b, gamma,
+    beta at the oracle's noise floor.  small_fused 1 / 0 at d = 16: both launch-bound routes; d = 64: the MFMA kernels."""
+    from graph_odenet_amd import _lib
+    lib = _lib.load()
+    adj = cora_adj(golden)
+    f = make_func(d, adj.to(dev()))
+    torch.manual_seed(1)
+    x0 = torch.randn(adj.shape[0], d, device=dev())
+    t = [0.0, 1.0]
+    R = torch.zeros(2, adj.shape[0], d)
+    R[1] = torch.randn(adj.shape[0], d)
+    old = lib.gode_get_option(b"small_fused")
+    lib.gode_set_option(b"small_fused", small_fused)
+    try:
+        got = product_grads(f, x0, t, R, 1e-3)
+        check_forward_bit_identical(f, x0, t, 1e-3, got[0])
+    finally:
+        lib.gode_set_option(b"small_fused", old)
+    (seq,) = got[3]
+    assert len(accepted_steps(seq)) >= 2
+    assert last_abscissa(seq) < 1.0, "the last step must overshoot t = 1 and be interpolated"
+    check_against_oracle(f, adj, x0, t, R, 1e-3, got)
+
+
+def test_rejected_attempts_contribute_nothing(golden):
+    """Cora d = 16, make_func(seed=11), x0 = randn under seed 12, rtol = atol = 1e-5: the oracle's fp32 controller
+    rejects the fourth attempt (dt 1.40, error ratio 12) after three accepted steps.  The rejected attempt's buffers
+    are reused and it leaves no trace in the gradient."""
+    adj = cora_adj(golden)
+    d = 16
+    f = make_func(d, adj.to(dev()), seed=11)
+    torch.manual_seed(12)
+    x0 = torch.randn(adj.shape[0], d, device=dev())
+    t = [0.0, 1.0]
+    R = torch.zeros(2, adj.shape[0], d)
+    R[1] = torch.randn(adj.shape[0], d)
+    got = product_grads(f, x0, t, R, 1e-5)
+    (seq,) = got[3]
+    assert sum(1 for a in seq if not a[1]) >= 1, seq
+    check_forward_bit_identical(f, x0, t, 1e-5, got[0])
+    check_against_oracle(f, adj, x0, t, R, 1e-5, got)
+
+
+def test_large_route_renumbered_vs_oracle(monkeypatch):
+    """R-MAT graph of 2^17 rows (the >= 65 536-row kernels: gemm_pc.hip, the bwd-wgrad product, masked-cotangent column
+    sums), d = 128, 32 groups, node_order="degree" (rows renumbered), rtol = atol = 1e-2 (two accepted steps on the CPU
+    oracle): oracle check, forward bit identity and recompute-mode bit identity."""
+    from graph_odenet_amd import odeint as OI, synth
+    g = synth.rmat_graph(17, 1 << 20, seed=1, device=dev())
+    assert g.n_rows >= 70001
+    rows = torch.repeat_interleave(torch.arange(g.n_rows), (g.rowptr[1:] - g.rowptr[:-1]).cpu().long())
+    adj = torch.sparse_coo_tensor(torch.stack([rows, g.col.cpu().long()]), g.val.cpu(), (g.n_rows, g.n_rows))
+    d = 128
+    f = make_func(d, g, seed=4, node_order="degree")
+    assert f.norm1.num_groups == 32
+    torch.manual_seed(5)
+    x0 = torch.randn(g.n_rows, d, device=dev())
+    t = [0.0, 1.0]
+    R = torch.zeros(2, g.n_rows, d)
+    R[1] = torch.randn(g.n_rows, d)
+    got = product_grads(f, x0, t, R, 1e-2)
+    assert OI._fields(f, x0)[0].row_order is not None, "the rows must really be renumbered"
+    assert len(accepted_steps(got[3][0])) >= 2
+    check_forward_bit_identical(f, x0, t, 1e-2, got[0])
+    check_against_oracle(f, adj, x0, t, R, 1e-2, got)
+    monkeypatch.setattr(OI, "BACKPROP_SAVE_MAX_BYTES", 0)
+    rec = product_grads(f, x0, t, R, 1e-2)
+    assert torch.equal(rec[1], got[1])
+    for k in PNAMES:
+        assert torch.equal(rec[2][k], got[2][k]), k
+
+
+@pytest.mark.parametrize("d", [16, 64])
+def test_recompute_mode_bit_identical(golden, d, monkeypatch):
+    """With BACKPROP_SAVE_MAX_BYTES = 0 (y_n and k_1 kept, every step re-run before its sweep) the output and the
+    gradients are bit for bit those of the save-everything mode; three output times, a loss on each."""
+    from graph_odenet_amd import odeint as OI
+    adj = cora_adj(golden)
+    f = make_func(d, adj.to(dev()), seed=2)
+    torch.manual_seed(3)
+    x0 = torch.randn(adj.shape[0], d, device=dev())
+    t = [0.0, 0.4, 1.0]
+    R = torch.randn(3, adj.shape[0], d)
+    got = product_grads(f, x0, t, R, 1e-3)
+    monkeypatch.setattr(OI, "BACKPROP_SAVE_MAX_BYTES", 0)
+    rec = product_grads(f, x0, t, R, 1e-3)
+    assert rec[3] == got[3]
+    assert torch.equal(rec[0], got[0])
+    assert torch.equal(rec[1], got[1])
+    for k in PNAMES:
+        assert torch.equal(rec[2][k], got[2][k]), k
+
+
+def test_generic_path_matches_fused_path(golden, monkeypatch):
+    """The same ODEfunc with the fused hook disabled (generic path: every accepted step re-run as torch ops under
+    autograd) on the fused run's attempt sequences, outputs at t = [0, 0.4, 1] with a loss on each: both paths at the
+    noise floor of the oracle, which restarts at every output time as the product does."""
+    from graph_odenet_amd import models
+    adj = cora_adj(golden)
+    d = 16
+    f = make_func(d, adj.to(dev()), seed=6)
+    torch.manual_seed(7)
+    x0 = torch.randn(adj.shape[0], d, device=dev())
+    t = [0.0, 0.4, 1.0]
+    R = torch.randn(3, adj.shape[0], d)
+    f.nfe = 0
+    fused = product_grads(f, x0, t, R, 1e-3)
+    nfe_fused = f.nfe
+    trace = fused[3]
+    assert len(trace) == 2
+    monkeypatch.setattr(models.ODEfunc, "gode_fields", lambda self, y0: None)
+    f.nfe = 0
+    generic = product_grads(f, x0, t, R, 1e-3, replay=trace)
+    assert f.nfe == nfe_fused, "the backward pass must not count its re-run evaluations"
+    assert [[a[:2] for a in seq] for seq in generic[3]] == [[a[:2] for a in seq] for seq in trace]
+    o32, gx32, gp32 = oracle_grads(f, adj, x0, t, R, 1e-3, torch.float32, trace)
+    o64, gx64, gp64 = oracle_grads(f, adj, x0, t, R, 1e-3, torch.float64, trace)
+    for got in (fused, generic):
+        noise_floor_check(got[0], o32, o64, "y(t)")
+        noise_floor_check(got[1], gx32, gx64, "dL/dx0")
+        for k in PNAMES:
+            noise_floor_check(got[2][k], gp32[k], gp64[k], "dL/d" + k)
+
+
+def test_gat_generic_path_vs_oracle(golden):
+    """A GAT ODE function (no fused backprop sweep: the generic path) under dopri5, rtol = atol = 1e-3, against autograd
+    through layers_ref.gat_odefunc on the product's attempt sequence."""
+    from graph_odenet_amd import gat_models, odeint as OI, solver
+    from oracle import layers_ref as L, solver_ref as S
+    ge = golden("cora_gat_edges.npz")
+    n = int(ge["n"])
+    src, tgt = T(ge["src"]).long(), T(ge["tgt"]).long()
+    e = src.numel()
+    Mtgt = torch.sparse_coo_tensor(torch.stack([T(ge["m_rows"]).long(), T(ge["m_cols"]).long()]), T(ge["m_vals"]), (n, e))
+    d = 16
+    torch.manual_seed(8)
+    f = gat_models.ODEfunc(d)
+    names = ("norm1.weight", "norm1.bias", "gc1.f.weight", "gc1.f.bias", "gc1.w.weight", "gc1.w.bias")
+    sd = {k: v.detach().clone() for k, v in f.named_parameters()}
+    x0 = torch.randn(n, d)
+    R = torch.randn(n, d)
+    f = f.to(dev())
+    f.set_adj(src.to(dev()), tgt.to(dev()), Mtgt.to(dev()))
+    x = x0.to(dev()).requires_grad_(True)
+    solver.TRACE = []
+    try:
+        out = OI.odeint(f, x, torch.tensor([0., 1.], device=dev()), rtol=1e-3, atol=1e-3)[1]
+        trace = solver.TRACE
+    finally:
+        solver.TRACE = None
+    assert out.grad_fn is not None
+    (out * R.to(dev())).sum().backward()
+
+    def oracle(dtype):
+        ps = [torch.nn.Parameter(sd[k].to(dtype).clone()) for k in names]
+        M = Mtgt.to(dtype)
+        xx = x0.to(dtype).clone().requires_grad_(True)
+        S.REPLAY = [list(seq) for seq in trace]
+        try:
+            o = S.odeint(lambda tt, y: L.gat_odefunc(tt.to(dtype), y, src, tgt, M, *ps), xx,
+                         torch.tensor([0., 1.], dtype=dtype), rtol=1e-3, atol=1e-3, method="dopri5")[1]
+        finally:
+            S.REPLAY = None
+        (o * R.to(dtype)).sum().backward()
+        return o.detach(), xx.grad, {k: p.grad for k, p in zip(names, ps)}
+    o32, gx32, gp32 = oracle(torch.float32)
+    o64, gx64, gp64 = oracle(torch.float64)
+    noise_floor_check(out, o32, o64, "GAT y(1)")
+    noise_floor_check(x.grad, gx32, gx64, "GAT dL/dx0")
+    for k, p in f.named_parameters():
+        noise_floor_check(p.grad, gp32[k], gp64[k], "GAT dL/d" + k)
+
+
+def test_ode_block_without_adjoint_default_method(golden):
+    """ODEBlock(f, adjoint=False) with the default method (dopri5): the adjoint block's output, the gradients of calling
+    odeint directly, and an nfe the backward pass leaves alone."""
+    from graph_odenet_amd import models, odeint as OI
+    adj = cora_adj(golden)
+    d = 16
+    f = make_func(d, adj.to(dev()), seed=11)
+    torch.manual_seed(12)
+    x0 = torch.randn(adj.shape[0], d, device=dev())
+    R = torch.randn(adj.shape[0], d, device=dev())
+    with torch.no_grad():
+        f.nfe = 0
+        OI.odeint(f, x0, torch.tensor([0., 1.], device=dev()), rtol=1e-3, atol=1e-3)
+        nfe_plain = f.nfe
+    f.nfe = 0
+    x = x0.clone().requires_grad_(True)
+    out = OI.odeint(f, x, torch.tensor([0., 1.], device=dev()), rtol=1e-3, atol=1e-3)[1]
+    assert f.nfe == nfe_plain > 0
+    f.zero_grad()
+    (out * R).sum().backward()
+    assert f.nfe == nfe_plain
+    direct = [x.grad.clone()] + [p.grad.clone() for p in f.parameters()]
+
+    outs = {}
+    for a in (True, False):
+        blk = models.ODEBlock(f, tol=1e-3, adjoint=a)
+        assert blk.method is None
+        f.zero_grad()
+        f.nfe = 0
+        x = x0.clone().requires_grad_(True)
+        y = blk(x, adj.to(dev()))
+        outs[a] = y.detach()
+        if not a:
+            assert y.grad_fn is not None
+            (y * R).sum().backward()
+            assert f.nfe == nfe_plain
+            got = [x.grad] + [p.grad for p in f.parameters()]
+            for g1, g2 in zip(got, direct):
+                assert torch.equal(g1, g2)
+    assert torch.equal(outs[True], outs[False])

@@ -2,8 +2,10 @@
 """Training-step time of odeint_adjoint against odeint backprop (odeint._OdeintBackprop), in one process with the two
 modes alternating: ODEGCN3 fwd + bwd + Adam on the C5 graph (R-MAT 2^20 nodes, 10^7 edges, d = 128, rk4 16 steps) and on
 Cora (d = 16, rk4 step 1/16), plus each mode's peak device memory.  Prints one JSON line.
+--method dopri5: the adaptive default instead (odeint._OdeintBackpropDopri5), rtol = atol = --tol.
 
   python tools/backprop_bench.py [--steps 3] [--rounds 3] [--scale 20] [--edges 10000000] [--no-cora] [--only MODE]
+                                 [--method rk4|dopri5] [--tol 1e-5]
 """
 import argparse
 import json
@@ -73,10 +75,18 @@ def main():
     ap.add_argument("--no-c5", action="store_true")
     ap.add_argument("--no-cora", action="store_true")
     ap.add_argument("--only", choices=["adjoint", "backprop"], default=None, help="time one mode (kernel profiles)")
+    ap.add_argument("--method", choices=["rk4", "dopri5"], default="rk4")
+    ap.add_argument("--tol", type=float, default=1e-5, help="rtol = atol of --method dopri5 (the reference's 1e-5)")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     modes = (args.only,) if args.only else ("adjoint", "backprop")
-    out = {"metric": "odeint backprop vs odeint_adjoint, ODEGCN3 fwd+bwd+Adam step"}
+    out = {"metric": "odeint backprop vs odeint_adjoint, ODEGCN3 fwd+bwd+Adam step", "method": args.method}
+    if args.method == "rk4":
+        ode = lambda steps: dict(method="rk4", step_size=1.0 / steps)       # noqa: E731
+        tag = lambda steps: dict(rk4_steps=steps)                           # noqa: E731
+    else:
+        ode = lambda steps: dict(method=None, tol=args.tol)                 # noqa: E731
+        tag = lambda steps: dict(tol=args.tol)                              # noqa: E731
     if not args.no_c5:
         from graph_odenet_amd.synth import rmat_graph
         g = rmat_graph(args.scale, args.edges, seed=0, device=dev)
@@ -87,9 +97,8 @@ def main():
         labels = torch.randint(0, 16, (n,), generator=gen, device=dev)
         idx = torch.randperm(n, generator=gen, device=dev)[: n // 10]
         torch.manual_seed(42)
-        m = models.ODEGCN3(nfeat=128, nhid=args.hidden, nclass=16, dropout=0.5, method="rk4",
-                           step_size=1.0 / args.ode_steps).to(dev)
-        out["c5"] = dict(nodes=n, hidden=args.hidden, rk4_steps=args.ode_steps,
+        m = models.ODEGCN3(nfeat=128, nhid=args.hidden, nclass=16, dropout=0.5, **ode(args.ode_steps)).to(dev)
+        out["c5"] = dict(nodes=n, hidden=args.hidden, **tag(args.ode_steps),
                          **alternate(m, Adam(m.parameters(), lr=0.01, weight_decay=5e-4), x, g, labels, idx,
                                      args.steps, args.rounds, args.warmup, modes))
         del m, g, x
@@ -97,8 +106,8 @@ def main():
     if not args.no_cora:
         adj, x, labels, idx = cora(dev)
         torch.manual_seed(0)
-        m = models.ODEGCN3(nfeat=x.shape[1], nhid=16, nclass=7, dropout=0.5, method="rk4", step_size=1 / 16).to(dev)
-        out["cora"] = dict(hidden=16, rk4_steps=16,
+        m = models.ODEGCN3(nfeat=x.shape[1], nhid=16, nclass=7, dropout=0.5, **ode(16)).to(dev)
+        out["cora"] = dict(hidden=16, **tag(16),
                            **alternate(m, Adam(m.parameters(), lr=0.01, weight_decay=5e-4), x, adj, labels, idx,
                                        20, args.rounds, 5, modes))
     print(json.dumps(out))
