@@ -260,12 +260,43 @@ def _feval_small(spec, t, terms, out, pre=None, alpha=1.0, cot=None, out2=None, 
                "gode_gcn_feval_small_next_f32")
 
 
-class GcnOdeField(Field):
+class _PackedParams:
+    """The one statement of the packed parameter buffer the C drivers read and add to: [W | b | gamma | beta | a_t]
+    (gode_gcn_ode_theta_len floats).  Needs self.s (the spec) and self.params_order (list of 'gamma', 'beta', 'W', 'b' in
+    func.parameters() order)."""
+
+    def _theta_len(self):
+        return (self.s.d + 1) * self.s.d + 3 * self.s.d + 1
+
+    def _packed_state(self, th, y, a):
+        """[y, a, a_t, W, b, gamma, beta] with the small components as views of the packed buffer th."""
+        d = self.s.d
+        nW = (d + 1) * d
+        comps = [y, a, th[nW + 3 * d:], th[:nW].view(d + 1, d), th[nW:nW + d], th[nW + d:nW + 2 * d],
+                 th[nW + 2 * d:nW + 3 * d]]
+        comps[2]._gode_packed = th            # keeps the base alive and lets the native step find it
+        return comps
+
+    def _in_params_order(self, comps):
+        m = {"W": comps[3], "b": comps[4], "gamma": comps[5], "beta": comps[6]}
+        return [m[k] for k in self.params_order]
+
+    def packed_grads(self, device):
+        """A zeroed packed buffer for the backprop sweeps to add the parameter gradients to."""
+        return torch.zeros(self._theta_len(), dtype=torch.float32, device=device)
+
+    def packed_param_grads(self, theta):
+        """Views of such a buffer, in func.parameters() order."""
+        return self._in_params_order(self._packed_state(theta, None, None))
+
+
+class GcnOdeField(_PackedParams, Field):
     n_components = 1
     fused = True
 
-    def __init__(self, spec, shared):
+    def __init__(self, spec, shared, params_order):
         self.s, self.w = spec, shared
+        self.params_order = params_order
         self.token = ("gcn", id(spec.graph))     # identity of the problem besides shapes and parameters (odeint plans)
 
     def eval(self, t, terms, out):
@@ -291,7 +322,7 @@ class GcnOdeField(Field):
             comps[0].copy_(out)
         return 4 * n_steps
 
-    # ---- backprop through a fixed-grid solve (odeint._OdeintBackprop; csrc/ode_driver.hip) ----------------------
+    # ---- backprop through a fixed-grid solve (odeint._OdeintBackprop under rk4; csrc/ode_driver.hip) -----------
     def rk4_forward_save(self, y0, y_end, save, t0, t1, n_steps, i0, i1):
         """Steps i0 .. i1-1 of the n_steps-step rk4 solve from t0 to t1, bit for bit rk4_native's launches; save[r] =
         [y_n, k_1, k_2, k_3, k_4] of step i0 + r (y0 is copied into save[0][0] unless it is that slice)."""
@@ -341,7 +372,7 @@ class GcnOdeField(Field):
                    "gode_gcn_ode_dopri5_step_forward")
         return sums
 
-    # ---- backprop through an adaptive solve (odeint._OdeintBackpropDopri5; csrc/ode_driver.hip) -----------------
+    # ---- backprop through an adaptive solve (odeint._OdeintBackprop under dopri5; csrc/ode_driver.hip) -------
     def dopri5_backprop_work(self, like):
         """Work arrays of dopri5_step_backprop for a state like `like`: 7 Ybar, two (ybar_n, kbar_1) pairs that take
         turns from step to step, 7 packed parameter parts."""
@@ -410,38 +441,26 @@ class GcnOdePartField(_PartMixin, GcnOdeField):
     rk4_backprop = None
     dopri5_step_backprop = None
 
-    def __init__(self, spec, shared):
-        GcnOdeField.__init__(self, spec, shared)
+    def __init__(self, spec, shared, params_order):
+        GcnOdeField.__init__(self, spec, shared, params_order)
         self.token = None
 
 
-class GcnOdeAdjointField(Field):
+class GcnOdeAdjointField(_PackedParams, Field):
     """Components: [y, a, a_t, W, b, gamma, beta] (b may be absent -> never, FixedGC always has bias here)."""
     fused = True
 
     def __init__(self, spec, shared, params_order):
         self.s, self.w = spec, shared
-        self.params_order = params_order      # list of 'gamma','beta','W','b' in func.parameters() order
+        self.params_order = params_order
         self.n_components = 7
         self.ratio_groups = [[0], [1], [2], [3, 4, 5, 6]]
 
     def new_state(self, y_end):
         """[y, a, a_t, W, b, gamma, beta]; the small components are views of ONE packed buffer laid out as the
         C driver expects: [W | b | gamma | beta | a_t]."""
-        self.theta = torch.zeros(self._theta_len(), dtype=torch.float32, device=y_end.device)
+        self.theta = self.packed_grads(y_end.device)
         return self._packed_state(self.theta, y_end.clone(), torch.zeros_like(y_end))
-
-    def _theta_len(self):
-        return (self.s.d + 1) * self.s.d + 3 * self.s.d + 1
-
-    def _packed_state(self, th, y, a):
-        """[y, a, a_t, W, b, gamma, beta] with the small components as views of the packed buffer th."""
-        d = self.s.d
-        nW = (d + 1) * d
-        comps = [y, a, th[nW + 3 * d:], th[:nW].view(d + 1, d), th[nW:nW + d], th[nW + d:nW + 2 * d],
-                 th[nW + 2 * d:nW + 3 * d]]
-        comps[2]._gode_packed = th            # keeps the base alive and lets the native step find it
-        return comps
 
     def rk4_native(self, comps, t0, t1, n_steps):
         lib = _lib.load()
@@ -462,8 +481,7 @@ class GcnOdeAdjointField(Field):
         return 4 * n_steps
 
     def param_grads(self, comps):
-        m = {"W": comps[3], "b": comps[4], "gamma": comps[5], "beta": comps[6]}
-        return [m[k] for k in self.params_order]
+        return self._in_params_order(comps)
 
     def _packed_like(self, y):
         """A work copy of the state with the small components as views of ONE packed buffer, as new_state lays it out."""

@@ -142,7 +142,7 @@ class ODEfunc(nn.Module):
                  id(self.gc1.weight): "W", id(self.gc1.bias): "b"}
         order = [names[id(p)] for p in plist]
         if getattr(spec.graph, "is_partitioned", False):
-            return GcnOdePartField(spec, sh), (lambda: GcnOdePartAdjointField(spec, sh, order)), tuple(plist)
+            return GcnOdePartField(spec, sh, order), (lambda: GcnOdePartAdjointField(spec, sh, order)), tuple(plist)
         # large graphs whose hot rows crowd a few address residues: integrate on the hubs-first renumbering
         # (gcn_ode.tuned_graph - a deterministic function of the graph and `node_order`); the solver permutes the
         # state rows on entry and exit, everything in between is row-local or the SpMM itself
@@ -151,7 +151,7 @@ class ODEfunc(nn.Module):
         def mark(field):
             field.row_order, field.row_inverse = rows, inverse
             return field
-        return mark(GcnOdeField(spec, sh)), (lambda: mark(GcnOdeAdjointField(spec, sh, order))), tuple(plist)
+        return mark(GcnOdeField(spec, sh, order)), (lambda: mark(GcnOdeAdjointField(spec, sh, order))), tuple(plist)
 
 
 class ODEfunc2(nn.Module):
@@ -189,8 +189,8 @@ class ODEBlock(nn.Module):
     def __init__(self, odefunc, tol=1e-5, method=None, step_size=None, node_order=None, adjoint=True):
         super(ODEBlock, self).__init__()
         self.odefunc = odefunc
-        # True (the reference): odeint_adjoint.  False: odeint, differentiable by backprop through the solve under rk4
-        # (odeint._OdeintBackprop) and under the adaptive default (odeint._OdeintBackpropDopri5)
+        # True (the reference): odeint_adjoint.  False: odeint, differentiable by backprop through the solve
+        # (odeint._OdeintBackprop, under rk4 and under the adaptive default)
         self.adjoint = bool(adjoint)
         if node_order is not None:            # extension: "auto" (default rule) | "given" | "degree" (gcn_ode.tuned_graph)
             from .gcn_ode import NODE_ORDERS

@@ -22,8 +22,8 @@ import torch
 
 from . import ops
 from . import solver
-from .solver import (DP_A, DP_B, DP_C, DP_MID, Dopri5Record, Dopri5Stats, Field, integrate_dopri5,
-                     integrate_dopri5_inplace, integrate_rk4, uniform_grid)
+from .solver import (DP_A, DP_B, DP_C, Dopri5Record, Dopri5Stats, Field, integrate_dopri5, integrate_dopri5_inplace,
+                     integrate_rk4, interp_weights, uniform_grid)
 
 
 NATIVE_RK4 = True      # fused fields: issue a whole rk4 solve from one C-ABI call (False: per-stage Python driver)
@@ -76,6 +76,13 @@ class AutogradAdjointField(Field):
         self.like = like
         self.n_components = 3 + len(self.params)
         self.ratio_groups = [[0], [1], [2]] + ([list(range(3, 3 + len(self.params)))] if self.params else [])
+
+    def new_state(self, y_end):
+        return [y_end.clone(), torch.zeros_like(y_end), torch.zeros(1, dtype=y_end.dtype, device=y_end.device)] + \
+               [torch.zeros_like(p) for p in self.params]
+
+    def param_grads(self, comps):
+        return comps[3:]
 
     def eval(self, t, terms, out):
         y = _materialise(terms[0])
@@ -140,13 +147,11 @@ def _integrate(field, comps, t0, t1, rtol, atol, method, options, stats):
     if method == "rk4":
         stats.nfe += _run_rk4(field, comps, t0, t1, uniform_grid(t0, t1, (options or {}).get("step_size")))
     else:
-        if getattr(field, "fixed_grid_only", False):
+        if field.fixed_grid_only:
             raise NotImplementedError("odeint: this field supports the fixed-grid method only (method='rk4')")
-        if hasattr(field, "adaptive"):
+        if field.big_components is not None:
             field.adaptive = True                  # row-partitioned fields: keep the small components global
-        prep = getattr(field, "prepare", None)
-        if prep is not None:
-            prep()
+        _prepare(field)
         integrate_dopri5_inplace(field, comps, t0, t1, rtol, atol, stats)
 
 
@@ -237,7 +242,7 @@ def _plan_for(func, y0, tl, method, options, params):
     plan = plans.get(key)
     if plan is None:
         fields = _fields(func, y0)
-        if not getattr(fields[0], "fused", False):
+        if not fields[0].fused:
             return None, fields
         if len(plans) >= 4:
             plans.clear()                       # a func that keeps changing graphs / shapes: start over
@@ -247,12 +252,9 @@ def _plan_for(func, y0, tl, method, options, params):
 
 
 def _run_rk4(field, comps, t0, t1, n):
-    prep = getattr(field, "prepare", None)
-    if prep is not None:
-        prep()
-    native = getattr(field, "rk4_native", None)
-    if native is not None and NATIVE_RK4:
-        return native(comps, t0, t1, n)          # whole solve issued from C (csrc/ode_driver.hip)
+    _prepare(field)
+    if field.rk4_native is not None and NATIVE_RK4:
+        return field.rk4_native(comps, t0, t1, n)          # whole solve issued from C (csrc/ode_driver.hip)
     return integrate_rk4(field, comps, t0, t1, n)
 
 
@@ -280,15 +282,27 @@ def _fields(func, y0):
     return AutogradField(func, y0), (lambda: AutogradAdjointField(func, params, y0)), params
 
 
-def _rows(field):
-    """(order, inverse) when the field integrates on renumbered nodes (state rows y' = y[order]), else (None, None)."""
-    return getattr(field, "row_order", None), getattr(field, "row_inverse", None)
+def _prepare(field):
+    if field.prepare is not None:
+        field.prepare()
 
 
-def _bump_nfe(func, n):
-    # fused fields do not call func.forward; keep the reference's counter (GCN/models.py:173) alive
+def _gather(y, index, out=None, copy=True):
+    """y[index]: the state rows into (index = field.row_order) or out of (field.row_inverse) a field's order; index is
+    None on a field that integrates the rows as given - then y itself with copy=False, else a copy.  out: written in
+    place."""
+    if index is not None:
+        return torch.index_select(y, 0, index, out=out)
+    if out is not None:
+        return out.copy_(y)
+    return y.clone() if copy else y
+
+
+def _bump_nfe(func, field, n, skipped=0):
+    # fused fields do not call func.forward; keep the reference's counter (GCN/models.py:173) alive.  skipped: evaluations
+    # counted whichever field ran (NFE_COUNTS_SKIPPED_DLDT_EVAL)
     if getattr(func, "_gode_counts_nfe", False):
-        func.nfe += n
+        func.nfe += (n if field.fused else 0) + skipped
 
 
 def _rk4_torch(func, y, t0, t1, n):
@@ -305,134 +319,6 @@ def _rk4_torch(func, y, t0, t1, n):
     return y
 
 
-class _OdeintBackprop(torch.autograd.Function):
-    """odeint under rk4 with gradients: the forward is odeint's own (bit for bit), the backward the exact derivative of
-    the discrete solution.  Fused fields offering rk4_forward_save / rk4_backprop (GcnOdeField) keep the stage
-    derivatives of every step and run the reverse sweep as one C call per interval (csrc/ode_driver.hip); any other field
-    re-runs each interval as torch ops through func under autograd from its saved start state (what torchdiffeq does)."""
-
-    @staticmethod
-    def forward(ctx, func, fields, tl, rtol, atol, options, y0, *params):
-        fwd = fields[0]
-        order, inverse = _rows(fwd)
-        step_size = (options or {}).get("step_size")
-        steps = [uniform_grid(tl[i - 1], tl[i], step_size) for i in range(1, len(tl))]
-        fused = getattr(fwd, "rk4_forward_save", None) is not None and NATIVE_RK4
-        y0c = y0.detach().contiguous()
-        outs = [y0c.clone()]
-        ctx.saved = None
-        with torch.no_grad():
-            if fused:
-                prep = getattr(fwd, "prepare", None)
-                if prep is not None:
-                    prep()
-                shape = tuple(y0c.shape)
-                save_all = 5 * sum(steps) * y0c.numel() * 4 <= BACKPROP_SAVE_MAX_BYTES
-                cur = y0c.clone() if order is None else y0c.index_select(0, order)
-                saved = []
-                for i in range(1, len(tl)):
-                    n = steps[i - 1]
-                    y_end = torch.empty_like(cur)
-                    if save_all:
-                        rec = torch.empty((n, 5) + shape, dtype=y0c.dtype, device=y0c.device)
-                        rec[0, 0].copy_(cur)
-                        fwd.rk4_forward_save(rec[0, 0], y_end, rec, tl[i - 1], tl[i], n, 0, n)
-                        saved.append(rec)
-                    else:
-                        ys = torch.empty((n,) + shape, dtype=y0c.dtype, device=y0c.device)
-                        ys[0].copy_(cur)
-                        rec = torch.empty((1, 5) + shape, dtype=y0c.dtype, device=y0c.device)
-                        for j in range(n):
-                            fwd.rk4_forward_save(ys[j], ys[j + 1] if j + 1 < n else y_end, rec, tl[i - 1], tl[i], n, j, j + 1)
-                        saved.append(ys)
-                    cur = y_end
-                    outs.append(cur.clone() if order is None else cur.index_select(0, inverse))
-                ctx.saved, ctx.save_all = saved, save_all
-                _bump_nfe(func, 4 * sum(steps))
-            else:
-                stats = Dopri5Stats()
-                ys = [y0c.clone() if order is None else y0c.index_select(0, order)]
-                for i in range(1, len(tl)):
-                    _integrate(fwd, ys, tl[i - 1], tl[i], rtol, atol, "rk4", options, stats)
-                    outs.append(ys[0].clone() if order is None else ys[0].index_select(0, inverse))
-                _bump_nfe(func, stats.nfe if getattr(fwd, "fused", False) else 0)
-        ans = torch.stack(outs)
-        ctx.func, ctx.fields, ctx.tl, ctx.steps, ctx.fused = func, fields, tl, steps, fused
-        ctx.outs = None if fused else outs
-        ctx.n_params = len(params)
-        return ans
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        grad_out = grad_out.contiguous()
-        tl, steps = ctx.tl, ctx.steps
-        params = ctx.fields[2] if ctx.fused else _params(ctx.func)
-        if ctx.fused:
-            fwd = ctx.fields[0]
-            order, inverse = _rows(fwd)
-            gather = (lambda g: g.clone()) if order is None else (lambda g: g.index_select(0, order))
-            a = gather(grad_out[-1])
-            s = fwd.s
-            d = s.d
-            nW = (d + 1) * d
-            theta = torch.zeros((nW + 3 * d + 1,), dtype=torch.float32, device=a.device)
-            scratch = rec1 = None
-            with torch.no_grad():
-                for i in range(len(tl) - 1, 0, -1):
-                    n, sv = steps[i - 1], ctx.saved[i - 1]
-                    if ctx.save_all:
-                        res = fwd.rk4_backprop(sv, a, theta, tl[i - 1], tl[i], n, 0, n)
-                        if res is not a:
-                            a.copy_(res)
-                    else:
-                        if rec1 is None:
-                            rec1 = torch.empty((1, 5) + tuple(a.shape), dtype=a.dtype, device=a.device)
-                            scratch = torch.empty_like(a)
-                        for j in range(n - 1, -1, -1):          # re-run the step into a one-step record, then sweep it
-                            fwd.rk4_forward_save(sv[j], scratch, rec1, tl[i - 1], tl[i], n, j, j + 1)
-                            res = fwd.rk4_backprop(rec1, a, theta, tl[i - 1], tl[i], n, j, j + 1)
-                            if res is not a:
-                                a.copy_(res)
-                    if i > 1:
-                        a.add_(gather(grad_out[i - 1]))
-                gy0 = (a if order is None else a.index_select(0, inverse)).add_(grad_out[0])
-            comps = [None, None, None, theta[:nW].view(d + 1, d), theta[nW:nW + d], theta[nW + d:nW + 2 * d],
-                     theta[nW + 2 * d:nW + 3 * d]]
-            pg = ctx.fields[1]().param_grads(comps)
-        else:
-            func = ctx.func
-            nfe0 = getattr(func, "nfe", None)
-            a = grad_out[-1]
-            pg = [None] * len(params)
-            for i in range(len(tl) - 1, 0, -1):
-                with torch.enable_grad():
-                    y = ctx.outs[i - 1].detach().requires_grad_(True)
-                    yt = _rk4_torch(func, y, tl[i - 1], tl[i], steps[i - 1])
-                    g = torch.autograd.grad(yt, (y,) + tuple(params), a, allow_unused=True)
-                a = g[0] + grad_out[i - 1] if g[0] is not None else grad_out[i - 1].clone()
-                for q, gq in enumerate(g[1:]):
-                    if gq is not None:
-                        pg[q] = gq if pg[q] is None else pg[q] + gq
-            gy0 = a
-            if nfe0 is not None:
-                func.nfe = nfe0                   # evaluations re-run by the backward pass are not counted (torchdiffeq's
-                                                  # odeint counts none in its backward)
-        return (None, None, None, None, None, None, gy0, *pg)
-
-
-def _interp_weights(x):
-    """(cy0, cy1, kc[7]): the 4th-order interpolation at abscissa x of a step as cy0 y_n + cy1 y_{n+1} + h sum kc_s k_s
-    (solver.integrate_dopri5 forms the same numbers)."""
-    x2, x3, x4 = x * x, x * x * x, x * x * x * x
-    wm = 16 * x4 - 32 * x3 + 16 * x2
-    cy0 = -8 * x4 + 18 * x3 - 11 * x2 + 1 + wm
-    cy1 = -8 * x4 + 14 * x3 - 5 * x2
-    kc = [wm * m for m in DP_MID]
-    kc[0] += -2 * x4 + 5 * x3 - 4 * x2 + x
-    kc[6] += 2 * x4 - 3 * x3 + x2
-    return cy0, cy1, kc
-
-
 def _dopri5_step_torch(func, y, t, h, x):
     """One Dormand-Prince step from y at t as differentiable torch ops through func; x: the interpolation abscissa of a
     last step that overshot the end time (None: the step's own end state is returned)."""
@@ -443,99 +329,175 @@ def _dopri5_step_torch(func, y, t, h, x):
     y1 = y + sum((h * b) * k for b, k in zip(DP_B, ks) if b != 0.0)
     if x is None:
         return y1
-    cy0, cy1, kc = _interp_weights(x)
+    cy0, cy1, kc = interp_weights(x)
     return cy0 * y + cy1 * y1 + sum((h * c) * k for c, k in zip(kc, ks) if c != 0.0)
 
 
-class _OdeintBackpropDopri5(torch.autograd.Function):
-    """odeint under adaptive dopri5 with gradients: the forward is odeint's own (bit for bit, the same launches on buffers
-    a solver.Dopri5Record keeps), the backward the exact derivative of the discrete solution with the accepted step
-    sizes as constants.  A fused field offering dopri5_step_backprop (GcnOdeField) keeps y_n and k_1..k_7 of every
-    accepted step - or y_n and k_1 past BACKPROP_SAVE_MAX_BYTES, each step then re-run by one native step call before
-    its sweep - and sweeps them in reverse, one C call per step (csrc/ode_driver.hip).  Any other field keeps y_n and
-    re-runs each accepted step as torch ops through func under autograd, k_1 = func(t_n, y_n) recomputed: the same
-    function of y_n as the derivative FSAL hands over, since Y_7 and y_{n+1} are the same combination."""
+class _Rk4Backprop:
+    """What _OdeintBackprop does per interval under fixed-grid rk4.  Fused (a field offering rk4_forward_save /
+    rk4_backprop: GcnOdeField): the record is [y_n, k_1..k_4] of every step, swept in reverse by one C call per interval
+    (csrc/ode_driver.hip) - or, when the whole solve outgrows BACKPROP_SAVE_MAX_BYTES, y_n alone, each step then re-run
+    into a one-step record just before its sweep.  Generic: the record is the interval's start state, from which the
+    interval is re-run as torch ops through func (what torchdiffeq does)."""
+    own_cotangent = True              # fused_reverse hands back the tensor it was given
+
+    def __init__(self, func, fwd, tl, rtol, atol, options, y0c):
+        self.func, self.fwd, self.tl, self.tols, self.options = func, fwd, tl, (rtol, atol), options
+        step_size = (options or {}).get("step_size")
+        self.steps = [uniform_grid(tl[i - 1], tl[i], step_size) for i in range(1, len(tl))]
+        self.fused = fwd.rk4_forward_save is not None and NATIVE_RK4
+        self.stats = Dopri5Stats()
+        if self.fused:
+            _prepare(fwd)
+            self.save_all = 5 * sum(self.steps) * y0c.numel() * 4 <= BACKPROP_SAVE_MAX_BYTES
+
+    def forward(self, i, cur, start):
+        fwd, t0, t1, n = self.fwd, self.tl[i - 1], self.tl[i], self.steps[i - 1]
+        if not self.fused:
+            ys = [cur]
+            _integrate(fwd, ys, t0, t1, *self.tols, "rk4", self.options, self.stats)
+            return start, ys[0]
+        shape, like = tuple(cur.shape), dict(dtype=cur.dtype, device=cur.device)
+        y_end = torch.empty_like(cur)
+        if self.save_all:
+            rec = torch.empty((n, 5) + shape, **like)
+            rec[0, 0].copy_(cur)
+            fwd.rk4_forward_save(rec[0, 0], y_end, rec, t0, t1, n, 0, n)
+        else:
+            rec = torch.empty((n,) + shape, **like)
+            rec[0].copy_(cur)
+            one = torch.empty((1, 5) + shape, **like)
+            for j in range(n):
+                fwd.rk4_forward_save(rec[j], rec[j + 1] if j + 1 < n else y_end, one, t0, t1, n, j, j + 1)
+        self.stats.nfe += 4 * n
+        return rec, y_end
+
+    def fused_reverse(self, i, rec, a, theta, work):
+        fwd, t0, t1, n = self.fwd, self.tl[i - 1], self.tl[i], self.steps[i - 1]
+        if self.save_all:
+            res = fwd.rk4_backprop(rec, a, theta, t0, t1, n, 0, n)
+            if res is not a:
+                a.copy_(res)
+            return a
+        if not work:
+            work.update(one=torch.empty((1, 5) + tuple(a.shape), dtype=a.dtype, device=a.device), y=torch.empty_like(a))
+        for j in range(n - 1, -1, -1):          # re-run the step into a one-step record, then sweep it
+            fwd.rk4_forward_save(rec[j], work["y"], work["one"], t0, t1, n, j, j + 1)
+            res = fwd.rk4_backprop(work["one"], a, theta, t0, t1, n, j, j + 1)
+            if res is not a:
+                a.copy_(res)
+        return a
+
+    def generic_reverse(self, i, rec):
+        yield rec, lambda y: _rk4_torch(self.func, y, self.tl[i - 1], self.tl[i], self.steps[i - 1])
+
+
+class _Dopri5Backprop:
+    """What _OdeintBackprop does per interval under adaptive dopri5; the accepted step sizes are constants of the
+    derivative.  The forward runs the solve's own launches on buffers a solver.Dopri5Record keeps.  Fused (a field offering
+    dopri5_step_backprop: GcnOdeField): y_n and k_1..k_7 of every accepted step - or y_n and k_1 past
+    BACKPROP_SAVE_MAX_BYTES, each step then re-run by one native step call before its sweep - swept in reverse, one C call
+    per step (csrc/ode_driver.hip).  Generic: y_n alone, each accepted step re-run as torch ops through func,
+    k_1 = func(t_n, y_n) recomputed: the same function of y_n as the derivative FSAL hands over, since Y_7 and y_{n+1} are
+    the same combination."""
+    own_cotangent = False             # fused_reverse hands back one of its work arrays
+
+    def __init__(self, func, fwd, tl, rtol, atol, options, y0c):
+        if fwd.fixed_grid_only:
+            raise NotImplementedError("odeint: this field supports the fixed-grid method only (method='rk4')")
+        self.func, self.fwd, self.tl, self.tols = func, fwd, tl, (rtol, atol)
+        self.fused = fwd.dopri5_step_backprop is not None and solver.DOPRI5_NATIVE
+        self.stats = Dopri5Stats()
+        self.left = BACKPROP_SAVE_MAX_BYTES
+        _prepare(fwd)
+
+    def forward(self, i, cur, start):
+        fused, left = self.fused, self.left
+        rec = Dopri5Record(7, left) if fused and left is not None else Dopri5Record(1 if fused else 0)
+        (cur,), _ = integrate_dopri5(self.fwd, [cur], self.tl[i - 1], self.tl[i], *self.tols, self.stats, record=rec)
+        if fused and left is not None:
+            self.left = left - rec.bytes if rec.keep == 7 else None      # past the bound: the later intervals keep k_1 only
+        return rec, cur
+
+    def fused_reverse(self, i, rec, a, theta, work):
+        fwd = self.fwd
+        if not work:
+            # turn: which (ybar_n, kbar_1) pair the next call writes: never the one it reads
+            work.update(arrays=fwd.dopri5_backprop_work(a), rerun=None, turn=0)
+        kbar7 = None
+        for j in range(len(rec.steps) - 1, -1, -1):
+            t, h, x, y, ks = rec.steps[j]
+            ks = [k[0] for k in ks]
+            if len(ks) < 7:                 # re-run the step into a one-step record (the forward's launches)
+                if work["rerun"] is None:
+                    work["rerun"] = [torch.empty_like(a) for _ in range(7)]
+                rerun = work["rerun"]
+                fwd.dopri5_step_native(y, [[ks[0]]] + [[b] for b in rerun[:6]], [rerun[6]], t, h, *self.tols)
+                ks = [ks[0]] + rerun[:6]
+            if x is None:
+                wy, wk = 1.0, [h * b for b in DP_B]
+            else:
+                cy0, cy1, kc = interp_weights(x)
+                wy, wk = cy0 + cy1, [h * (cy1 * b + c) for b, c in zip(DP_B, kc)]
+            a, kbar7 = fwd.dopri5_step_backprop(y[0], ks, a, kbar7, wy, wk, t, h, j == 0, work["arrays"], work["turn"], theta)
+            work["turn"] ^= 1
+        return a
+
+    def generic_reverse(self, i, rec):
+        for (t, h, x, y, _) in reversed(rec.steps):
+            yield (_gather(y[0], self.fwd.row_inverse, copy=False),
+                   lambda yn, t=t, h=h, x=x: _dopri5_step_torch(self.func, yn, t, h, x))
+
+
+class _OdeintBackprop(torch.autograd.Function):
+    """odeint with gradients: the forward is odeint's own (bit for bit), the backward the exact derivative of the
+    discrete solution.  Per interval of t the method's strategy (_Rk4Backprop / _Dopri5Backprop) supplies
+        forward(i, cur, start) -> (record, end state)       cur in the field's row order, start in the caller's,
+        fused_reverse(i, record, a, theta, work) -> a       the field's reverse sweep; theta gathers parameter gradients,
+        generic_reverse(i, record) -> (y, step) pairs       last piece first: step(y) re-runs a piece as torch ops,
+    and this class everything around them."""
 
     @staticmethod
-    def forward(ctx, func, fields, tl, rtol, atol, y0, *params):
-        fwd = fields[0]
-        order, inverse = _rows(fwd)
-        fused = getattr(fwd, "dopri5_step_backprop", None) is not None and solver.DOPRI5_NATIVE
-        if getattr(fwd, "fixed_grid_only", False):
-            raise NotImplementedError("odeint: this field supports the fixed-grid method only (method='rk4')")
+    def forward(ctx, func, fwd, tl, rtol, atol, method, options, y0, *params):
         y0c = y0.detach().contiguous()
         outs = [y0c.clone()]
-        stats = Dopri5Stats()
         records = []
         with torch.no_grad():
-            prep = getattr(fwd, "prepare", None)
-            if prep is not None:
-                prep()
-            cur = y0c.clone() if order is None else y0c.index_select(0, order)
-            left = BACKPROP_SAVE_MAX_BYTES
+            sweep = (_Rk4Backprop if method == "rk4" else _Dopri5Backprop)(func, fwd, tl, rtol, atol, options, y0c)
+            cur = _gather(y0c, fwd.row_order)
             for i in range(1, len(tl)):
-                rec = Dopri5Record(7, left) if fused and left is not None else Dopri5Record(1 if fused else 0)
-                (cur,), _ = integrate_dopri5(fwd, [cur], tl[i - 1], tl[i], rtol, atol, stats, record=rec)
-                if fused and left is not None:
-                    left = left - rec.bytes if rec.keep == 7 else None      # past the bound: the later intervals keep k_1 only
+                rec, cur = sweep.forward(i, cur, outs[-1])
                 records.append(rec)
-                outs.append(cur.clone() if order is None else cur.index_select(0, inverse))
-        _bump_nfe(func, stats.nfe if getattr(fwd, "fused", False) else 0)
-        ctx.func, ctx.fields, ctx.tl, ctx.tols, ctx.fused, ctx.records = func, fields, tl, (rtol, atol), fused, records
+                outs.append(_gather(cur, fwd.row_inverse))
+        _bump_nfe(func, fwd, sweep.stats.nfe)
+        ctx.func, ctx.fwd, ctx.tl, ctx.sweep, ctx.records = func, fwd, tl, sweep, records
         return torch.stack(outs)
 
     @staticmethod
     def backward(ctx, grad_out):
         grad_out = grad_out.contiguous()
-        tl, records = ctx.tl, ctx.records
-        fwd = ctx.fields[0]
-        order, inverse = _rows(fwd)
-        if ctx.fused:
-            gather = (lambda g: g.clone()) if order is None else (lambda g: g.index_select(0, order))
-            a = gather(grad_out[-1])
-            d = fwd.s.d
-            nW = (d + 1) * d
-            theta = torch.zeros((nW + 3 * d + 1,), dtype=torch.float32, device=a.device)
-            work = fwd.dopri5_backprop_work(a)
-            rerun = None
-            turn = 0                                    # which (ybar_n, kbar_1) pair the next call writes: never the one it reads
+        func, fwd, tl, sweep, records = ctx.func, ctx.fwd, ctx.tl, ctx.sweep, ctx.records
+        if sweep.fused:
+            a = _gather(grad_out[-1], fwd.row_order)
+            theta = fwd.packed_grads(a.device)
+            work = {}
             with torch.no_grad():
                 for i in range(len(tl) - 1, 0, -1):
-                    steps = records[i - 1].steps
-                    kbar7 = None
-                    for j in range(len(steps) - 1, -1, -1):
-                        t, h, x, y, ks = steps[j]
-                        ks = [k[0] for k in ks]
-                        if len(ks) < 7:                 # re-run the step into a one-step record (the forward's launches)
-                            if rerun is None:
-                                rerun = [torch.empty_like(a) for _ in range(7)]
-                            fwd.dopri5_step_native(y, [[ks[0]]] + [[b] for b in rerun[:6]], [rerun[6]], t, h, *ctx.tols)
-                            ks = [ks[0]] + rerun[:6]
-                        if x is None:
-                            wy, wk = 1.0, [h * b for b in DP_B]
-                        else:
-                            cy0, cy1, kc = _interp_weights(x)
-                            wy, wk = cy0 + cy1, [h * (cy1 * b + c) for b, c in zip(DP_B, kc)]
-                        a, kbar7 = fwd.dopri5_step_backprop(y[0], ks, a, kbar7, wy, wk, t, h, j == 0, work, turn, theta)
-                        turn ^= 1
+                    a = sweep.fused_reverse(i, records[i - 1], a, theta, work)
                     if i > 1:
-                        a = a.add_(gather(grad_out[i - 1]))
-                gy0 = (a.clone() if order is None else a.index_select(0, inverse)).add_(grad_out[0])
-            comps = [None, None, None, theta[:nW].view(d + 1, d), theta[nW:nW + d], theta[nW + d:nW + 2 * d],
-                     theta[nW + 2 * d:nW + 3 * d]]
-            pg = ctx.fields[1]().param_grads(comps)
+                        a.add_(_gather(grad_out[i - 1], fwd.row_order))
+                gy0 = _gather(a, fwd.row_inverse, copy=not sweep.own_cotangent).add_(grad_out[0])
+            pg = fwd.packed_param_grads(theta)
         else:
-            func = ctx.func
             params = _params(func)
             nfe0 = getattr(func, "nfe", None)
             a = grad_out[-1]
             pg = [None] * len(params)
             for i in range(len(tl) - 1, 0, -1):
-                for (t, h, x, y, _) in reversed(records[i - 1].steps):
+                for y_start, step in sweep.generic_reverse(i, records[i - 1]):
                     with torch.enable_grad():
-                        yn = (y[0] if order is None else y[0].index_select(0, inverse)).detach().requires_grad_(True)
-                        g = torch.autograd.grad(_dopri5_step_torch(func, yn, t, h, x), (yn,) + tuple(params), a,
-                                                allow_unused=True)
+                        y = y_start.detach().requires_grad_(True)
+                        g = torch.autograd.grad(step(y), (y,) + tuple(params), a, allow_unused=True)
                     a = g[0] if g[0] is not None else torch.zeros_like(a)
                     for q, gq in enumerate(g[1:]):
                         if gq is not None:
@@ -543,38 +505,37 @@ class _OdeintBackpropDopri5(torch.autograd.Function):
                 a = a + grad_out[i - 1]
             gy0 = a
             if nfe0 is not None:
-                func.nfe = nfe0                   # evaluations re-run by the backward pass are not counted
-        return (None, None, None, None, None, gy0, *pg)
+                func.nfe = nfe0                   # evaluations re-run by the backward pass are not counted (torchdiffeq's
+                                                  # odeint counts none in its backward)
+        return (None, None, None, None, None, None, None, gy0, *pg)
 
 
 def odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None):
     """torchdiffeq's odeint.  With grad mode on and y0 or a parameter of func requiring grad the result is differentiable
-    (backprop through the solve: _OdeintBackprop under rk4, _OdeintBackpropDopri5 under dopri5; t gets no gradient);
-    otherwise - and always on row-partitioned fields - a forward solve without gradient support."""
+    (backprop through the solve: _OdeintBackprop; t gets no gradient); otherwise - and always on row-partitioned fields -
+    a forward solve without gradient support."""
     _check_state(y0)
     tl = _times(t)
     method = _method(method)
     fields = _fields(func, y0)
     fwd = fields[0]
-    if torch.is_grad_enabled() and getattr(fwd, "big_components", None) is None:
+    if torch.is_grad_enabled() and fwd.big_components is None:
         params = _params(func)
         if y0.requires_grad or params:
             same = len(fields[2]) == len(params) and all(p is q for p, q in zip(fields[2], params))
-            hook = "rk4_forward_save" if method == "rk4" else "dopri5_step_backprop"
-            if getattr(fwd, hook, None) is not None and not same:
-                fields = (AutogradField(func, y0), None, params)      # the fused field does not cover these parameters
-            if method != "rk4":
-                return _OdeintBackpropDopri5.apply(func, fields, tl, float(rtol), float(atol), y0, *params)
-            return _OdeintBackprop.apply(func, fields, tl, float(rtol), float(atol), options, y0, *params)
+            sweep = fwd.rk4_forward_save if method == "rk4" else fwd.dopri5_step_backprop
+            if sweep is not None and not same:
+                fwd = AutogradField(func, y0)         # the fused field does not cover these parameters
+            return _OdeintBackprop.apply(func, fwd, tl, float(rtol), float(atol), method, options, y0, *params)
     stats = Dopri5Stats()
-    order, inverse = _rows(fwd)
-    ys = [y0.detach().contiguous().clone() if order is None else y0.detach().index_select(0, order)]
-    outs = [y0.detach().contiguous().clone()]
+    y0c = y0.detach().contiguous()
+    ys = [_gather(y0c, fwd.row_order)]
+    outs = [y0c.clone()]
     with torch.no_grad():
         for i in range(1, len(tl)):
             _integrate(fwd, ys, tl[i - 1], tl[i], rtol, atol, method, options, stats)
-            outs.append(ys[0].clone() if order is None else ys[0].index_select(0, inverse))
-    _bump_nfe(func, stats.nfe if getattr(fwd, "fused", False) else 0)
+            outs.append(_gather(ys[0], fwd.row_inverse))
+    _bump_nfe(func, fwd, stats.nfe)
     return torch.stack(outs)
 
 
@@ -583,17 +544,14 @@ class _OdeintAdjoint(torch.autograd.Function):
     def forward(ctx, func, tl, rtol, atol, method, options, last_only, y0, *params):
         plan, (fwd, mk_adj, plist) = _plan_for(func, y0, tl, method, options, params)
         stats = Dopri5Stats()
-        order, inverse = _rows(fwd)
+        order, inverse = fwd.row_order, fwd.row_inverse
         y0c = y0.detach().contiguous()
         # ans_p[i] = state at tl[i] in the field's row order (what the adjoint starts from); every slice is written in
         # place - the start by the renumbering gather, each later one by the integrator working on that slice - so a
         # solve moves the state through memory twice around the integration instead of once per clone and stack
         # (at 2^20 x 128 a pass is 0.2 ms; the clone-and-stack form made ten of them per forward pass)
         ans_p = torch.empty((len(tl),) + tuple(y0c.shape), dtype=y0c.dtype, device=y0c.device)
-        if order is None:
-            ans_p[0].copy_(y0c)
-        else:
-            torch.index_select(y0c, 0, order, out=ans_p[0])     # state rows in the renumbered graph's order
+        _gather(y0c, order, out=ans_p[0])                       # state rows in the renumbered graph's order
         if plan is not None and plan.gf is None and plan.seen_f >= 1 and not plan.no_capture:
             plan.gf = _try_capture(plan, fwd, [ans_p[0].clone()], tl[0], tl[1])
         if plan is not None and plan.gf is not None:
@@ -609,24 +567,23 @@ class _OdeintAdjoint(torch.autograd.Function):
                     ans_p[i].copy_(ys[0])
             if plan is not None:
                 plan.seen_f += 1
-        _bump_nfe(func, stats.nfe if getattr(fwd, "fused", False) else 0)
+        _bump_nfe(func, fwd, stats.nfe)
         ctx.last_only = bool(last_only)
         if last_only:
             # only y(t[-1]) leaves (what the reference's ODEBlock keeps, GCN/models.py:200 `out[1]`): no copy of y0 into
             # a stacked result, and the backward pass gets the cotangent of that one state instead of a zero-filled stack
-            ans = ans_p[-1].clone() if order is None else torch.index_select(ans_p[-1], 0, inverse)
+            ans = _gather(ans_p[-1], inverse)
         elif order is None:
             ans = ans_p
         else:
             ans = torch.empty_like(ans_p)
             ans[0].copy_(y0c)
             for i in range(1, len(tl)):
-                torch.index_select(ans_p[i], 0, inverse, out=ans[i])
+                _gather(ans_p[i], inverse, out=ans[i])
         ctx.func, ctx.tl, ctx.rtol, ctx.atol, ctx.method, ctx.options = func, tl, rtol, atol, method, options
         ctx.mk_adj = mk_adj
         ctx.fwd = fwd
         ctx.plan = plan
-        ctx.n_params = len(params)
         ctx.rows = (order, inverse)
         ctx.save_for_backward(ans_p)
         return ans
@@ -637,7 +594,7 @@ class _OdeintAdjoint(torch.autograd.Function):
         func, tl = ctx.func, ctx.tl
         grad_out = grad_out.contiguous()
         order, inverse = ctx.rows
-        back = (lambda g: g) if order is None else (lambda g: g.index_select(0, inverse))
+        back = lambda g: _gather(g, inverse, copy=False)      # noqa: E731
         last_only = ctx.last_only
         n_t = len(tl)
 
@@ -648,7 +605,7 @@ class _OdeintAdjoint(torch.autograd.Function):
 
         def g_at(i):                                  # the same in the field's row order (one gather, when asked for)
             g = g_raw(i)
-            return g if (g is None or order is None) else g.index_select(0, order)
+            return None if g is None else _gather(g, order, copy=False)
 
         def add_start(g):                             # + cotangent of the start state, rows already in the caller's order
             g0 = g_raw(0) if n_t > 1 else None
@@ -663,7 +620,7 @@ class _OdeintAdjoint(torch.autograd.Function):
                 vals = [ans[1], g_at(1)] + [None] * (len(plan.gb.inputs) - 2)
                 comps = plan.gb.run(vals)
                 gy0 = add_start(back(comps[1]))
-            _bump_nfe(func, plan.gb.nfe + ((n_t - 1) if NFE_COUNTS_SKIPPED_DLDT_EVAL else 0))
+            _bump_nfe(func, plan.adj, plan.gb.nfe, (n_t - 1) if NFE_COUNTS_SKIPPED_DLDT_EVAL else 0)
             return (None, None, None, None, None, None, None, gy0, *plan.adj.param_grads(comps))
         if plan is not None:
             plan.seen_b += 1
@@ -672,15 +629,8 @@ class _OdeintAdjoint(torch.autograd.Function):
         ctx_tmp = torch.empty_like(ans[0])
         stats = Dopri5Stats()
         with torch.no_grad():
-            comps = adj.new_state(ans[-1]) if hasattr(adj, "new_state") else None
-            if comps is None:
-                comps = [ans[-1].clone(), torch.zeros_like(ans[-1]),
-                         torch.zeros(1, dtype=ans.dtype, device=ans.device)]
-                comps += [torch.zeros_like(p) for p in adj.params]
-            if order is None:
-                comps[1].copy_(g_raw(-1))
-            else:
-                torch.index_select(g_raw(-1), 0, order, out=comps[1])
+            comps = adj.new_state(ans[-1])
+            _gather(g_raw(-1), order, out=comps[1])
             for i in range(len(tl) - 1, 0, -1):
                 comps[0].copy_(ans[i])
                 if ctx.method != "rk4":
@@ -691,7 +641,7 @@ class _OdeintAdjoint(torch.autograd.Function):
                     gi = g_at(i)
                     if gi is not None:
                         comps[2].sub_((ctx_tmp * gi).sum().reshape(1))
-                    if getattr(adj, "adaptive", None) is not None:
+                    if adj.big_components is not None:
                         adj.adaptive = True
                         adj.reduce_small(comps[2])      # row-partitioned: a_t is a sum over all rows
                 _integrate(adj, comps, tl[i], tl[i - 1], ctx.rtol, ctx.atol, ctx.method, ctx.options, stats)
@@ -701,9 +651,8 @@ class _OdeintAdjoint(torch.autograd.Function):
             # no gather of a slice that is all zeros whenever the loss only looks at the end state
             gy0 = add_start(back(comps[1]))
         skipped = (n_t - 1) if (ctx.method == "rk4" and NFE_COUNTS_SKIPPED_DLDT_EVAL) else 0
-        _bump_nfe(func, (stats.nfe if getattr(adj, "fused", False) else 0) + skipped)
-        pg = adj.param_grads(comps) if hasattr(adj, "param_grads") else comps[3:]
-        return (None, None, None, None, None, None, None, gy0, *pg)
+        _bump_nfe(func, adj, stats.nfe, skipped)
+        return (None, None, None, None, None, None, None, gy0, *adj.param_grads(comps))
 
 
 def odeint_adjoint(func, y0, t, rtol=1e-6, atol=1e-12, method=None, options=None, _last_only=False):

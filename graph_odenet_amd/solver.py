@@ -49,16 +49,68 @@ DP_MID = [
 ]
 
 
+def interp_weights(x):
+    """(cy0, cy1, kc[7]): the 4th-order fit through (y_n, y_mid, y_{n+1}, f_n, f_{n+1}) of a step at abscissa x, as
+    cy0 y_n + cy1 y_{n+1} + h sum kc_s k_s."""
+    x2, x3, x4 = x * x, x * x * x, x * x * x * x
+    wm = 16 * x4 - 32 * x3 + 16 * x2
+    cy0 = -8 * x4 + 18 * x3 - 11 * x2 + 1 + wm
+    cy1 = -8 * x4 + 14 * x3 - 5 * x2
+    kc = [wm * m for m in DP_MID]
+    kc[0] += -2 * x4 + 5 * x3 - 4 * x2 + x
+    kc[6] += 2 * x4 - 3 * x3 + x2
+    return cy0, cy1, kc
+
+
 class Field:
     """A vector field over a list of state components.
 
     eval(t, terms, out): terms[c] is the (coef, tensor) list whose sum is the stage value of
     component c; out[c] receives d(component c)/dt.  t is a python float.
+
+    Everything below `eval` is optional and states the whole protocol between the fields and the two solver modules:
+    a field offers a member by overriding it, and None / False / () means "absent" (the solvers then take the plain path).
     """
     n_components = 1
 
     def eval(self, t, terms, out):   # pragma: no cover - interface
         raise NotImplementedError
+
+    # ---- both integrators -----------------------------------------------------------------------------------------
+    prepare = None                # prepare(): odeint, once before a solve issues launches (refresh packed parameters)
+    alloc_like = None             # alloc_like(y, n) -> n work copies of the state y: both integrators, at their start
+    fused = False                 # the field never calls func.forward: odeint adds the solve's nfe to func.nfe itself
+    row_order = None              # the field integrates y[row_order] (models.ODEfunc marks it): odeint gathers on entry
+    row_inverse = None            # ... and gathers with row_inverse on exit
+    token = None                  # identity of the problem besides shapes and parameters (what func.gode_plan_token gives)
+    # ---- fixed-grid rk4 -------------------------------------------------------------------------------------------
+    rk4_native = None             # rk4_native(comps, t0, t1, n) -> nfe: odeint, the whole solve as one C call
+    eval_combine = None           # eval_combine(t, terms, pre, coef, out) -> components whose new solution it wrote to
+    #                               out: integrate_rk4, instead of eval for the last stage of a step
+    begin_rk4_step = None         # begin_rk4_step() -> bool: integrate_rk4 before the stages of a step; True = this step's
+    finish_rk4_step = None        # ... deferred_components are advanced in place by finish_rk4_step(weights, y) after them
+    deferred_components = ()
+    fixed_grid_only = False       # odeint refuses the adaptive method on this field
+    # ---- adaptive dopri5 ------------------------------------------------------------------------------------------
+    dopri5_step_native = None     # dopri5_step_native(y, kk, y1, t, h, rtol, atol) -> error sums per ratio group (fp64,
+    #                               on the device): integrate_dopri5, one attempted step as one C call
+    ratio_groups = None           # components whose error norms pool (a state tensor of torchdiffeq): both error norms
+    # ---- row-partitioned fields (big_components is not None) ------------------------------------------------------------
+    big_components = None         # the components that are row slices; odeint keeps such fields forward-only
+    adaptive = False              # set by odeint before an adaptive solve: the small components are then kept global
+    global_numel = None           # global_numel(c, t) -> elements of component c over all ranks: the error norms
+    reduce_error_sums = None      # reduce_error_sums(sums) -> the per-component sums over all ranks: the error norms
+    reduce_small = None           # reduce_small(t): sum a small component over the ranks in place (adjoint, adaptive)
+    # ---- adjoint fields (odeint._OdeintAdjoint.backward) ---------------------------------------------------------------
+    new_state = None              # new_state(y_end) -> [y, a = 0, a_t = 0, parameter gradients = 0 ...]
+    param_grads = None            # param_grads(comps) -> the gradients in func.parameters() order (+ extra inputs)
+    # ---- backprop through the solve (odeint._OdeintBackprop); a field offering a sweep offers the packed pair too ----------
+    rk4_forward_save = None       # rk4_forward_save(y0, y_end, save, t0, t1, n, i0, i1): steps i0..i1-1, stages recorded
+    rk4_backprop = None           # rk4_backprop(save, a, theta, t0, t1, n, i0, i1) -> tensor holding dL/dy before step i0
+    dopri5_step_backprop = None   # dopri5_step_backprop(y, k, g, kbar7, wy, wk, t, h, first, work, turn, theta)
+    dopri5_backprop_work = None   # dopri5_backprop_work(like) -> the work arrays dopri5_step_backprop takes
+    packed_grads = None           # packed_grads(device) -> zeroed buffer `theta` the sweeps add parameter gradients to
+    packed_param_grads = None     # packed_param_grads(theta) -> the gradients in func.parameters() order
 
 
 def _stage_terms(y, ks, coefs, h):
@@ -96,17 +148,17 @@ def integrate_rk4(field, y, t0, t1, n_steps, work=None):
     stage and the solution / stage buffers swap roles), so callers read `y[c]` afterwards."""
     # a field may lay out the work copies itself (the adjoint field packs its small components into one buffer, which
     # the fused launch-bound stage writes in one launch)
-    alloc = getattr(field, "alloc_like", None) or _alloc_like
+    alloc = field.alloc_like or _alloc_like
     ks = work if work is not None else alloc(y, 4)
     h = (t1 - t0) / n_steps
     nfe = 0
     nc = len(y)
-    fused = getattr(field, "eval_combine", None)
+    fused = field.eval_combine
     # a field may keep the stage derivatives of its SMALL components (a_t, parameter gradients: the adjoint ODE is linear
     # in them and no stage input reads them) as block partials and close the four stages of a step with ONE launch that
     # adds h * sum_s b_s k_s to the solution (gat_ode, one head or H, on launch-bound graphs): begin_rk4_step() before the
     # stages, finish_rk4_step(weights, y) after them returns the components it has advanced
-    begin, finish = getattr(field, "begin_rk4_step", None), getattr(field, "finish_rk4_step", None)
+    begin, finish = field.begin_rk4_step, field.finish_rk4_step
     for i in range(n_steps):
         t = t0 + i * h
         deferred = begin is not None and begin()
@@ -162,8 +214,7 @@ REPLAY = None
 
 def _numel(field, y, c):
     """Elements of component c in the WHOLE problem (a row-partitioned field holds a slice of the big components)."""
-    g = getattr(field, "global_numel", None)
-    return g(c, y[c]) if g is not None else y[c].numel()
+    return field.global_numel(c, y[c]) if field.global_numel is not None else y[c].numel()
 
 
 # Norm of the initial-step heuristic (Hairer-Norsett-Wanner II.4) on a state of several tensors - the adjoint solve's
@@ -190,10 +241,9 @@ def _rms_groups(terms_per_comp, y, rtol, atol, field, pooled):
     nc = len(y)
     outs = [ops.rk_scaled_sumsq(terms_per_comp[c], y[c], rtol, atol) for c in range(nc)]
     sums = torch.cat(outs).tolist()
-    red = getattr(field, "reduce_error_sums", None)
-    if red is not None:
-        sums = red(sums)
-    groups = [list(range(nc))] if pooled else (getattr(field, "ratio_groups", None) or [[c] for c in range(nc)])
+    if field.reduce_error_sums is not None:
+        sums = field.reduce_error_sums(sums)
+    groups = [list(range(nc))] if pooled else (field.ratio_groups or [[c] for c in range(nc)])
     return [math.sqrt(sum(sums[c] for c in grp) / sum(_numel(field, y, c) for c in grp)) for grp in groups]
 
 
@@ -230,7 +280,7 @@ def _optimal_step(last, ratio, safety=0.9, ifactor=10.0, dfactor=0.2, order=5):
 
 
 class Dopri5Record:
-    """What backprop through an adaptive solve keeps of it (odeint._OdeintBackpropDopri5): one entry per accepted step,
+    """What backprop through an adaptive solve keeps of it (odeint._OdeintBackprop under dopri5): one entry per accepted step,
     (t_n, h_n, x, y_n, [k_1..k_keep]) with x the interpolation abscissa of a last step that overshot the end time, else
     None.  keep = 7: all stage derivatives; 1: k_1 only; 0: the state alone.  The entries hold the solve's own buffers,
     which the solve then leaves alone; with max_bytes given, a record of 7 that outgrows it drops to 1."""
@@ -261,8 +311,8 @@ def integrate_dopri5(field, y, t0, t1, rtol, atol, stats=None, max_steps=100000,
     span = abs(t1 - t0)
     # a field may lay out the work copies of the state itself (e.g. small components packed in one buffer) and may
     # offer the whole step as one native call (csrc/ode_driver.hip) when `dopri5_native` is set
-    alloc = getattr(field, "alloc_like", None) or (lambda yy, n: _alloc_like(yy, n))
-    native = getattr(field, "dopri5_step_native", None) if DOPRI5_NATIVE else None
+    alloc = field.alloc_like or _alloc_like
+    native = field.dopri5_step_native if DOPRI5_NATIVE else None
     ks = alloc(y, 7)
     y1, tmp = alloc(y, 2)
     field.eval(t0, [[(1.0, y[c])] for c in range(nc)], ks[0])
@@ -285,7 +335,7 @@ def integrate_dopri5(field, y, t0, t1, rtol, atol, stats=None, max_steps=100000,
         order = [fsal] + [i for i in range(7) if i != fsal]
         kk = [ks[i] for i in order]
         t = t0 + sgn * tau
-        groups = getattr(field, "ratio_groups", None) or [[c] for c in range(nc)]
+        groups = field.ratio_groups or [[c] for c in range(nc)]
         if native is not None:
             gsums = native(y, kk, y1, t, h, rtol, atol).tolist()     # one call, one device->host sync
             stats.nfe += 6
@@ -299,9 +349,8 @@ def integrate_dopri5(field, y, t0, t1, rtol, atol, stats=None, max_steps=100000,
             sums = [ops.rk_error_sumsq(y[c], y1[c], [(h * DP_E[s], kk[s][c]) for s in range(7) if DP_E[s] != 0.0],
                                        rtol, atol) for c in range(nc)]
             sums = torch.cat(sums).tolist()          # the one device->host sync of this step
-            red = getattr(field, "reduce_error_sums", None)
-            if red is not None:
-                sums = red(sums)                     # row-partitioned state: every rank sees the global sums
+            if field.reduce_error_sums is not None:
+                sums = field.reduce_error_sums(sums)     # row-partitioned state: every rank sees the global sums
             ratios = [sum(sums[c] for c in grp) / sum(_numel(field, y, c) for c in grp) for grp in groups]
         ratio = max(ratios)
         accept = all(r <= 1.0 for r in ratios) if forced is None else bool(forced[len(seq)][1])
@@ -320,15 +369,7 @@ def integrate_dopri5(field, y, t0, t1, rtol, atol, stats=None, max_steps=100000,
                         if res[c] is not y1[c]:
                             res[c].copy_(y1[c])
                 else:
-                    x2, x3, x4 = x * x, x * x * x, x * x * x * x
-                    wm = 16 * x4 - 32 * x3 + 16 * x2
-                    cy0 = -8 * x4 + 18 * x3 - 11 * x2 + 1 + wm
-                    cy1 = -8 * x4 + 14 * x3 - 5 * x2
-                    cf0 = -2 * x4 + 5 * x3 - 4 * x2 + x
-                    cf1 = 2 * x4 - 3 * x3 + x2
-                    kc = [wm * m for m in DP_MID]
-                    kc[0] += cf0
-                    kc[6] += cf1
+                    cy0, cy1, kc = interp_weights(x)
                     for c in range(nc):
                         ops.lincomb_(res[c], [(cy0, y[c]), (cy1, y1[c])] +
                                      [(h * kc[s], kk[s][c]) for s in range(7) if kc[s] != 0.0])

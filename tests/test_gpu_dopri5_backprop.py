@@ -1,4 +1,4 @@
-"""Backprop through odeint under adaptive dopri5 (odeint._OdeintBackpropDopri5): the gradient of the computed discrete
+"""Backprop through odeint under adaptive dopri5 (odeint._OdeintBackprop): the gradient of the computed discrete
 solution w.r.t. y0 and the ODE function's parameters with the accepted step sizes as constants, against autograd through
 the oracle solver (solver_ref.odeint dopri5 + the reference layer math, whose step sizes are Python floats) replaying
 the product's own attempt sequence - on the three kernel routes of the fused GCN field and on the generic path."""

@@ -2,7 +2,7 @@
 """Training-step time of odeint_adjoint against odeint backprop (odeint._OdeintBackprop), in one process with the two
 modes alternating: ODEGCN3 fwd + bwd + Adam on the C5 graph (R-MAT 2^20 nodes, 10^7 edges, d = 128, rk4 16 steps) and on
 Cora (d = 16, rk4 step 1/16), plus each mode's peak device memory.  Prints one JSON line.
---method dopri5: the adaptive default instead (odeint._OdeintBackpropDopri5), rtol = atol = --tol.
+--method dopri5: the adaptive default instead (the same Function, its dopri5 strategy), rtol = atol = --tol.
 
   python tools/backprop_bench.py [--steps 3] [--rounds 3] [--scale 20] [--edges 10000000] [--no-cora] [--only MODE]
                                  [--method rk4|dopri5] [--tol 1e-5]
