@@ -219,6 +219,14 @@ SIGNATURES = {
                                     c_p, c_p]),
     "gode_edge_outer_sum_acc_f32": (c_i, [c_p, c_p, c_p, ctypes.c_int32, ctypes.POINTER(c_p), ctypes.POINTER(c_p),
                                           ctypes.POINTER(c_f), c_i64, c_i64, c_i, c_p, c_p]),
+    "gode_edge_ode_feval_save_f32": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_p, ctypes.POINTER(LinComb), c_f, c_p, c_p,
+                                           c_p]),
+    "gode_edge_ode_stage_bwd_supported": (c_i, [c_i64, c_i64, ctypes.c_int32]),
+    "gode_edge_ode_stage_bwd_f32": (c_i, [c_p, c_p, c_p, c_p, c_p, ctypes.POINTER(LinComb), c_f, c_p, ctypes.POINTER(LinComb), c_f,
+                                          c_p, c_p, c_p, ctypes.c_int32, c_f, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p, c_p,
+                                          c_p]),
+    "gode_edge_ode_step_close_f32": (c_i, [ctypes.c_int32, ctypes.POINTER(c_p), ctypes.POINTER(c_p), ctypes.POINTER(c_p),
+                                           ctypes.POINTER(c_p), ctypes.POINTER(c_f), c_i64, c_i64, c_i64, c_p, c_p]),
     "gode_segment_attention_f32_fwd": (c_i, [c_p, c_p, c_p, c_i64, c_p, c_i64, c_i64, c_p, c_p, c_p]),
     "gode_segment_attention_f32_bwd": (c_i, [c_p, c_p, c_p, c_i64, c_p, c_p, c_p, c_i64, c_i64, c_p, c_p, c_p]),
     "gode_assign_csr_supported": (c_i, [c_i64, c_i64]),

@@ -113,6 +113,12 @@ __device__ __forceinline__ float lc_load1(const LinComb& lc, int64_t idx) {
     return r;
 }
 
+// Stage cotangent of a relu stage, scale * (sum cot) masked by fout > 0 (edge_ode.hip, edge_backprop.hip)
+__device__ __forceinline__ float masked_cot(const LinComb& cot, float scale, const float* __restrict__ fout, int64_t idx) {
+    const float g = scale * lc_load1(cot, idx);          // the load is unconditional; the mask is a select
+    return fout[idx] > 0.f ? g : 0.f;
+}
+
 // When the first coefficient is exactly 1 the first term is taken as-is so that
 // a one-term {1.0, y} combination reproduces y bit for bit.
 __device__ __forceinline__ float wave_sum(float v) {

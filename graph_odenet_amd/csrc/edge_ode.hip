@@ -1,8 +1,10 @@
 // edge_ode.hip — the edge-conditioned ODE function of the QM9 models,
 //     S = [t | GN(X)] W  (gemm.hip),   f = relu(Etgt . bmm(A, S[Esrc]) + b),
-// and its vector-Jacobian product (qc_ode.py).  Three entry points:
+// and its vector-Jacobian product (qc_ode.py).  Four entry points:
 //   gode_edge_ode_feval_f32      message + per-target sum + bias + relu (+ the RK solution combine) in one launch; the
 //                                E x h message array is never written
+//   gode_edge_ode_feval_save_f32 the same launch, also storing f itself (the stage derivative a folded last rk4 stage
+//                                never materialises: backprop through the solve needs it as the relu mask)
 //   gode_edge_ode_vjp_f32        masked stage cotangent dM formed from its RK terms inside the kernel; dS through the source
 //                                incidence (launch-bound batches) or dxe per edge (large batches); no dA
 //   gode_edge_outer_sum_acc_f32  dA (+)= sum_s w_s (val dM_s[tgt]) (x) S_s[src]: the four stages of a fixed-grid step in
@@ -14,21 +16,17 @@
 constexpr int kEdgeOdeMaxH = 112;        // the padded h x (h + 1) LDS tile + index triples stay under 64 KB
 constexpr int kVjpRound = 16;            // edges of a source whose cotangent rows are staged together
 
-__device__ __forceinline__ float masked_cot(const LinComb& cot, float scale, const float* __restrict__ fout, int64_t idx) {
-    const float g = scale * lc_load1(cot, idx);          // the load is unconditional; the mask is a select
-    return fout[idx] > 0.f ? g : 0.f;
-}
-
 // block per target atom v.  The index triples (edge id, value, source atom) of up to 256 of its edges are fetched
 // together; the matrix of edge q + 1 is requested (into registers) before the products of edge q start, so an edge
 // costs one load round trip, overlapped with the previous edge's arithmetic.  Thread i owns output element i and reads
 // row i of the LDS tile at stride h + 1 (conflict-free).
-template <int PF>
+// SAVE: relu(z) is also stored to ksave, before the pre / alpha combine.
+template <int PF, bool SAVE>
 __global__ __launch_bounds__(256) void edge_ode_feval_kernel(const int* __restrict__ rowptr, const int* __restrict__ eid,
                                                              const float* __restrict__ val, const int* __restrict__ src,
                                                              const float* __restrict__ A, const float* __restrict__ S,
                                                              int h, const float* __restrict__ bias, LinComb pre, float alpha,
-                                                             float* __restrict__ out) {
+                                                             float* __restrict__ out, float* __restrict__ ksave) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     __shared__ int es[256], ss[256];
     __shared__ float vs[256];
@@ -77,6 +75,7 @@ __global__ __launch_bounds__(256) void edge_ode_feval_kernel(const int* __restri
     if (tid < h) {
         const int64_t idx = (int64_t)v * h + tid;
         const float r = fmaxf(acc + bias[tid], 0.f);
+        if (SAVE) ksave[idx] = r;
         out[idx] = pre.n > 0 ? fmaf(alpha, r, lc_load1(pre, idx)) : alpha * r;
     }
 }
@@ -181,26 +180,46 @@ __global__ __launch_bounds__(256) void edge_outer_sum_acc_kernel(const int* __re
 
 extern "C" int gode_edge_ode_supported(int64_t h) { return h >= 1 && h <= kEdgeOdeMaxH ? 1 : 0; }
 
-extern "C" int gode_edge_ode_feval_f32(const int32_t* rowptr, const int32_t* eid, const float* val, const int32_t* src,
-                                       const float* A, const float* S, int64_t h, int64_t n_rows, const float* bias,
-                                       const gode_lincomb_t* pre, float alpha, float* out, void* stream) {
+namespace {
+int feval_launch(const int32_t* rowptr, const int32_t* eid, const float* val, const int32_t* src, const float* A,
+                 const float* S, int64_t h, int64_t n_rows, const float* bias, const gode_lincomb_t* pre, float alpha,
+                 float* out, float* ksave, bool save, void* stream) {
     if (n_rows < 0 || h <= 0) return GODE_E_SHAPE;
     if (h > kEdgeOdeMaxH || n_rows > INT32_MAX) return GODE_E_RANGE;
     int rc = check_lincomb(pre, false); if (rc) return rc;
     if (n_rows == 0) return 0;
-    if (!rowptr || !src || !A || !S || !bias || !out) return GODE_E_NULLPTR;
+    if (!rowptr || !src || !A || !S || !bias || !out || (save && !ksave)) return GODE_E_NULLPTR;
+    if (save) {
+        if (ksave == out) return GODE_E_SHAPE;
+        for (int j = 0; pre && j < pre->n; ++j) if (pre->ptr[j] == ksave) return GODE_E_SHAPE;
+    }
     hipStream_t s = (hipStream_t)stream;
     LinComb lp = make_lincomb(pre);
     const size_t lds = (size_t)(h + h * (h + 1)) * sizeof(float);
-#define GODE_EF(PFV) { if (lds > 48 * 1024) { rc = gode_set_lds_once((const void*)edge_ode_feval_kernel<PFV>, lds); if (rc) return rc; } \
+#define GODE_EF2(PFV, SV) { if (lds > 48 * 1024) { rc = gode_set_lds_once((const void*)edge_ode_feval_kernel<PFV, SV>, lds); if (rc) return rc; } \
         const int slot = gode_prof_begin(s, h, n_rows, (int64_t)lp.n, GODE_PROF_EDGE_FEVAL);                                \
-        hipLaunchKernelGGL(edge_ode_feval_kernel<PFV>, dim3((unsigned)n_rows), dim3(256), lds, s, rowptr, eid, val, src, A, S, \
-                           (int)h, bias, lp, alpha, out);                                                                    \
+        hipLaunchKernelGGL((edge_ode_feval_kernel<PFV, SV>), dim3((unsigned)n_rows), dim3(256), lds, s, rowptr, eid, val, src, A, S, \
+                           (int)h, bias, lp, alpha, out, ksave);                                                             \
         gode_prof_end(s, slot); }
+#define GODE_EF(PFV) { if (save) GODE_EF2(PFV, true) else GODE_EF2(PFV, false) }
     if (h <= 32) GODE_EF(4) else if (h <= 64) GODE_EF(16) else GODE_EF(49)
 #undef GODE_EF
+#undef GODE_EF2
     GODE_LAUNCH_CHECK();
     return 0;
+}
+}  // namespace
+
+extern "C" int gode_edge_ode_feval_f32(const int32_t* rowptr, const int32_t* eid, const float* val, const int32_t* src,
+                                       const float* A, const float* S, int64_t h, int64_t n_rows, const float* bias,
+                                       const gode_lincomb_t* pre, float alpha, float* out, void* stream) {
+    return feval_launch(rowptr, eid, val, src, A, S, h, n_rows, bias, pre, alpha, out, nullptr, false, stream);
+}
+
+extern "C" int gode_edge_ode_feval_save_f32(const int32_t* rowptr, const int32_t* eid, const float* val, const int32_t* src,
+                                            const float* A, const float* S, int64_t h, int64_t n_rows, const float* bias,
+                                            const gode_lincomb_t* pre, float alpha, float* out, float* k, void* stream) {
+    return feval_launch(rowptr, eid, val, src, A, S, h, n_rows, bias, pre, alpha, out, k, true, stream);
 }
 
 extern "C" int gode_edge_ode_vjp_f32(const int32_t* ms_rowptr, const int32_t* ms_eid, const int32_t* edge_row,

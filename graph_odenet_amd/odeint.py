@@ -41,7 +41,8 @@ NFE_COUNTS_SKIPPED_DLDT_EVAL = True
 # bytes (2^20 x 128 state, 16 steps: 40 GiB); above it only y_n is kept and each step is re-run into a one-step record just
 # before its reverse sweep (the same launches: gradients bit for bit those of the save-everything mode).
 # Backprop through a fused dopri5 solve keeps y_n and k_1..k_7 of every accepted step (8 n d floats per step) under the same
-# bound; a solve that outgrows it keeps y_n and k_1 and re-runs each step (one native step call) before its sweep.
+# bound; a solve that outgrows it keeps y_n and k_1 and re-runs each step (one native step call) before its sweep.  A field
+# with a sweep but no dopri5_step_native (qc_ode.EdgeOdeField) has nothing to re-run a step with and keeps all seven always.
 BACKPROP_SAVE_MAX_BYTES = 48 << 30
 
 
@@ -395,11 +396,11 @@ class _Rk4Backprop:
 class _Dopri5Backprop:
     """What _OdeintBackprop does per interval under adaptive dopri5; the accepted step sizes are constants of the
     derivative.  The forward runs the solve's own launches on buffers a solver.Dopri5Record keeps.  Fused (a field offering
-    dopri5_step_backprop: GcnOdeField): y_n and k_1..k_7 of every accepted step - or y_n and k_1 past
-    BACKPROP_SAVE_MAX_BYTES, each step then re-run by one native step call before its sweep - swept in reverse, one C call
-    per step (csrc/ode_driver.hip).  Generic: y_n alone, each accepted step re-run as torch ops through func,
-    k_1 = func(t_n, y_n) recomputed: the same function of y_n as the derivative FSAL hands over, since Y_7 and y_{n+1} are
-    the same combination."""
+    dopri5_step_backprop: GcnOdeField, qc_ode.EdgeOdeField): y_n and k_1..k_7 of every accepted step - or y_n and k_1 past
+    BACKPROP_SAVE_MAX_BYTES, each step then re-run by one native step call before its sweep (never for a field without
+    dopri5_step_native: it keeps all seven) - swept in reverse, one call per step (csrc/ode_driver.hip; qc_ode.py).
+    Generic: y_n alone, each accepted step re-run as torch ops through func, k_1 = func(t_n, y_n) recomputed: the same
+    function of y_n as the derivative FSAL hands over, since Y_7 and y_{n+1} are the same combination."""
     own_cotangent = False             # fused_reverse hands back one of its work arrays
 
     def __init__(self, func, fwd, tl, rtol, atol, options, y0c):
@@ -413,7 +414,10 @@ class _Dopri5Backprop:
 
     def forward(self, i, cur, start):
         fused, left = self.fused, self.left
-        rec = Dopri5Record(7, left) if fused and left is not None else Dopri5Record(1 if fused else 0)
+        if fused and self.fwd.dopri5_step_native is None:
+            rec = Dopri5Record(7)                 # no native step to re-run a step with: all seven, whatever the bound
+        else:
+            rec = Dopri5Record(7, left) if fused and left is not None else Dopri5Record(1 if fused else 0)
         (cur,), _ = integrate_dopri5(self.fwd, [cur], self.tl[i - 1], self.tl[i], *self.tols, self.stats, record=rec)
         if fused and left is not None:
             self.left = left - rec.bytes if rec.keep == 7 else None      # past the bound: the later intervals keep k_1 only
@@ -522,7 +526,8 @@ def odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None):
     if torch.is_grad_enabled() and fwd.big_components is None:
         params = _params(func)
         if y0.requires_grad or params:
-            same = len(fields[2]) == len(params) and all(p is q for p, q in zip(fields[2], params))
+            covered = tuple(fields[2]) + _extra_inputs(func)       # a field with a sweep returns the extra inputs' gradients too
+            same = len(covered) == len(params) and all(p is q for p, q in zip(covered, params))
             sweep = fwd.rk4_forward_save if method == "rk4" else fwd.dopri5_step_backprop
             if sweep is not None and not same:
                 fwd = AutogradField(func, y0)         # the fused field does not cover these parameters

@@ -922,6 +922,7 @@ def edge_outer_sum(edge_row, edge_val, src, pairs, like):
 EDGE_ODE_FUSED_MAX_EDGES = 4096
 # kinds of the launches above in a gode_prof_* profile (include/graphode.h)
 PROF_EDGE_FEVAL, PROF_EDGE_VJP, PROF_EDGE_OUTER_STEP, PROF_EDGE_OUTER_STAGE = 5, 6, 7, 8
+PROF_EDGE_STAGE_BWD, PROF_EDGE_STEP_CLOSE = 9, 10           # csrc/edge_backprop.hip
 
 
 def edge_ode_supported(h):
@@ -934,10 +935,11 @@ def _need_edge_matrices(A, E, h):
         raise ValueError("edge_ode: edge_data must be E x h x h = (%d, %d, %d), got %s" % (E, h, h, tuple(A.shape)))
 
 
-def edge_ode_feval(Mt, src, A, S, bias, out, pre_terms=None, alpha=1.0):
-    """out = (sum pre_terms) + alpha * relu(Mt . bmm(A, S[src]) + bias) in one launch; Mt: CSR of Etgt (N x E)."""
+def edge_ode_feval(Mt, src, A, S, bias, out, pre_terms=None, alpha=1.0, k_out=None):
+    """out = (sum pre_terms) + alpha * relu(Mt . bmm(A, S[src]) + bias) in one launch; Mt: CSR of Etgt (N x E).
+    k_out: also receives relu(...) itself (gode_edge_ode_feval_save_f32; the same bits in out)."""
     lib = _lib.load()
-    _need(S, "S"); _need(bias, "bias"); _need(out, "out"); _need(src, "Esrc", torch.int32)
+    _need(S, "S"); _need(bias, "bias"); _need(out, "out"); _need(src, "Esrc", torch.int32); _need(k_out, "k_out")
     if S.dim() != 2 or S.shape[0] != Mt.n_rows:
         raise ValueError("edge_ode_feval: S has shape %s, the batch has %d atoms" % (tuple(S.shape), Mt.n_rows))
     n, h = S.shape
@@ -952,6 +954,13 @@ def edge_ode_feval(Mt, src, A, S, bias, out, pre_terms=None, alpha=1.0):
         if any(t.data_ptr() == out.data_ptr() for _, t in pre_terms):
             raise ValueError("edge_ode_feval: out must not be a pre term")
         pre = lincomb(pre_terms)
+    if k_out is not None:
+        if k_out.numel() != n * h:
+            raise ValueError("edge_ode_feval: k_out must be n x h")
+        check(lib.gode_edge_ode_feval_save_f32(ptr(Mt.rowptr), ptr(Mt.col), ptr(Mt.val), ptr(src), ptr(A), ptr(S), h, n, ptr(bias),
+                                               ctypes.byref(pre) if pre is not None else None, float(alpha), ptr(out),
+                                               ptr(k_out), stream_ptr()), "gode_edge_ode_feval_save_f32")
+        return out
     check(lib.gode_edge_ode_feval_f32(ptr(Mt.rowptr), ptr(Mt.col), ptr(Mt.val), ptr(src), ptr(A), ptr(S), h, n, ptr(bias),
                                       ctypes.byref(pre) if pre is not None else None, float(alpha), ptr(out), stream_ptr()),
           "gode_edge_ode_feval_f32")
@@ -983,6 +992,59 @@ def edge_ode_vjp(Ms_inc, edge_row, edge_val, A, cot_terms, cot_scale, fout, dM, 
     lc = lincomb(cot_terms)
     check(lib.gode_edge_ode_vjp_f32(ptr(rp), ptr(eid), ptr(edge_row), ptr(edge_val), ptr(A), ctypes.byref(lc), float(cot_scale),
                                     ptr(fout), h, n, E, ptr(dM), ptr(dS), ptr(dxe), stream_ptr()), "gode_edge_ode_vjp_f32")
+
+
+def edge_ode_stage_bwd_supported(n_rows, h, groups):
+    return bool(_lib.load().gode_edge_ode_stage_bwd_supported(int(n_rows), int(h), int(groups)))
+
+
+def edge_ode_stage_bwd(Ms_inc, edge_row, edge_val, A, cot_terms, cot_scale, k, y_terms, t, gamma, beta, W, groups, eps, dM, dS,
+                       ybar, dgamma_rows, dbeta_rows, S=None):
+    """The reverse of one stage k = f(t, sum y_terms) in one launch (gode_edge_ode_stage_bwd_f32): dM = cot_scale *
+    (sum cot_terms) * [k > 0], dS through the source incidence Ms_inc (N x E), ybar = the GroupNorm / time / GEMM VJP of dS,
+    the rows' dgamma / dbeta shares, and S = [t | GN(Y)] W when given."""
+    lib = _lib.load()
+    n, h = k.shape
+    E = edge_row.numel()
+    outs = (dM, dS, ybar, dgamma_rows, dbeta_rows) + ((S,) if S is not None else ())
+    for x in (k, gamma, beta, W) + outs:
+        _need(x, "edge_ode_stage_bwd operand")
+    _need(edge_row, "edge_row", torch.int32); _need(edge_val, "edge_val")
+    _need_edge_matrices(A, E, h)
+    if _need_terms(cot_terms, "cot") != n * h or _need_terms(y_terms, "y") != n * h or any(x.numel() != n * h for x in outs):
+        raise ValueError("edge_ode_stage_bwd: the terms and the outputs must be n x h")
+    if Ms_inc.n_rows != n or Ms_inc.n_cols != E or W.numel() != (h + 1) * h or gamma.numel() != h or beta.numel() != h:
+        raise ValueError("edge_ode_stage_bwd: the source incidence must be n x E, W (h + 1) x h, gamma and beta h")
+    lc, ly = lincomb(cot_terms), lincomb(y_terms)
+    check(lib.gode_edge_ode_stage_bwd_f32(ptr(Ms_inc.rowptr), ptr(Ms_inc.col), ptr(edge_row), ptr(edge_val), ptr(A),
+                                          ctypes.byref(lc), float(cot_scale), ptr(k), ctypes.byref(ly), float(t), ptr(gamma),
+                                          ptr(beta), ptr(W), int(groups), float(eps), h, n, E, ptr(dM), ptr(dS), ptr(ybar),
+                                          ptr(dgamma_rows), ptr(dbeta_rows), ptr(S), stream_ptr()),
+          "gode_edge_ode_stage_bwd_f32")
+
+
+def edge_ode_step_close(stages, n_rows, h, theta):
+    """theta = [W | b | gamma | beta] += the parameter gradients of stages = [(wpart, dM, dgamma_rows, dbeta_rows, t_s), ...]
+    (at most 8) in one launch: the wgrad partials with row 0 scaled by t_s, and the column sums of the three row arrays."""
+    lib = _lib.load()
+    q = len(stages)
+    if not 1 <= q <= 8:
+        raise ValueError("edge_ode_step_close: 1 .. 8 stages")
+    n_wparts = lib.gode_wgrad_parts(n_rows)
+    arrs = [(ctypes.c_void_p * q)() for _ in range(4)]
+    for i, st in enumerate(stages):
+        for a, x, ln in zip(arrs, st[:4], (n_wparts * (h + 1) * h, n_rows * h, n_rows * h, n_rows * h)):
+            _need(x, "edge_ode_step_close operand")
+            if x.numel() != ln:
+                raise ValueError("edge_ode_step_close: an operand of stage %d has %d elements, not %d" % (i, x.numel(), ln))
+            a[i] = x.data_ptr()
+    _need(theta, "theta")
+    if theta.numel() < (h + 4) * h:
+        raise ValueError("edge_ode_step_close: theta holds [W | b | gamma | beta]")
+    ts = (ctypes.c_float * q)(*[float(st[4]) for st in stages])
+    check(lib.gode_edge_ode_step_close_f32(q, arrs[0], arrs[1], arrs[2], arrs[3], ts, n_wparts, n_rows, h, ptr(theta),
+                                           stream_ptr()), "gode_edge_ode_step_close_f32")
+    return theta
 
 
 def edge_outer_sum_acc(edge_row, edge_val, src, pairs, weights, dA, accumulate):

@@ -26,6 +26,17 @@ Error-ratio groups (dopri5): y, a, a_t, and theta TOGETHER WITH a_A.  torchdiffe
 it returns a gradient for as ONE flat tensor (its f_params); the only way it returns dL/d(edge_data) at all is with
 edge_data among func's parameters - which is also how the tests' oracle gets it - so a_A is counted with the parameters.
 
+Backprop through the solve (odeint, adjoint=False) on launch-bound batches: the forward records k_s of every stage (the last
+rk4 stage through gode_edge_ode_feval_save_f32), so the reverse of a stage evaluates nothing again:
+
+    dM, dS, Ybar_s, the rows' dgamma / dbeta shares, S      gode_edge_ode_stage_bwd_f32            (1 launch)
+    dW partials                                              gode_wgrad_f32                         (1 launch)
+
+and a step of S swept stages ends with ONE gode_edge_ode_step_close_f32 (parameter gradients of all its stages into the
+packed buffer [W | b | gamma | beta | a_A]), ONE gode_edge_outer_sum_acc_f32 over its (dM_s, S_s) pairs when edge_data asks
+for a gradient, and at most one combine of the cotangent: 2 S + 3 launches.  Larger batches keep the generic path (the
+interval re-run as torch ops under autograd).
+
 Under fixed-grid rk4 the four stages of a step share A: each stage keeps its (dM, S) pair (N x h each) and ONE
 gode_edge_outer_sum_acc_f32 pass per step applies the RK weights and adds into a_A (solver.integrate_rk4's
 begin_rk4_step / finish_rk4_step); a_A then has no stage buffers and no RK combine.  Under dopri5 every stage writes
@@ -38,7 +49,7 @@ import torch.nn.functional as F
 from . import _lib, ops
 from .functional import GroupNorm
 from .qc_layers import EdgeGraphConvolution, _edges, _EdgeSet
-from .solver import Field
+from .solver import DP_A, DP_C, RK38_A, RK38_B, RK38_C, Field, _stage_terms
 
 
 def _edge_index(Esrc, Etgt):
@@ -118,7 +129,7 @@ class EdgeODEfunc(nn.Module):
         names = {id(self.norm1.weight): "gamma", id(self.norm1.bias): "beta", id(self.gc1.weight): "W", id(self.gc1.bias): "b"}
         order = [names[id(p)] for p in plist]
         want_A, fixed = A.requires_grad, self.fixed_grid
-        return EdgeOdeField(spec, work), (lambda: EdgeOdeAdjointField(spec, work, order, want_A, fixed)), tuple(plist)
+        return EdgeOdeField(spec, work, order, want_A), (lambda: EdgeOdeAdjointField(spec, work, order, want_A, fixed)), tuple(plist)
 
 
 class EdgeOdeSpec:
@@ -160,18 +171,152 @@ class _Work:
         self.colsum_scratch = torch.empty(max(lib.gode_colsum_scratch_bytes(n, d), 16), dtype=torch.uint8, device=device)
 
 
+class _BackpropWork:
+    """Buffers of a reverse sweep: per swept stage of a step (dopri5: up to 7) the (dM, S) pair, the rows' dgamma / dbeta
+    shares and the wgrad partials, which the step's closing launches read; one dS; the four Ybar of an rk4 step."""
+    STAGES = 7
+
+    def __init__(self, spec, device, want_S):
+        n, d, q = spec.n, spec.d, self.STAGES
+        f = dict(dtype=torch.float32, device=device)
+        self.dM, self.gr, self.br = torch.empty(q, n, d, **f), torch.empty(q, n, d, **f), torch.empty(q, n, d, **f)
+        self.S = torch.empty(q, n, d, **f) if want_S else None
+        self.wp = torch.empty(q, _lib.load().gode_wgrad_parts(n), (d + 1) * d, **f)
+        self.dS = torch.empty(n, d, **f)
+        self.ybar = [torch.empty(n, d, **f) for _ in range(4)]
+
+
 class EdgeOdeField(Field):
     """The forward field.  eval_combine folds the solution combine y + h sum b_s k_s of a fixed-grid step into the launch
-    that ends its last stage."""
+    that ends its last stage.  Built with the parameter order (gode_fields) on a launch-bound batch it also offers the
+    backprop half of the protocol (solver.Field); it has no dopri5_step_native, so a dopri5 record keeps all seven k_s.
+    Memory of that half: packed_param_grads hands out views of the one packed buffer, so as long as a parameter's .grad is
+    such a view the whole buffer stays alive, its E h^2 edge-matrix tail included; and the field is rebuilt with every
+    batch, so every odeint call that is backpropagated allocates a _BackpropWork (7 x 3 or 4 n x d arrays and 7 sets of
+    wgrad partials).  Both are small at the launch-bound sizes this half is limited to (under 4 096 edges)."""
     n_components = 1
     fused = True
     BIAS_DIRECT_MAX_ROWS = 1024      # up to here the rows of dM are the bias gradient's partials; above, block partials first
+    BACKPROP_FUSED = True            # False: no backprop members (odeint re-runs each interval as torch ops under autograd)
 
-    def __init__(self, spec, work):
+    def __init__(self, spec, work, order=None, want_A=False):
         self.s, self.w = spec, work
         self.slot = 0
+        if order is not None and self.BACKPROP_FUSED and not spec.large and \
+                ops.edge_ode_stage_bwd_supported(spec.n, spec.d, spec.groups):
+            self.order, self.want_A, self._bwork = order, bool(want_A), None
+            self.rk4_forward_save, self.rk4_backprop = self._rk4_forward_save, self._rk4_backprop
+            self.dopri5_step_backprop, self.dopri5_backprop_work = self._dopri5_step_backprop, self._dopri5_backprop_work
+            self.packed_grads, self.packed_param_grads = self._packed_grads, self._packed_param_grads
 
-    def _forward(self, t, y_terms, out, pre=None, alpha=1.0):
+    # ---- backprop through the solve (odeint._OdeintBackprop): launch-bound batches -----------------------------------------
+    def _packed_grads(self, device):
+        """Zeroed [W | b | gamma | beta | a_A (E h^2, only when edge_data asks for a gradient)]."""
+        s = self.s
+        return torch.zeros(s.n_theta + (s.A.numel() if self.want_A else 0), dtype=torch.float32, device=device)
+
+    def _packed_param_grads(self, theta):
+        """The gradients in func.parameters() order, then edge_data's (E x h x h)."""
+        s = self.s
+        v = s.views(theta)
+        return [v[k] for k in self.order] + ([theta[s.n_theta:].view_as(s.A)] if self.want_A else [])
+
+    def _bw(self, device):
+        if self._bwork is None:
+            self._bwork = _BackpropWork(self.s, device, self.want_A)
+        return self._bwork
+
+    def _stage_bwd(self, q, cot, k, yin, t, ybar):
+        """The reverse of one stage k = f(t, sum yin) with cotangent terms cot, into slot q of the step's buffers: 2 launches.
+        Returns what the step's closing launch needs of it."""
+        s, es, b = self.s, self.s.es, self._bw(k.device)
+        ops.edge_ode_stage_bwd(es.Ms_inc, es.edge_row, es.edge_val, s.A, cot, 1.0, k, yin, t, s.gamma, s.beta, s.W, s.groups,
+                               s.eps, b.dM[q], b.dS, ybar, b.gr[q], b.br[q], S=b.S[q] if self.want_A else None)
+        ops.wgrad(yin, s.n, s.d, s.groups, s.eps, s.gamma, s.beta, b.dS, True, part=b.wp[q])
+        return (b.wp[q], b.dM[q], b.gr[q], b.br[q], t)
+
+    def _close_step(self, stages, theta):
+        """theta += the parameter gradients of the step's swept stages (1 launch) and the edge-matrix gradient (1 launch)."""
+        s, es, b = self.s, self.s.es, self._bwork
+        ops.edge_ode_step_close(stages, s.n, s.d, theta)
+        if self.want_A:
+            ops.edge_outer_sum_acc(es.edge_row, es.edge_val, es.src, [(b.dM[q], b.S[q]) for q in range(len(stages))],
+                                   [1.0] * len(stages), theta[s.n_theta:].view_as(s.A), True)
+
+    def _rk4_forward_save(self, y0, y_end, save, t0, t1, n_steps, i0, i1):
+        """Steps i0 .. i1-1 with the launches of solver.integrate_rk4 on this field (the same bits); save[r] = [y_n, k_1..k_4]
+        of step i0 + r, k_4 stored by the launch that folds the last stage into the solution."""
+        if y0.data_ptr() != save[0, 0].data_ptr():
+            save[0, 0].copy_(y0)
+        h = (t1 - t0) / n_steps
+        for i in range(i0, i1):
+            rec = save[i - i0]
+            y, ks = [rec[0]], [[rec[1 + q]] for q in range(4)]
+            t = t0 + i * h
+            for q in range(3):
+                self.eval(t + RK38_C[q] * h, _stage_terms(y, ks, RK38_A[q], h), ks[q])
+            pre = [(1.0, y[0])] + [(h * RK38_B[q], ks[q][0]) for q in range(3)]
+            y_next = save[i - i0 + 1, 0] if i + 1 < i1 else y_end
+            self._forward(t + RK38_C[3] * h, _stage_terms(y, ks, RK38_A[3], h)[0], y_next, pre=pre, alpha=h * RK38_B[3],
+                          k_out=ks[3][0])
+
+    def _rk4_backprop(self, save, a, theta, t0, t1, n_steps, i0, i1):
+        """Reverse sweep over the records of steps i0 .. i1-1: kbar_s = h b_s a + h sum_{r > s} a_rs Ybar_r, Ybar_s through
+        the stage, a += sum_s Ybar_s.  `a` is advanced in place and returned."""
+        h = (t1 - t0) / n_steps
+        yb = self._bw(a.device).ybar
+        for i in range(i1 - 1, i0 - 1, -1):
+            rec = save[i - i0]
+            y, ks = [rec[0]], [[rec[1 + q]] for q in range(4)]
+            t = t0 + i * h
+            stages = []
+            for q in range(3, -1, -1):
+                cot = [(h * RK38_B[q], a)] + [(h * RK38_A[r][q], yb[r]) for r in range(q + 1, 4) if RK38_A[r][q] != 0.0]
+                stages.append(self._stage_bwd(len(stages), cot, ks[q][0], _stage_terms(y, ks, RK38_A[q], h)[0],
+                                              t + RK38_C[q] * h, yb[q]))
+            self._close_step(stages, theta)
+            ops.lincomb_(a, [(1.0, a)] + [(1.0, b) for b in yb])
+        return a
+
+    def _dopri5_backprop_work(self, like):
+        """Work arrays of dopri5_step_backprop: 7 Ybar and two (ybar_n, kbar_1) pairs that take turns from step to step."""
+        return {"ybar": [torch.empty_like(like) for _ in range(7)],
+                "pairs": [(torch.empty_like(like), torch.empty_like(like)) for _ in range(2)]}
+
+    def _dopri5_step_backprop(self, y, k, g, kbar7, wy, wk, t, h, first, work, turn, theta):
+        """Reverse sweep over one accepted step, the algebra of gode_gcn_ode_dopri5_step_backprop (csrc/ode_driver.hip):
+        kbar_s = wk[s] g + h sum_{r > s} a_rs Ybar_r (+ kbar7 on the last stage), Ybar_s through the stage for s = 7..2 (and 1
+        when `first`), ybar_n = wy g + sum Ybar_s; a stage whose cotangent has no term is skipped.  Returns (ybar_n, kbar_1)
+        in work["pairs"][turn]; kbar_1 is None when `first`."""
+        ybar = work["ybar"]
+        ybar_n, kbar1 = work["pairs"][turn]
+        swept = [False] * 7
+
+        def cotangent(q):
+            c = [(wk[q], g)] if wk[q] != 0.0 else []
+            c += [(h * DP_A[r][q], ybar[r]) for r in range(q + 1, 7) if DP_A[r][q] != 0.0 and swept[r]]
+            return c + [(1.0, kbar7)] if (q == 6 and kbar7 is not None) else c
+        stages = []
+        for q in range(6, -1 if first else 0, -1):
+            cot = cotangent(q)
+            if not cot:
+                continue
+            yin = _stage_terms([y], [[x] for x in k], DP_A[q], h)[0]
+            stages.append(self._stage_bwd(len(stages), cot, k[q], yin, t + DP_C[q] * h, ybar[q]))
+            swept[q] = True
+        pre = [(wy, g)] + [(1.0, ybar[q]) for q in range(7) if swept[q]]
+        c0 = None if first else cotangent(0)
+        if c0:
+            ops.lincomb_multi_([ybar_n, kbar1], [pre, c0])
+        else:
+            ops.lincomb_(ybar_n, pre)
+            if not first:
+                kbar1.zero_()
+        if stages:
+            self._close_step(stages, theta)
+        return ybar_n, (None if first else kbar1)
+
+    def _forward(self, t, y_terms, out, pre=None, alpha=1.0, k_out=None):
         s, w, es = self.s, self.w, self.s.es
         S = w.S4[self.slot]
         x_out = w.X if (len(y_terms) > 1 and self.n_components > 1) else None
@@ -182,7 +327,7 @@ class EdgeOdeField(Field):
                                                     _lib.stream_ptr()), "gode_edge_matvec_msg_f32")
             ops.spmm(es.Mt, w.msg, bias=s.b, relu=True, out=out, pre_terms=pre, alpha=alpha)
         else:
-            ops.edge_ode_feval(es.Mt, es.src, s.A, S, s.b, out, pre_terms=pre, alpha=alpha)
+            ops.edge_ode_feval(es.Mt, es.src, s.A, S, s.b, out, pre_terms=pre, alpha=alpha, k_out=k_out)
         return [(1.0, w.X)] if x_out is not None else y_terms
 
     def eval(self, t, terms, out):

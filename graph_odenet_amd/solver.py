@@ -107,7 +107,9 @@ class Field:
     # ---- backprop through the solve (odeint._OdeintBackprop); a field offering a sweep offers the packed pair too ----------
     rk4_forward_save = None       # rk4_forward_save(y0, y_end, save, t0, t1, n, i0, i1): steps i0..i1-1, stages recorded
     rk4_backprop = None           # rk4_backprop(save, a, theta, t0, t1, n, i0, i1) -> tensor holding dL/dy before step i0
-    dopri5_step_backprop = None   # dopri5_step_backprop(y, k, g, kbar7, wy, wk, t, h, first, work, turn, theta)
+    dopri5_step_backprop = None   # dopri5_step_backprop(y, k, g, kbar7, wy, wk, t, h, first, work, turn, theta); a field
+    #                               offering it without dopri5_step_native gets all seven k_s of every step, whatever the
+    #                               byte bound (there is nothing to re-run a step with)
     dopri5_backprop_work = None   # dopri5_backprop_work(like) -> the work arrays dopri5_step_backprop takes
     packed_grads = None           # packed_grads(device) -> zeroed buffer `theta` the sweeps add parameter gradients to
     packed_param_grads = None     # packed_param_grads(theta) -> the gradients in func.parameters() order

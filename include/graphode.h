@@ -812,6 +812,39 @@ int gode_edge_outer_sum_acc_f32(const int32_t* edge_row, const float* edge_val, 
                                 const float* w /* host[n_terms] */, int64_t h, int64_t n_edges, int accumulate, float* dA,
                                 void* stream);
 
+/* ---- backprop through a solve over the edge-conditioned ODE function, launch-bound batches ----------
+ * (stage_bwd and step_close: csrc/edge_backprop.hip; feval_save: csrc/edge_ode.hip, a flag on the feval kernel)
+ * feval_save: gode_edge_ode_feval_f32 (the same launch, the same bits in out) that also stores f = relu(z) to k (n_rows x h):
+ *   the last stage of a fixed-grid step is folded into the solution combine and never exists otherwise.  k must not be out
+ *   or a term of pre (GODE_E_SHAPE).
+ * stage_bwd: the reverse of ONE stage k = f(t, Y) in one launch, a block per atom u; cot / yin: the stage cotangent and the
+ *   stage input Y as combinations of up to 8 terms (host); ms_rowptr / ms_eid: CSR of the source incidence as for the vjp.
+ *     dM[u]   = cot_scale * (sum cot)[u] * [k[u] > 0],   dS[u] = sum_{e: src_e = u} A_e^T (val_e dM[tgt_e])
+ *     ybar[u] = GN'(Y[u])^T (W[1:] dS[u])                (ATen's GroupNorm backward)
+ *     dgamma_rows[u], dbeta_rows[u]: the row's shares of the affine gradients (n_rows x h each; their column sums are the
+ *       gradients),   S[u] = [t | GN(Y[u])] W  when S is given (the edge-matrix outer sum reads it).
+ *   The weight gradient is gode_wgrad_f32 on (yin, dS).  No output may be k or a term of cot / yin (GODE_E_SHAPE).
+ *   Shapes: gode_edge_ode_stage_bwd_supported - h <= 112 and 1, 2 or 3 channels per group - else GODE_E_UNSUPPORTED.
+ * step_close: one launch per RK step over n_stages <= 8 reversed stages; theta = [W (h+1)h | b | gamma | beta] gains
+ *     W     += sum_s scale_s * sum_p wpart_s[p]   (n_wparts partial rows of (h+1) h each; scale_s = ts[s] on row 0, else 1)
+ *     b     += sum_s colsum(dM_s),   gamma += sum_s colsum(dgamma_rows_s),   beta += sum_s colsum(dbeta_rows_s).
+ * Every sum in a fixed order; no float atomics. */
+int gode_edge_ode_feval_save_f32(const int32_t* rowptr, const int32_t* eid, const float* val, const int32_t* src,
+                                 const float* A, const float* S, int64_t h, int64_t n_rows, const float* bias,
+                                 const gode_lincomb_t* pre /* host, nullable */, float alpha, float* out, float* k,
+                                 void* stream);
+int gode_edge_ode_stage_bwd_supported(int64_t n_rows, int64_t h, int32_t groups);
+int gode_edge_ode_stage_bwd_f32(const int32_t* ms_rowptr, const int32_t* ms_eid, const int32_t* edge_row,
+                                const float* edge_val, const float* A, const gode_lincomb_t* cot /* host */, float cot_scale,
+                                const float* k, const gode_lincomb_t* yin /* host */, float t, const float* gamma,
+                                const float* beta, const float* W, int32_t groups, float eps, int64_t h, int64_t n_rows,
+                                int64_t n_edges, float* dM, float* dS, float* ybar, float* dgamma_rows, float* dbeta_rows,
+                                float* S /* nullable */, void* stream);
+int gode_edge_ode_step_close_f32(int32_t n_stages, const float* const* wpart /* host[n_stages] */,
+                                 const float* const* dM /* host[n_stages] */, const float* const* dgamma_rows /* host[n_stages] */,
+                                 const float* const* dbeta_rows /* host[n_stages] */, const float* ts /* host[n_stages] */,
+                                 int64_t n_wparts, int64_t n_rows, int64_t h, float* theta, void* stream);
+
 /* ---- measurement aid (bench.py): HIP-event brackets around the dominant kernels ----------
  * While a profiler is enabled (process-wide; one measuring client at a time), every gode_spmm_csr_f32 main-kernel launch
  * and every MFMA-path launch of the dense kernels (gn_gemm_fwd / gn_gemm_bwd / wgrad) records a start/stop event pair
@@ -831,6 +864,9 @@ int gode_edge_outer_sum_acc_f32(const int32_t* edge_row, const float* edge_val, 
 #define GODE_PROF_EDGE_VJP   6
 #define GODE_PROF_EDGE_OUTER_STEP  7   /* gode_edge_outer_sum_acc_f32 accumulating: one pass per RK step */
 #define GODE_PROF_EDGE_OUTER_STAGE 8   /* the same kernel overwriting: one stage's own dA */
+/* csrc/edge_backprop.hip (d = h; rows = atoms; extra = cotangent + stage-input terms / stages closed) */
+#define GODE_PROF_EDGE_STAGE_BWD  9    /* gode_edge_ode_stage_bwd_f32: the reverse of one stage */
+#define GODE_PROF_EDGE_STEP_CLOSE 10   /* gode_edge_ode_step_close_f32: one pass per RK step */
 /* which kernel of the family ran, OR-ed into the kind of a dense launch (kind & 0xff = family, kind >> 8 = form):
  * exact-fp32 MFMA kernel; bf16-piece kernel, every wave loading + cutting + multiplying; bf16-piece kernel in
  * producer / consumer form (wgrad_split_kernel, gemm_pc.hip) */
