@@ -15,8 +15,13 @@
 // Bound: HBM.  Algorithmic bytes per launch: nnz*(4+4+4d) + (N+1)*4 + N*d*4.
 #include "common.h"
 #include "prof.h"
+#include "options.h"
+#include <algorithm>
 
 namespace {
+
+constexpr int SPMM_PIPE_TILES = 4;            // tiles a block of spmm_vec4_pipe_kernel walks (option spmm_pipe = 1)
+constexpr int SPMM_PIPE_MIN_BLOCKS = 4096;    // ... while the launch keeps at least this many blocks
 
 struct Epilogue {
     const float* bias;
@@ -35,7 +40,8 @@ struct Epilogue {
 
 // OUT3: the launch has a third output (ep.Y3) - a variant of its own, so that the kernels every other product runs keep
 // their registers
-template <int LPR, bool OUT3 = false>
+// COT = false: for a launch without a cotangent output (ep.Y2 is null there)
+template <int LPR, bool OUT3 = false, bool COT = true>
 __device__ __forceinline__ float4 epilogue_store4(const Epilogue& ep, float4 z, int row, int lane,
                                                   int64_t d, float* Y, int64_t ldy) {
     if (ep.bias) {
@@ -53,7 +59,7 @@ __device__ __forceinline__ float4 epilogue_store4(const Epilogue& ep, float4 z, 
         y.x *= ep.alpha; y.y *= ep.alpha; y.z *= ep.alpha; y.w *= ep.alpha;
     }
     *reinterpret_cast<float4*>(Y + (int64_t)row * ldy + lane * 4) = y;
-    if (ep.Y2) {
+    if (COT && ep.Y2) {
         const int64_t o = (int64_t)row * d + lane * 4;
         float4 g;
         if (OUT3) {              // a second combination of the cotangent terms, row by row beside Y2
@@ -151,6 +157,134 @@ __global__ __launch_bounds__(256) void spmm_vec4_kernel(
     if (!active) return;
     if (slot < 0) epilogue_store4<LPR, OUT3>(ep, acc, row, lane, (int64_t)LPR * 4, Y, ldy);
     else *reinterpret_cast<float4*>(partial + (int64_t)slot * (LPR * 4) + lane * 4) = acc;
+}
+
+// ---- the same product, several tiles per block with the records' indices fetched ahead (option spmm_pipe) -----------
+// A tile is what a block of spmm_vec4_kernel owns: the 256 / LPR records [t * 256 / LPR, (t + 1) * 256 / LPR).  A lane
+// group walks one record of each of its block's tiles with the loop above (same multiply-add chain, same epilogue, same
+// slab write: every output bit is that kernel's), but only the block's first record costs the three dependent round
+// trips of a record there (items, col / val, gathers): the block reads the items entries of ALL its tiles at once into
+// LDS, and while record i gathers, the first col / val chunk of record i + 1 is in flight, requested BEFORE the gathers
+// of record i - loads return in order, so the wait for the gathers covers it.  Every such request is an unconditional
+// load from a clamped address with the result selected afterwards (a load under a branch is waited for where the
+// branch joins).  For launches without a cotangent output (ep.Y2): with one, the rows the epilogue streams bound the
+// short records already (profiles/spmm_phase_probe.txt) and the per-tile column sums would tie the block's waves
+// together at every tile.
+constexpr int SPMM_PIPE_RECS = 1024;          // records of a block's tiles held in LDS (16 KB)
+constexpr int spmm_pipe_max_tiles(int lpr) { return std::min(64, SPMM_PIPE_RECS / (256 / lpr)); }
+
+// Fields of record gid (REC: from the record list; else row = record, bounds from rowptr).  gid may lie past the list.
+template <bool REC>
+__device__ __forceinline__ int4 pipe_load_rec(const int4* __restrict__ items, const int* __restrict__ rowptr, int gid, int n_items) {
+    const int g = min(gid, n_items - 1);
+    if (REC) return items[g];
+    return make_int4(g, rowptr[g], rowptr[g + 1], -1);
+}
+
+// One chunk of a record: entries [b, b + len) of col / val, lane j takes entry j (len may be <= 0 or > LPR).  Lanes
+// past the end re-read the last entry, an empty chunk reads `safe` (any two readable dwords); both come out as 0.
+__device__ __forceinline__ void pipe_load_chunk(const int* __restrict__ col, const float* __restrict__ val,
+                                                const int* __restrict__ safe, int b, int len, int lane, int& c, float& v) {
+    const int64_t i = (int64_t)b + min(lane, len - 1);
+    const int* cp = len > 0 ? col + i : safe;
+    const float* vp = (len > 0 && val) ? val + i : reinterpret_cast<const float*>(safe);
+    const int cl = *cp;
+    const float vl = *vp;
+    c = lane < len ? cl : 0;
+    v = lane < len ? (val ? vl : 1.f) : 0.f;
+}
+
+// Registers: left alone hipcc takes 66-72 VGPRs (7 waves per SIMD); held to 64 (the 8 waves per SIMD spmm_vec4_kernel runs
+// with) it needs no scratch except at LPR = 4 and 64, which keep 66.
+template <int LPR, bool REC>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((LPR == 4 || LPR == 64) ? 7 : 8, 8)))
+void spmm_vec4_pipe_kernel(
+    const int* __restrict__ rowptr, const int* __restrict__ col, const float* __restrict__ val,
+    const int4* __restrict__ items, int n_items, float* __restrict__ partial,
+    const float* __restrict__ X, int64_t ldx, float* __restrict__ Y, int64_t ldy, Epilogue ep,
+    int tiles)
+{
+    constexpr int U = 4;
+    constexpr int GPT = 256 / LPR;                             // records per tile
+    constexpr int NQ = (spmm_pipe_max_tiles(LPR) * GPT + 255) / 256;
+    // a record here: {dst = its row (slot < 0) or ~slot (a split row's slab), b, len, 1 / 0 for a record past the list}
+    __shared__ int4 recs[SPMM_PIPE_RECS];
+    const int lane = threadIdx.x & (LPR - 1);
+    const int grp = threadIdx.x / LPR;
+    const float* Xl = X + lane * 4;
+    // block b walks tiles b, b + B, b + 2 B, ... (B = gridDim.x): one tile of each stratum of the length-sorted list, so
+    // no block carries a noticeable share of the long records (consecutive tiles: the long part of the launch 0.46 ->
+    // 0.89 ms, profiles/spmm_phase_probe.txt)
+    const int t0 = (int)blockIdx.x, step = (int)gridDim.x;
+    const int n_here = (tiles - t0 + step - 1) / step;      // >= 1: gridDim.x <= tiles
+    {
+        const int cnt = n_here * GPT;                          // <= SPMM_PIPE_RECS (launch_vec4)
+        int4 r[NQ]; int gid[NQ];
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+            const int i = min((int)threadIdx.x + 256 * q, cnt - 1);
+            gid[q] = (t0 + (i / GPT) * step) * GPT + (i % GPT);
+            r[q] = pipe_load_rec<REC>(items, rowptr, gid[q], n_items);
+        }
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+            const bool in = gid[q] < n_items;
+            if ((int)threadIdx.x + 256 * q < cnt)
+                recs[threadIdx.x + 256 * q] = make_int4(r[q].w < 0 ? r[q].x : ~r[q].w, r[q].y, in ? r[q].z - r[q].y : 0, in ? 1 : 0);
+        }
+    }
+    __syncthreads();
+
+    int c; float v;
+    pipe_load_chunk(col, val, rowptr, recs[grp].y, recs[grp].z, lane, c, v);
+    for (int j = 0; j < n_here; ++j) {
+        // requested before this record's gathers: the next record's first chunk
+        const int4 nx = recs[min(j + 1, n_here - 1) * GPT + grp];
+        int nc; float nv;
+        pipe_load_chunk(col, val, rowptr, nx.y, j + 1 < n_here ? nx.z : 0, lane, nc, nv);
+
+        const int4 cur = recs[j * GPT + grp];
+        const int dst = cur.x, b = cur.y, len = cur.z;
+        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int base = 0; __any(base < len); base += LPR) {
+            if (base > 0) {                                    // (wave-uniform) the later chunks of a long record, as above
+                c = 0; v = 0.f;
+                if (base + lane < len) {
+                    c = col[b + base + lane];
+                    v = val ? val[b + base + lane] : 1.f;
+                }
+            }
+            const int cnt = len - base;   // may be <= 0 or > LPR
+            for (int k = 0; k < LPR; k += U) {
+                if (!__any(k < cnt)) break;
+                int cc[U]; float vv[U]; float4 xv[U];
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    cc[u] = __shfl(c, k + u, LPR);
+                    vv[u] = __shfl(v, k + u, LPR);
+                }
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    xv[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+                    if (k + u < cnt && k + u < LPR)
+                        xv[u] = *reinterpret_cast<const float4*>(Xl + (int64_t)cc[u] * ldx);
+                }
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    acc.x = fmaf(vv[u], xv[u].x, acc.x); acc.y = fmaf(vv[u], xv[u].y, acc.y);
+                    acc.z = fmaf(vv[u], xv[u].z, acc.z); acc.w = fmaf(vv[u], xv[u].w, acc.w);
+                }
+            }
+        }
+        // the next chunk is taken up HERE: it was requested before the gathers, so it has arrived, and no wait for it
+        // may land behind this record's stores (a store is acknowledged a round trip later)
+        asm volatile("" : "+v"(nc), "+v"(nv));
+        if (cur.w) {
+            if (dst >= 0) epilogue_store4<LPR, false, false>(ep, acc, dst, lane, (int64_t)LPR * 4, Y, ldy);
+            else *reinterpret_cast<float4*>(partial + (int64_t)(~dst) * (LPR * 4) + lane * 4) = acc;
+        }
+        c = nc; v = nv;
+    }
 }
 
 // Small-graph variant: a whole wave per record.  The wave's 64/LPR sub-groups of LPR lanes each take every
@@ -364,6 +498,20 @@ int launch_vec4(const int* rowptr, const int* col, const float* val, const int4*
     const int64_t blocks = (threads + 255) / 256;
     if (blocks > 0) {
         const int slot = gode_prof_begin(s, (int64_t)LPR * 4, n_items, (int64_t)ep.pre.n + ep.cot.n + (ep.Y2 ? 1 : 0) + (ep.Y3 ? 1 : 0));
+        const int pipe = gode_opt_spmm_pipe();
+        if (pipe != 0 && !ep.Y2) {
+            // tiles per block: 1 = SPMM_PIPE_TILES, but never fewer than SPMM_PIPE_MIN_BLOCKS blocks (two rounds of
+            // 256 CUs x 8 resident blocks) while there are that many tiles; >= 2 sets it as given (measurements, tests)
+            int64_t per = pipe == 1 ? std::max<int64_t>(1, std::min<int64_t>(SPMM_PIPE_TILES, blocks / SPMM_PIPE_MIN_BLOCKS)) : pipe;
+            per = std::min<int64_t>(per, spmm_pipe_max_tiles(LPR));
+            const int64_t grid = (blocks + per - 1) / per;
+            if (items)
+                hipLaunchKernelGGL((spmm_vec4_pipe_kernel<LPR, true>), dim3((unsigned)grid), dim3(256), 0, s,
+                                   rowptr, col, val, items, n_items, partial, X, ldx, Y, ldy, ep, (int)blocks);
+            else
+                hipLaunchKernelGGL((spmm_vec4_pipe_kernel<LPR, false>), dim3((unsigned)grid), dim3(256), 0, s,
+                                   rowptr, col, val, items, n_items, partial, X, ldx, Y, ldy, ep, (int)blocks);
+        } else
         hipLaunchKernelGGL((spmm_vec4_kernel<LPR, OUT3>), dim3((unsigned)blocks), dim3(256), 0, s,
                            rowptr, col, val, items, n_items, partial, X, ldx, Y, ldy, ep);
         gode_prof_end(s, slot);

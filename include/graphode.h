@@ -71,8 +71,10 @@ int         gode_abi_version(void);
  * default: the forward product likewise - bit 0: launches of <= 2 terms, bit 1: launches of >= 3 terms or with x_out;
  * 0: the round-2 selection by "gemm_split"), "rk_close_once" (1 default / 0: above 65 536 rows at d = 128 the rk4
  * drivers form the closing combination of a step once, in the launch that already holds its terms, instead of loading
- * the four arrays again in the closing launch; same bits either way).  Initial values come from GODE_GEMM_SPLIT / GODE_OVERLAP /
- * GODE_WGRAD_SPLIT / GODE_BWD_PC / GODE_FWD_PC.
+ * the four arrays again in the closing launch; same bits either way), "spmm_pipe" (1 default / 0 / 2..64: sparse
+ * products of more than 65 536 records without a cotangent output walk several tiles of 256 / (d / 4) records per block,
+ * the records' indices fetched ahead; 0: one tile per block; 2..64: that many tiles per block; same bits in every case).
+ * Initial values come from GODE_GEMM_SPLIT / GODE_OVERLAP / GODE_WGRAD_SPLIT / GODE_BWD_PC / GODE_FWD_PC / GODE_SPMM_PIPE.
  * Returns 0 or GODE_E_UNSUPPORTED. */
 int         gode_set_option(const char* name, int value);
 int         gode_get_option(const char* name);
