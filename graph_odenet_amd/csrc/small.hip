@@ -18,7 +18,12 @@
 //             sum_i [1|xn_i]^T dS_i, bias gradient sum_i dZ_i, dgamma / dbeta: per-wave register accumulators, one
 //             block partial row per block - ONE launch; a third (gode_reduce_segments_f32) closes the stage.
 // Same mathematics as the multi-launch path; the forward sums in another order ((A xn) W vs A (xn W): differences of a
-// few ulp, inside the 1e-5 parity bar - tests/test_gpu_gcn.py runs both against the oracle).
+// few ulp, inside the 1e-5 parity bar).  Tests: tests/test_gpu_gcn_small.py holds every launch of this file against an
+// fp64 reference at 1, 2 and 4 channels per GroupNorm group, both lane groupings and the row counts at which the grids
+// loop, the extra-output forms bit for bit against the plain ones, and short solves with four channels per group against
+// the oracle and the multi-launch path; tests/test_gpu_gcn.py runs the solves with ONE channel per group (GroupNorm then
+// returns beta whatever the state: its bars are that width's noise floor) against the oracle on Cora and against the
+// multi-launch path.
 //
 // Work decomposition: a wave owns a row at a time; a lane holds 4 consecutive columns (float4), so d/4 lanes span a row
 // and the wave's 256/d sub-groups share the row's non-zeros (whose indices are fetched 64 at a time, so that the gathers of a

@@ -260,6 +260,73 @@ def _feval_small(spec, t, terms, out, pre=None, alpha=1.0, cot=None, out2=None, 
                "gode_gcn_feval_small_next_f32")
 
 
+def _byref(lc):
+    return ctypes.byref(lc) if lc is not None else None
+
+
+def _feval_small_save(spec, t, terms, out, k, pre=None, alpha=1.0):
+    """The same evaluation, which also stores relu(z) into k (the launch that closes a step of a backprop solve)."""
+    lib = _lib.load()
+    fs = _func_struct(spec)
+    lx = _lib.lincomb(terms)
+    lp = _lib.lincomb(pre) if pre is not None else None
+    _lib.check(lib.gode_gcn_feval_small_save_f32(ctypes.byref(fs), ctypes.byref(lx), float(t), float(alpha), _byref(lp),
+                                                 _lib.ptr(out), _lib.ptr(k), _lib.stream_ptr()),
+               "gode_gcn_feval_small_save_f32")
+
+
+def _vjp_small(spec, terms, dZ, ka, part, pre=None, out_scale=1.0, fs=None):
+    """ka = (sum pre) + out_scale * dx and the block partial rows (gode_gcn_small_parts x gode_gcn_small_part_len) of one
+    stage, from the masked cotangent dZ."""
+    lib = _lib.load()
+    fs = _func_struct(spec) if fs is None else fs
+    lx = _lib.lincomb(terms)
+    lp = _lib.lincomb(pre) if pre is not None else None
+    _lib.check(lib.gode_gcn_vjp_small_f32(ctypes.byref(fs), ctypes.byref(lx), _lib.ptr(dZ), float(out_scale), _byref(lp),
+                                          _lib.ptr(ka), _lib.ptr(part), _lib.stream_ptr()), "gode_gcn_vjp_small_f32")
+
+
+def _vjp_small_next(spec, terms, dZ, ka, part, cot_next, k_next, dZ_next, pre=None, out_scale=1.0):
+    """The same launch, which also writes dZ_next = (sum cot_next) * [k_next > 0] (a term of cot_next that is `ka` itself
+    is this launch's result) - what the reverse sweep of a backprop solve does between its stages."""
+    lib = _lib.load()
+    fs = _func_struct(spec)
+    lx = _lib.lincomb(terms)
+    lp = _lib.lincomb(pre) if pre is not None else None
+    ln = _lib.lincomb(cot_next)
+    _lib.check(lib.gode_gcn_vjp_small_next_f32(ctypes.byref(fs), ctypes.byref(lx), _lib.ptr(dZ), float(out_scale), _byref(lp),
+                                               _lib.ptr(ka), _lib.ptr(part), ctypes.byref(ln), _lib.ptr(k_next),
+                                               _lib.ptr(dZ_next), _lib.stream_ptr()), "gode_gcn_vjp_small_next_f32")
+
+
+def _finish_small(spec, part, ktheta, t, fs=None):
+    """ktheta = [W (row 0 scaled by t) | b | gamma | beta | a_t] of one stage from its block partial rows."""
+    lib = _lib.load()
+    fs = _func_struct(spec) if fs is None else fs
+    _lib.check(lib.gode_gcn_small_finish_f32(ctypes.byref(fs), _lib.ptr(part), _lib.ptr(ktheta), float(t),
+                                             _lib.stream_ptr()), "gode_gcn_small_finish_f32")
+
+
+def _finish_small_multi(spec, part, kthetas, ts):
+    """len(kthetas) <= 8 stages at once; `part` holds their partial buffers back to back."""
+    lib = _lib.load()
+    fs = _func_struct(spec)
+    n = len(kthetas)
+    _lib.check(lib.gode_gcn_small_finish_multi_f32(ctypes.byref(fs), _lib.ptr(part), n,
+                                                   (ctypes.c_void_p * n)(*[k.data_ptr() for k in kthetas]),
+                                                   (ctypes.c_float * n)(*[float(t) for t in ts]), _lib.stream_ptr()),
+               "gode_gcn_small_finish_multi_f32")
+
+
+def _finish_small4(spec, part, theta, wb, ts):
+    """theta += sum_s wb[s] * (stage s of _finish_small at ts[s]) over the four partial buffers held back to back in `part`."""
+    lib = _lib.load()
+    fs = _func_struct(spec)
+    wbh, tsh = (ctypes.c_float * 4)(*[float(v) for v in wb]), (ctypes.c_float * 4)(*[float(v) for v in ts])
+    _lib.check(lib.gode_gcn_small_finish4_f32(ctypes.byref(fs), _lib.ptr(part), _lib.ptr(theta), wbh, tsh, _lib.stream_ptr()),
+               "gode_gcn_small_finish4_f32")
+
+
 class _PackedParams:
     """The one statement of the packed parameter buffer the C drivers read and add to: [W | b | gamma | beta | a_t]
     (gode_gcn_ode_theta_len floats).  Needs self.s (the spec) and self.params_order (list of 'gamma', 'beta', 'W', 'b' in
@@ -530,19 +597,13 @@ class GcnOdeAdjointField(_PackedParams, Field):
         if packed is not None and small_fused(s):
             # launch-bound graphs: f-eval (+ masked cotangent), VJP (+ block partials), their reduction - three launches,
             # the same ones the C drivers issue (csrc/small.hip)
-            lib = _lib.load()
             last = pre is not None
             _feval_small(s, t, y_terms, out[0], pre=pre[0] if last else None, alpha=coef if last else 1.0,
                          cot=[(-c, x) for (c, x) in terms[1]], out2=dZ)
             fs = _func_struct(s)
-            lx = _lib.lincomb(y_terms)
-            lp = _lib.lincomb(pre[1]) if last else None
             part = w.small_part(s.groups)
-            _lib.check(lib.gode_gcn_vjp_small_f32(ctypes.byref(fs), ctypes.byref(lx), _lib.ptr(dZ), float(coef if last else 1.0),
-                                                  ctypes.byref(lp) if lp is not None else None, _lib.ptr(out[1]), _lib.ptr(part),
-                                                  _lib.stream_ptr()), "gode_gcn_vjp_small_f32")
-            _lib.check(lib.gode_gcn_small_finish_f32(ctypes.byref(fs), _lib.ptr(part), _lib.ptr(packed), float(t),
-                                                     _lib.stream_ptr()), "gode_gcn_small_finish_f32")
+            _vjp_small(s, y_terms, dZ, out[1], part, pre=pre[1] if last else None, out_scale=coef if last else 1.0, fs=fs)
+            _finish_small(s, part, packed, t, fs=fs)
             return
         ops.gn_time_gemm(y_terms, n, d, s.groups, s.eps, s.gamma, s.beta, s.W, True, t, out=w.S)
         # k_y = relu(A S + b);  dZ = (-a) * mask

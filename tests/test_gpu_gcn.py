@@ -1050,7 +1050,10 @@ def test_fused_small_graph_path_matches_multi_launch_path(d, method, n):
     gather is row-local) against the multi-launch path of the large graphs (option small_fused 0) through the same ODE
     block, C drivers and Python drivers: states to 1e-5, gradients to the noise floor of the width (one channel per
     GroupNorm group at d = 16 / 32), on a graph with a 300-neighbour hub, isolated rows and duplicate-free random edges;
-    the fused path also against the fp64 oracle on Cora in test_odegcn3_rk4_forward_backward_vs_oracle_on_cora."""
+    the fused path also against the fp64 oracle on Cora in test_odegcn3_rk4_forward_backward_vs_oracle_on_cora.
+    The gradient bars here are the noise floor of ONE channel per group (GroupNorm returns beta whatever the state, rstd =
+    316); the comparison on a state-dependent field (four channels per group, 1e-5 / 2e-5) is
+    test_gpu_gcn_small.py::test_short_solve_on_state_dependent_field."""
     from graph_odenet_amd import _lib, models, odeint as OI
     lib = _lib.load()
     torch.manual_seed(d)
