@@ -887,7 +887,7 @@ def dense_first_nonzero(M):
     return out
 
 
-EDGE_OUTER_MAX_TERMS = 8        # GODE_MAX_TERMS: message steps whose edge-matrix gradient one launch sums
+EDGE_OUTER_MAX_TERMS = _lib.GODE_MAX_TERMS        # message steps whose edge-matrix gradient one launch sums
 
 
 def edge_outer_sum_supported(h):
@@ -921,8 +921,8 @@ def edge_outer_sum(edge_row, edge_val, src, pairs, like):
 # sources; from it on, a workgroup per edge (gode_edge_matvec_msg_f32 + SpMM forward, per-edge dxe + SpMM backward)
 EDGE_ODE_FUSED_MAX_EDGES = 4096
 # kinds of the launches above in a gode_prof_* profile (include/graphode.h)
-PROF_EDGE_FEVAL, PROF_EDGE_VJP, PROF_EDGE_OUTER_STEP, PROF_EDGE_OUTER_STAGE = 5, 6, 7, 8
-PROF_EDGE_STAGE_BWD, PROF_EDGE_STEP_CLOSE = 9, 10           # csrc/edge_backprop.hip
+PROF_EDGE_FEVAL, PROF_EDGE_VJP, PROF_EDGE_OUTER_STEP, PROF_EDGE_OUTER_STAGE, PROF_EDGE_STAGE_BWD, PROF_EDGE_STEP_CLOSE = (
+    _lib.CONSTANTS["GODE_PROF_EDGE_" + k] for k in ("FEVAL", "VJP", "OUTER_STEP", "OUTER_STAGE", "STAGE_BWD", "STEP_CLOSE"))
 
 
 def edge_ode_supported(h):

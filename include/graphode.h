@@ -13,6 +13,7 @@
  *     (a hipStream_t passed as void*);
  *   - return value: 0 = success, >0 = hipError_t of a failed launch,
  *     <0 = argument-validation code (GODE_E_*); no C++ exception crosses.
+ *   - the Python binding is read from this text at import (graph_odenet_amd/_abi.py raises on a declaration it cannot follow).
  *
  * Reference call sites replaced (paths relative to the reference checkout):
  *   gode_spmm_csr_f32            GCN/layers.py:33,71   torch.spmm(adj, support) (+bias :35,73; relu GCN/models.py:178)

@@ -69,3 +69,137 @@ def test_header_is_plain_c99():
     assert res.returncode == 0, res.stderr
     code = re.sub(r"/\*.*?\*/", "", open(hdr).read(), flags=re.S)        # comments may cite torch call sites
     assert "torch" not in code.lower() and "at::" not in code and "std::" not in code
+
+
+# ---- the binding is derived from the header (graph_odenet_amd/_abi.py) ------------------------------------------
+
+HEADER = os.path.join(ROOT, "include", "graphode.h")
+
+
+def test_struct_layout_matches_the_c_compiler(tmp_path):
+    """sizeof of every struct and offsetof / size of every member, as the host C compiler lays the header out, against the
+    ctypes classes read from the same header (padding, arrays, structs by value)."""
+    import keyword
+    import shutil
+    import subprocess
+    cc = shutil.which("gcc") or shutil.which("cc")
+    if cc is None:
+        import pytest
+        pytest.skip("no C compiler in this environment")
+    assert len(_lib.STRUCTS) == 10
+    lines, expect = [], []
+    for tag, cls in _lib.STRUCTS.items():
+        lines.append('printf("%s %%zu\\n", sizeof(%s));' % (tag, tag))
+        expect.append("%s %d" % (tag, ctypes.sizeof(cls)))
+        for name, _ in cls._fields_:
+            cname = name[:-1] if name.endswith("_") and keyword.iskeyword(name[:-1]) else name
+            lines.append('printf("%s.%s %%zu %%zu\\n", offsetof(%s, %s), sizeof(((%s*)0)->%s));' % (tag, cname, tag, cname, tag, cname))
+            expect.append("%s.%s %d %d" % (tag, cname, getattr(cls, name).offset, getattr(cls, name).size))
+    src = tmp_path / "layout.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "graphode.h"\nint main(void) {\n%s\nreturn 0; }\n' % "\n".join(lines))
+    exe = str(tmp_path / "layout")
+    res = subprocess.run([cc, "-std=c99", "-I", os.path.dirname(HEADER), "-o", exe, str(src)], capture_output=True, text=True)
+    assert res.returncode == 0, res.stderr
+    got = subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split("\n")
+    assert [g for g in got if g] == expect
+
+
+def test_public_struct_names_are_the_derived_classes():
+    for py, tag in (("LinComb", "gode_lincomb_t"), ("SpmmEpilogue", "gode_spmm_epilogue_t"), ("Graph", "gode_graph_t"),
+                    ("GcnOdeFunc", "gode_gcn_odefunc_t"), ("GatProj", "gode_gat_proj_t"), ("Rk4Workspace", "gode_rk4_workspace_t"),
+                    ("ReduceSeg", "gode_reduce_seg_t"), ("GatOdeFunc", "gode_gat_odefunc_t"),
+                    ("GatWorkspace", "gode_gat_workspace_t"), ("AdamArgs", "gode_adam_args_t")):
+        assert getattr(_lib, py) is _lib.STRUCTS[tag]
+    txt = open(HEADER).read()
+    for name in ("GODE_MAX_TERMS", "GODE_ADAM_MAX_TENSORS"):
+        assert getattr(_lib, name) == int(re.search(r"#define %s (\d+)" % name, txt).group(1))
+
+
+def scalar_kinds(name):
+    """(ctypes scalar type or None for a pointer) per parameter of prototype `name`, from the header text."""
+    from graph_odenet_amd._abi import SCALARS
+    txt = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    params = re.search(r"\b%s\s*\(([^)]*)\)" % name, txt).group(1)
+    params = [] if params.strip() == "void" else params.split(",")
+    return [None if "*" in p or "[" in p else SCALARS[p.replace("const", " ").split()[0]] for p in params]
+
+
+def test_scalar_kinds_of_mixed_prototypes():
+    for name, scalars in (("gode_gcn_ode_rk4_forward", [ctypes.c_float, ctypes.c_float, ctypes.c_int32]),
+                          ("gode_gcn_ode_dopri5_step_forward", [ctypes.c_double, ctypes.c_double, ctypes.c_float, ctypes.c_float]),
+                          ("gode_gcn_ode_dopri5_step_backprop", [ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int32])):
+        want = scalar_kinds(name)
+        assert [k for k in want if k is not None] == scalars        # the header says what the issue quotes
+        argtypes = _lib.SIGNATURES[name][1]
+        assert len(argtypes) == len(want)
+        for got, k in zip(argtypes, want):
+            if k is None:
+                assert got is ctypes.c_void_p or issubclass(got, ctypes._Pointer)
+            else:
+                assert got is k
+    for name, (_, argtypes) in _lib.SIGNATURES.items():             # and every prototype, by the same reading
+        want = scalar_kinds(name)
+        assert len(want) == len(argtypes), name
+        assert [a if k is not None else None for a, k in zip(argtypes, want)] == want, name
+
+
+def test_missing_header_is_an_error(monkeypatch, tmp_path):
+    import pytest
+    monkeypatch.setattr(_lib, "HEADER_PATH", str(tmp_path / "graphode.h"))
+    with pytest.raises(_lib.GraphodeLibraryError, match="graphode.h"):
+        _lib._read_header()
+
+
+SNIPPET = """
+#define GODE_N 3
+typedef struct gode_in { int64_t a, b; float* p; float* q; } gode_in_t;
+typedef struct gode_out {
+    int32_t n;              /* a comment; with a semicolon */
+    gode_in_t x, y;
+    float coef[GODE_N]; const float* ptr[GODE_N]; float* k[4];
+    const float* as; double class;
+    void* scratch;
+} gode_out_t;
+int gode_none(void);
+const char* gode_name(int code);
+void* gode_make(int n);
+void gode_drop(void* p);
+int64_t gode_f(const gode_out_t* o, gode_in_t v, float* const* k /* 7 */, float** r, const double wk[], const char* s,
+               const float* const* m, int32_t, double t);
+"""
+
+
+def test_reader_on_a_snippet():
+    from graph_odenet_amd import _abi
+    c_p = ctypes.c_void_p
+    consts, structs, sigs = _abi.parse(SNIPPET)
+    assert consts == {"GODE_N": 3}
+    inner, outer = structs["gode_in_t"], structs["gode_out_t"]
+    assert inner._fields_ == [("a", ctypes.c_int64), ("b", ctypes.c_int64), ("p", c_p), ("q", c_p)]
+    assert outer._fields_ == [("n", ctypes.c_int32), ("x", inner), ("y", inner), ("coef", ctypes.c_float * 3), ("ptr", c_p * 3),
+                              ("k", c_p * 4), ("as_", c_p), ("class_", ctypes.c_double), ("scratch", c_p)]
+    assert (outer.x.offset, outer.y.offset, outer.coef.offset, outer.ptr.offset) == (8, 40, 72, 88)
+    assert sigs == {"gode_none": (ctypes.c_int, []), "gode_name": (ctypes.c_char_p, [ctypes.c_int]),
+                    "gode_make": (c_p, [ctypes.c_int]), "gode_drop": (None, [c_p]),
+                    "gode_f": (ctypes.c_int64, [ctypes.POINTER(outer), inner, c_p, c_p, c_p, ctypes.c_char_p, c_p,
+                                                ctypes.c_int32, ctypes.c_double])}
+
+
+def test_reader_raises_on_what_it_cannot_read():
+    import pytest
+    from graph_odenet_amd import _abi
+    for bad, named in (("int gode_f(size_t n);", "size_t"),                                  # unknown type
+                       ("int gode_f(const thing_t* p);", "thing_t"),                         # unknown pointee
+                       ("int gode_f(int (*cb)(int), int n);", r"\(\*cb\)"),                  # function pointer
+                       ("int gode_f(unsigned int n);", "unsigned int n"),
+                       ("uint8_t gode_f(void);", "uint8_t"),
+                       ("typedef struct gode_s { int a : 3; } gode_s_t;", "a : 3"),          # bit-field
+                       ("typedef struct gode_s { float c[0x10]; } gode_s_t;", "0x10"),       # non-decimal bound
+                       ("typedef struct gode_s { float c[GODE_UNSET]; } gode_s_t;", "GODE_UNSET"),
+                       ("typedef struct gode_s { size_t n; } gode_s_t;", "size_t"),
+                       ("typedef struct gode_s { struct { int a; } in; } gode_s_t;", "gode_s"),
+                       ("typedef struct gode_s { *p; } gode_s_t;", r"\*p"),
+                       ("extern int gode_counter;", "gode_counter"),
+                       ("static inline int gode_f(void) { return 0; }", "gode_f")):
+        with pytest.raises(_abi.HeaderError, match=named):
+            _abi.parse(bad)
