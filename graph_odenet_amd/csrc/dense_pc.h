@@ -7,6 +7,11 @@
 int gode_pc_fwd_launch(const LinComb& lc, int64_t n_rows, float eps, const float* gamma, const float* beta,
                        const float* W, int has_time, float t, float* S, float* xout, const float* aux_coef, float* aux,
                        int cg, hipStream_t s);   // aux (nullable): second combination of the terms, 4 terms only
+// diagonal-only rows in the forward product (gemm_pc.hip, DIAG): diag[i] = a_ii of such a row, 0 elsewhere; skip[i] != 0:
+// the S row is not stored; K[i, :] = relu(a_ii S[i, :] + bias) for the rows with diag[i] != 0.  All four non-null.
+struct FwdDiag { const float* diag; const float* skip; const float* bias; float* K; };
+int gode_pc_fwd_diag_launch(const LinComb& lc, int64_t n_rows, float eps, const float* gamma, const float* beta,
+                            const float* W, int has_time, float t, float* S, const FwdDiag& dg, int cg, hipStream_t s);   // 1-3 terms, cg 0 / 4
 int gode_pc_bwd_launch(const LinComb& lc, int64_t n_rows, float eps, const float* gamma, const float* W, int has_time,
                        const float* dS, float out_scale, const LinComb& pre, float* dx, float* dgamma_part,
                        float* dbeta_part, int64_t n_part, int cg, hipStream_t s);

@@ -123,14 +123,20 @@ struct TileWalk {
 //      slower: two terms 0.326 against 0.282 ms, one term equal; tools/dev/pc_ab.py, same process, interleaved.)
 // AUX (NX > 0 only): aux[row, :] = sum_j acoef.c[j] x_j[row, :], a second combination of the raw terms the producers hold
 //      (the closing combination of an rk4 step beside the last stage's product), same multiply-add chain as the first.
+// DIAG: for a row i whose only entry in the adjacency is its own diagonal (dg.diag[i] = a_ii, not 0) the launch also stores
+//      K[i, :] = relu(a_ii * S[i, :] + bias) - what the SpMM that follows would make of that row (its one-entry record:
+//      acc = fmaf(a_ii, S, 0), then epilogue_store4's + bias and max; the same chain on the same numbers, so the same
+//      bits), so that SpMM can run without those rows.  A row with dg.skip[i] != 0 is gathered by nobody (its column
+//      holds the diagonal alone as well): its S row is not stored.  A flag of its own: every other instantiation keeps
+//      its registers.
 // ---------------------------------------------------------------------------------------------------------------
-template <int CG, int NX, bool XOUT, int R, bool AUX = false>
+template <int CG, int NX, bool XOUT, int R, bool AUX = false, bool DIAG = false>
 __global__ __launch_bounds__(1024, 1) void gn_gemm_fwd_pc_kernel(LinComb xin, int n_rows, float eps,
                                                                 const float* __restrict__ gamma,
                                                                 const float* __restrict__ beta,
                                                                 const float* __restrict__ W, int has_time, float t,
                                                                 float* __restrict__ S, float* __restrict__ xout,
-                                                                AuxCoef acoef, float* __restrict__ aux)
+                                                                AuxCoef acoef, float* __restrict__ aux, FwdDiag dg)
 {
     static_assert(!AUX || NX > 0, "the second combination needs the raw terms");
     constexpr int PIECE_B = Img<R>::PIECE_B, BUF_B = Img<R>::BUF_B;
@@ -209,18 +215,41 @@ __global__ __launch_bounds__(1024, 1) void gn_gemm_fwd_pc_kernel(LinComb xin, in
     f32x4 t0 = {0.f, 0.f, 0.f, 0.f};
     if (has_time) { const float4 w0 = ld4(W + n0 + 4 * g); t0 = (f32x4){t * w0.x, t * w0.y, t * w0.z, t * w0.w}; }
     const int rd_off = r * LDK * 2 + g * 16;
+    float4 bv = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (DIAG) bv = ld4(dg.bias + n0 + 4 * g);
     lds_barrier();                                                         // tile 0 staged
     for (int k = 0; k < tw.mine; ++k) {
         f32x4 acc[R / 16];
 #pragma unroll
         for (int rt = 0; rt < R / 16; ++rt) acc[rt] = t0;
-        tile_product<R>(lds + (k & 1) * BUF_B + rd_off, A, acc);
         const int row0 = tw.tile(k) * R + r;
+        float dsc[R / 16], skp[R / 16];
+        if (DIAG) {                               // at the head of the tile, unconditional, from a clamped row
+#pragma unroll
+            for (int rt = 0; rt < R / 16; ++rt) {
+                const int rc = min(row0 + 16 * rt, n_rows - 1);
+                dsc[rt] = dg.diag[rc];
+                skp[rt] = dg.skip[rc];
+            }
+        }
+        tile_product<R>(lds + (k & 1) * BUF_B + rd_off, A, acc);
 #pragma unroll
         for (int rt = 0; rt < R / 16; ++rt) {
             const int row = row0 + 16 * rt;
-            if (row < n_rows)
-                *reinterpret_cast<float4*>(S + (int64_t)row * D + n0 + 4 * g) = make_float4(acc[rt][0], acc[rt][1], acc[rt][2], acc[rt][3]);
+            if (row < n_rows) {
+                if (!DIAG || skp[rt] == 0.f)
+                    *reinterpret_cast<float4*>(S + (int64_t)row * D + n0 + 4 * g) = make_float4(acc[rt][0], acc[rt][1], acc[rt][2], acc[rt][3]);
+                if (DIAG && dsc[rt] != 0.f) {
+                    float m[4];
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) {
+                        m[c] = fmaf(dsc[rt], acc[rt][c], 0.f);
+                        asm volatile("" : "+v"(m[c]));        // the record's sum is rounded before the bias is added
+                    }
+                    *reinterpret_cast<float4*>(dg.K + (int64_t)row * D + n0 + 4 * g) =
+                        make_float4(fmaxf(m[0] + bv.x, 0.f), fmaxf(m[1] + bv.y, 0.f), fmaxf(m[2] + bv.z, 0.f), fmaxf(m[3] + bv.w, 0.f));
+                }
+            }
         }
         lds_barrier();
     }
@@ -666,7 +695,7 @@ int gode_pc_fwd_launch(const LinComb& lc, int64_t n_rows, float eps, const float
       rc = set_lds_pc(gn_gemm_fwd_pc_kernel<CGV, NXV, XO, RV, AX>, lds); if (rc) return rc;                        \
       const int slot = gode_prof_begin(s, D, n_rows, (int64_t)lc.n - 1 + (XO ? 1 : 0) + (AX ? 1 : 0), GODE_PROF_GEMM_FWD | GODE_PROF_FORM_PC); \
       hipLaunchKernelGGL((gn_gemm_fwd_pc_kernel<CGV, NXV, XO, RV, AX>), dim3((unsigned)blocks), dim3(1024), lds, s, \
-                         lc, (int)n_rows, eps, gamma, beta, W, has_time, t, S, xout, ac, aux);                    \
+                         lc, (int)n_rows, eps, gamma, beta, W, has_time, t, S, xout, ac, aux, FwdDiag{});         \
       gode_prof_end(s, slot);                                                                                      \
       GODE_LAUNCH_CHECK(); return 0; }
 #define GODE_FPC2(CGV, NXV, RV) { if (xout) GODE_FPC5(CGV, NXV, true, RV, false) else GODE_FPC5(CGV, NXV, false, RV, false) }
@@ -684,6 +713,31 @@ int gode_pc_fwd_launch(const LinComb& lc, int64_t n_rows, float eps, const float
 #undef GODE_FPC
 #undef GODE_FPC2
 #undef GODE_FPC5
+    return GODE_E_UNSUPPORTED;
+}
+
+// the forward product that also stores the aggregate of the diagonal-only rows (DIAG): 1-3 terms, no x_out, no second
+// combination - stages 0-2 of a forward rk4 step
+int gode_pc_fwd_diag_launch(const LinComb& lc, int64_t n_rows, float eps, const float* gamma, const float* beta,
+                            const float* W, int has_time, float t, float* S, const FwdDiag& dg, int cg, hipStream_t s)
+{
+    int rc = 0;
+    AuxCoef ac;
+    for (int j = 0; j < GODE_MAX_TERMS; ++j) ac.c[j] = 0.f;
+#define GODE_FPCD(CGV, NXV)                                                                                        \
+    { const size_t lds = 2 * (size_t)Img<32>::BUF_B;                                                               \
+      const int64_t blocks = pc_blocks(n_rows, 32);                                                                \
+      rc = set_lds_pc(gn_gemm_fwd_pc_kernel<CGV, NXV, false, 32, false, true>, lds); if (rc) return rc;            \
+      const int slot = gode_prof_begin(s, D, n_rows, (int64_t)lc.n - 1, GODE_PROF_GEMM_FWD | GODE_PROF_FORM_PC);   \
+      hipLaunchKernelGGL((gn_gemm_fwd_pc_kernel<CGV, NXV, false, 32, false, true>), dim3((unsigned)blocks), dim3(1024), lds, s, \
+                         lc, (int)n_rows, eps, gamma, beta, W, has_time, t, S, (float*)nullptr, ac, (float*)nullptr, dg); \
+      gode_prof_end(s, slot);                                                                                      \
+      GODE_LAUNCH_CHECK(); return 0; }
+#define GODE_FPCDN(CGV) { if (lc.n == 1) GODE_FPCD(CGV, 1) else if (lc.n == 2) GODE_FPCD(CGV, 2) else if (lc.n == 3) GODE_FPCD(CGV, 3) }
+    if (!dg.diag || !dg.skip || !dg.bias || !dg.K) return GODE_E_UNSUPPORTED;
+    if (cg == 0) GODE_FPCDN(0) else if (cg == 4) GODE_FPCDN(4)
+#undef GODE_FPCDN
+#undef GODE_FPCD
     return GODE_E_UNSUPPORTED;
 }
 

@@ -132,10 +132,24 @@ struct StepClose { gode_lincomb_t pre; float alpha; bool once; };
 // Gf then Sp of one evaluation on the large route: out = f(t, sum xin) through S, or the closed step (`close`).  On the
 // once route Gf leaves the closing combination in `out`, which Sp then reads and overwrites.  k_save: Sp also stores the
 // plain derivative there (the k_4 a backprop record keeps).
+// diag_ok (plain evaluations only): the ODE function carries A's core list and the caller runs the forward rk4 solve -
+// Gf also stores `out` of the diagonal-only rows and Sp runs without them, where Gf reports that it did (per launch:
+// the fp32-MFMA forward kernel, option fwd_pc 0, has no such form)
 int feval_large(const gode_gcn_odefunc_t* f, const gode_lincomb_t& xin, float t, float* S, float* out,
-                const StepClose* close, float* k_save, void* stream) {
+                const StepClose* close, float* k_save, void* stream, bool diag_ok = false) {
     const int64_t d = f->d;
     bool p_formed = false;
+    if (diag_ok && !close && !k_save) {
+        int32_t taken = 0;
+        GODE_TRY(gode_gn_time_gemm_diag_f32(&xin, f->n, d, f->groups, f->eps, f->gamma, f->beta, f->W, d, 1, t, S, f->a_diag,
+                                            f->at_diag, f->b, out, &taken, stream));
+        gode_spmm_epilogue_t ep = relu_bias_epilogue(f);
+        if (!taken) return spmm(f->A, S, out, d, &ep, stream);
+        ep.n_items_full = f->A.n_items;                         // same kernels, same name in the profile
+        const gode_graph_t& g = f->A;
+        return gode_spmm_csr_f32(g.rowptr, g.col, g.val, f->a_core_items, f->a_n_core, g.long_rows, g.n_long, g.partial,
+                                 S, d, out, d, g.n_rows, d, &ep, stream);
+    }
     if (close && close->once) {
         GODE_TRY(gf_last_stage(f, xin, close->pre, t, S, nullptr, out, &p_formed, stream));
     } else {
@@ -152,13 +166,14 @@ int feval_large(const gode_gcn_odefunc_t* f, const gode_lincomb_t& xin, float t,
 // One step of the forward solve from y at time t: k_1..k_3 into k[0..2], y_{n+1} into ynext (which may be k[3]: the
 // folded last stage never materialises k_4) - or, keep_k4, k_4 into k[3] as well (ynext is then another array).
 int rk4_forward_step(const gode_gcn_odefunc_t* f, const gode_rk4_workspace_t* ws, const float* y, float* const* k,
-                     float* ynext, bool keep_k4, double t, double h, bool fused, bool close_once, void* stream) {
+                     float* ynext, bool keep_k4, double t, double h, bool fused, bool close_once, void* stream,
+                     bool diag_ok = false) {
     for (int s = 0; s < 4; ++s) {
         const gode_lincomb_t xin = stage_terms(y, k, s, h);
         const float ts = (float)(t + C38[s] * h);
         if (s < 3) {
             if (fused) GODE_TRY(gode_gcn_feval_small_f32(f, &xin, ts, 1.f, nullptr, nullptr, nullptr, k[s], stream));
-            else GODE_TRY(feval_large(f, xin, ts, ws->S, k[s], nullptr, nullptr, stream));
+            else GODE_TRY(feval_large(f, xin, ts, ws->S, k[s], nullptr, nullptr, stream, diag_ok));
             continue;
         }
         const StepClose close = {combine_terms(y, k, h), (float)(h * B38[3]), close_once};
@@ -185,8 +200,13 @@ extern "C" int gode_gcn_ode_rk4_forward(const gode_gcn_odefunc_t* f, float* y, f
     float* k[4] = {ws->ky[0], ws->ky[1], ws->ky[2], ws->ky[3]};
     const bool fused = fused_small(f);
     const bool close_once = close_once_route(f);
+    // diagonal-only rows of A (option diag_rows; large route at d = 128): stages 0-2.  The last stage stays on the full
+    // list: its closing combination is written by the same launch's producer waves, and the consumer would have to read
+    // it back inside the launch.
+    const bool diag_ok = gode_opt_diag_rows() && !fused && f->n > kMergedFinishMaxRows && f->d == 128 && f->a_core_items &&
+                         f->a_diag && f->at_diag && f->A.items && f->a_n_core > 0 && f->a_n_core <= f->A.n_items;
     for (int i = 0; i < n_steps; ++i) {
-        GODE_TRY(rk4_forward_step(f, ws, cur, k, k[3], false, (double)t0 + i * h, h, fused, close_once, stream));
+        GODE_TRY(rk4_forward_step(f, ws, cur, k, k[3], false, (double)t0 + i * h, h, fused, close_once, stream, diag_ok));
         float* tmp = cur; cur = k[3]; k[3] = tmp;      // k[3] holds the new solution
     }
     *result = cur;
@@ -312,6 +332,11 @@ extern "C" int gode_gcn_ode_rk4_adjoint(const gode_gcn_odefunc_t* f, float* y, f
     // are launches of the previous step on the caller's stream, ahead of these in stream order.
     const bool close_once = bw && close_once_route(f);
     bool py_formed = false;
+    // Isolated rows (option diag_rows; one-pass branch only): (A^T dZ)[i] = a_ii dZ[i] needs no gather and nobody gathers
+    // dZ[i], so Sp(g) stores a_ii dZ[i] straight into dS and SpT(g) runs on A^T's list without those rows.  The bias
+    // gradient must come from Sp(g)'s per-block column sums: those rows of dZ itself are not written.
+    const bool at_core = bw && y2rows > 0 && gode_opt_diag_rows() && f->at_core_items && f->at_diag && f->AT.items &&
+                         f->at_n_core > 0 && f->at_n_core <= f->AT.n_items;
     // Gf(g) from the y-chain as it stands (stage g's step must be the current one: Sp of a last stage swaps the chain)
     auto gf = [&](int g, void* st) -> int {
         const gode_lincomb_t yin = stage_terms(ycur, ky, g % 4, h);
@@ -344,10 +369,25 @@ extern "C" int gode_gcn_ode_rk4_adjoint(const gode_gcn_odefunc_t* f, float* y, f
             }
             py_formed = false;
         }
+        if (at_core) {
+            // Sp(g) writes rows of dS.  Its last reader is the one-pass dense launch of stage g - 1, which this branch
+            // issues on the caller's stream ahead of Sp(g); the side stream's launches of this branch (column sums and
+            // the reductions of the partials) never read dS.  The other branch reads dS on the side stream (Wg) while
+            // Sp runs, which is why it keeps the full list.
+            ep.Y2_scale = f->at_diag;
+            ep.Y2_scaled = ws->dS;
+        }
         if (two && g > 0) GODE_HIP(hipStreamWaitEvent(hs, ov->gf, 0));          // S of this stage was produced on the side stream
         GODE_TRY(spmm(f->A, Sbuf[g & 1], ky[s], d, &ep, stream));               // Sp(g): k_y (or new y) and dZ
         if (s == 3) { float* tmp = ycur; ycur = ky[3]; ky[3] = tmp; }           // the y-chain as Gf(g+1) will see it
         if (two && wg_pending) GODE_HIP(hipStreamWaitEvent(hs, ov->wg, 0));     // previous Wg still reads dS
+        if (at_core) {                                                          // SpT(g) without the rows Sp(g) has stored
+            gode_spmm_epilogue_t pt = {};
+            pt.alpha = 1.f;
+            pt.n_items_full = f->AT.n_items;                                    // same kernels, same name in the profile
+            GODE_TRY(gode_spmm_csr_f32(f->AT.rowptr, f->AT.col, f->AT.val, f->at_core_items, f->at_n_core, f->AT.long_rows,
+                                       f->AT.n_long, f->AT.partial, ws->dZ, d, ws->dS, d, f->AT.n_rows, d, &pt, stream));
+        } else
         GODE_TRY(spmm(f->AT, ws->dZ, ws->dS, d, nullptr, stream));              // SpT(g): alone on the chip
         if (two) {
             GODE_HIP(hipEventRecord(ov->spt, hs));

@@ -11,3 +11,4 @@ int gode_opt_bwd_wgrad();     // GODE_BWD_WGRAD (default 1): VJP and weight grad
 int gode_opt_y2_colsum();     // GODE_Y2_COLSUM (default 1): the adjoint rk4 driver reduces a stage's bias gradient from the per-block column sums its forward-recompute SpMM leaves (workspace y2_colsum) instead of from dZ
 int gode_opt_rk_close_once(); // GODE_RK_CLOSE_ONCE (default 1): the rk4 drivers above 65 536 rows at d = 128 form a step's closing combination y + h sum b_j k_j once, in the launch that already holds its four terms (last stage's dense product / SpMM), and the closing launch reads that one array
 int gode_opt_spmm_pipe();     // GODE_SPMM_PIPE (default 1): the thread-group SpMM (> 65 536 records) without a cotangent output walks several tiles of records per block, the records' indices fetched ahead (spmm.hip: spmm_vec4_pipe_kernel), same bits; 0 = one tile per block (spmm_vec4_kernel); 2..64 = that many tiles per block (measurements and tests)
+int gode_opt_diag_rows();     // GODE_DIAG_ROWS (default 1): where the ODE function carries the core record lists (gode_gcn_odefunc_t: a_core_items / a_diag, at_core_items / at_diag), the rk4 drivers above 65 536 rows take the rows that hold their diagonal only out of SpMM launches - forward solve, stages 0-2: the dense launch stores relu(a_ii S[i] + b) itself; adjoint solve, one-pass branch: Sp(g) stores a_ii dZ[i] of an isolated row straight into dS; same bits; 0 = the full lists

@@ -36,12 +36,16 @@ struct Epilogue {
     float* K;        // nullable (gode_spmm_csr_save_f32): K = act(Z + bias), ld = d, before the combine with pre / alpha
     float* Y3;       // nullable, with Y2: Y3 = sum_j c3[j] * cot.ptr[j] (unmasked), from the values loaded for Y2
     float c3[GODE_MAX_TERMS];
+    const float* y2_scale;   // nullable, with Y2: a row whose scale is not 0 stores fmaf(scale, g, 0) to y2_dst instead of g to Y2
+    float* y2_dst;
 };
 
 // OUT3: the launch has a third output (ep.Y3) - a variant of its own, so that the kernels every other product runs keep
 // their registers
 // COT = false: for a launch without a cotangent output (ep.Y2 is null there)
-template <int LPR, bool OUT3 = false, bool COT = true>
+// SCALE: the launch may carry ep.y2_scale (spmm_vec4_kernel only: the finishing launch never meets a scaled row - a split
+// row has more than one entry - and the wave-per-record kernels refuse the field), so the others keep their registers
+template <int LPR, bool OUT3 = false, bool COT = true, bool SCALE = false>
 __device__ __forceinline__ float4 epilogue_store4(const Epilogue& ep, float4 z, int row, int lane,
                                                   int64_t d, float* Y, int64_t ldy) {
     if (ep.bias) {
@@ -61,6 +65,8 @@ __device__ __forceinline__ float4 epilogue_store4(const Epilogue& ep, float4 z, 
     *reinterpret_cast<float4*>(Y + (int64_t)row * ldy + lane * 4) = y;
     if (COT && ep.Y2) {
         const int64_t o = (int64_t)row * d + lane * 4;
+        // asked for with the cotangent terms below: one dword per record (row is a row of the matrix for every caller)
+        const float sc = (SCALE && ep.y2_scale) ? ep.y2_scale[row] : 0.f;
         float4 g;
         if (OUT3) {              // a second combination of the cotangent terms, row by row beside Y2
             float4 g3;
@@ -71,7 +77,11 @@ __device__ __forceinline__ float4 epilogue_store4(const Epilogue& ep, float4 z, 
         }
         g.x = z.x > 0.f ? g.x : 0.f; g.y = z.y > 0.f ? g.y : 0.f;
         g.z = z.z > 0.f ? g.z : 0.f; g.w = z.w > 0.f ? g.w : 0.f;
-        *reinterpret_cast<float4*>(ep.Y2 + o) = g;
+        // a scaled row goes to y2_dst as the transposed product's one-entry record would leave it: acc = fmaf(a_ii, g, 0),
+        // no epilogue - the same instruction on the same numbers.  The column sums take the unscaled g either way.
+        const bool scaled = SCALE && sc != 0.f;
+        const float4 st = scaled ? make_float4(fmaf(sc, g.x, 0.f), fmaf(sc, g.y, 0.f), fmaf(sc, g.z, 0.f), fmaf(sc, g.w, 0.f)) : g;
+        *reinterpret_cast<float4*>((scaled ? ep.y2_dst : ep.Y2) + o) = st;
         return g;
     }
     return make_float4(0.f, 0.f, 0.f, 0.f);
@@ -148,14 +158,14 @@ __global__ __launch_bounds__(256) void spmm_vec4_kernel(
     if (ep.colpart) {                                  // (block-uniform) nobody leaves before the block's column sums
         float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
         if (active) {
-            if (slot < 0) g = epilogue_store4<LPR, OUT3>(ep, acc, row, lane, (int64_t)LPR * 4, Y, ldy);
+            if (slot < 0) g = epilogue_store4<LPR, OUT3, true, true>(ep, acc, row, lane, (int64_t)LPR * 4, Y, ldy);
             else *reinterpret_cast<float4*>(partial + (int64_t)slot * (LPR * 4) + lane * 4) = acc;
         }
         block_colsum_store<LPR>(g, ep.colpart + (int64_t)blockIdx.x * (LPR * 4));
         return;
     }
     if (!active) return;
-    if (slot < 0) epilogue_store4<LPR, OUT3>(ep, acc, row, lane, (int64_t)LPR * 4, Y, ldy);
+    if (slot < 0) epilogue_store4<LPR, OUT3, true, true>(ep, acc, row, lane, (int64_t)LPR * 4, Y, ldy);
     else *reinterpret_cast<float4*>(partial + (int64_t)slot * (LPR * 4) + lane * 4) = acc;
 }
 
@@ -477,11 +487,13 @@ __global__ __launch_bounds__(256) void spmm_finish_generic_kernel(
 template <int LPR, bool OUT3>
 int launch_vec4(const int* rowptr, const int* col, const float* val, const int4* items, int n_items,
                 const int4* long_rows, int n_long, float* partial, const float* X, int64_t ldx,
-                float* Y, int64_t ldy, const Epilogue& ep, hipStream_t s) {
-    if (LPR < 64 && n_items > 0 && n_items <= 65536) {         // too few records to fill the chip: a wave per record
-        if (ep.colpart) return GODE_E_UNSUPPORTED;             // (gode_spmm_y2_colsum_rows is 0 for such a graph)
+                float* Y, int64_t ldy, const Epilogue& ep, int64_t full_items, hipStream_t s) {
+    // full_items: the record count of the matrix's whole list (n_items unless `items` is a sub-list of it) - it picks the
+    // kernel, so that a sub-list adds every row's numbers in the whole list's order, and names the product to the profiler
+    if (LPR < 64 && n_items > 0 && full_items <= 65536) {      // too few records to fill the chip: a wave per record
+        if (ep.colpart || ep.y2_scale) return GODE_E_UNSUPPORTED;   // (gode_spmm_y2_colsum_rows is 0 for such a graph)
         const int64_t wb = ((int64_t)n_items * 64 + 255) / 256;
-        const int slot = gode_prof_begin(s, (int64_t)LPR * 4, n_items, (int64_t)ep.pre.n + ep.cot.n + (ep.Y2 ? 1 : 0) + (ep.Y3 ? 1 : 0));
+        const int slot = gode_prof_begin(s, (int64_t)LPR * 4, full_items, (int64_t)ep.pre.n + ep.cot.n + (ep.Y2 ? 1 : 0) + (ep.Y3 ? 1 : 0));
         hipLaunchKernelGGL((spmm_vec4_wave_kernel<LPR, OUT3>), dim3((unsigned)wb), dim3(256), 0, s,
                            rowptr, col, val, items, n_items, partial, X, ldx, Y, ldy, ep);
         gode_prof_end(s, slot);
@@ -497,7 +509,7 @@ int launch_vec4(const int* rowptr, const int* col, const float* val, const int4*
     const int64_t threads = (int64_t)n_items * LPR;
     const int64_t blocks = (threads + 255) / 256;
     if (blocks > 0) {
-        const int slot = gode_prof_begin(s, (int64_t)LPR * 4, n_items, (int64_t)ep.pre.n + ep.cot.n + (ep.Y2 ? 1 : 0) + (ep.Y3 ? 1 : 0));
+        const int slot = gode_prof_begin(s, (int64_t)LPR * 4, full_items, (int64_t)ep.pre.n + ep.cot.n + (ep.Y2 ? 1 : 0) + (ep.Y3 ? 1 : 0));
         const int pipe = gode_opt_spmm_pipe();
         if (pipe != 0 && !ep.Y2) {
             // tiles per block: 1 = SPMM_PIPE_TILES, but never fewer than SPMM_PIPE_MIN_BLOCKS blocks (two rounds of
@@ -575,24 +587,34 @@ int spmm_csr_impl(const int32_t* rowptr, const int32_t* col, const float* val,
         if (ep.Y3 == Y || ep.Y3 == Y2 || ep.Y3 == K) return GODE_E_RANGE;
         for (int j = 0; j < ep.cot.n; ++j) if (ep.Y3 == ep.cot.ptr[j]) return GODE_E_RANGE;
     }
+    ep.y2_scale = (epi && Y2) ? epi->Y2_scale : nullptr;
+    ep.y2_dst = ep.y2_scale ? epi->Y2_scaled : nullptr;
+    if (epi && !Y2 && (epi->Y2_scale || epi->Y2_scaled)) return GODE_E_NULLPTR;
+    if (ep.y2_scale) {
+        if (!ep.y2_dst) return GODE_E_NULLPTR;
+        if (ep.y2_dst == Y || ep.y2_dst == Y2 || ep.y2_dst == K || ep.y2_dst == ep.Y3 || ep.y2_dst == X) return GODE_E_RANGE;
+        for (int j = 0; j < ep.cot.n; ++j) if (ep.y2_dst == ep.cot.ptr[j]) return GODE_E_RANGE;
+        for (int j = 0; j < ep.pre.n; ++j) if (ep.y2_dst == ep.pre.ptr[j]) return GODE_E_RANGE;
+    }
+    const int64_t full_items = (epi && epi->n_items_full > n_items) ? epi->n_items_full : n_items;
     if (ep.colpart && ((((uintptr_t)ep.colpart) & 15) || gode_spmm_y2_colsum_rows(n_items, n_long, d) == 0)) return GODE_E_UNSUPPORTED;
 
     const bool al = !(((uintptr_t)X) & 15) && !(((uintptr_t)Y) & 15) && (ldx % 4 == 0) && (ldy % 4 == 0) &&
                     (!bias || !(((uintptr_t)bias) & 15)) && (!partial || !(((uintptr_t)partial) & 15)) &&
                     (!Y2 || (!(((uintptr_t)Y2) & 15) && lincomb_aligned16(cot))) && lincomb_aligned16(pre) &&
-                    !(((uintptr_t)K) & 15) && !(((uintptr_t)ep.Y3) & 15);
+                    !(((uintptr_t)K) & 15) && !(((uintptr_t)ep.Y3) & 15) && !(((uintptr_t)ep.y2_dst) & 15);
     const int4* it4 = reinterpret_cast<const int4*>(items);
     const int4* lr4 = reinterpret_cast<const int4*>(long_rows);
     if (al && d % 4 == 0) {
         switch (d / 4) {
-#define GODE_CASE(L) case L: return ep.Y3 ? launch_vec4<L, true>(rowptr, col, val, it4, (int)n_items, lr4, (int)n_long, partial, X, ldx, Y, ldy, ep, s) \
-                                        : launch_vec4<L, false>(rowptr, col, val, it4, (int)n_items, lr4, (int)n_long, partial, X, ldx, Y, ldy, ep, s);
+#define GODE_CASE(L) case L: return ep.Y3 ? launch_vec4<L, true>(rowptr, col, val, it4, (int)n_items, lr4, (int)n_long, partial, X, ldx, Y, ldy, ep, full_items, s) \
+                                        : launch_vec4<L, false>(rowptr, col, val, it4, (int)n_items, lr4, (int)n_long, partial, X, ldx, Y, ldy, ep, full_items, s);
             GODE_CASE(1) GODE_CASE(2) GODE_CASE(4) GODE_CASE(8) GODE_CASE(16) GODE_CASE(32) GODE_CASE(64)
 #undef GODE_CASE
             default: break;
         }
     }
-    if (ep.colpart) return GODE_E_UNSUPPORTED;                 // unaligned operands: no per-block column sums on the generic kernels
+    if (ep.colpart || ep.y2_scale) return GODE_E_UNSUPPORTED;  // unaligned operands: no per-block column sums, no scaled rows on the generic kernels
     int G = 1; while (G < d && G < 64) G <<= 1;
     if (d == 1 && it4 != nullptr) {                    // record lists only: whole short rows are cheaper one thread each
         const int64_t blocks = ((int64_t)n_items * 64 + 255) / 256;

@@ -139,6 +139,11 @@ def _func_struct(spec):
     fs.n, fs.d, fs.groups, fs.eps = spec.graph.n_rows, spec.d, spec.groups, spec.eps
     fs.W, fs.b = spec.W.data_ptr(), spec.b.data_ptr()
     fs.gamma, fs.beta = spec.gamma.data_ptr(), spec.beta.data_ptr()
+    core = getattr(spec.graph, "_at_core", None)        # A^T's records without the isolated rows (tuned_graph's gate)
+    if core is not None:
+        fs.at_core_items, fs.at_n_core, fs.at_diag = core.items.data_ptr(), core.n_items, core.diag.data_ptr()
+        a = spec.graph.__dict__["_a_core"]
+        fs.a_core_items, fs.a_n_core, fs.a_diag = a.items.data_ptr(), a.n_items, a.diag.data_ptr()
     return fs
 
 
@@ -191,6 +196,40 @@ def gather_imbalance(graph, d, inverse=None):
     return max(max(hh) * m / max(sum(hh), 1) for hh in h)
 
 
+# ---- diagonal-only rows leave the block's SpMM launches ("Diagonal-only rows") ----------------
+# A row whose only entry is its own diagonal costs a product a record, a row read and a row written (16 + 8 + 8 d bytes,
+# 1 048 at d = 128) for a scaled copy of a row the launch before it held in registers.  With the core lists
+# (CSRGraph.diag_rows / isolated_rows) that launch stores the row itself:
+#   adjoint solve   rows isolated in A and A^T leave the product with A^T; the launch that forms dZ stores a_ii dZ[i] into
+#                   dS instead of dZ[i] into dZ (same bytes) and loads one dword of the scale per record - a memory sector
+#                   of up to 64 bytes each, the rows of neighbouring records not being neighbours;
+#   forward solve   rows diagonal-only in A leave the product with A; the dense launch before it stores relu(a_ii S[i] + b)
+#                   (512 B more, and 512 B less where the row is isolated and its S row is dropped) and loads two dwords per
+#                   row, coalesced.
+# At the worst 64 n bytes per adjoint stage and 8 n per forward stage against 1 048 n_isolated saved in each: even at a
+# share of 1/16.  The block takes the lists from twice that share on, an exact integer count:
+#       8 * n_isolated >= n_rows,    n_rows > 65 536   (csrc/ode_driver.hip uses the lists on the large route only).
+# Below that no list is built and nothing changes.  R-MAT 2^20 / 10 M edges with self loops: 45.4 % of the rows.
+CORE_LIST_MIN_ROWS = 65536
+CORE_LIST_MIN_SHARE_INV = 8
+
+
+def _hand_core_list(g, info):
+    """Decide (from counts alone) whether the ODE block gets the core lists of A and A^T; if so build them on `g`."""
+    if getattr(g, "items", None) is None or g.n_rows <= CORE_LIST_MIN_ROWS or g.transpose().items is None:
+        return
+    if "_at_core" not in g.__dict__:
+        iso = g.transpose().isolated_rows()
+        take = CORE_LIST_MIN_SHARE_INV * iso.n_flagged >= g.n_rows and iso.n_items > 0
+        if take:
+            iso.items                                               # built here, once, not inside a solve
+            g.diag_rows().items
+        g.__dict__["_at_core"] = iso if take else None
+        g.__dict__["_a_core"] = g.diag_rows() if take else None      # A's list for the forward solve: every diagonal-only row of A
+        g.__dict__["_isolated_count"] = iso.n_flagged
+    info.update(isolated_rows=g.__dict__["_isolated_count"], core_lists=g.__dict__["_at_core"] is not None)
+
+
 def tuned_graph(graph, d, node_order="auto"):
     """(graph the ODE block should integrate on, order, inverse) - order is None when the graph is used as given.
     y' = y[order] are the state rows in the renumbered graph; y = y'[inverse].  Deterministic in (graph, d, node_order)."""
@@ -217,6 +256,8 @@ def tuned_graph(graph, d, node_order="auto"):
         if take:
             res = (graph.relabel(order), order, inverse)
             info["renumbered"] = True
+    if square and not (res[0].device.type == "cuda" and torch.cuda.is_current_stream_capturing()):
+        _hand_core_list(res[0], info)
     graph.__dict__.setdefault("_tuned_info", {})[(d, node_order)] = info
     cache[(d, node_order)] = res
     return res

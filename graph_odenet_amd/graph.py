@@ -48,6 +48,8 @@ class CSRGraph:
             self.items, self.n_items, self.long_rows, self.n_long, self.n_slots = None, self.n_rows, None, 0, 0
         self._partial = {}
         self._T = None
+        self._diag_rows = None
+        self._isolated_rows = None
 
     # -- balanced record list -------------------------------------------------
     def _build_items(self):
@@ -92,6 +94,28 @@ class CSRGraph:
             buf = torch.empty(self.n_slots * d, dtype=torch.float32, device=self.device)
             self._partial[d] = buf
         return buf
+
+    # -- diagonal-only rows -----------------------------------------------------
+    def diag_rows(self):
+        """Rows whose product is a scaled copy, Y[i] = a_ii * X[i]: exactly one stored entry, on the diagonal, with a
+        value that is not 0.0 (a pattern-only matrix stores 1.0).  An empty row, a row whose one entry is off the
+        diagonal or is a stored 0.0, and every split row are ordinary rows.  Built once per graph (one host
+        synchronisation, like the transpose) and cached; `relabel` makes a new graph, whose property is this one
+        permuted: the same rows under their new numbers, the same values.  Nothing else of the graph changes."""
+        if self._diag_rows is None:
+            if self.items is None:
+                raise ValueError("diag_rows: the graph has no record list")
+            self._diag_rows = DiagRows(self)
+        return self._diag_rows
+
+    def isolated_rows(self):
+        """The rows flagged by diag_rows() here AND in the transpose (square matrices): no product with either matrix
+        gathers such a row.  `diag` and the core list as in diag_rows(), for this smaller set; cached."""
+        if self._isolated_rows is None:
+            if self.n_rows != self.n_cols or self.items is None:
+                raise ValueError("isolated_rows: square matrices with a record list only")
+            self._isolated_rows = DiagRows(self, among=self.transpose().diag_rows().diag)
+        return self._isolated_rows
 
     # -- transpose (CSR by source) for the backward pass -----------------------
     def transpose(self):
@@ -146,6 +170,38 @@ class CSRGraph:
         """nnz*(4+4+4d) + (N+1)*4 + N*d*4 (value term dropped when pattern-only)."""
         per = 4 + (4 if self.val is not None else 0) + 4 * d
         return self.nnz * per + (self.n_rows + 1) * 4 + self.n_rows * d * 4
+
+
+class DiagRows:
+    """CSRGraph.diag_rows() / isolated_rows(): `diag` (n_rows floats: a_ii on a flagged row, 0 elsewhere), `n_flagged`, and
+    the core record list `items` / `n_items`: the graph's records without those of the flagged rows, in the same order.
+    `among` (a diag array of the same length, nullable): only rows flagged there as well are flagged here."""
+
+    def __init__(self, g, among=None):
+        n = g.n_rows
+        rp = g.rowptr.to(torch.int64)
+        self.diag = torch.zeros(n, dtype=torch.float32, device=g.device)
+        if n > 0 and g.nnz > 0:
+            first = torch.clamp(rp[:-1], max=g.nnz - 1)
+            rows = torch.arange(n, device=g.device, dtype=torch.int64)
+            v = g.val[first] if g.val is not None else torch.ones(n, dtype=torch.float32, device=g.device)
+            flag = ((rp[1:] - rp[:-1]) == 1) & (g.col.to(torch.int64)[first] == rows) & (v != 0)
+            if among is not None:
+                flag = flag & (among != 0)
+            self.diag = torch.where(flag, v, self.diag)
+        self.n_flagged = int((self.diag != 0).sum())                  # the one host synchronisation
+        self.n_items = g.n_items - self.n_flagged                     # a flagged row is one record
+        self._g, self._items = g, None
+
+    @property
+    def items(self):
+        if self._items is None:                                       # built on first use: a caller may only want the count
+            g = self._g
+            keep = self.diag[g.items[:, 0].to(torch.int64)] == 0
+            self._items = g.items[keep].contiguous()
+            assert self._items.shape[0] == self.n_items
+            self._g = None
+        return self._items
 
 
 def from_coo(rows, cols, vals, n_rows, n_cols, split=DEFAULT_SPLIT, coalesce=True):

@@ -74,8 +74,11 @@ int         gode_abi_version(void);
  * drivers form the closing combination of a step once, in the launch that already holds its terms, instead of loading
  * the four arrays again in the closing launch; same bits either way), "spmm_pipe" (1 default / 0 / 2..64: sparse
  * products of more than 65 536 records without a cotangent output walk several tiles of 256 / (d / 4) records per block,
- * the records' indices fetched ahead; 0: one tile per block; 2..64: that many tiles per block; same bits in every case).
- * Initial values come from GODE_GEMM_SPLIT / GODE_OVERLAP / GODE_WGRAD_SPLIT / GODE_BWD_PC / GODE_FWD_PC / GODE_SPMM_PIPE.
+ * the records' indices fetched ahead; 0: one tile per block; 2..64: that many tiles per block; same bits in every case),
+ * "diag_rows" (1 default / 0: the rk4 forward and adjoint drivers use the core record lists of A and A^T where the ODE
+ * function carries them, see gode_gcn_odefunc_t; 0: the full lists; same bits either way).
+ * Initial values come from GODE_GEMM_SPLIT / GODE_OVERLAP / GODE_WGRAD_SPLIT / GODE_BWD_PC / GODE_FWD_PC / GODE_SPMM_PIPE /
+ * GODE_DIAG_ROWS.
  * Returns 0 or GODE_E_UNSUPPORTED. */
 int         gode_set_option(const char* name, int value);
 int         gode_get_option(const char* name);
@@ -112,6 +115,15 @@ typedef struct gode_spmm_epilogue {
                                unmasked) - a second combination of the cotangent terms, formed from the values the launch has
                                loaded for Y2 with the multiply-add chain of gode_lincomb_f32.  Must not be one of the terms */
     float          cot_out_coef[GODE_MAX_TERMS];
+    const float*   Y2_scale;  /* nullable, with Y2 and Y2_scaled: n_rows floats.  The Y2 row g of a row whose scale is not 0.0 is
+                               stored as fmaf(scale, g, 0.f) into Y2_scaled and NOT into Y2 (that row of Y2 stays as it was);
+                               its contribution to Y2_colsum stays the unscaled g.  For a row i that no product with the
+                               transposed matrix gathers and whose own row there is its diagonal alone, Y2_scaled is
+                               (A^T Y2)[i] = a_ii * Y2[i], bit for bit what the product's one-entry record gives */
+    float*         Y2_scaled; /* n_rows x d, ld = d, 16-byte aligned like Y2; not Y, Y2, cot_out or a term */
+    int64_t        n_items_full; /* 0, or the record count of the matrix's whole list when `items` is a sub-list of it (a core
+                               list).  The kernels are chosen by this count, so every row of the sub-list adds the numbers the
+                               whole list would in the same order, and the profiler's `rows` field reports it */
 } gode_spmm_epilogue_t;
 
 /* rows of the Y2_colsum array for a graph's record lists (0: the shape runs on kernels without it - small graphs,
@@ -185,6 +197,18 @@ int gode_gn_time_gemm_xout_f32(const gode_lincomb_t* xin /* host */, int64_t n_r
                                int32_t groups, float eps, const float* gamma, const float* beta,
                                const float* W, int64_t d_out, int has_time, float t,
                                float* S, float* x_out, void* stream);
+/* gode_gn_time_gemm_f32 that, where it runs on the producer / consumer kernel (d_in = d_out = 128, >= 65 536 rows, option
+ * "fwd_pc", 1-3 terms, 0 or 4 channels per group), ALSO stores for every row i with diag[i] != 0
+ *   K[i,:] = max(fmaf(diag[i], S[i,:], 0) + bias, 0)
+ * - what gode_spmm_csr_f32 with bias and relu makes of a row whose only entry is diag[i] on the diagonal, bit for bit - and
+ * does not store S[i,:] of a row with skip[i] != 0 (a row no product gathers).  diag, skip: n_rows floats; bias: [d_out];
+ * K: n_rows x d_out contiguous, 16-byte aligned, not S and none of the terms.  *taken (host) = 1 where that form ran;
+ * = 0 where the plain launch was issued instead (S complete, K untouched): the caller decides per launch. */
+int gode_gn_time_gemm_diag_f32(const gode_lincomb_t* xin /* host */, int64_t n_rows, int64_t d_in,
+                               int32_t groups, float eps, const float* gamma, const float* beta,
+                               const float* W, int64_t d_out, int has_time, float t,
+                               float* S, const float* diag, const float* skip, const float* bias, float* K,
+                               int32_t* taken /* host */, void* stream);
 /* Same, and additionally aux_out[i,:] = sum_j aux_coef[j]*xin.ptr[j][i,:]: a second combination of the SAME terms (host
  * aux_coef[xin.n]), formed from the term values the launch has loaded anyway with the multiply-add chain of
  * gode_lincomb_f32 (bit for bit that launch's result).  aux_out: n_rows x d_in contiguous, 16-byte aligned, none of the
@@ -533,6 +557,19 @@ typedef struct gode_gcn_odefunc {
     int32_t groups; float eps;          /* GroupNorm(groups, d), eps */
     const float* W;                     /* (d+1) x d, row 0 = time row */
     const float* b; const float* gamma; const float* beta;
+    /* nullable (all three or none; zero = the launches as they were).  Rows that are isolated - their only stored entry
+     * in A and in A^T is their own non-zero diagonal a_ii - need no gather in the adjoint's product with A^T:
+     * at_diag[i] = a_ii for such a row and 0 elsewhere (n floats), at_core_items = AT.items without the records of those
+     * rows, in the same order (at_n_core records of 4 int32; AT.long_rows / AT.partial serve both lists).  The one-pass
+     * branch of gode_gcn_ode_rk4_adjoint (more than 65 536 rows, option "diag_rows") then stores a_ii * dZ[i] of such a
+     * row from the launch that forms dZ and runs the product with A^T on the core list. */
+    const int32_t* at_core_items; int64_t at_n_core; const float* at_diag;
+    /* nullable (both or none, with the three above).  a_diag[i] = a_ii for a row whose only stored entry in A is its own
+     * non-zero diagonal (whatever its column holds), 0 elsewhere; a_core_items = A.items without the records of those
+     * rows (a_n_core records).  gode_gcn_ode_rk4_forward (more than 65 536 rows, option "diag_rows") then lets the dense
+     * launch of stages 0-2 store relu(a_ii S[i] + b) of such a row (gode_gn_time_gemm_diag_f32; skip = at_diag) and runs
+     * the stage's SpMM on the core list - per launch, where the dense launch reports that form taken. */
+    const int32_t* a_core_items; int64_t a_n_core; const float* a_diag;
 } gode_gcn_odefunc_t;
 
 typedef struct gode_rk4_workspace {
