@@ -9,9 +9,15 @@ int gode_pc_fwd_launch(const LinComb& lc, int64_t n_rows, float eps, const float
                        int cg, hipStream_t s);   // aux (nullable): second combination of the terms, 4 terms only
 // diagonal-only rows in the forward product (gemm_pc.hip, DIAG): diag[i] = a_ii of such a row, 0 elsewhere; skip[i] != 0:
 // the S row is not stored; K[i, :] = relu(a_ii S[i, :] + bias) for the rows with diag[i] != 0.  All four non-null.
-struct FwdDiag { const float* diag; const float* skip; const float* bias; float* K; };
+// alpha: the last-stage form only (gode_pc_fwd_diag_aux_launch).
+struct FwdDiag { const float* diag; const float* skip; const float* bias; float* K; float alpha; };
 int gode_pc_fwd_diag_launch(const LinComb& lc, int64_t n_rows, float eps, const float* gamma, const float* beta,
                             const float* W, int has_time, float t, float* S, const FwdDiag& dg, int cg, hipStream_t s);   // 1-3 terms, cg 0 / 4
+// AUX and DIAG: 4 terms, cg 0 / 4; dg.K is the array of the second combination P (coefficients aux_coef) and receives
+// fmaf(dg.alpha, relu(a_ii S[i, :] + bias), P[i, :]) on the rows with diag[i] != 0, P on the others
+int gode_pc_fwd_diag_aux_launch(const LinComb& lc, int64_t n_rows, float eps, const float* gamma, const float* beta,
+                                const float* W, int has_time, float t, float* S, const float* aux_coef, const FwdDiag& dg,
+                                int cg, hipStream_t s);
 int gode_pc_bwd_launch(const LinComb& lc, int64_t n_rows, float eps, const float* gamma, const float* W, int has_time,
                        const float* dS, float out_scale, const LinComb& pre, float* dx, float* dgamma_part,
                        float* dbeta_part, int64_t n_part, int cg, hipStream_t s);

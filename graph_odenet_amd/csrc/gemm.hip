@@ -1474,6 +1474,41 @@ extern "C" int gode_gn_time_gemm_diag_f32(const gode_lincomb_t* xin, int64_t n_r
     return gode_gn_time_gemm_f32(xin, n_rows, d_in, groups, eps, gamma, beta, W, d_out, has_time, t, S, stream);
 }
 
+// The last stage of a forward rk4 step: gode_gn_time_gemm_xout_aux_f32 without x_out whose producer / consumer form (four
+// terms, gemm_pc.hip: AUX and DIAG) also closes the diagonal-only rows - K receives the second combination P on the rows
+// with diag == 0 and fmaf(alpha, relu(a_ii S + bias), P) on the others.  *taken = 0: the plain launch with the second
+// combination is issued (or GODE_E_UNSUPPORTED returned, nothing launched) exactly as gode_gn_time_gemm_xout_aux_f32 does.
+extern "C" int gode_gn_time_gemm_diag_aux_f32(const gode_lincomb_t* xin, int64_t n_rows, int64_t d_in, int32_t groups,
+                                              float eps, const float* gamma, const float* beta, const float* W,
+                                              int64_t d_out, int has_time, float t, float* S, const float* aux_coef,
+                                              float* K, float alpha, const float* diag, const float* skip,
+                                              const float* bias, int32_t* taken, void* stream)
+{
+    if (!taken) return GODE_E_NULLPTR;
+    *taken = 0;
+    int rc = check_common(xin, n_rows, d_in, groups, d_out); if (rc) return rc;
+    if (!aux_coef || !K) return GODE_E_NULLPTR;
+    if (n_rows == 0) return 0;
+    if (!W || !S) return GODE_E_NULLPTR;
+    const int cg = fast_cg(d_in, d_out, groups);
+    const bool al = lincomb_aligned16(xin) && !(((uintptr_t)S) & 15) && !(((uintptr_t)W) & 15) &&
+                    (!gamma || !(((uintptr_t)gamma) & 15)) && (!beta || !(((uintptr_t)beta) & 15)) &&
+                    !(((uintptr_t)bias) & 15) && !(((uintptr_t)K) & 15);
+    bool distinct = diag && skip && bias && K != S;
+    for (int j = 0; distinct && j < xin->n; ++j) distinct = K != xin->ptr[j];
+    // the selection of the plain launch (below), for the term count the form exists for
+    if (distinct && cg >= 0 && al && d_in == 128 && xin->n == 4 && (n_rows >= kWgradSplitMinRows || gode_opt_wgrad_split_small()) &&
+        (gode_opt_fwd_pc() & 2)) {
+        const FwdDiag dg = {diag, skip, bias, K, alpha};
+        rc = gode_pc_fwd_diag_aux_launch(make_lincomb(xin), n_rows, eps, gamma, beta, W, has_time ? 1 : 0, t, S, aux_coef, dg,
+                                         cg, (hipStream_t)stream);
+        if (rc == 0) *taken = 1;
+        if (rc != GODE_E_UNSUPPORTED) return rc;
+    }
+    return gode_gn_time_gemm_xout_aux_f32(xin, n_rows, d_in, groups, eps, gamma, beta, W, d_out, has_time, t, S, nullptr,
+                                          aux_coef, K, stream);
+}
+
 // aux_out == nullptr: the plain launch.  With aux_out every branch below either launches a kernel that forms it or
 // returns GODE_E_UNSUPPORTED before anything is launched; the kernel taken is the one the plain launch would take.
 extern "C" int gode_gn_time_gemm_xout_aux_f32(const gode_lincomb_t* xin, int64_t n_rows, int64_t d_in, int32_t groups,

@@ -129,6 +129,14 @@ struct TileWalk {
 //      bits), so that SpMM can run without those rows.  A row with dg.skip[i] != 0 is gathered by nobody (its column
 //      holds the diagonal alone as well): its S row is not stored.  A flag of its own: every other instantiation keeps
 //      its registers.
+// AUX and DIAG together (the last stage of a forward rk4 step; aux and dg.K are ONE array): the product that follows is
+//      Sp(3), y_new = P + alpha relu(A S + b) with P = aux read and overwritten in place.  For a diagonal-only row the
+//      consumer stores y_new[i, :] = fmaf(alpha, relu(a_ii S[i, :] + bias), P[i, :]) itself - again the one-entry record's
+//      chain, with the pre-term {1.0, P} as lc_load4 forms it.  P[i, :] comes from the producers through a second LDS tile
+//      per buffer (fp32, R rows of LDX floats, the hand-over of gn_gemm_bwd_pc_kernel<.., XLDS>): written in stage(k)
+//      before the barrier that publishes tile k, read before the barrier that ends the consumers' iteration k,
+//      overwritten by stage(k + 2) after it.  The producers do NOT store P of such a row to memory: two waves of one
+//      block storing to one address are ordered by nothing, so the consumer has to be that row's only writer.
 // ---------------------------------------------------------------------------------------------------------------
 template <int CG, int NX, bool XOUT, int R, bool AUX = false, bool DIAG = false>
 __global__ __launch_bounds__(1024, 1) void gn_gemm_fwd_pc_kernel(LinComb xin, int n_rows, float eps,
@@ -139,7 +147,12 @@ __global__ __launch_bounds__(1024, 1) void gn_gemm_fwd_pc_kernel(LinComb xin, in
                                                                 AuxCoef acoef, float* __restrict__ aux, FwdDiag dg)
 {
     static_assert(!AUX || NX > 0, "the second combination needs the raw terms");
-    constexpr int PIECE_B = Img<R>::PIECE_B, BUF_B = Img<R>::BUF_B;
+    // the closing combination goes to the consumers through LDS.  Its statements sit behind `if constexpr`: behind a plain
+    // `if` the producers' lambdas capture dg in every instantiation, which moved ten other kernels by 1-3 VGPRs
+    constexpr bool LAST = AUX && DIAG;
+    static_assert(!LAST || !XOUT, "the last-stage form has no x_out");
+    constexpr int PIECE_B = Img<R>::PIECE_B, PT_OFF = Img<R>::BUF_B;
+    constexpr int BUF_B = Img<R>::BUF_B + (LAST ? R * LDX * 4 : 0);       // piece images | fp32 tile of P
     constexpr int RPT = R / 8;                    // rows per staging thread
     extern __shared__ __attribute__((aligned(16))) float smem[];
     char* lds = reinterpret_cast<char*>(smem);
@@ -152,12 +165,14 @@ __global__ __launch_bounds__(1024, 1) void gn_gemm_fwd_pc_kernel(LinComb xin, in
         const float4 btv = beta ? ld4(beta + tcol) : make_float4(0.f, 0.f, 0.f, 0.f);
         constexpr int NXR = NX > 0 ? NX : 1;
         float4 xr[NXR][RPT];
+        float pdg[RPT];                           // LAST: dg.diag of the rows in flight
         auto prefetch = [&](int k) {              // unconditional loads from clamped rows: no wait at a branch join
             const int tile = tw.clamped(k);
 #pragma unroll
             for (int p = 0; p < RPT; ++p) {
                 const int row = tile * R + RPT * trow + p;
                 const int64_t off = (int64_t)(row < n_rows ? row : n_rows - 1) * D + tcol;
+                if constexpr (LAST) pdg[p] = dg.diag[row < n_rows ? row : n_rows - 1];
                 if (NX > 0) {
 #pragma unroll
                     for (int j = 0; j < NXR; ++j) xr[j][p] = ld4(xin.ptr[j] + off);
@@ -191,7 +206,12 @@ __global__ __launch_bounds__(1024, 1) void gn_gemm_fwd_pc_kernel(LinComb xin, in
                         a.x = fmaf(c, xr[j][p].x, a.x); a.y = fmaf(c, xr[j][p].y, a.y);
                         a.z = fmaf(c, xr[j][p].z, a.z); a.w = fmaf(c, xr[j][p].w, a.w);
                     }
-                    if (row < n_rows) *reinterpret_cast<float4*>(aux + (int64_t)row * D + tcol) = a;
+                    if constexpr (LAST) {         // to the consumers; to memory only where no consumer stores the row
+                        *reinterpret_cast<float4*>(lds + (k & 1) * BUF_B + PT_OFF + ((RPT * trow + p) * LDX + tcol) * 4) = a;
+                        if (row < n_rows && pdg[p] == 0.f) *reinterpret_cast<float4*>(aux + (int64_t)row * D + tcol) = a;
+                    } else {
+                        if (row < n_rows) *reinterpret_cast<float4*>(aux + (int64_t)row * D + tcol) = a;
+                    }
                 }
                 float4 xn = gn_forward_v<CG>(x, eps, gmv, btv);
                 if (row >= n_rows) xn = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -215,8 +235,23 @@ __global__ __launch_bounds__(1024, 1) void gn_gemm_fwd_pc_kernel(LinComb xin, in
     f32x4 t0 = {0.f, 0.f, 0.f, 0.f};
     if (has_time) { const float4 w0 = ld4(W + n0 + 4 * g); t0 = (f32x4){t * w0.x, t * w0.y, t * w0.z, t * w0.w}; }
     const int rd_off = r * LDK * 2 + g * 16;
+    const int pt_off = PT_OFF + (r * LDX + n0 + 4 * g) * 4;
     float4 bv = make_float4(0.f, 0.f, 0.f, 0.f);
     if (DIAG) bv = ld4(dg.bias + n0 + 4 * g);
+    // DIAG: dg.diag / dg.skip of the lane's rows, unconditional, from a clamped tile and row, ONE TILE AHEAD of their use.
+    // Loaded at the head of their own tile they were waited for behind that tile's predecessor's stores (loads and
+    // stores share a counter and the stores sit in branches, so the wait is for all of them): +37 / +70 / +59 us on the
+    // 1 / 2 / 3-term launch where the bytes explain 10; a tile ahead: +23 / +38 / +30 us (tools/dev/pc_ab.py --diag).
+    float dscn[R / 16], skpn[R / 16];
+    auto load_flags = [&](int k) {
+#pragma unroll
+        for (int rt = 0; rt < R / 16; ++rt) {
+            const int rc = min(tw.clamped(k) * R + r + 16 * rt, n_rows - 1);
+            dscn[rt] = dg.diag[rc];
+            skpn[rt] = dg.skip[rc];
+        }
+    };
+    if constexpr (DIAG) load_flags(0);
     lds_barrier();                                                         // tile 0 staged
     for (int k = 0; k < tw.mine; ++k) {
         f32x4 acc[R / 16];
@@ -224,13 +259,10 @@ __global__ __launch_bounds__(1024, 1) void gn_gemm_fwd_pc_kernel(LinComb xin, in
         for (int rt = 0; rt < R / 16; ++rt) acc[rt] = t0;
         const int row0 = tw.tile(k) * R + r;
         float dsc[R / 16], skp[R / 16];
-        if (DIAG) {                               // at the head of the tile, unconditional, from a clamped row
+        if constexpr (DIAG) {                     // this tile's flags were requested a tile ago; now the next tile's
 #pragma unroll
-            for (int rt = 0; rt < R / 16; ++rt) {
-                const int rc = min(row0 + 16 * rt, n_rows - 1);
-                dsc[rt] = dg.diag[rc];
-                skp[rt] = dg.skip[rc];
-            }
+            for (int rt = 0; rt < R / 16; ++rt) { dsc[rt] = dscn[rt]; skp[rt] = skpn[rt]; }
+            load_flags(k + 1);
         }
         tile_product<R>(lds + (k & 1) * BUF_B + rd_off, A, acc);
 #pragma unroll
@@ -246,8 +278,13 @@ __global__ __launch_bounds__(1024, 1) void gn_gemm_fwd_pc_kernel(LinComb xin, in
                         m[c] = fmaf(dsc[rt], acc[rt][c], 0.f);
                         asm volatile("" : "+v"(m[c]));        // the record's sum is rounded before the bias is added
                     }
-                    *reinterpret_cast<float4*>(dg.K + (int64_t)row * D + n0 + 4 * g) =
-                        make_float4(fmaxf(m[0] + bv.x, 0.f), fmaxf(m[1] + bv.y, 0.f), fmaxf(m[2] + bv.z, 0.f), fmaxf(m[3] + bv.w, 0.f));
+                    float4 kv = make_float4(fmaxf(m[0] + bv.x, 0.f), fmaxf(m[1] + bv.y, 0.f), fmaxf(m[2] + bv.z, 0.f), fmaxf(m[3] + bv.w, 0.f));
+                    if constexpr (LAST) {         // epilogue_store4 with pre = {1.0, P}: p = fmaf(1, P, 0), y = fmaf(alpha, k, p)
+                        const float4 pv = *reinterpret_cast<const float4*>(lds + (k & 1) * BUF_B + pt_off + rt * 16 * LDX * 4);
+                        kv = make_float4(fmaf(dg.alpha, kv.x, fmaf(1.f, pv.x, 0.f)), fmaf(dg.alpha, kv.y, fmaf(1.f, pv.y, 0.f)),
+                                         fmaf(dg.alpha, kv.z, fmaf(1.f, pv.z, 0.f)), fmaf(dg.alpha, kv.w, fmaf(1.f, pv.w, 0.f)));
+                    }
+                    *reinterpret_cast<float4*>(dg.K + (int64_t)row * D + n0 + 4 * g) = kv;
                 }
             }
         }
@@ -738,6 +775,31 @@ int gode_pc_fwd_diag_launch(const LinComb& lc, int64_t n_rows, float eps, const 
     if (cg == 0) GODE_FPCDN(0) else if (cg == 4) GODE_FPCDN(4)
 #undef GODE_FPCDN
 #undef GODE_FPCD
+    return GODE_E_UNSUPPORTED;
+}
+
+// the last stage of a forward rk4 step (AUX and DIAG): four terms, no x_out; dg.K receives the closing combination P on
+// the rows with dg.diag == 0 and y_new = fmaf(dg.alpha, relu(a_ii S + bias), P) on the others.  The profiler bracket is
+// the one of the plain AUX launch this one replaces.
+int gode_pc_fwd_diag_aux_launch(const LinComb& lc, int64_t n_rows, float eps, const float* gamma, const float* beta,
+                                const float* W, int has_time, float t, float* S, const float* aux_coef, const FwdDiag& dg,
+                                int cg, hipStream_t s)
+{
+    int rc = 0;
+    if (lc.n != 4 || !aux_coef || !dg.diag || !dg.skip || !dg.bias || !dg.K) return GODE_E_UNSUPPORTED;
+    AuxCoef ac;
+    for (int j = 0; j < GODE_MAX_TERMS; ++j) ac.c[j] = j < lc.n ? aux_coef[j] : 0.f;
+#define GODE_FPCL(CGV)                                                                                             \
+    { const size_t lds = 2 * ((size_t)Img<32>::BUF_B + 32 * LDX * 4);                                              \
+      const int64_t blocks = pc_blocks(n_rows, 32);                                                                \
+      rc = set_lds_pc(gn_gemm_fwd_pc_kernel<CGV, 4, false, 32, true, true>, lds); if (rc) return rc;               \
+      const int slot = gode_prof_begin(s, D, n_rows, (int64_t)lc.n - 1 + 1, GODE_PROF_GEMM_FWD | GODE_PROF_FORM_PC); \
+      hipLaunchKernelGGL((gn_gemm_fwd_pc_kernel<CGV, 4, false, 32, true, true>), dim3((unsigned)blocks), dim3(1024), lds, s, \
+                         lc, (int)n_rows, eps, gamma, beta, W, has_time, t, S, (float*)nullptr, ac, dg.K, dg);    \
+      gode_prof_end(s, slot);                                                                                      \
+      GODE_LAUNCH_CHECK(); return 0; }
+    if (cg == 0) GODE_FPCL(0) else if (cg == 4) GODE_FPCL(4)
+#undef GODE_FPCL
     return GODE_E_UNSUPPORTED;
 }
 

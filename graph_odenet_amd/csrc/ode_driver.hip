@@ -113,14 +113,19 @@ bool close_once_route(const gode_gcn_odefunc_t* f) {
 
 // Gf of a last stage (input terms xin) that also leaves P (terms pre) in `p_out`.  *formed = false (and the plain launch
 // issued) where the kernel the options select cannot: the caller then closes the step from the four terms as before.
+// diag_taken (forward solve, no x_out; the ODE function carries A's core list): the launch may also close the
+// diagonal-only rows, p_out[i] = P[i] + alpha relu(a_ii S[i] + b), and says in *diag_taken whether it did.
 int gf_last_stage(const gode_gcn_odefunc_t* f, const gode_lincomb_t& xin, const gode_lincomb_t& pre, float t, float* S,
-                  float* x_out, float* p_out, bool* formed, void* stream) {
+                  float* x_out, float* p_out, bool* formed, void* stream, float alpha = 0.f, int32_t* diag_taken = nullptr) {
     *formed = false;
     bool distinct = p_out != S && p_out != x_out;
     for (int j = 0; j < xin.n; ++j) distinct = distinct && p_out != xin.ptr[j];
     if (distinct && xin.n == pre.n) {       // same arrays in the same order (every A38[3][j] is non-zero)
-        const int rc = gode_gn_time_gemm_xout_aux_f32(&xin, f->n, f->d, f->groups, f->eps, f->gamma, f->beta, f->W, f->d, 1, t, S,
-                                                      x_out, pre.coef, p_out, stream);
+        const int rc = (diag_taken && !x_out)
+            ? gode_gn_time_gemm_diag_aux_f32(&xin, f->n, f->d, f->groups, f->eps, f->gamma, f->beta, f->W, f->d, 1, t, S,
+                                             pre.coef, p_out, alpha, f->a_diag, f->at_diag, f->b, diag_taken, stream)
+            : gode_gn_time_gemm_xout_aux_f32(&xin, f->n, f->d, f->groups, f->eps, f->gamma, f->beta, f->W, f->d, 1, t, S,
+                                             x_out, pre.coef, p_out, stream);
         if (rc != GODE_E_UNSUPPORTED) { *formed = rc == 0; return rc; }
     }
     return gode_gn_time_gemm_xout_f32(&xin, f->n, f->d, f->groups, f->eps, f->gamma, f->beta, f->W, f->d, 1, t, S, x_out, stream);
@@ -132,9 +137,10 @@ struct StepClose { gode_lincomb_t pre; float alpha; bool once; };
 // Gf then Sp of one evaluation on the large route: out = f(t, sum xin) through S, or the closed step (`close`).  On the
 // once route Gf leaves the closing combination in `out`, which Sp then reads and overwrites.  k_save: Sp also stores the
 // plain derivative there (the k_4 a backprop record keeps).
-// diag_ok (plain evaluations only): the ODE function carries A's core list and the caller runs the forward rk4 solve -
-// Gf also stores `out` of the diagonal-only rows and Sp runs without them, where Gf reports that it did (per launch:
-// the fp32-MFMA forward kernel, option fwd_pc 0, has no such form)
+// diag_ok (plain evaluations, and the closed step on the once route without k_save under option diag_last): the ODE
+// function carries A's core list and the caller runs the forward rk4 solve - Gf also stores `out` of the diagonal-only
+// rows and Sp runs without them, where Gf reports that it did (per launch: the fp32-MFMA forward kernel, option fwd_pc
+// 0, has no such form)
 int feval_large(const gode_gcn_odefunc_t* f, const gode_lincomb_t& xin, float t, float* S, float* out,
                 const StepClose* close, float* k_save, void* stream, bool diag_ok = false) {
     const int64_t d = f->d;
@@ -150,15 +156,23 @@ int feval_large(const gode_gcn_odefunc_t* f, const gode_lincomb_t& xin, float t,
         return gode_spmm_csr_f32(g.rowptr, g.col, g.val, f->a_core_items, f->a_n_core, g.long_rows, g.n_long, g.partial,
                                  S, d, out, d, g.n_rows, d, &ep, stream);
     }
+    int32_t last_taken = 0;
     if (close && close->once) {
-        GODE_TRY(gf_last_stage(f, xin, close->pre, t, S, nullptr, out, &p_formed, stream));
+        const bool diag_last = diag_ok && !k_save && gode_opt_diag_last();
+        GODE_TRY(gf_last_stage(f, xin, close->pre, t, S, nullptr, out, &p_formed, stream, close->alpha,
+                               diag_last ? &last_taken : nullptr));
     } else {
         GODE_TRY(gode_gn_time_gemm_f32(&xin, f->n, d, f->groups, f->eps, f->gamma, f->beta, f->W, d, 1, t, S, stream));
     }
     gode_spmm_epilogue_t ep = relu_bias_epilogue(f);
     if (close) { ep.pre = p_formed ? one_term(out) : close->pre; ep.alpha = close->alpha; }
-    if (!k_save) return spmm(f->A, S, out, d, &ep, stream);
     const gode_graph_t& g = f->A;
+    if (last_taken) {                                           // `out` holds y_new on the diagonal-only rows, P elsewhere
+        ep.n_items_full = g.n_items;
+        return gode_spmm_csr_f32(g.rowptr, g.col, g.val, f->a_core_items, f->a_n_core, g.long_rows, g.n_long, g.partial,
+                                 S, d, out, d, g.n_rows, d, &ep, stream);
+    }
+    if (!k_save) return spmm(f->A, S, out, d, &ep, stream);
     return gode_spmm_csr_save_f32(g.rowptr, g.col, g.val, g.items, g.n_items, g.long_rows, g.n_long, g.partial,
                                   S, d, out, d, g.n_rows, d, &ep, k_save, stream);
 }
@@ -177,7 +191,7 @@ int rk4_forward_step(const gode_gcn_odefunc_t* f, const gode_rk4_workspace_t* ws
             continue;
         }
         const StepClose close = {combine_terms(y, k, h), (float)(h * B38[3]), close_once};
-        if (!fused) GODE_TRY(feval_large(f, xin, ts, ws->S, ynext, &close, keep_k4 ? k[3] : nullptr, stream));
+        if (!fused) GODE_TRY(feval_large(f, xin, ts, ws->S, ynext, &close, keep_k4 ? k[3] : nullptr, stream, diag_ok));
         else if (keep_k4) GODE_TRY(gode_gcn_feval_small_save_f32(f, &xin, ts, close.alpha, &close.pre, ynext, k[3], stream));
         else GODE_TRY(gode_gcn_feval_small_f32(f, &xin, ts, close.alpha, &close.pre, nullptr, nullptr, ynext, stream));
     }
@@ -200,9 +214,9 @@ extern "C" int gode_gcn_ode_rk4_forward(const gode_gcn_odefunc_t* f, float* y, f
     float* k[4] = {ws->ky[0], ws->ky[1], ws->ky[2], ws->ky[3]};
     const bool fused = fused_small(f);
     const bool close_once = close_once_route(f);
-    // diagonal-only rows of A (option diag_rows; large route at d = 128): stages 0-2.  The last stage stays on the full
-    // list: its closing combination is written by the same launch's producer waves, and the consumer would have to read
-    // it back inside the launch.
+    // diagonal-only rows of A (option diag_rows; large route at d = 128): stages 0-2, and on the closing-combination-once
+    // route the last stage as well (option diag_last): the producer waves of its dense launch hand the closing combination
+    // to the consumer waves through LDS, and the consumer is the only writer of a diagonal-only row of y_new.
     const bool diag_ok = gode_opt_diag_rows() && !fused && f->n > kMergedFinishMaxRows && f->d == 128 && f->a_core_items &&
                          f->a_diag && f->at_diag && f->A.items && f->a_n_core > 0 && f->a_n_core <= f->A.n_items;
     for (int i = 0; i < n_steps; ++i) {

@@ -76,9 +76,11 @@ int         gode_abi_version(void);
  * products of more than 65 536 records without a cotangent output walk several tiles of 256 / (d / 4) records per block,
  * the records' indices fetched ahead; 0: one tile per block; 2..64: that many tiles per block; same bits in every case),
  * "diag_rows" (1 default / 0: the rk4 forward and adjoint drivers use the core record lists of A and A^T where the ODE
- * function carries them, see gode_gcn_odefunc_t; 0: the full lists; same bits either way).
+ * function carries them, see gode_gcn_odefunc_t; 0: the full lists; same bits either way), "diag_last" (1 default / 0:
+ * under "diag_rows" and "rk_close_once" the last stage of a forward rk4 step uses A's core list as well,
+ * gode_gn_time_gemm_diag_aux_f32; 0: stages 0-2 only; same bits either way).
  * Initial values come from GODE_GEMM_SPLIT / GODE_OVERLAP / GODE_WGRAD_SPLIT / GODE_BWD_PC / GODE_FWD_PC / GODE_SPMM_PIPE /
- * GODE_DIAG_ROWS.
+ * GODE_DIAG_ROWS / GODE_DIAG_LAST.
  * Returns 0 or GODE_E_UNSUPPORTED. */
 int         gode_set_option(const char* name, int value);
 int         gode_get_option(const char* name);
@@ -221,6 +223,21 @@ int gode_gn_time_gemm_xout_aux_f32(const gode_lincomb_t* xin /* host */, int64_t
                                    const float* W, int64_t d_out, int has_time, float t,
                                    float* S, float* x_out /* nullable */, const float* aux_coef /* host */,
                                    float* aux_out, void* stream);
+/* gode_gn_time_gemm_xout_aux_f32 without x_out for the last stage of a forward rk4 step, where the product that follows
+ * is K = P + alpha * relu(A S + bias) with the closing combination P = aux_out read and overwritten in place.  Where it
+ * runs on the producer / consumer kernel (d_in = d_out = 128, >= 65 536 rows, option "fwd_pc" bit 1, 4 terms, 0 or 4
+ * channels per group) K receives P[i,:] on the rows with diag[i] == 0 and, on the others,
+ *   K[i,:] = fmaf(alpha, max(fmaf(diag[i], S[i,:], 0) + bias, 0), P[i,:])
+ * - what gode_spmm_csr_f32 with bias, relu, pre = {1.0, K} and alpha makes of a row whose only entry is diag[i] on the
+ * diagonal, bit for bit, so that product can run without those rows - and S[i,:] of a row with skip[i] != 0 is not
+ * stored.  diag, skip, bias, K as for gode_gn_time_gemm_diag_f32.  *taken (host) = 1 where that form ran; = 0 where the
+ * call did what gode_gn_time_gemm_xout_aux_f32 does (K = P on every row, or GODE_E_UNSUPPORTED and nothing launched). */
+int gode_gn_time_gemm_diag_aux_f32(const gode_lincomb_t* xin /* host */, int64_t n_rows, int64_t d_in,
+                                   int32_t groups, float eps, const float* gamma, const float* beta,
+                                   const float* W, int64_t d_out, int has_time, float t,
+                                   float* S, const float* aux_coef /* host */, float* K, float alpha,
+                                   const float* diag, const float* skip, const float* bias,
+                                   int32_t* taken /* host */, void* stream);
 
 /* Two square products (d_out = d_in = d) over the same input in one launch: Sa = [t | xn] Wa, Sb = [t | xn] Wb
  * (the two message projections of the GAT ODE function); x_out as above. */
@@ -568,7 +585,8 @@ typedef struct gode_gcn_odefunc {
      * non-zero diagonal (whatever its column holds), 0 elsewhere; a_core_items = A.items without the records of those
      * rows (a_n_core records).  gode_gcn_ode_rk4_forward (more than 65 536 rows, option "diag_rows") then lets the dense
      * launch of stages 0-2 store relu(a_ii S[i] + b) of such a row (gode_gn_time_gemm_diag_f32; skip = at_diag) and runs
-     * the stage's SpMM on the core list - per launch, where the dense launch reports that form taken. */
+     * the stage's SpMM on the core list - per launch, where the dense launch reports that form taken.  The last stage
+     * does the same on the closed step (gode_gn_time_gemm_diag_aux_f32; options "rk_close_once" and "diag_last"). */
     const int32_t* a_core_items; int64_t a_n_core; const float* a_diag;
 } gode_gcn_odefunc_t;
 

@@ -1,13 +1,16 @@
-"""A/B of the run-time option diag_rows on the benchmark's training step, in ONE process.
+"""A/B of the run-time option diag_rows - or, with --option diag_last, of that option under diag_rows 1 - on the
+benchmark's training step, in ONE process.
 
 The step is bench.py's (R-MAT 2^20 rows / 10 M edges, d = 128, ODEGCN3 rk4 16 steps, adjoint backward, Adam; one GPU).
 The option is set to 1, 0, 1, 0, 1 in turn; each reading is one warm-up step and three timed steps between device
 synchronisations (parallel.run_timed, the helper bench.py times with).  Option 0 issues the launches of the code before
 the option existed (the forward solve's products with A and the adjoint's products with A^T on their full record lists,
 no row stored by the dense launch or by the launch that forms dZ in their place), so the 0 readings are the yardstick; a gain counts when every 1 reading beats every 0 reading and the mean gap is at
-least three times the spread among readings of the same setting.
+least three times the spread among readings of the same setting (--min-ratio; diag_last was held to five times).
+diag_last 0 likewise issues the launches of the code before that option: the last stage of every forward rk4 step on A's
+full list.
 
-    python tools/diag_rows_ab.py [--scale 20] [--edges 10000000] [--ode-steps 16] [--steps 3] [--warmup 1]
+    python tools/diag_rows_ab.py [--option diag_rows] [--scale 20] [--edges 10000000] [--ode-steps 16] [--steps 3] [--warmup 1]
 """
 import argparse
 import json
@@ -30,7 +33,9 @@ def main():
     ap.add_argument("--ode-steps", type=int, default=16)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--order", default="1,0,1,0,1", help="settings of diag_rows, one reading each")
+    ap.add_argument("--order", default="1,0,1,0,1", help="settings of the option, one reading each")
+    ap.add_argument("--option", default="diag_rows", choices=["diag_rows", "diag_last"])
+    ap.add_argument("--min-ratio", type=float, default=3.0, help="mean gap over same-setting spread that counts as a gain")
     args = ap.parse_args()
     from graph_odenet_amd import _lib, models, parallel
     from graph_odenet_amd.optim import Adam
@@ -59,32 +64,33 @@ def main():
         opt.step()
         return loss
 
-    old = lib.gode_get_option(b"diag_rows")
+    name = args.option.encode()
+    old = lib.gode_get_option(name)
     readings = []
     try:
         for _ in range(2):                       # both settings' kernels loaded before the first reading
             for v in (1, 0):
-                assert lib.gode_set_option(b"diag_rows", v) == 0
+                assert lib.gode_set_option(name, v) == 0
                 step()
         torch.cuda.synchronize()
         for v in [int(t) for t in args.order.split(",")]:
-            assert lib.gode_set_option(b"diag_rows", v) == 0 and lib.gode_get_option(b"diag_rows") == v
+            assert lib.gode_set_option(name, v) == 0 and lib.gode_get_option(name) == v
             elapsed, loss = parallel.run_timed(step, args.steps, args.warmup, dev)
             ms = 1e3 * elapsed / args.steps
             readings.append((v, ms))
-            print("diag_rows %d: %8.2f ms/step   (loss %.5f)" % (v, ms, float(loss)), flush=True)
+            print("%s %d: %8.2f ms/step   (loss %.5f)" % (args.option, v, ms, float(loss)), flush=True)
     finally:
-        lib.gode_set_option(b"diag_rows", old)
+        lib.gode_set_option(name, old)
     on = [ms for v, ms in readings if v == 1]
     off = [ms for v, ms in readings if v == 0]
-    res = {"readings": [{"diag_rows": v, "ms_per_step": round(ms, 2)} for v, ms in readings]}
+    res = {"readings": [{args.option: v, "ms_per_step": round(ms, 2)} for v, ms in readings]}
     if on and off:
         gap = sum(off) / len(off) - sum(on) / len(on)
         spread = max(max(on) - min(on), max(off) - min(off))
         res.update({"mean_on_ms": round(sum(on) / len(on), 2), "mean_off_ms": round(sum(off) / len(off), 2),
                     "gap_ms": round(gap, 2), "same_setting_spread_ms": round(spread, 2),
                     "every_on_beats_every_off": max(on) < min(off),
-                    "gap_at_least_3x_spread": gap >= 3.0 * spread})
+                    "gap_at_least_%gx_spread" % args.min_ratio: gap >= args.min_ratio * spread})
     res["graph"] = {str(k): v for k, v in g.__dict__.get("_tuned_info", {}).items()}
     print(json.dumps(res))
 

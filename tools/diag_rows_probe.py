@@ -11,7 +11,12 @@ Then the two launches of an adjoint stage that the option diag_rows changes, tim
 epilogue (which stores the isolated rows' share of A^T dZ itself) and SpT(g) on A^T's list without those rows - with no
 row taken out, with n / 8 of them (the share at which gcn_ode.tuned_graph starts to hand the list over) and with all.
 
+Last, the product of the forward solve's last stage (section "last"): relu, bias, pre = {1.0, P} read and overwritten in
+place, alpha = h b_3 - on A's whole list against A's core list, alternating as above.  That is the premise of taking the
+diagonal-only rows out of that launch as well (option diag_last).
+
     python tools/diag_rows_probe.py [--scale 20] [--edges 10000000] > profiles/diag_rows_probe.txt
+    python tools/diag_rows_probe.py --sections last > profiles/diag_last_probe.txt
 """
 import argparse
 import ctypes
@@ -27,6 +32,38 @@ sys.path.insert(0, ROOT)
 D = 128
 
 
+def last_stage(args, lib, _lib, g, S, timed, ode_steps=16):
+    """Sp(3) of a forward rk4 step: y_new = P + h b_3 relu(A S + b), P and y_new in one array."""
+    n = g.n_rows
+    dr = g.diag_rows()
+    gen = torch.Generator(device=S.device).manual_seed(8)
+    bias = torch.randn(D, generator=gen, device=S.device)
+    P = torch.randn(n, D, generator=gen, device=S.device)
+    alpha = (1.0 / ode_steps) * 0.125                        # h b_3 of the 3/8 rule
+
+    def launch(items, cnt):
+        ep = _lib.SpmmEpilogue()
+        ep.bias, ep.relu, ep.alpha, ep.n_items_full = bias.data_ptr(), 1, alpha, g.n_items
+        ep.pre = _lib.lincomb([(1.0, P)])
+        _lib.check(lib.gode_spmm_csr_f32(_lib.ptr(g.rowptr), _lib.ptr(g.col), _lib.ptr(g.val), _lib.ptr(items), cnt,
+                                         _lib.ptr(g.long_rows), g.n_long, _lib.ptr(g.partial(D)), _lib.ptr(S), D, _lib.ptr(P), D,
+                                         n, D, ctypes.byref(ep), _lib.stream_ptr()), "gode_spmm_csr_f32")
+
+    print("last stage of a forward rk4 step: relu, bias, pre = {1.0, P} in place, alpha = %.6f; A flags %d of %d rows (%.2f %%)"
+          % (alpha, dr.n_flagged, n, 100.0 * dr.n_flagged / n))
+    print("%-5s %-5s %9s %9s %13s" % ("round", "list", "records", "ms", "min..max"))
+    med = {"full": [], "core": []}
+    for r in range(args.rounds):
+        for lname, items, cnt in (("full", g.items, g.n_items), ("core", dr.items, dr.n_items)):
+            m, lo, hi = timed(lambda: launch(items, cnt))
+            med[lname].append(m)
+            print("%-5d %-5s %9d %9.4f %5.3f..%5.3f" % (r, lname, cnt, m, lo, hi), flush=True)
+    full, core = statistics.median(med["full"]), statistics.median(med["core"])
+    print("last stage: full %.4f ms, core %.4f ms, difference %.4f ms per launch (spread among rounds: full %.4f, core %.4f); "
+          "the rule: build the dense form only if the difference is at least 0.05 ms\n"
+          % (full, core, full - core, max(med["full"]) - min(med["full"]), max(med["core"]) - min(med["core"])), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scale", type=int, default=20)
@@ -34,7 +71,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--launches", type=int, default=10)
     ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--sections", default="plain,adjoint,last", help="which of the three parts to run")
     args = ap.parse_args()
+    sections = set(args.sections.split(","))
+    assert sections and sections <= {"plain", "adjoint", "last"}, args.sections
     from graph_odenet_amd import _lib, gcn_ode
     from graph_odenet_amd.synth import rmat_graph
     lib = _lib.load()
@@ -71,8 +111,9 @@ def main():
 
     both = (g.diag_rows().diag != 0) & (g.transpose().diag_rows().diag != 0)
     print("diagonal-only in A and in A^T: %d rows (%.2f %%)" % (int(both.sum()), 100.0 * int(both.sum()) / n))
-    print("\n%-3s %-5s %-5s %9s %9s %9s %13s" % ("", "round", "list", "records", "MB", "ms", "min..max"))
-    for gname, gr in (("A", g), ("A^T", g.transpose())):
+    if "plain" in sections:
+        print("\n%-3s %-5s %-5s %9s %9s %9s %13s" % ("", "round", "list", "records", "MB", "ms", "min..max"))
+    for gname, gr in (("A", g), ("A^T", g.transpose())) if "plain" in sections else ():
         dr = gr.diag_rows()
         lists = (("full", gr.items, gr.n_items), ("core", dr.items, dr.n_items))
         med = {"full": [], "core": []}
@@ -89,6 +130,11 @@ def main():
               "(spread among rounds: full %.4f, core %.4f)\n"
               % (gname, dr.n_flagged, n, 100.0 * dr.n_flagged / n, full, core, full - core,
                  max(med["full"]) - min(med["full"]), max(med["core"]) - min(med["core"])), flush=True)
+
+    if "last" in sections:
+        last_stage(args, lib, _lib, g, X, timed)
+    if "adjoint" not in sections:
+        return
 
     # ---- the pair of an adjoint stage: Sp(g) with the cotangent epilogue (bias, relu, two terms, dZ, per-block column
     # sums), then SpT(g) = A^T dZ.  "full": as before the option; "isolated": Sp(g) stores a_ii dZ[i] of every isolated row
