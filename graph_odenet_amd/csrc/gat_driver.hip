@@ -6,6 +6,8 @@
 // and the error-ratio sums, so that an adaptive step on a citation-size graph is one call instead of ~200.
 // The launch sequence of one evaluation is graph_odenet_amd/gat_ode.py (GatOdeField / GatOdeAdjointField), which
 // branches on the head count where this file does.
+// At the end of the file: backprop through rk4 and dopri5 solves on launch-bound graphs (gode_gat_ode_rk4_forward_save,
+// gode_gat_ode_rk4_backprop, gode_gat_ode_dopri5_step_backprop), whose stage reverse is the adjoint stage's (stage_vjp).
 #include "rk_driver.h"
 #include "options.h"
 
@@ -85,18 +87,22 @@ int eval_forward(const gode_gat_odefunc_t* f, const gode_gat_workspace_t* w, god
     return gode_gat_agg_f32_fwd(&f->mt, f->src, f->tgt, &pr, f->d, f->bf, w->a, w->amax, f->eps, ky, w->wgt, w->den, stream);
 }
 
-// theta-k layout: [Wsrc ((d+1)*d) | Wtgt ((d+1)*d) | Wlog ((d+1)*2H) | bf (d) | bw (H) | gamma (d) | beta (d)]   (H = 1: one head)
-int eval_adjoint(const gode_gat_odefunc_t* f, const gode_gat_workspace_t* w, gode_lincomb_t yin, const gode_lincomb_t& ain,
-                 float t, float* ky, float* ka, float* kat, float* kth, void* stream) {
+// The reverse of one evaluation k = f(t, sum yin) with cotangent cot_scale * (sum cot), shared by the adjoint step (cot = a,
+// scale -1) and the backprop sweeps (cot = kbar_s, scale +1): f evaluated again at the stage input (ky, which masks the
+// cotangent: the relu), the aggregation's VJP, the path through the maxima, the incidence sums into dPs / dPt / dA2 and -
+// with `part`, on launch-bound graphs - the dense VJP into ka (+ pre) and into the partial slot `part`.  yin names the
+// combined input on return.  part == NULL: the caller issues the dense half itself.
+int stage_vjp(const gode_gat_odefunc_t* f, const gode_gat_workspace_t* w, gode_lincomb_t* yin, const gode_lincomb_t& cot,
+              float cot_scale, float t, float* ky, float* ka, const gode_lincomb_t* pre, float* part, void* stream) {
     const int64_t H = n_heads(f);
-    const int64_t n = f->n, d = f->d, o = d / H, nv = n * H, nW = (d + 1) * d, nL = (d + 1) * 2 * H;
-    GODE_TRY(eval_forward(f, w, &yin, t, ky, stream));                  // yin now names the combined input
+    const int64_t n = f->n, d = f->d, o = d / H, nv = n * H;
+    GODE_TRY(eval_forward(f, w, yin, t, ky, stream));                  // yin now names the combined input
     const gode_gat_proj_t pr = proj_of(f, w);
     int32_t did = 0;
-    GODE_TRY(gode_gat_agg_f32_bwd(&f->mt, f->src, f->tgt, &pr, o, H > 1 ? w->zeros : f->bf, w->wgt, w->den, ky, nullptr, &ain,
-                                  -1.f, w->dz, w->da, w->dPt, o, w->dA2 + 1, 2, &did, stream));
+    GODE_TRY(gode_gat_agg_f32_bwd(&f->mt, f->src, f->tgt, &pr, o, H > 1 ? w->zeros : f->bf, w->wgt, w->den, ky, nullptr, &cot,
+                                  cot_scale, w->dz, w->da, w->dPt, o, w->dA2 + 1, 2, &did, stream));
     if (f->n_edges > 0) {
-        if (H > 1 && raw_logits(f) && !did && w->small_part)     // first half; the dense VJP launch below closes the step
+        if (H > 1 && raw_logits(f) && !did && part)     // first half; the dense VJP launch below closes the step
             GODE_TRY(gode_gat_maxpath_heads_part_f32(w->a, w->da, f->n_edges, H, f->tgt, w->heads_scratch, stream));
         else if (H > 1 && raw_logits(f))
             GODE_TRY(gode_gat_maxpath_heads_raw_f32(w->a, w->da, f->n_edges, H, f->tgt, did ? w->dA2 + 1 : nullptr, 2,
@@ -119,13 +125,23 @@ int eval_adjoint(const gode_gat_odefunc_t* f, const gode_gat_workspace_t* w, god
         GODE_TRY(gode_gat_scatter_f32(f->ms_inc.rowptr, f->ms_inc.col, f->mt_inc.rowptr, f->mt_inc.col, w->dz, w->da, o, nv,
                                       w->dPs, o, w->dPt, o, w->dA2, w->dA2 + 1, 2, stream));
     }
-    if (w->small_part && small_dense(f)) {      // k_a and all parameter-gradient partials in one launch, one more to close
-        GODE_TRY(gode_gat_dense_vjp_small_f32(&yin, n, d, f->groups, f->eps_gn, f->gamma, f->beta, f->Wsrc, f->Wtgt, f->Wlog, H,
-                                              w->dPs, w->dPt, w->dA2, 1.f, nullptr, ka, w->small_part,
-                                              (H > 1 && raw_logits(f) && !did && f->n_edges > 0) ? w->heads_scratch : nullptr, f->src, f->tgt,
-                                              f->n_edges, f->Wpacked, stream));
-        return gode_gat_small_finish_f32(w->small_part, n, d, H, t, kth, kat, stream);
-    }
+    if (!part) return 0;
+    // k_a and all parameter-gradient partials in one launch; a closing launch reads the partials
+    return gode_gat_dense_vjp_small_f32(yin, n, d, f->groups, f->eps_gn, f->gamma, f->beta, f->Wsrc, f->Wtgt, f->Wlog, H,
+                                        w->dPs, w->dPt, w->dA2, 1.f, pre, ka, part,
+                                        (H > 1 && raw_logits(f) && !did && f->n_edges > 0) ? w->heads_scratch : nullptr, f->src, f->tgt,
+                                        f->n_edges, f->Wpacked, stream);
+}
+
+// theta-k layout: [Wsrc ((d+1)*d) | Wtgt ((d+1)*d) | Wlog ((d+1)*2H) | bf (d) | bw (H) | gamma (d) | beta (d)]   (H = 1: one head)
+// An adjoint stage: the stage VJP with cotangent -a, then the parameter derivative closed from what it left.
+int eval_adjoint(const gode_gat_odefunc_t* f, const gode_gat_workspace_t* w, gode_lincomb_t yin, const gode_lincomb_t& ain,
+                 float t, float* ky, float* ka, float* kat, float* kth, void* stream) {
+    const int64_t H = n_heads(f);
+    const int64_t n = f->n, d = f->d, nW = (d + 1) * d, nL = (d + 1) * 2 * H;
+    float* part = (w->small_part && small_dense(f)) ? w->small_part : nullptr;
+    GODE_TRY(stage_vjp(f, w, &yin, ain, -1.f, t, ky, ka, nullptr, part, stream));
+    if (part) return gode_gat_small_finish_f32(part, n, d, H, t, kth, kat, stream);      // one more launch to close
     float* g_src = kth; float* g_tgt = kth + nW; float* g_log = kth + 2 * nW;
     float* g_bf = g_log + nL; float* g_bw = g_bf + d; float* g_gamma = g_bw + H; float* g_beta = g_gamma + d;
     const int64_t nb = gode_gemm_bwd_parts(n);
@@ -248,4 +264,137 @@ extern "C" int gode_gat_ode_dopri5_step_adjoint(const gode_gat_odefunc_t* f, con
     }
     GODE_TRY(gode_lincomb_multi_f32(outs, sols, lens, 4, stream));
     return gode_rk_errnorm_multi_f32(sums, e0, e1, errs, lens, 4, rtol, atol, err_scratch, stream);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Backprop through the solve on launch-bound graphs (odeint._OdeintBackprop; the GCN forms are in ode_driver.hip and
+// the algebra is stated there).  The reverse of a stage is stage_vjp with cotangent scale +1: the stage is evaluated
+// again (k_scratch) rather than its saved k_s read, because the aggregation's VJP wants the edge weights and sums the
+// evaluation leaves in the workspace.  Every swept stage writes its parameter partials into a slot of its own and ONE
+// gode_gat_small_close_stages_f32 launch per step adds them to theta.
+// ---------------------------------------------------------------------------------------------------------------
+namespace {
+
+int check_sweep(const gode_gat_odefunc_t* f, const gode_gat_workspace_t* w) {
+    int rc = check_common(f, w, true); if (rc) return rc;
+    if (!small_dense(f) || !w->small_part) return GODE_E_UNSUPPORTED;
+    return 0;
+}
+int check_steps(int32_t n_steps, int32_t step_begin, int32_t step_end) {
+    if (n_steps <= 0 || step_begin < 0 || step_end > n_steps || step_begin >= step_end) return GODE_E_SHAPE;
+    return 0;
+}
+inline int64_t part_slot(const gode_gat_odefunc_t* f) {
+    return gode_gat_small_parts(f->n, f->d) * gode_gat_small_part_len(f->d, n_heads(f));
+}
+
+}  // namespace
+
+extern "C" int gode_gat_ode_rk4_forward_save(const gode_gat_odefunc_t* f, const float* y0, float* y_end, float* save,
+                                             const gode_gat_workspace_t* ws, float t0, float t1, int32_t n_steps,
+                                             int32_t step_begin, int32_t step_end, void* stream)
+{
+    if (!f || !ws || !y0 || !y_end || !save) return GODE_E_NULLPTR;
+    int rc = check_steps(n_steps, step_begin, step_end); if (rc) return rc;
+    rc = check_sweep(f, ws); if (rc) return rc;
+    const int64_t nd = f->n * f->d;
+    const double h = ((double)t1 - (double)t0) / n_steps;
+    if (y0 != save) {                                            // record 0 starts with a copy of y0
+        const gode_lincomb_t c = one_term(y0);
+        GODE_TRY(gode_lincomb_f32(save, &c, nd, stream));
+    }
+    for (int i = step_begin; i < step_end; ++i) {
+        float* rec = save + (int64_t)(i - step_begin) * 5 * nd;
+        float* k[4] = {rec + nd, rec + 2 * nd, rec + 3 * nd, rec + 4 * nd};
+        float* ynext = (i + 1 < step_end) ? rec + 5 * nd : y_end;      // the next record's y_n, or the result
+        const double t = (double)t0 + i * h;
+        for (int s = 0; s < 4; ++s) {
+            gode_lincomb_t yin = stage_terms(rec, k, s, h);
+            GODE_TRY(eval_forward(f, ws, &yin, (float)(t + C38[s] * h), k[s], stream));
+        }
+        gode_lincomb_t sol = one_term(rec);
+        for (int s = 0; s < 4; ++s) { sol.coef[sol.n] = (float)(h * B38[s]); sol.ptr[sol.n] = k[s]; ++sol.n; }
+        GODE_TRY(gode_lincomb_f32(ynext, &sol, nd, stream));
+    }
+    return 0;
+}
+
+extern "C" int gode_gat_ode_rk4_backprop(const gode_gat_odefunc_t* f, const float* save, float* a, float* theta,
+                                         float* const* ybar, float* k_scratch, float* parts, const gode_gat_workspace_t* ws,
+                                         float t0, float t1, int32_t n_steps, int32_t step_begin, int32_t step_end,
+                                         void* stream)
+{
+    if (!f || !ws || !save || !a || !theta || !ybar || !k_scratch || !parts) return GODE_E_NULLPTR;
+    for (int s = 0; s < 4; ++s) if (!ybar[s]) return GODE_E_NULLPTR;
+    int rc = check_steps(n_steps, step_begin, step_end); if (rc) return rc;
+    for (int s = 0; s < 4; ++s) {
+        if (ybar[s] == a || ybar[s] == k_scratch) return GODE_E_SHAPE;
+        for (int r = s + 1; r < 4; ++r) if (ybar[s] == ybar[r]) return GODE_E_SHAPE;
+    }
+    if (k_scratch == a) return GODE_E_SHAPE;
+    rc = check_sweep(f, ws); if (rc) return rc;
+    const int64_t n = f->n, d = f->d, nd = n * d, H = n_heads(f), slot = part_slot(f);
+    const double h = ((double)t1 - (double)t0) / n_steps;
+    for (int i = step_end - 1; i >= step_begin; --i) {
+        float* y = (float*)save + (int64_t)(i - step_begin) * 5 * nd;     // read only
+        float* k[4] = {y + nd, y + 2 * nd, y + 3 * nd, y + 4 * nd};
+        const double t = (double)t0 + i * h;
+        float ts[4];
+        for (int s = 3; s >= 0; --s) {
+            ts[s] = (float)(t + C38[s] * h);
+            const gode_lincomb_t cot = stage_cotangent(TAB38, a, (float)(h * B38[s]), ybar, s, h);
+            gode_lincomb_t yin = stage_terms(y, k, s, h);
+            GODE_TRY(stage_vjp(f, ws, &yin, cot, 1.f, ts[s], k_scratch, ybar[s], nullptr, parts + s * slot, stream));
+        }
+        GODE_TRY(gode_gat_small_close_stages_f32(parts, n, d, H, 4, ts, theta, stream));
+        const gode_lincomb_t sum = sweep_pre(TAB38, a, 1.f, ybar, 0);    // a + Ybar_1 + .. + Ybar_4
+        GODE_TRY(gode_lincomb_f32(a, &sum, nd, stream));
+    }
+    return 0;
+}
+
+extern "C" int gode_gat_ode_dopri5_step_backprop(const gode_gat_odefunc_t* f, const float* y, float* const* k, const float* g,
+                                                 const float* kbar7, double wy, const double* wk, double t, double h,
+                                                 int32_t first, float* const* ybar, float* ybar_n, float* kbar1, float* theta,
+                                                 float* k_scratch, float* parts, const gode_gat_workspace_t* ws, void* stream)
+{
+    if (!f || !ws || !y || !k || !g || !wk || !ybar || !ybar_n || !theta || !k_scratch || !parts) return GODE_E_NULLPTR;
+    if (!first && !kbar1) return GODE_E_NULLPTR;
+    for (int s = 0; s < 7; ++s) if (!k[s]) return GODE_E_NULLPTR;
+    for (int s = first ? 0 : 1; s < 7; ++s) if (!ybar[s]) return GODE_E_NULLPTR;
+    if (ybar_n == g || ybar_n == kbar7 || ybar_n == k_scratch || k_scratch == g || k_scratch == kbar7) return GODE_E_SHAPE;
+    if (!first && (kbar1 == g || kbar1 == kbar7 || kbar1 == ybar_n || kbar1 == k_scratch)) return GODE_E_SHAPE;
+    for (int s = first ? 0 : 1; s < 7; ++s) {
+        if (ybar[s] == g || ybar[s] == kbar7 || ybar[s] == ybar_n || (!first && ybar[s] == kbar1) || ybar[s] == k_scratch)
+            return GODE_E_SHAPE;
+        for (int r = s + 1; r < 7; ++r) if (ybar[s] == ybar[r]) return GODE_E_SHAPE;
+    }
+    int rc = check_sweep(f, ws); if (rc) return rc;
+    const int64_t n = f->n, d = f->d, nd = n * d, H = n_heads(f), slot = part_slot(f);
+    const int last = first ? 0 : 1;                // the last stage the sweep pushes through f
+    bool dead[7] = {};
+    float ts[7];
+    int live = 0;
+    auto cotangent = [&](int s) {
+        gode_lincomb_t c = stage_cotangent(TABDP, g, (float)wk[s], ybar, s, h, dead);
+        if (s == 6 && kbar7) { c.coef[c.n] = 1.f; c.ptr[c.n] = kbar7; ++c.n; }
+        return c;
+    };
+    for (int s = 6; s >= last; --s) {
+        const gode_lincomb_t cot = cotangent(s);
+        if (cot.n == 0) { dead[s] = true; continue; }
+        ts[live] = (float)(t + DPC[s] * h);
+        gode_lincomb_t yin = dp_terms(y, k, DPA[s], s, h, true);
+        GODE_TRY(stage_vjp(f, ws, &yin, cot, 1.f, ts[live], k_scratch, ybar[s], nullptr, parts + live * slot, stream));
+        ++live;
+    }
+    // ybar_n = wy g + sum Ybar_s, and (not first) kbar_1 for the step before: one launch
+    float* outs[2] = {ybar_n, kbar1};
+    gode_lincomb_t lcs[2] = {sweep_pre(TABDP, g, (float)wy, ybar, last, dead), first ? gode_lincomb_t() : cotangent(0)};
+    int64_t lens[2] = {nd, nd};
+    int count = first ? 1 : 2;
+    if (count == 2 && lcs[1].n == 0) { GODE_TRY(gode_zero_f32(kbar1, nd, stream)); count = 1; }
+    GODE_TRY(gode_lincomb_multi_f32(outs, lcs, lens, count, stream));
+    if (live == 0) return 0;
+    return gode_gat_small_close_stages_f32(parts, n, d, H, live, ts, theta, stream);
 }

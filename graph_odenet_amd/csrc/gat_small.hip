@@ -16,6 +16,8 @@
 //                                  bw = odd columns of colsum(dA2)), dgamma, dbeta, and the block's share of
 //                                  a_t = colsums . W[0, :]: replaces 3 + 3 + 2 launches
 //   gode_gat_small_finish_f32      k_theta and k_a_t from the partials: one launch, every load in flight at once
+//   gode_gat_small_close_stages_f32  theta += sum_s k_theta(stage s) over the up to seven stages a backprop sweep pushed
+//                                  through f in one step (gat_driver.hip): one launch, one barrier for all slots
 //
 // Work decomposition as in small.hip: a wave owns a row at a time, a lane holds 4 consecutive columns, the wave's
 // 256/d sub-groups stride over the reduction index of the dense products and are combined with xor-shuffles (fixed
@@ -23,6 +25,7 @@
 #include "common.h"
 #include "dense_common.h"
 #include "options.h"
+#include "prof.h"
 
 namespace {
 
@@ -650,23 +653,31 @@ struct GatFinish {
     // fixed-grid Runge-Kutta step (the adjoint ODE is linear in them and a fixed grid never looks at them in between)
     int n_slots; float ts[4]; float w[4];
 };
+// where entry j of [k_theta | a_t'] sits in a partial row (-1: j is past a_t'), and whether it is in a time row
+__device__ __forceinline__ int gat_finish_source(int j, int d, int nl, int nlp, int heads, int out_len, int plen, bool& is_time_row)
+{
+    const int nW = (d + 1) * d, nL = (d + 1) * nl;
+    const int oBf = 2 * nW + nL, oBw = oBf + d, oGm = oBw + heads;       // theta offsets; gamma, beta are contiguous in both
+    // partial rows are in the VJP kernel's LDS layout: two (d+1) x (d+1) blocks, one (d+1) x (NLP+1) block, dgamma, dbeta, a_t
+    const int RS = d + 1, RSL = nlp + 1, rT = (d + 1) * RS, rL = 2 * rT, rG = rL + (d + 1) * RSL;
+    is_time_row = false;
+    if (j > out_len) return -1;
+    if (j == out_len) return plen - 1;                                   // a_t'
+    if (j < 2 * nW) { const int b = j >= nW, jj = j - b * nW, r = jj / d; is_time_row = r == 0; return b * rT + r * RS + (jj - r * d); }
+    if (j < oBf) { const int jj = j - 2 * nW, r = jj / nl; is_time_row = r == 0; return rL + r * RSL + (jj - r * nl); }
+    if (j < oBw) return rT + (j - oBf);                                  // bf = colsum(dPt): the time row of the Wtgt block
+    if (j < oGm) return rL + 2 * (j - oBw) + 1;                          // bw_h = colsum(dA2)[2h + 1]
+    return rG + (j - oGm);                                               // dgamma | dbeta
+}
+
 __global__ __launch_bounds__(1024) void gat_small_finish_kernel(GatFinish g)
 {
     __shared__ float sm[32][33];
     const int jj = threadIdx.x & 31, qq = threadIdx.x >> 5;
     const int j = (int)blockIdx.x * 32 + jj;
-    const int d = g.d, nW = (d + 1) * d, nL = (d + 1) * g.nl;
-    const int oBf = 2 * nW + nL, oBw = oBf + d, oGm = oBw + g.heads;     // theta offsets; gamma, beta are contiguous in both
-    // partial rows are in the VJP kernel's LDS layout: two (d+1) x (d+1) blocks, one (d+1) x (NLP+1) block, dgamma, dbeta, a_t
-    const int RS = d + 1, RSL = g.nlp + 1, rT = (d + 1) * RS, rL = 2 * rT, rG = rL + (d + 1) * RSL;
-    int src = -1; float scale = 1.f; bool is_time_row = false;
-    if (j < g.out_len) {
-        if (j < 2 * nW) { const int b = j >= nW, jj = j - b * nW, r = jj / d; src = b * rT + r * RS + (jj - r * d); if (r == 0) { scale = g.t; is_time_row = true; } }
-        else if (j < oBf) { const int jj = j - 2 * nW, r = jj / g.nl; src = rL + r * RSL + (jj - r * g.nl); if (r == 0) { scale = g.t; is_time_row = true; } }
-        else if (j < oBw) src = rT + (j - oBf);                          // bf = colsum(dPt): the time row of the Wtgt block
-        else if (j < oGm) src = rL + 2 * (j - oBw) + 1;                  // bw_h = colsum(dA2)[2h + 1]
-        else src = rG + (j - oGm);                                       // dgamma | dbeta
-    } else if (j == g.out_len) src = g.plen - 1;                         // a_t'
+    bool is_time_row;
+    const int src = gat_finish_source(j, g.d, g.nl, g.nlp, g.heads, g.out_len, g.plen, is_time_row);
+    const float scale = is_time_row ? g.t : 1.f;
     const int n_rounds = g.n_slots > 0 ? g.n_slots : 1;
     float total = 0.f;
     for (int sl = 0; sl < n_rounds; ++sl) {
@@ -705,6 +716,60 @@ __global__ __launch_bounds__(1024) void gat_small_finish_kernel(GatFinish g)
         } else {
             if (j < g.out_len) g.ktheta[j] = total; else *g.kat = total;
         }
+    }
+}
+
+// theta += sum_s k_theta(stage s) over the n_slots <= 7 stages a backprop sweep pushed through f in one step (the RK weights
+// are already inside the stages' cotangents; a backprop sweep has no a_t).  Same thread layout and the same sums per slot
+// as the kernel above - the 16 partial-row loads of a slot in flight at once - but every slot is summed into a register
+// of its own before ONE barrier, where the kernel above takes a barrier pair per slot.  (As compiled, a slot's loads are
+// waited for before the next slot's are issued: the slots are still up to seven load round trips, one after the other.)
+// The slots are added slot 0 first.  `unit` is 1.0 passed at RUN time: fmaf(unit, sc * tsum, total) is the multiply-add
+// of the four-slot closing launch with unit weights (the same bits), and with a literal 1 the compiler may contract
+// sc * tsum + total into fma(sc, tsum, total), which rounds the product away and breaks that equality.
+constexpr int kGatCloseSlots = 7;
+struct GatClose {
+    const float* part; int n_part, plen, d, nl, nlp, heads, out_len, n_slots;
+    float ts[kGatCloseSlots]; float unit; float* theta;
+};
+__global__ __launch_bounds__(1024) void gat_small_close_stages_kernel(GatClose g)
+{
+    __shared__ float sm[kGatCloseSlots][32][33];
+    const int jj = threadIdx.x & 31, qq = threadIdx.x >> 5;
+    const int j = (int)blockIdx.x * 32 + jj;
+    bool is_time_row = false;
+    const int src = j < g.out_len ? gat_finish_source(j, g.d, g.nl, g.nlp, g.heads, g.out_len, g.plen, is_time_row) : -1;
+    float v[kGatCloseSlots];
+#pragma unroll
+    for (int sl = 0; sl < kGatCloseSlots; ++sl) {
+        v[sl] = 0.f;
+        if (sl < g.n_slots && src >= 0) {                                // n_slots is uniform over the grid
+            const float* part = g.part + (int64_t)sl * g.n_part * g.plen;
+            for (int p0 = qq; p0 < g.n_part; p0 += 32 * 16) {           // 16 independent loads in flight per thread and slot
+                float x[16];
+#pragma unroll
+                for (int u = 0; u < 16; ++u) {
+                    const int p = p0 + 32 * u;
+                    x[u] = p < g.n_part ? part[(int64_t)p * g.plen + src] : 0.f;
+                }
+#pragma unroll
+                for (int u = 0; u < 16; ++u) v[sl] += x[u];
+            }
+        }
+    }
+#pragma unroll
+    for (int sl = 0; sl < kGatCloseSlots; ++sl) sm[sl][qq][jj] = v[sl];
+    __syncthreads();
+    if (qq == 0 && src >= 0) {
+        float total = 0.f;
+        for (int sl = 0; sl < g.n_slots; ++sl) {
+            float tsum = sm[sl][0][jj];
+#pragma unroll
+            for (int k = 1; k < 32; ++k) tsum += sm[sl][k][jj];
+            const float sc = is_time_row ? g.ts[sl] : 1.f;
+            total = fmaf(g.unit, sc * tsum, total);
+        }
+        g.theta[j] += total;
     }
 }
 
@@ -881,6 +946,30 @@ extern "C" int gode_gat_small_finish_step_f32(const float* part, int64_t n_rows,
     for (int q = 0; q < 4; ++q) { g.ts[q] = q < n_slots ? ts[q] : 0.f; g.w[q] = q < n_slots ? w[q] : 0.f; }
     const int blocks = (g.out_len + 1 + 31) / 32;
     hipLaunchKernelGGL(gat_small_finish_kernel, dim3((unsigned)blocks), dim3(1024), 0, (hipStream_t)stream, g);
+    GODE_LAUNCH_CHECK();
+    return 0;
+}
+
+// The closing launch of a backprop sweep's step (gat_driver.hip): theta += sum_s k_theta(stage s) over n_slots <= 7 partial
+// buffers laid out one after the other, stage s evaluated at ts[s]; unit weights, no a_t.
+extern "C" int gode_gat_small_close_stages_f32(const float* part, int64_t n_rows, int64_t d, int64_t heads, int32_t n_slots,
+                                               const float* ts /* host */, float* theta, void* stream)
+{
+    if (heads < 1) heads = 1;
+    if (!part || !ts || !theta) return GODE_E_NULLPTR;
+    if (n_rows <= 0 || d <= 0 || n_slots < 1 || n_slots > kGatCloseSlots) return GODE_E_SHAPE;
+    if (!gode_gat_small_supported(n_rows, d, (int32_t)d, heads)) return GODE_E_UNSUPPORTED;     // the kernels' shapes, whatever the grouping
+    GatClose g;
+    g.part = part; g.n_part = (int)gode_gat_small_parts(n_rows, d); g.plen = (int)gode_gat_small_part_len(d, heads);
+    g.d = (int)d; g.nl = (int)(2 * heads); g.nlp = g.nl <= 4 ? 4 : 16; g.heads = (int)heads;
+    g.out_len = (int)(2 * (d + 1) * d + (d + 1) * 2 * heads + d + heads + 2 * d);
+    g.n_slots = n_slots; g.unit = 1.f; g.theta = theta;
+    for (int q = 0; q < kGatCloseSlots; ++q) g.ts[q] = q < n_slots ? ts[q] : 0.f;
+    const int blocks = (g.out_len + 31) / 32;
+    hipStream_t s = (hipStream_t)stream;
+    const int slot = gode_prof_begin(s, d, n_rows, (int64_t)n_slots, GODE_PROF_GAT_STEP_CLOSE);
+    hipLaunchKernelGGL(gat_small_close_stages_kernel, dim3((unsigned)blocks), dim3(1024), 0, s, g);
+    gode_prof_end(s, slot);
     GODE_LAUNCH_CHECK();
     return 0;
 }

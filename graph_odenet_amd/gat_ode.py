@@ -22,6 +22,13 @@ so that the aggregation runs with zero bias and amax = 0.  The branches on H are
 The adjoint integrates [y, a, a_t, theta] with theta = [Wsrc | Wtgt | Wlog | bf | bw | gamma | beta] packed in ONE
 buffer (one RK combine launch for all parameters); the gradient is converted back to the parameters' layout once,
 at the end of the solve.
+
+Backprop through the solve (odeint, adjoint=False) on launch-bound graphs - GatOdeField.small(), no padded logit columns:
+the forward field offers the backprop half of solver.Field's protocol, issued from C (csrc/gat_driver.hip:
+gode_gat_ode_rk4_forward_save / _rk4_backprop / _dopri5_step_backprop).  The reverse of a stage is the adjoint stage's
+launch sequence with the stage's cotangent kbar_s in place of -a; each swept stage leaves its parameter partials in a slot of
+its own and one gode_gat_small_close_stages_f32 launch per step adds them to the packed theta.  Elsewhere the members stay
+None and odeint re-runs each interval as torch ops under autograd.
 """
 import ctypes
 
@@ -143,20 +150,61 @@ class _Work:
         small = not spec.pad_logits and lib.gode_gat_small_supported(n, d, spec.groups, H)
         self.small_part = ops.gat_small_part(n, d, H, device) if small else None
         self.step_parts = None                 # four such buffers, one per stage of a fixed-grid step (allocated on first use)
+        self.sweep = None                      # work arrays of the backprop sweeps (_SweepWork, allocated on first use)
+
+
+class _SweepWork:
+    """Work arrays of the backprop sweeps of one (graph, d, H): 7 Ybar (rk4 uses four), two (ybar_n, kbar_1) pairs that take
+    turns from step to step, the re-evaluated stage derivative and 7 slots of parameter partials."""
+
+    def __init__(self, spec, small_part):
+        f = dict(dtype=torch.float32, device=small_part.device)
+        self.ybar = [torch.empty(spec.n, spec.d, **f) for _ in range(7)]
+        self.pairs = [(torch.empty(spec.n, spec.d, **f), torch.empty(spec.n, spec.d, **f)) for _ in range(2)]
+        self.k_scratch = torch.empty(spec.n, spec.d, **f)
+        self.parts = torch.empty(7 * small_part.numel(), **f)
+
+
+def theta_param_grads(s, order, theta):
+    """The packed gradient theta (laid out as GatOdeSpec.off) in the parameters' own layout, in `order` (the names
+    gat_fields gives func.parameters()): one head or H."""
+    i, o, H = s.i, s.o, s.heads
+    if H == 1:
+        v = s.views(theta)
+        gWf = torch.cat([v["Wsrc"].t(), v["Wtgt"].t()], 1).contiguous()                          # o x 2i
+        gww = torch.cat([v["Wlog"][:, 0], v["Wlog"][:, 1]]).view(1, 2 * i).contiguous()           # 1 x 2i
+        m = {"gamma": v["gamma"].clone(), "beta": v["beta"].clone(), "Wf": gWf, "bf": v["bf"].clone(),
+             "ww": gww, "bw": v["bw"].clone()}
+        return [m[k] for k in order]
+    v = s.views(theta.clone())                       # one copy; everything below is a view of it or one permuted copy
+    m = {"gamma": v["gamma"], "beta": v["beta"]}
+    gWf = torch.cat([v["Wsrc"].view(i, H, o).permute(1, 2, 0), v["Wtgt"].view(i, H, o).permute(1, 2, 0)], 2)    # H x o x 2i
+    gww = v["Wlog"].view(i, H, 2).permute(1, 2, 0).reshape(H, 1, 2 * i)                                         # H x 1 x 2i
+    gbf, gbw = v["bf"].view(H, o), v["bw"].view(H, 1)
+    for h in range(H):
+        m["Wf%d" % h], m["bf%d" % h], m["ww%d" % h], m["bw%d" % h] = gWf[h], gbf[h], gww[h], gbw[h]
+    return [m[k] for k in order]
 
 
 class GatOdeField(Field):
     """f(t, x) = relu(layer([t | GroupNorm(x)])) as a kernel sequence.  Adaptive steps run as one C call
     (csrc/gat_driver.hip) except with padded logit columns (H heads above PAD_LOGITS_MIN_ROWS nodes), where the solver
-    takes the per-stage path."""
+    takes the per-stage path.  Built with the parameter order (gat_fields) on a launch-bound graph - small(), no padded
+    logit columns - it also offers the backprop half of the protocol (solver.Field), issued from csrc/gat_driver.hip."""
     n_components = 1
     fused = True
+    BACKPROP_FUSED = True            # False: no backprop members (odeint re-runs each interval as torch ops under autograd)
 
-    def __init__(self, spec, work):
+    def __init__(self, spec, work, order=None):
         self.s, self.w = spec, work
         self.token = ("gat-heads" if spec.heads > 1 else "gat", id(spec.eg))
         if spec.pad_logits:
             self.dopri5_step_native = None
+        if order is not None and self.BACKPROP_FUSED and not spec.pad_logits and self.small():
+            self.order = order
+            self.rk4_forward_save, self.rk4_backprop = self._rk4_forward_save, self._rk4_backprop
+            self.dopri5_step_backprop, self.dopri5_backprop_work = self._dopri5_step_backprop, self._dopri5_backprop_work
+            self.packed_grads, self.packed_param_grads = self._packed_grads, self._packed_param_grads
 
     def prepare(self):
         self.s.refresh()
@@ -221,6 +269,58 @@ class GatOdeField(Field):
                    "gode_gat_ode_dopri5_step_forward")
         return sums
 
+    # ---- backprop through the solve (odeint._OdeintBackprop): launch-bound graphs, csrc/gat_driver.hip ------------------
+    def _packed_grads(self, device):
+        """Zeroed theta = [Wsrc | Wtgt | Wlog | bf | bw | gamma | beta]."""
+        return torch.zeros(self.s.n_theta, dtype=torch.float32, device=device)
+
+    def _packed_param_grads(self, theta):
+        return theta_param_grads(self.s, self.order, theta)
+
+    def _sweep_work(self):
+        w = self.w
+        if w.sweep is None:
+            w.sweep = _SweepWork(self.s, w.small_part)
+        return w.sweep
+
+    def _rk4_forward_save(self, y0, y_end, save, t0, t1, n_steps, i0, i1):
+        """Steps i0 .. i1-1 with the launches of solver.integrate_rk4 on this field (the same bits); save[r] = [y_n, k_1..k_4]
+        of step i0 + r."""
+        fs, ws = self._structs(True)
+        _lib.check(_lib.load().gode_gat_ode_rk4_forward_save(
+            ctypes.byref(fs), _lib.ptr(y0), _lib.ptr(y_end), _lib.ptr(save), ctypes.byref(ws), float(t0), float(t1), int(n_steps),
+            int(i0), int(i1), _lib.stream_ptr()), "gode_gat_ode_rk4_forward_save")
+
+    def _rk4_backprop(self, save, a, theta, t0, t1, n_steps, i0, i1):
+        """Reverse sweep over the records of steps i0 .. i1-1; `a` is advanced in place and returned, theta incremented."""
+        fs, ws = self._structs(True)
+        sw = self._sweep_work()
+        ybar = (ctypes.c_void_p * 4)(*[b.data_ptr() for b in sw.ybar[:4]])
+        _lib.check(_lib.load().gode_gat_ode_rk4_backprop(
+            ctypes.byref(fs), _lib.ptr(save), _lib.ptr(a), _lib.ptr(theta), ybar, _lib.ptr(sw.k_scratch), _lib.ptr(sw.parts),
+            ctypes.byref(ws), float(t0), float(t1), int(n_steps), int(i0), int(i1), _lib.stream_ptr()),
+            "gode_gat_ode_rk4_backprop")
+        return a
+
+    def _dopri5_backprop_work(self, like):
+        sw = self._sweep_work()
+        return {"ybar": sw.ybar, "pairs": sw.pairs}
+
+    def _dopri5_step_backprop(self, y, k, g, kbar7, wy, wk, t, h, first, work, turn, theta):
+        """Reverse sweep over one accepted step (gode_gat_ode_dopri5_step_backprop).  Returns (ybar_n, kbar_1) in
+        work["pairs"][turn]; kbar_1 is None when `first`."""
+        fs, ws = self._structs(True)
+        sw = self._sweep_work()
+        ybar_n, kbar1 = work["pairs"][turn]
+        kptr = (ctypes.c_void_p * 7)(*[x.data_ptr() for x in k])
+        ybar = (ctypes.c_void_p * 7)(*[b.data_ptr() for b in work["ybar"]])
+        wka = (ctypes.c_double * 7)(*[float(v) for v in wk])
+        _lib.check(_lib.load().gode_gat_ode_dopri5_step_backprop(
+            ctypes.byref(fs), _lib.ptr(y), kptr, _lib.ptr(g), _lib.ptr(kbar7), float(wy), wka, float(t), float(h),
+            1 if first else 0, ybar, _lib.ptr(ybar_n), _lib.ptr(kbar1), _lib.ptr(theta), _lib.ptr(sw.k_scratch),
+            _lib.ptr(sw.parts), ctypes.byref(ws), _lib.stream_ptr()), "gode_gat_ode_dopri5_step_backprop")
+        return ybar_n, (None if first else kbar1)
+
     def _project(self, t, y_terms):
         """Ps, Pt, A2 of the stage input; returns the term list later launches of the stage should read."""
         s, w = self.s, self.w
@@ -275,23 +375,7 @@ class GatOdeAdjointField(GatOdeField):
                 torch.zeros(s.n_theta, dtype=torch.float32, device=y_end.device)]
 
     def param_grads(self, comps):
-        s = self.s
-        i, o, H = s.i, s.o, s.heads
-        if H == 1:
-            v = s.views(comps[3])
-            gWf = torch.cat([v["Wsrc"].t(), v["Wtgt"].t()], 1).contiguous()                          # o x 2i
-            gww = torch.cat([v["Wlog"][:, 0], v["Wlog"][:, 1]]).view(1, 2 * i).contiguous()           # 1 x 2i
-            m = {"gamma": v["gamma"].clone(), "beta": v["beta"].clone(), "Wf": gWf, "bf": v["bf"].clone(),
-                 "ww": gww, "bw": v["bw"].clone()}
-            return [m[k] for k in self.order]
-        v = s.views(comps[3].clone())                    # one copy; everything below is a view of it or one permuted copy
-        m = {"gamma": v["gamma"], "beta": v["beta"]}
-        gWf = torch.cat([v["Wsrc"].view(i, H, o).permute(1, 2, 0), v["Wtgt"].view(i, H, o).permute(1, 2, 0)], 2)    # H x o x 2i
-        gww = v["Wlog"].view(i, H, 2).permute(1, 2, 0).reshape(H, 1, 2 * i)                                         # H x 1 x 2i
-        gbf, gbw = v["bf"].view(H, o), v["bw"].view(H, 1)
-        for h in range(H):
-            m["Wf%d" % h], m["bf%d" % h], m["ww%d" % h], m["bw%d" % h] = gWf[h], gbf[h], gww[h], gbw[h]
-        return [m[k] for k in self.order]
+        return theta_param_grads(self.s, self.order, comps[3])
 
     def dopri5_step_native(self, y, kk, y1, t, h, rtol, atol):
         lib = _lib.load()
@@ -427,4 +511,4 @@ def gat_fields(odefunc, layer, eg, n, names, y0):
     if work is None:
         work = cache[key] = _Work(spec, y0.device)
     order = [names[id(p)] for p in plist]
-    return GatOdeField(spec, work), (lambda: GatOdeAdjointField(spec, work, order)), tuple(plist)
+    return GatOdeField(spec, work, order), (lambda: GatOdeAdjointField(spec, work, order)), tuple(plist)

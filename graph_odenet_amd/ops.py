@@ -342,6 +342,22 @@ def gat_small_finish_step(parts, n_rows, d, heads, ts, ws, theta, at):
           "gode_gat_small_finish_step_f32")
 
 
+def gat_small_close_stages(parts, n_rows, d, heads, ts, theta):
+    """theta += sum_s k_theta(stage s) from the partial buffers of the len(ts) <= 7 stages a backprop sweep pushed through f
+    in one step, laid out one after the other in `parts` (csrc/gat_small.hip: unit weights, no a_t, one launch)."""
+    lib = _lib.load()
+    _need(parts, "parts"); _need(theta, "theta")
+    k = len(ts)
+    if not 1 <= k <= 7:
+        raise ValueError("gat_small_close_stages: one to seven stages")
+    if parts.numel() < k * lib.gode_gat_small_parts(n_rows, d) * lib.gode_gat_small_part_len(d, heads) or \
+            theta.numel() < lib.gode_gat_ode_theta_len_heads(d, heads):
+        raise ValueError("gat_small_close_stages: buffers have wrong size")
+    tsa = (ctypes.c_float * 7)(*([float(v) for v in ts] + [0.0] * (7 - k)))
+    check(lib.gode_gat_small_close_stages_f32(ptr(parts), n_rows, d, heads, k, tsa, ptr(theta), stream_ptr()),
+          "gode_gat_small_close_stages_f32")
+
+
 def gn_time_gemm_bwd(x_terms, n_rows, d_in, groups, eps, gamma, W, has_time, dS, out_scale=1.0, out=None,
                      want_affine_grads=True, pre_terms=None, parts=None):
     """Returns (dx, dgamma_part, dbeta_part); parts are [n_part, d_in] block partials (or None).

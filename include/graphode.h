@@ -794,6 +794,14 @@ int gode_gat_small_finish_f32(const float* part, int64_t n_rows, int64_t d, int6
 int gode_gat_small_finish_step_f32(const float* part, int64_t n_rows, int64_t d, int64_t heads, int32_t n_slots,
                                    const float* ts /* host */, const float* w /* host */, float* theta, float* at,
                                    void* stream);
+/* The closing launch of one step of a backprop sweep (gode_gat_ode_rk4_backprop, gode_gat_ode_dopri5_step_backprop):
+ * theta += sum_s k_theta(stage s) over the n_slots (1..7) stages the step pushed through f, k_theta as finish defines it
+ * with t = ts[s], stage s's partials at part + s * parts * part_len.  Unit weights (the RK weights are inside the stages'
+ * cotangents) and no a_t; slot 0 is added first; nothing outside the gode_gat_ode_theta_len_heads(d, heads) floats of theta
+ * is touched.  For n_slots <= 4 the result is bit for bit gode_gat_small_finish_step_f32's with w = 1.
+ * GODE_E_SHAPE: n_slots outside 1..7; GODE_E_UNSUPPORTED: a shape gode_gat_small_supported refuses. */
+int gode_gat_small_close_stages_f32(const float* part, int64_t n_rows, int64_t d, int64_t heads, int32_t n_slots,
+                                    const float* ts /* host */, float* theta, void* stream);
 /* The LDS images of [Wsrc | Wtgt | Wlog] both kernels stage (row-major with padded logit columns for project, transposed
  * without the time row for dense_vjp), formed once per solve - the weights do not change inside one - so that staging is
  * a straight 16-byte copy: packed holds gode_gat_small_pack_len(d, heads) floats.  Passing NULL for `packed` makes the
@@ -812,6 +820,37 @@ int gode_gat_ode_dopri5_step_adjoint(const gode_gat_odefunc_t* f, const float* y
                                      float* const* ktheta, float* y1, float* a1, float* a_t1, float* theta1,
                                      const gode_gat_workspace_t* ws, double t, double h, float rtol, float atol,
                                      double* sums /* 4 */, void* err_scratch, void* stream);
+
+/* Backprop through rk4 and dopri5 solves of the GAT ODE function (one head or H) on launch-bound graphs: where
+ * gode_gat_small_supported(n, d, groups, heads) holds, the option small_fused is on and ws->small_part is set - else
+ * GODE_E_UNSUPPORTED, before any launch.  The entry points mirror gode_gcn_ode_rk4_forward_save / _rk4_backprop /
+ * _dopri5_step_backprop (records, step ranges, the algebra of the sweeps: see there).  ws as for the adjoint step.
+ * The reverse of a stage k_s = f(t_s, Y_s) with cotangent kbar_s: f is evaluated again at Y_s (into k_scratch, n x d, which
+ * masks kbar_s: the relu), then the launches of an adjoint stage with cotangent scale +1 - Ybar_s = J_s^T kbar_s into its
+ * own array and the partials of (df/dtheta)_s^T kbar_s into a slot of `parts` (slots of gode_gat_small_parts(n, d) *
+ * gode_gat_small_part_len(d, heads) floats, one after the other); ONE gode_gat_small_close_stages_f32 launch per step adds
+ * the swept stages' parameter parts to theta (gode_gat_ode_theta_len_heads floats, incremented).  One stream.
+ * forward_save: the launches solver.integrate_rk4 issues on this field (per stage project / logits / aggregation, then the
+ *   solution combine), filling the records [ y_n | k_1 | k_2 | k_3 | k_4 ]; y0 is copied into record 0 unless it is record 0
+ *   itself; y_end receives the state after step step_end - 1 (bit for bit the plain solve's).
+ * rk4_backprop: per step, stages 4..1: kbar_s = h b_s a + h sum_{r > s} a_rs Ybar_r, Ybar_s into ybar[s-1] (4 n x d work
+ *   arrays), stage s's partials into slot s-1 of parts (>= 4 slots), then a += sum_s Ybar_s in one combine: a = dL/dy after
+ *   step step_end - 1 on entry, dL/dy before step step_begin on return (advanced in place).
+ * dopri5_step_backprop: one accepted step; y, k, g, kbar7, wy, wk, t, h, first, ybar, ybar_n, kbar1 and the skipping of a
+ *   stage without a cotangent term as for gode_gcn_ode_dopri5_step_backprop.  first != 0: kbar_1 is pushed through f here
+ *   (Ybar_1 into ybar[0]) and kbar1 is not written.  ybar_n (and kbar1) come from one gode_lincomb_multi_f32; swept stage
+ *   number i (from stage 7 down) writes slot i of parts (7 slots). */
+int gode_gat_ode_rk4_forward_save(const gode_gat_odefunc_t* f, const float* y0, float* y_end, float* save,
+                                  const gode_gat_workspace_t* ws, float t0, float t1, int32_t n_steps,
+                                  int32_t step_begin, int32_t step_end, void* stream);
+int gode_gat_ode_rk4_backprop(const gode_gat_odefunc_t* f, const float* save, float* a, float* theta,
+                              float* const* ybar /* 4 */, float* k_scratch, float* parts, const gode_gat_workspace_t* ws,
+                              float t0, float t1, int32_t n_steps, int32_t step_begin, int32_t step_end, void* stream);
+int gode_gat_ode_dopri5_step_backprop(const gode_gat_odefunc_t* f, const float* y, float* const* k /* 7 */, const float* g,
+                                      const float* kbar7 /* nullable */, double wy, const double* wk /* host, 7 */,
+                                      double t, double h, int32_t first, float* const* ybar /* 7 */, float* ybar_n,
+                                      float* kbar1, float* theta, float* k_scratch, float* parts,
+                                      const gode_gat_workspace_t* ws, void* stream);
 
 /* ---- Set2Set readout: LSTM cell, one launch per direction (csrc/lstm.hip; replaces the single-layer `self.lstm` step of
  * QC/set2set.py:44-47,61 = torch.lstm_cell: two library GEMMs + a cell kernel forward, four GEMMs + reductions backward).
@@ -925,6 +964,8 @@ int gode_edge_ode_step_close_f32(int32_t n_stages, const float* const* wpart /* 
 /* csrc/edge_backprop.hip (d = h; rows = atoms; extra = cotangent + stage-input terms / stages closed) */
 #define GODE_PROF_EDGE_STAGE_BWD  9    /* gode_edge_ode_stage_bwd_f32: the reverse of one stage */
 #define GODE_PROF_EDGE_STEP_CLOSE 10   /* gode_edge_ode_step_close_f32: one pass per RK step */
+/* csrc/gat_small.hip (rows = nodes; extra = stages closed) */
+#define GODE_PROF_GAT_STEP_CLOSE 11    /* gode_gat_small_close_stages_f32: one pass per swept step of a backprop sweep */
 /* which kernel of the family ran, OR-ed into the kind of a dense launch (kind & 0xff = family, kind >> 8 = form):
  * exact-fp32 MFMA kernel; bf16-piece kernel, every wave loading + cutting + multiplying; bf16-piece kernel in
  * producer / consumer form (wgrad_split_kernel, gemm_pc.hip) */
