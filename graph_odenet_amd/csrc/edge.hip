@@ -1196,12 +1196,31 @@ bool pf_ok(const Proj& pv, int64_t o, const void* p0, const void* p1) {
     return !(al & 15);
 }
 
+// ---- routes ---------------------------------------------------------------------------------------------------------
+// Every dispatch decision of the one-head family is one host function that returns a route code (graphode.h:
+// GODE_GAT_ROUTE_* family | form << 8); the launching entry points switch on its value and the *_route queries return it.
+int route_code(int family, int form) { return family | (form << 8); }
+int route_family(int rt) { return rt & 0xff; }
+int route_form(int rt) { return rt >> 8; }
+// columns per lane of the lane-group / wave / scatter kernels: o <= 64 * MAXC
+int maxc_form(int64_t o) {
+    const int G = pow2_group((int)o);
+    const int maxc = (int)((o + G - 1) / G);
+    return maxc <= 1 ? 1 : maxc <= 2 ? 2 : maxc <= 4 ? 4 : 8;
+}
+
+int logits_route(int64_t n_edges) {
+    return route_code(n_edges <= kOneBlockEdges ? GODE_GAT_ROUTE_ONE_BLOCK : GODE_GAT_ROUTE_TWO_STAGE, 0);
+}
+
 int launch_logits(const Proj& pv, const float* bw, const int32_t* src, const int32_t* tgt, int64_t n_edges,
                   float* a, float* amax, float* scratch, hipStream_t s) {
-    if (n_edges <= kOneBlockEdges) {
+    switch (route_family(logits_route(n_edges))) {
+    case GODE_GAT_ROUTE_ONE_BLOCK:
         hipLaunchKernelGGL(gat_logits_small_kernel, dim3(1), dim3(1024), 0, s, pv, bw, src, tgt, (int)n_edges, a, amax);
         GODE_LAUNCH_CHECK();
         return 0;
+    default: break;
     }
     int64_t b = (n_edges + 255) / 256; if (b > 1024) b = 1024; if (b < 1) b = 1;
     hipLaunchKernelGGL(gat_logits_kernel, dim3((unsigned)b), dim3(256), 0, s, pv, bw, src, tgt, (int)n_edges, a, scratch);
@@ -1211,22 +1230,41 @@ int launch_logits(const Proj& pv, const float* bw, const int32_t* src, const int
     return 0;
 }
 
+// aggregation over a plain CSR (no records): prefetched, wave per row, or lane group per row
+int agg_fwd_csr_route(const Proj& pv, int64_t o, int64_t n_rows, const void* out, const void* bf) {
+    if (n_rows > kWaveRows) return route_code(GODE_GAT_ROUTE_GROUP, maxc_form(o));
+    if (pf_ok(pv, o, out, bf)) return route_code(GODE_GAT_ROUTE_PF, (int)(o / 4));
+    return route_code(GODE_GAT_ROUTE_WAVE, maxc_form(o));
+}
+int agg_bwd_csr_route(const Proj& pv, int64_t o, int64_t n_rows, const void* out, const void* bf, const void* dout,
+                      const void* dz, const LinComb& cot) {
+    bool cot_al = true;
+    for (int j = 0; j < cot.n; ++j) cot_al = cot_al && !(((uintptr_t)cot.ptr[j]) & 15);
+    if (n_rows <= kWaveRows && cot_al && pf_ok(pv, o, out, bf) && !((((uintptr_t)dz) | ((uintptr_t)dout)) & 15))
+        return route_code(GODE_GAT_ROUTE_PF, (int)(o / 4));
+    if (n_rows <= kWaveRows || cot.n > 0)                    // the cotangent-combining form exists as wave kernel only
+        return route_code(GODE_GAT_ROUTE_WAVE, maxc_form(o));
+    return route_code(GODE_GAT_ROUTE_GROUP, maxc_form(o));
+}
+
 int launch_agg_fwd(const int32_t* rowptr, const int32_t* eid, const float* val, const int32_t* src, const int32_t* tgt,
                    const Proj& pv, int64_t o, const float* bf, const float* a, const float* amax, float eps,
-                   int64_t n_rows, float* out, float* w_out, float* den_out, hipStream_t s, HeadMax hm = HeadMax{nullptr, 0, 0}) {
+                   int64_t n_rows, float* out, float* w_out, float* den_out, hipStream_t s, int rt, HeadMax hm = HeadMax{nullptr, 0, 0}) {
     const int G = pow2_group((int)o);
-    const int maxc = (int)((o + G - 1) / G);
-    const bool wave = n_rows <= kWaveRows;
-    if (hm.H > 0 && !wave) return GODE_E_UNSUPPORTED;          // per-head partial maxima: wave kernels only
+    const int family = route_family(rt), form = route_form(rt);
+    const bool wave = family == GODE_GAT_ROUTE_WAVE;
+    if (hm.H > 0 && family == GODE_GAT_ROUTE_GROUP) return GODE_E_UNSUPPORTED;          // per-head partial maxima: wave kernels only
     const int64_t blocks = wave ? (n_rows + 3) / 4 : (n_rows * G + 255) / 256;
-    if (wave && pf_ok(pv, o, out, bf)) {
+    switch (family) {
+    case GODE_GAT_ROUTE_PF:
 #define GODE_PF(L, W) hipLaunchKernelGGL((gat_agg_fwd_pf_kernel<L, W>), dim3((unsigned)((n_rows + 4 * (64 / W) - 1) / (4 * (64 / W)))), dim3(256), 0, s, \
                                          rowptr, eid, val, src, tgt, pv, bf, a, amax, hm, eps, (int)n_rows, out, w_out, den_out)
-        switch ((int)o / 4) { case 1: GODE_PF(1, 16); break; case 2: GODE_PF(2, 16); break; case 4: GODE_PF(4, 64); break; case 8: GODE_PF(8, 64); break; default: GODE_PF(16, 64); break; }
+        switch (form) { case 1: GODE_PF(1, 16); break; case 2: GODE_PF(2, 16); break; case 4: GODE_PF(4, 64); break; case 8: GODE_PF(8, 64); break;
+                        case 16: GODE_PF(16, 64); break; default: return GODE_E_UNSUPPORTED; }
 #undef GODE_PF
-        GODE_LAUNCH_CHECK();
-        return 0;
-    }
+        break;
+    case GODE_GAT_ROUTE_WAVE:
+    case GODE_GAT_ROUTE_GROUP:
 #define GODE_AGG(M)                                                                                              \
     do {                                                                                                         \
         if (wave) hipLaunchKernelGGL(gat_agg_fwd_wave_kernel<M>, dim3((unsigned)blocks), dim3(256), 0, s, rowptr, eid, val, \
@@ -1234,8 +1272,12 @@ int launch_agg_fwd(const int32_t* rowptr, const int32_t* eid, const float* val, 
         else hipLaunchKernelGGL(gat_agg_fwd_kernel<M>, dim3((unsigned)blocks), dim3(256), 0, s, rowptr, eid, val, \
                                 src, tgt, pv, (int)o, bf, a, amax, eps, (int)n_rows, G, out, w_out, den_out);     \
     } while (0)
-    if (maxc <= 1) GODE_AGG(1); else if (maxc <= 2) GODE_AGG(2); else if (maxc <= 4) GODE_AGG(4); else GODE_AGG(8);
+        switch (form) { case 1: GODE_AGG(1); break; case 2: GODE_AGG(2); break; case 4: GODE_AGG(4); break; case 8: GODE_AGG(8); break;
+                        default: return GODE_E_UNSUPPORTED; }
 #undef GODE_AGG
+        break;
+    default: return GODE_E_UNSUPPORTED;
+    }
     GODE_LAUNCH_CHECK();
     return 0;
 }
@@ -1243,21 +1285,21 @@ int launch_agg_fwd(const int32_t* rowptr, const int32_t* eid, const float* val, 
 int launch_agg_bwd(const int32_t* rowptr, const int32_t* eid, const float* val, const int32_t* src, const int32_t* tgt,
                    const Proj& pv, int64_t o, const float* bf, const float* w, const float* den, const float* out,
                    const float* dout, const LinComb& cot, float cot_scale, int64_t n_rows, float* dz, float* da,
-                   hipStream_t s) {
+                   hipStream_t s, int rt) {
     const int G = pow2_group((int)o);
-    const int maxc = (int)((o + G - 1) / G);
-    const bool wave = n_rows <= kWaveRows || cot.n > 0;      // the cotangent-combining form exists as wave kernel only
+    const int family = route_family(rt), form = route_form(rt);
+    const bool wave = family == GODE_GAT_ROUTE_WAVE;
     const int64_t blocks = wave ? (n_rows + 3) / 4 : (n_rows * G + 255) / 256;
-    bool cot_al = true;
-    for (int j = 0; j < cot.n; ++j) cot_al = cot_al && !(((uintptr_t)cot.ptr[j]) & 15);
-    if (wave && n_rows <= kWaveRows && cot_al && pf_ok(pv, o, out, bf) && !((((uintptr_t)dz) | ((uintptr_t)dout)) & 15)) {
+    switch (family) {
+    case GODE_GAT_ROUTE_PF:
 #define GODE_PF(L, W) hipLaunchKernelGGL((gat_agg_bwd_pf_kernel<L, W>), dim3((unsigned)((n_rows + 4 * (64 / W) - 1) / (4 * (64 / W)))), dim3(256), 0, s, \
                                          rowptr, eid, val, src, tgt, pv, bf, w, den, out, dout, cot, cot_scale, (int)n_rows, dz, da)
-        switch ((int)o / 4) { case 1: GODE_PF(1, 16); break; case 2: GODE_PF(2, 16); break; case 4: GODE_PF(4, 64); break; case 8: GODE_PF(8, 64); break; default: GODE_PF(16, 64); break; }
+        switch (form) { case 1: GODE_PF(1, 16); break; case 2: GODE_PF(2, 16); break; case 4: GODE_PF(4, 64); break; case 8: GODE_PF(8, 64); break;
+                        case 16: GODE_PF(16, 64); break; default: return GODE_E_UNSUPPORTED; }
 #undef GODE_PF
-        GODE_LAUNCH_CHECK();
-        return 0;
-    }
+        break;
+    case GODE_GAT_ROUTE_WAVE:
+    case GODE_GAT_ROUTE_GROUP:
 #define GODE_AGG(M)                                                                                              \
     do {                                                                                                         \
         if (wave) hipLaunchKernelGGL(gat_agg_bwd_wave_kernel<M>, dim3((unsigned)blocks), dim3(256), 0, s, rowptr, eid, val, \
@@ -1265,8 +1307,12 @@ int launch_agg_bwd(const int32_t* rowptr, const int32_t* eid, const float* val, 
         else hipLaunchKernelGGL(gat_agg_bwd_kernel<M>, dim3((unsigned)blocks), dim3(256), 0, s, rowptr, eid, val, \
                                 src, tgt, pv, (int)o, bf, w, den, out, dout, (int)n_rows, G, dz, da);             \
     } while (0)
-    if (maxc <= 1) GODE_AGG(1); else if (maxc <= 2) GODE_AGG(2); else if (maxc <= 4) GODE_AGG(4); else GODE_AGG(8);
+        switch (form) { case 1: GODE_AGG(1); break; case 2: GODE_AGG(2); break; case 4: GODE_AGG(4); break; case 8: GODE_AGG(8); break;
+                        default: return GODE_E_UNSUPPORTED; }
 #undef GODE_AGG
+        break;
+    default: return GODE_E_UNSUPPORTED;
+    }
     GODE_LAUNCH_CHECK();
     return 0;
 }
@@ -1276,12 +1322,19 @@ int launch_agg_bwd(const int32_t* rowptr, const int32_t* eid, const float* val, 
 // ---- the same three steps over separately stored projections, plus the fused pieces of the ODE-function VJP --------
 extern "C" int gode_gat_logits_f32(const gode_gat_proj_t* proj, const float* bw, const int32_t* src, const int32_t* tgt,
                                    int64_t n_edges, float* a, float* amax, float* scratch, void* stream) {
+    const int rt = gode_gat_logits_f32_route(proj, bw, src, tgt, n_edges, a, amax, scratch, stream);
+    if (rt <= 0) return rt;
+    return launch_logits(proj_of(proj), bw, src, tgt, n_edges, a, amax, scratch, (hipStream_t)stream);
+}
+extern "C" int gode_gat_logits_f32_route(const gode_gat_proj_t* proj, const float* bw, const int32_t* src, const int32_t* tgt,
+                                         int64_t n_edges, float* a, float* amax, float* scratch, void* stream) {
+    (void)bw; (void)stream;
     if (!proj || !amax || !scratch) return GODE_E_NULLPTR;
     if (n_edges < 0) return GODE_E_SHAPE;
     if (n_edges > INT32_MAX) return GODE_E_RANGE;
     const Proj pv = proj_of(proj);
     if (n_edges > 0) { int rc = check_proj(pv, 1); if (rc) return rc; if (!src || !tgt || !a) return GODE_E_NULLPTR; }
-    return launch_logits(pv, bw, src, tgt, n_edges, a, amax, scratch, (hipStream_t)stream);
+    return logits_route(n_edges);
 }
 
 namespace {
@@ -1295,9 +1348,10 @@ bool rec_ok(const gode_graph_t* mt, const Proj& pv, int64_t o, const void* p0, c
 }
 }  // namespace
 
-extern "C" int gode_gat_agg_f32_fwd(const gode_graph_t* mt, const int32_t* src, const int32_t* tgt,
-                                    const gode_gat_proj_t* proj, int64_t o, const float* bf, const float* a,
-                                    const float* amax, float eps, float* out, float* w_out, float* den_out, void* stream) {
+extern "C" int gode_gat_agg_f32_fwd_route(const gode_graph_t* mt, const int32_t* src, const int32_t* tgt,
+                                          const gode_gat_proj_t* proj, int64_t o, const float* bf, const float* a,
+                                          const float* amax, float eps, float* out, float* w_out, float* den_out, void* stream) {
+    (void)eps; (void)stream;
     if (!mt) return GODE_E_NULLPTR;
     const int64_t n_rows = mt->n_rows;
     if (n_rows < 0 || o <= 0) return GODE_E_SHAPE;
@@ -1307,9 +1361,20 @@ extern "C" int gode_gat_agg_f32_fwd(const gode_graph_t* mt, const int32_t* src, 
     if (n_rows > INT32_MAX || o > 512) return (o > 512) ? GODE_E_UNSUPPORTED : GODE_E_RANGE;
     const Proj pv = proj_of(proj);
     int rc = check_proj(pv, o); if (rc) return rc;
+    if (rec_ok(mt, pv, o, out, bf ? (const void*)bf : (const void*)out)) return route_code(GODE_GAT_ROUTE_REC, (int)(o / 4));
+    return agg_fwd_csr_route(pv, o, n_rows, out, bf);
+}
+
+extern "C" int gode_gat_agg_f32_fwd(const gode_graph_t* mt, const int32_t* src, const int32_t* tgt,
+                                    const gode_gat_proj_t* proj, int64_t o, const float* bf, const float* a,
+                                    const float* amax, float eps, float* out, float* w_out, float* den_out, void* stream) {
+    const int rt = gode_gat_agg_f32_fwd_route(mt, src, tgt, proj, o, bf, a, amax, eps, out, w_out, den_out, stream);
+    if (rt <= 0) return rt;
+    const int64_t n_rows = mt->n_rows;
+    const Proj pv = proj_of(proj);
     hipStream_t s = (hipStream_t)stream;
-    if (rec_ok(mt, pv, o, out, bf ? (const void*)bf : (const void*)out)) {
-        const int lpr = (int)(o / 4);
+    if (route_family(rt) == GODE_GAT_ROUTE_REC) {
+        const int lpr = route_form(rt);
         const int64_t blocks = (mt->n_items * lpr + 255) / 256;
         const int64_t fblocks = (mt->n_long * lpr + 255) / 256;
 #define GODE_REC(L)                                                                                                   \
@@ -1321,22 +1386,22 @@ extern "C" int gode_gat_agg_f32_fwd(const gode_graph_t* mt, const int32_t* src, 
                                    (const int4*)mt->long_rows, (int)mt->n_long, (const float*)mt->partial, eps, out, den_out); \
         } while (0)
         switch (lpr) { case 4: GODE_REC(4); break; case 8: GODE_REC(8); break; case 16: GODE_REC(16); break;
-                       case 32: GODE_REC(32); break; default: GODE_REC(64); break; }
+                       case 32: GODE_REC(32); break; case 64: GODE_REC(64); break; default: return GODE_E_UNSUPPORTED; }
 #undef GODE_REC
         GODE_LAUNCH_CHECK();
         return 0;
     }
-    return launch_agg_fwd(mt->rowptr, mt->col, mt->val, src, tgt, pv, o, bf, a, amax, eps, n_rows, out, w_out, den_out, s);
+    return launch_agg_fwd(mt->rowptr, mt->col, mt->val, src, tgt, pv, o, bf, a, amax, eps, n_rows, out, w_out, den_out, s, rt);
 }
 
-extern "C" int gode_gat_agg_f32_bwd(const gode_graph_t* mt, const int32_t* src, const int32_t* tgt,
-                                    const gode_gat_proj_t* proj, int64_t o, const float* bf, const float* w,
-                                    const float* den, const float* out, const float* dout, const gode_lincomb_t* cot,
-                                    float cot_scale, float* dz, float* da, float* dpt, int64_t ld_dpt, float* dat,
-                                    int64_t ld_dat, int32_t* did_target_sums, void* stream) {
+extern "C" int gode_gat_agg_f32_bwd_route(const gode_graph_t* mt, const int32_t* src, const int32_t* tgt,
+                                          const gode_gat_proj_t* proj, int64_t o, const float* bf, const float* w,
+                                          const float* den, const float* out, const float* dout, const gode_lincomb_t* cot,
+                                          float cot_scale, float* dz, float* da, float* dpt, int64_t ld_dpt, float* dat,
+                                          int64_t ld_dat, int32_t* did_target_sums, void* stream) {
+    (void)cot_scale; (void)stream;
     if (!mt) return GODE_E_NULLPTR;
     const int64_t n_rows = mt->n_rows;
-    if (did_target_sums) *did_target_sums = 0;
     if (n_rows < 0 || o <= 0) return GODE_E_SHAPE;
     if (n_rows == 0) return 0;
     if (!proj || !mt->rowptr || !den || !out) return GODE_E_NULLPTR;
@@ -1347,11 +1412,28 @@ extern "C" int gode_gat_agg_f32_bwd(const gode_graph_t* mt, const int32_t* src, 
     else if (!dout) return GODE_E_NULLPTR;
     const Proj pv = proj_of(proj);
     int rc = check_proj(pv, o); if (rc) return rc;
+    if (dpt && dat && did_target_sums && ld_dpt >= o && !(ld_dpt % 4) && ld_dat >= 1 && !(((uintptr_t)dpt | (uintptr_t)dz) & 15) &&
+        (!use_cot || lincomb_aligned16(cot)) && rec_ok(mt, pv, o, out, use_cot ? (const void*)out : (const void*)dout))
+        return route_code(GODE_GAT_ROUTE_REC, (int)(o / 4));
+    return agg_bwd_csr_route(pv, o, n_rows, out, bf, dout, dz, make_lincomb(use_cot ? cot : nullptr));
+}
+
+extern "C" int gode_gat_agg_f32_bwd(const gode_graph_t* mt, const int32_t* src, const int32_t* tgt,
+                                    const gode_gat_proj_t* proj, int64_t o, const float* bf, const float* w,
+                                    const float* den, const float* out, const float* dout, const gode_lincomb_t* cot,
+                                    float cot_scale, float* dz, float* da, float* dpt, int64_t ld_dpt, float* dat,
+                                    int64_t ld_dat, int32_t* did_target_sums, void* stream) {
+    if (mt && did_target_sums) *did_target_sums = 0;
+    const int rt = gode_gat_agg_f32_bwd_route(mt, src, tgt, proj, o, bf, w, den, out, dout, cot, cot_scale, dz, da, dpt, ld_dpt,
+                                              dat, ld_dat, did_target_sums, stream);
+    if (rt <= 0) return rt;
+    const int64_t n_rows = mt->n_rows;
+    const bool use_cot = cot && cot->n > 0;
+    const Proj pv = proj_of(proj);
     hipStream_t s = (hipStream_t)stream;
     const LinComb lc = make_lincomb(use_cot ? cot : nullptr);
-    if (dpt && dat && did_target_sums && ld_dpt >= o && !(ld_dpt % 4) && ld_dat >= 1 && !(((uintptr_t)dpt | (uintptr_t)dz) & 15) &&
-        (!use_cot || lincomb_aligned16(cot)) && rec_ok(mt, pv, o, out, use_cot ? (const void*)out : (const void*)dout)) {
-        const int lpr = (int)(o / 4);
+    if (route_family(rt) == GODE_GAT_ROUTE_REC) {
+        const int lpr = route_form(rt);
         const int64_t blocks = (mt->n_items * lpr + 255) / 256;
         const int64_t fblocks = (mt->n_long * lpr + 255) / 256;
 #define GODE_REC(L)                                                                                                   \
@@ -1365,14 +1447,14 @@ extern "C" int gode_gat_agg_f32_bwd(const gode_graph_t* mt, const int32_t* src, 
                                    dat, ld_dat);                                                                      \
         } while (0)
         switch (lpr) { case 4: GODE_REC(4); break; case 8: GODE_REC(8); break; case 16: GODE_REC(16); break;
-                       case 32: GODE_REC(32); break; default: GODE_REC(64); break; }
+                       case 32: GODE_REC(32); break; case 64: GODE_REC(64); break; default: return GODE_E_UNSUPPORTED; }
 #undef GODE_REC
         GODE_LAUNCH_CHECK();
         *did_target_sums = 1;
         return 0;
     }
     return launch_agg_bwd(mt->rowptr, mt->col, mt->val, src, tgt, pv, o, bf, w, den, out, dout, lc, cot_scale, n_rows,
-                          dz, da, s);
+                          dz, da, s, rt);
 }
 
 extern "C" int64_t gode_gat_maxpath_scratch_bytes(int64_t n_edges) {
@@ -1380,19 +1462,30 @@ extern "C" int64_t gode_gat_maxpath_scratch_bytes(int64_t n_edges) {
     return 1024 * (int64_t)(sizeof(float) + sizeof(int));
 }
 
-extern "C" int gode_gat_maxpath_f32(const float* a, const float* amax, float* da, int64_t n_edges,
-                                    const int32_t* tgt, float* dat, int64_t ld_dat, void* scratch, void* stream) {
+extern "C" int gode_gat_maxpath_f32_route(const float* a, const float* amax, float* da, int64_t n_edges,
+                                          const int32_t* tgt, float* dat, int64_t ld_dat, void* scratch, void* stream) {
+    (void)tgt; (void)ld_dat; (void)stream;
     if (n_edges < 0) return GODE_E_SHAPE;
     if (n_edges == 0) return 0;
     if (!a || !amax || !da) return GODE_E_NULLPTR;
     if (n_edges > INT32_MAX) return GODE_E_RANGE;
+    if (n_edges <= kOneBlockEdges && !dat) return route_code(GODE_GAT_ROUTE_ONE_BLOCK, 0);
+    if (!scratch) return GODE_E_NULLPTR;
+    return route_code(GODE_GAT_ROUTE_TWO_STAGE, 0);
+}
+
+extern "C" int gode_gat_maxpath_f32(const float* a, const float* amax, float* da, int64_t n_edges,
+                                    const int32_t* tgt, float* dat, int64_t ld_dat, void* scratch, void* stream) {
+    const int rt = gode_gat_maxpath_f32_route(a, amax, da, n_edges, tgt, dat, ld_dat, scratch, stream);
+    if (rt <= 0) return rt;
     hipStream_t s = (hipStream_t)stream;
-    if (n_edges <= kOneBlockEdges && !dat) {
+    switch (route_family(rt)) {
+    case GODE_GAT_ROUTE_ONE_BLOCK:
         hipLaunchKernelGGL(gat_maxpath_kernel, dim3(1), dim3(1024), 0, s, a, amax, da, (int)n_edges);
         GODE_LAUNCH_CHECK();
         return 0;
+    default: break;
     }
-    if (!scratch) return GODE_E_NULLPTR;
     int64_t nb = (n_edges + 4095) / 4096; if (nb > 1024) nb = 1024; if (nb < 1) nb = 1;
     float* psum = (float*)scratch;
     int* pidx = (int*)(psum + 1024);
@@ -1518,7 +1611,7 @@ extern "C" int gode_gat_agg_heads_f32_fwd(const gode_graph_t* mt, const int32_t*
     HeadMax hm;
     hm.pmax = (const float*)scratch + 2 * (int64_t)kHeadBlocks * heads; hm.n_part = n_edges > 0 ? head_blocks(n_edges) : 0; hm.H = (int)heads;
     return launch_agg_fwd(mt->rowptr, mt->col, mt->val, src, tgt, pv, o, bf, a, nullptr, eps, n_rows, out, w_out, den_out,
-                          (hipStream_t)stream, hm);
+                          (hipStream_t)stream, agg_fwd_csr_route(pv, o, n_rows, out, bf), hm);
 }
 
 // the first half only: per-block sums of da and arg-max candidates stay in `scratch`; gode_gat_dense_vjp_small_f32 closes the
@@ -1566,32 +1659,50 @@ extern "C" int gode_gat_maxpath_heads_raw_f32(const float* a, float* da, int64_t
     return 0;
 }
 
-extern "C" int gode_gat_scatter_f32(const int32_t* rowptr_src, const int32_t* eid_src, const int32_t* rowptr_tgt,
-                                    const int32_t* eid_tgt, const float* dz, const float* da, int64_t o, int64_t n_rows,
-                                    float* dps, int64_t ld_s, float* dpt, int64_t ld_t, float* das, float* dat,
-                                    int64_t ld_a, void* stream) {
+extern "C" int gode_gat_scatter_f32_route(const int32_t* rowptr_src, const int32_t* eid_src, const int32_t* rowptr_tgt,
+                                          const int32_t* eid_tgt, const float* dz, const float* da, int64_t o, int64_t n_rows,
+                                          float* dps, int64_t ld_s, float* dpt, int64_t ld_t, float* das, float* dat,
+                                          int64_t ld_a, void* stream) {
+    (void)eid_src; (void)eid_tgt; (void)da; (void)stream;
     if (n_rows < 0 || o <= 0 || ld_s < o || ld_t < o || ld_a < 1) return GODE_E_SHAPE;
     if (n_rows == 0) return 0;
     // eid_* / dz / da may be NULL for an edgeless graph (every row is empty and nothing is dereferenced)
     if (!rowptr_src || !rowptr_tgt || !dps || !dpt || !das || !dat) return GODE_E_NULLPTR;
     if (n_rows > INT32_MAX || o > 512) return (o > 512) ? GODE_E_UNSUPPORTED : GODE_E_RANGE;
+    if ((o == 4 || o == 8 || o == 16 || o == 32 || o == 64) && !(ld_s % 4) && !(ld_t % 4) &&
+        !((((uintptr_t)dz) | ((uintptr_t)dps) | ((uintptr_t)dpt)) & 15))
+        return route_code(GODE_GAT_ROUTE_PF, (int)(o / 4));
+    return route_code(GODE_GAT_ROUTE_WAVE, maxc_form(o));
+}
+
+extern "C" int gode_gat_scatter_f32(const int32_t* rowptr_src, const int32_t* eid_src, const int32_t* rowptr_tgt,
+                                    const int32_t* eid_tgt, const float* dz, const float* da, int64_t o, int64_t n_rows,
+                                    float* dps, int64_t ld_s, float* dpt, int64_t ld_t, float* das, float* dat,
+                                    int64_t ld_a, void* stream) {
+    const int rt = gode_gat_scatter_f32_route(rowptr_src, eid_src, rowptr_tgt, eid_tgt, dz, da, o, n_rows, dps, ld_s, dpt, ld_t,
+                                              das, dat, ld_a, stream);
+    if (rt <= 0) return rt;
     const int G = pow2_group((int)o);
-    const int maxc = (int)((o + G - 1) / G);
     const int64_t blocks = (n_rows + 3) / 4;
     hipStream_t s = (hipStream_t)stream;
-    if ((o == 4 || o == 8 || o == 16 || o == 32 || o == 64) && !(ld_s % 4) && !(ld_t % 4) &&
-        !((((uintptr_t)dz) | ((uintptr_t)dps) | ((uintptr_t)dpt)) & 15)) {
+    const int form = route_form(rt);
+    switch (route_family(rt)) {
+    case GODE_GAT_ROUTE_PF:
 #define GODE_PF(L, W) hipLaunchKernelGGL((gat_scatter_pf_kernel<L, W>), dim3((unsigned)((n_rows + 4 * (64 / W) - 1) / (4 * (64 / W)))), dim3(256), 0, s, \
                                          rowptr_src, eid_src, rowptr_tgt, eid_tgt, dz, da, (int)n_rows, dps, ld_s, dpt, ld_t, das, dat, ld_a)
-        switch ((int)o / 4) { case 1: GODE_PF(1, 16); break; case 2: GODE_PF(2, 16); break; case 4: GODE_PF(4, 64); break; case 8: GODE_PF(8, 64); break; default: GODE_PF(16, 64); break; }
+        switch (form) { case 1: GODE_PF(1, 16); break; case 2: GODE_PF(2, 16); break; case 4: GODE_PF(4, 64); break; case 8: GODE_PF(8, 64); break;
+                        case 16: GODE_PF(16, 64); break; default: return GODE_E_UNSUPPORTED; }
 #undef GODE_PF
-        GODE_LAUNCH_CHECK();
-        return 0;
-    }
+        break;
+    case GODE_GAT_ROUTE_WAVE:
 #define GODE_SC(M) hipLaunchKernelGGL(gat_scatter_kernel<M>, dim3((unsigned)blocks), dim3(256), 0, s, rowptr_src, eid_src, \
                                       rowptr_tgt, eid_tgt, dz, da, (int)o, (int)n_rows, G, dps, ld_s, dpt, ld_t, das, dat, ld_a)
-    if (maxc <= 1) GODE_SC(1); else if (maxc <= 2) GODE_SC(2); else if (maxc <= 4) GODE_SC(4); else GODE_SC(8);
+        switch (form) { case 1: GODE_SC(1); break; case 2: GODE_SC(2); break; case 4: GODE_SC(4); break; case 8: GODE_SC(8); break;
+                        default: return GODE_E_UNSUPPORTED; }
 #undef GODE_SC
+        break;
+    default: return GODE_E_UNSUPPORTED;
+    }
     GODE_LAUNCH_CHECK();
     return 0;
 }

@@ -706,6 +706,23 @@ def gat_logits(proj, bw, src, tgt, a, amax):
                                   stream_ptr()), "gode_gat_logits_f32")
 
 
+def gat_logits_route(proj, bw, src, tgt, a, amax):
+    """The route gat_logits takes on these arguments (gode_gat_logits_f32_route: nothing is launched)."""
+    lib = _lib.load()
+    E = src.numel()
+    sc = _scratch(a.device, lib.gode_gat_logits_scratch_bytes(E))
+    return lib.gode_gat_logits_f32_route(ctypes.byref(proj), ptr(bw), ptr(src), ptr(tgt), E, ptr(a), ptr(amax), ptr(sc), None)
+
+
+# Route codes of the one-head attention family (graphode.h: GODE_GAT_ROUTE_*): family | form << 8
+GAT_ROUTE_PF, GAT_ROUTE_WAVE, GAT_ROUTE_GROUP, GAT_ROUTE_REC, GAT_ROUTE_ONE_BLOCK, GAT_ROUTE_TWO_STAGE = (
+    _lib.CONSTANTS["GODE_GAT_ROUTE_" + k] for k in ("PF", "WAVE", "GROUP", "REC", "ONE_BLOCK", "TWO_STAGE"))
+
+
+def gat_route(family, form=0):
+    return family | (form << 8)
+
+
 def _edge_csr(eg, width):
     """gode_graph_t of the CSR-by-target of an EdgeGraph (col = NULL when the edges are target-sorted)."""
     mt = eg.Mt
@@ -728,6 +745,52 @@ def gat_agg_fwd(eg, proj, o, bf, a, amax, eps, out, w, den):
     gs = _edge_csr(eg, o + 4)
     check(lib.gode_gat_agg_f32_fwd(ctypes.byref(gs), ptr(eg.src), ptr(eg.tgt), ctypes.byref(proj), o, ptr(bf), ptr(a),
                                    ptr(amax), float(eps), ptr(out), ptr(w), ptr(den), stream_ptr()), "gode_gat_agg_f32_fwd")
+
+
+def gat_agg_fwd_route(eg, proj, o, bf, a, amax, eps, out, w, den):
+    """The route gat_agg_fwd takes on these arguments (nothing is launched)."""
+    lib = _lib.load()
+    gs = _edge_csr(eg, o + 4)
+    return lib.gode_gat_agg_f32_fwd_route(ctypes.byref(gs), ptr(eg.src), ptr(eg.tgt), ctypes.byref(proj), o, ptr(bf), ptr(a),
+                                          ptr(amax), float(eps), ptr(out), ptr(w), ptr(den), None)
+
+
+def _agg_bwd_args(eg, proj, o, bf, w, den, out, dz, da, dPt, dA2, dout, cot_terms, cot_scale, did):
+    lc = None
+    if cot_terms is not None:
+        if _need_terms(cot_terms, "cot") != out.numel():
+            raise ValueError("gat_agg_bwd: cotangent terms have wrong size")
+        lc = lincomb(cot_terms)
+    elif dout is None:
+        raise ValueError("gat_agg_bwd: dout or cot_terms required")
+    gs = _edge_csr(eg, o + 4)
+    at_ptr = ctypes.c_void_p(dA2.data_ptr() + 4) if dA2 is not None else None
+    return (ctypes.byref(gs), ptr(eg.src), ptr(eg.tgt), ctypes.byref(proj), o, ptr(bf), ptr(w), ptr(den), ptr(out), ptr(dout),
+            ctypes.byref(lc) if lc is not None else None, float(cot_scale), ptr(dz), ptr(da), ptr(dPt), o, at_ptr, 2,
+            ctypes.byref(did)), (gs, lc)
+
+
+def gat_agg_bwd(eg, proj, o, bf, w, den, out, dz, da, dPt=None, dA2=None, dout=None, cot_terms=None, cot_scale=1.0):
+    """The aggregation's backward alone (first piece of gat_vjp): fills dz[E, o] and da[E] WITHOUT the path through the
+    maximum.  Returns True when the record route also formed the target-side sums dPt and dA2[:, 1]."""
+    lib = _lib.load()
+    for t, nm in ((out, "out"), (dz, "dz"), (da, "da"), (dout, "dout"), (dPt, "dPt"), (dA2, "dA2")):
+        _need(t, nm)
+    did = ctypes.c_int32(0)
+    args, keep = _agg_bwd_args(eg, proj, o, bf, w, den, out, dz, da, dPt, dA2, dout, cot_terms, cot_scale, did)
+    check(lib.gode_gat_agg_f32_bwd(*args, stream_ptr()), "gode_gat_agg_f32_bwd")
+    del keep
+    return bool(did.value)
+
+
+def gat_agg_bwd_route(eg, proj, o, bf, w, den, out, dz, da, dPt=None, dA2=None, dout=None, cot_terms=None, cot_scale=1.0):
+    """The route gat_agg_bwd (and gat_vjp) takes on these arguments (nothing is launched)."""
+    lib = _lib.load()
+    did = ctypes.c_int32(0)
+    args, keep = _agg_bwd_args(eg, proj, o, bf, w, den, out, dz, da, dPt, dA2, dout, cot_terms, cot_scale, did)
+    rt = lib.gode_gat_agg_f32_bwd_route(*args, None)
+    del keep
+    return rt
 
 
 def gat_logits_heads(proj, src, tgt, heads, a, hmax=None, bw=None):
@@ -774,20 +837,11 @@ def gat_vjp(eg, proj, o, bf, a, amax, w, den, out, dz, da, dPs, dPt, dA2, dout=N
     lib = _lib.load()
     for t, nm in ((out, "out"), (dz, "dz"), (da, "da"), (dout, "dout"), (dPs, "dPs"), (dPt, "dPt"), (dA2, "dA2")):
         _need(t, nm)
-    lc = None
-    if cot_terms is not None:
-        if _need_terms(cot_terms, "cot") != out.numel():
-            raise ValueError("gat_vjp: cotangent terms have wrong size")
-        lc = lincomb(cot_terms)
-    elif dout is None:
-        raise ValueError("gat_vjp: dout or cot_terms required")
-    gs = _edge_csr(eg, o + 4)
     did = ctypes.c_int32(0)
+    args, keep = _agg_bwd_args(eg, proj, o, bf, w, den, out, dz, da, dPt, dA2, dout, cot_terms, cot_scale, did)
     at_ptr = ctypes.c_void_p(dA2.data_ptr() + 4)
-    check(lib.gode_gat_agg_f32_bwd(ctypes.byref(gs), ptr(eg.src), ptr(eg.tgt), ctypes.byref(proj), o, ptr(bf), ptr(w),
-                                   ptr(den), ptr(out), ptr(dout), ctypes.byref(lc) if lc is not None else None,
-                                   float(cot_scale), ptr(dz), ptr(da), ptr(dPt), o, at_ptr, 2, ctypes.byref(did),
-                                   stream_ptr()), "gode_gat_agg_f32_bwd")
+    check(lib.gode_gat_agg_f32_bwd(*args, stream_ptr()), "gode_gat_agg_f32_bwd")
+    del keep
     if eg.E > 0 and heads > 1 and raw_scratch is not None and defer_maxpath and not did.value:
         # first half only; gat_dense_vjp_small(..., maxfix=(raw_scratch, eg.src, eg.tgt)) closes the step
         check(lib.gode_gat_maxpath_heads_part_f32(ptr(a), ptr(da), eg.E, int(heads), ptr(eg.tgt), ptr(raw_scratch), stream_ptr()),
@@ -814,22 +868,39 @@ def gat_vjp(eg, proj, o, bf, a, amax, w, den, out, dz, da, dPs, dPt, dA2, dout=N
         gat_scatter(eg.Ms_inc, eg.Mt_inc, dz, da, dPs, dPt, dA2)
 
 
-def gat_maxpath_(a, amax, da):
-    """da[first argmax(a)] -= da.sum()   (stand-alone form; gat_vjp applies it itself)."""
+def gat_maxpath_(a, amax, da, tgt=None, dat=None, ld_dat=1):
+    """da[first argmax(a)] -= da.sum()   (stand-alone form; gat_vjp applies it itself).  With tgt and dat (target-side sums
+    formed before the correction, element v at dat[v * ld_dat]) the same amount leaves dat[tgt[first argmax]]."""
+    lib = _lib.load()
+    _need(dat, "dat")
+    sc = _scratch(a.device, lib.gode_gat_maxpath_scratch_bytes(a.numel()))
+    check(lib.gode_gat_maxpath_f32(ptr(a), ptr(amax), ptr(da), a.numel(), ptr(tgt), ptr(dat), int(ld_dat), ptr(sc), stream_ptr()),
+          "gode_gat_maxpath_f32")
+
+
+def gat_maxpath_route(a, amax, da, tgt=None, dat=None, ld_dat=1):
+    """The route gat_maxpath_ takes on these arguments (nothing is launched)."""
     lib = _lib.load()
     sc = _scratch(a.device, lib.gode_gat_maxpath_scratch_bytes(a.numel()))
-    check(lib.gode_gat_maxpath_f32(ptr(a), ptr(amax), ptr(da), a.numel(), None, None, 0, ptr(sc), stream_ptr()),
-          "gode_gat_maxpath_f32")
+    return lib.gode_gat_maxpath_f32_route(ptr(a), ptr(amax), ptr(da), a.numel(), ptr(tgt), ptr(dat), int(ld_dat), ptr(sc), None)
+
+
+def _scatter_args(Ms_inc, Mt_inc, dz, da, dPs, dPt, dA2):
+    n, o = dPs.shape
+    return (ptr(Ms_inc.rowptr), ptr(Ms_inc.col), ptr(Mt_inc.rowptr), ptr(Mt_inc.col), ptr(dz), ptr(da), o, n, ptr(dPs), o,
+            ptr(dPt), o, ctypes.c_void_p(dA2.data_ptr()), ctypes.c_void_p(dA2.data_ptr() + 4), 2)
 
 
 def gat_scatter(Ms_inc, Mt_inc, dz, da, dPs, dPt, dA2):
     """Edge cotangents summed per source node into dPs / dA2[:,0] and per target node into dPt / dA2[:,1]."""
     lib = _lib.load()
     _need(dz, "dz"); _need(da, "da"); _need(dPs, "dPs"); _need(dPt, "dPt"); _need(dA2, "dA2")
-    n, o = dPs.shape
-    check(lib.gode_gat_scatter_f32(ptr(Ms_inc.rowptr), ptr(Ms_inc.col), ptr(Mt_inc.rowptr), ptr(Mt_inc.col), ptr(dz),
-                                   ptr(da), o, n, ptr(dPs), o, ptr(dPt), o, ctypes.c_void_p(dA2.data_ptr()),
-                                   ctypes.c_void_p(dA2.data_ptr() + 4), 2, stream_ptr()), "gode_gat_scatter_f32")
+    check(lib.gode_gat_scatter_f32(*_scatter_args(Ms_inc, Mt_inc, dz, da, dPs, dPt, dA2), stream_ptr()), "gode_gat_scatter_f32")
+
+
+def gat_scatter_route(Ms_inc, Mt_inc, dz, da, dPs, dPt, dA2):
+    """The route gat_scatter takes on these arguments (nothing is launched)."""
+    return _lib.load().gode_gat_scatter_f32_route(*_scatter_args(Ms_inc, Mt_inc, dz, da, dPs, dPt, dA2), None)
 
 
 def time_row_fixup_(g_row0, w_row0, t, at, accumulate):

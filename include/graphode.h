@@ -421,6 +421,24 @@ typedef struct gode_gat_proj {
 } gode_gat_proj_t;
 int gode_gat_logits_f32(const gode_gat_proj_t* proj, const float* bw, const int32_t* src, const int32_t* tgt,
                         int64_t n_edges, float* a, float* amax, float* scratch, void* stream);
+/* Route queries.  Every launching entry point of the one-head family has a *_route twin that takes the SAME arguments,
+ * launches nothing, reads only the host structs (mt, proj, cot) and the VALUES of the pointers, and returns the same
+ * negative validation code, 0 where the launching call returns before any launch, or the route the launching call takes:
+ *   route = family | form << 8
+ *   family  GODE_GAT_ROUTE_PF     prefetched-index kernels, form = LPR = o / 4 (1, 2: four rows per wave; 4, 8, 16: a wave per row)
+ *           GODE_GAT_ROUTE_WAVE   a wave per row, form = MAXC (1, 2, 4, 8: o <= 64 * MAXC)
+ *           GODE_GAT_ROUTE_GROUP  a lane group per row, form = MAXC
+ *           GODE_GAT_ROUTE_REC    balanced records (+ the finishing launch when rows are split), form = LPR = o / 4
+ *           GODE_GAT_ROUTE_ONE_BLOCK / GODE_GAT_ROUTE_TWO_STAGE   logits and max path, form 0
+ * The launching entry points switch on the value of the same function. */
+#define GODE_GAT_ROUTE_PF        1
+#define GODE_GAT_ROUTE_WAVE      2
+#define GODE_GAT_ROUTE_GROUP     3
+#define GODE_GAT_ROUTE_REC       4
+#define GODE_GAT_ROUTE_ONE_BLOCK 5
+#define GODE_GAT_ROUTE_TWO_STAGE 6
+int gode_gat_logits_f32_route(const gode_gat_proj_t* proj, const float* bw, const int32_t* src, const int32_t* tgt,
+                              int64_t n_edges, float* a, float* amax, float* scratch, void* stream);
 /* mt: CSR by target over the edges (col = edge ids of each target in increasing order, or NULL when the edge list is
  * target-sorted so that edge k is CSR position k), val = Mtgt values (nullable), plus the balanced record list.
  * Above 65 536 targets, with col == NULL and o in {16, 32, 64, 128, 256}, the aggregation runs over the records like
@@ -429,6 +447,9 @@ int gode_gat_logits_f32(const gode_gat_proj_t* proj, const float* bw, const int3
 int gode_gat_agg_f32_fwd(const gode_graph_t* mt, const int32_t* src, const int32_t* tgt,
                          const gode_gat_proj_t* proj, int64_t o, const float* bf, const float* a, const float* amax,
                          float eps, float* out, float* w_out, float* den_out, void* stream);
+int gode_gat_agg_f32_fwd_route(const gode_graph_t* mt, const int32_t* src, const int32_t* tgt,
+                               const gode_gat_proj_t* proj, int64_t o, const float* bf, const float* a, const float* amax,
+                               float eps, float* out, float* w_out, float* den_out, void* stream);
 /* cotangent: dout (n_rows x o), or - when cot (host, nullable) has terms - cot_scale * (sum_j cot_j) masked by out > 0,
  * i.e. the stage cotangent of the adjoint solve pushed through the relu that follows the layer.
  * dz[E x o], da[E] are always written.  dpt / dat / did_target_sums (all nullable): on the record path the kernel also
@@ -439,12 +460,20 @@ int gode_gat_agg_f32_bwd(const gode_graph_t* mt, const int32_t* src, const int32
                          const float* out, const float* dout, const gode_lincomb_t* cot, float cot_scale,
                          float* dz, float* da, float* dpt, int64_t ld_dpt, float* dat, int64_t ld_dat,
                          int32_t* did_target_sums, void* stream);
+/* (does not write *did_target_sums: the launching call sets it to 1 exactly on GODE_GAT_ROUTE_REC) */
+int gode_gat_agg_f32_bwd_route(const gode_graph_t* mt, const int32_t* src, const int32_t* tgt,
+                               const gode_gat_proj_t* proj, int64_t o, const float* bf, const float* w, const float* den,
+                               const float* out, const float* dout, const gode_lincomb_t* cot, float cot_scale,
+                               float* dz, float* da, float* dpt, int64_t ld_dpt, float* dat, int64_t ld_dat,
+                               int32_t* did_target_sums, void* stream);
 /* gradient path through the global maximum of the logits (GAT/layers.py:47): da[e*] -= S, S = sum(da), e* = first
  * argmax; when dat (nullable, with tgt) holds target-side sums formed before the correction, dat[tgt[e*]*ld_dat] -= S.
  * scratch: >= gode_gat_maxpath_scratch_bytes(n_edges) bytes (may be NULL for n_edges <= 32 768 without dat). */
 int64_t gode_gat_maxpath_scratch_bytes(int64_t n_edges);
 int gode_gat_maxpath_f32(const float* a, const float* amax, float* da, int64_t n_edges, const int32_t* tgt,
                          float* dat, int64_t ld_dat, void* scratch, void* stream);
+int gode_gat_maxpath_f32_route(const float* a, const float* amax, float* da, int64_t n_edges, const int32_t* tgt,
+                               float* dat, int64_t ld_dat, void* scratch, void* stream);
 /* H independent heads on one graph run as ONE head on the H-fold graph (node v*H + h = head h of node v, so an
  * N x H*o projection matrix is the (N*H) x o matrix of the virtual nodes; edge e becomes the H edges
  * src*H+h -> tgt*H+h, target-sorted) through the entry points above with amax -> 0.f.  The reference's maximum
@@ -483,6 +512,10 @@ int gode_gat_scatter_f32(const int32_t* rowptr_src, const int32_t* eid_src, cons
                          const int32_t* eid_tgt, const float* dz, const float* da, int64_t o, int64_t n_rows,
                          float* dps, int64_t ld_s, float* dpt, int64_t ld_t, float* das, float* dat, int64_t ld_a,
                          void* stream);
+int gode_gat_scatter_f32_route(const int32_t* rowptr_src, const int32_t* eid_src, const int32_t* rowptr_tgt,
+                               const int32_t* eid_tgt, const float* dz, const float* da, int64_t o, int64_t n_rows,
+                               float* dps, int64_t ld_s, float* dpt, int64_t ld_t, float* das, float* dat, int64_t ld_a,
+                               void* stream);
 /* time row of a weight gradient inside the adjoint: at (+)= <g_row0, w_row0>;  g_row0 *= t  (len floats) */
 int gode_time_row_fixup_f32(float* g_row0, const float* w_row0, int64_t len, float t, float* at, int accumulate,
                             void* stream);
