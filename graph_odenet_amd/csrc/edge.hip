@@ -7,13 +7,14 @@
 // The reference materialises h = [x[src] | x[tgt]] (E x 2i) and runs two Linear layers on it.
 // Here the Linear layers are applied at NODE level by the caller (P = x * [Wf_src | Wf_tgt |
 // ww_src | ww_tgt], one dense GEMM) and the kernels gather N x o rows per edge:
-//   z_e = P[src_e, 0:o] + P[tgt_e, o:2o] + bf,  y_e = relu(z_e)
+//   z_e = P[src_e, 0:o] + P[tgt_e, o:2o] + bf,  y_e = act(z_e)   (relu, or any GODE_GAT_ACT_* as a kernel argument)
 //   a_e = P[src_e, 2o] + P[tgt_e, 2o+1] + bw,   w_e = exp(a_e - max_e a_e)
 //   out_v = sum_{e in row v of Mtgt} val * w_e * y_e / (sum val * w_e + eps)
 // Edges of a target are visited in edge-id order (the order torch.spmm sums a coalesced Mtgt).
 // Bound: HBM (launch-bound at Citeseer/QM9 sizes).  Algorithmic bytes per layer:
 //   GAT: E*(2*4 idx + 4*o gather + 4 logit) + 2*N*o*4;  QC: E*h*h*4 + E*h*8 + N*h*8.
 #include "common.h"
+#include <cmath>
 
 namespace {
 
@@ -71,9 +72,46 @@ __global__ __launch_bounds__(256) void final_max_kernel(const float* pmax, int n
     if (threadIdx.x == 0) out[0] = m;
 }
 
+// ---- the message activation -----------------------------------------------------------------------------------------------
+// y_e = act(z_e) in the forward; the backward needs y (for da) and g * act'(z) (dz, g = val * w * dA).  The aggregation
+// kernels take the activation as a type: ActRelu is the reference's default (GAT/layers.py:16) and the only form the ODE
+// function uses; ActAny is every GODE_GAT_ACT_* behind ONE further instantiation per kernel form, chosen by a switch on a
+// kernel argument (wave-uniform: a scalar branch).  Accurate expf / expm1f / tanhf only.  At z == 0 the derivative is the
+// one torch's autograd gives: 0 for relu, the slope for leaky_relu, alpha for elu.
+struct ActRelu {
+    __device__ __forceinline__ float f(float z) const { return fmaxf(z, 0.f); }
+    __device__ __forceinline__ float d(float z, float, float g) const { return z > 0.f ? g : 0.f; }
+};
+struct ActAny {
+    int code; float p;                  // GODE_GAT_ACT_*; slope of leaky_relu / alpha of elu
+    __device__ __forceinline__ float f(float z) const {
+        switch (code) {
+        case GODE_GAT_ACT_IDENTITY: return z;
+        case GODE_GAT_ACT_LEAKY_RELU: return z > 0.f ? z : p * z;
+        case GODE_GAT_ACT_ELU: return z > 0.f ? z : p * expm1f(z);
+        case GODE_GAT_ACT_TANH: return tanhf(z);
+        case GODE_GAT_ACT_SIGMOID: return 1.f / (1.f + expf(-z));
+        default: return fmaxf(z, 0.f);
+        }
+    }
+    // g * act'(z), given y = act(z)
+    __device__ __forceinline__ float d(float z, float y, float g) const {
+        switch (code) {
+        case GODE_GAT_ACT_IDENTITY: return g;
+        case GODE_GAT_ACT_LEAKY_RELU: return z > 0.f ? g : p * g;
+        case GODE_GAT_ACT_ELU: return z > 0.f ? g : g * (p * expf(z));
+        case GODE_GAT_ACT_TANH: return g * (1.f - y * y);
+        case GODE_GAT_ACT_SIGMOID: return g * (y * (1.f - y));
+        default: return z > 0.f ? g : 0.f;
+        }
+    }
+};
+template <class ACT>
+__device__ __forceinline__ float4 act_f4(const ACT& act, float4 z) { return make_float4(act.f(z.x), act.f(z.y), act.f(z.z), act.f(z.w)); }
+
 // One group of G lanes (power of two <= 64) per target row; lane handles columns c, c+G, ...
 // up to MAXC columns per lane (o <= G*MAXC).
-template <int MAXC>
+template <int MAXC, class ACT>
 __global__ __launch_bounds__(256) void gat_agg_fwd_kernel(const int* __restrict__ rowptr, const int* __restrict__ eid,
                                                           const float* __restrict__ val,
                                                           const int* __restrict__ src, const int* __restrict__ tgt,
@@ -81,7 +119,7 @@ __global__ __launch_bounds__(256) void gat_agg_fwd_kernel(const int* __restrict_
                                                           const float* __restrict__ bf, const float* __restrict__ a,
                                                           const float* __restrict__ amax, float eps, int n_rows, int G,
                                                           float* __restrict__ out, float* __restrict__ w_out,
-                                                          float* __restrict__ s_out) {
+                                                          float* __restrict__ s_out, ACT act) {
     const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int v = (int)(tid / G);
     const int lane = threadIdx.x & (G - 1);
@@ -104,7 +142,7 @@ __global__ __launch_bounds__(256) void gat_agg_fwd_kernel(const int* __restrict_
             const int c = lane + q * G;
             if (c < o) {
                 const float z = ps[c] + pt[c] + bias[q];
-                acc[q] = fmaf(we, fmaxf(z, 0.f), acc[q]);
+                acc[q] = fmaf(we, act.f(z), acc[q]);
             }
         }
     }
@@ -122,7 +160,7 @@ __global__ __launch_bounds__(256) void gat_agg_fwd_kernel(const int* __restrict_
 //   per edge: dy = val*w*dA ; dz = dy*(z>0) -> dz_out[e,:] ; dw = val*(dA.y + dsum) ; da[e] = dw*w
 //   dPtgt[v] (+)= sum_e dz  is NOT formed here (tgt[e] may be any node): dz is scattered by the caller
 //   with two SpMM launches over the src / tgt incidence matrices.
-template <int MAXC>
+template <int MAXC, class ACT>
 __global__ __launch_bounds__(256) void gat_agg_bwd_kernel(const int* __restrict__ rowptr, const int* __restrict__ eid,
                                                           const float* __restrict__ val,
                                                           const int* __restrict__ src, const int* __restrict__ tgt,
@@ -130,7 +168,7 @@ __global__ __launch_bounds__(256) void gat_agg_bwd_kernel(const int* __restrict_
                                                           const float* __restrict__ bf, const float* __restrict__ w,
                                                           const float* __restrict__ den, const float* __restrict__ out,
                                                           const float* __restrict__ dout, int n_rows, int G,
-                                                          float* __restrict__ dz, float* __restrict__ da) {
+                                                          float* __restrict__ dz, float* __restrict__ da, ACT act) {
     const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int v = (int)(tid / G);
     const int lane = threadIdx.x & (G - 1);
@@ -163,9 +201,9 @@ __global__ __launch_bounds__(256) void gat_agg_bwd_kernel(const int* __restrict_
             const int c = lane + q * G;
             if (c < o) {
                 const float z = ps[c] + pt[c] + bias[q];
-                const float y = fmaxf(z, 0.f);
+                const float y = act.f(z);
                 part += dA[q] * y;
-                dz[(int64_t)e * o + c] = z > 0.f ? vv * we * dA[q] : 0.f;
+                dz[(int64_t)e * o + c] = act.d(z, y, vv * we * dA[q]);
             }
         }
         for (int off = G >> 1; off > 0; off >>= 1) part += __shfl_xor(part, off, 64);
@@ -178,7 +216,7 @@ __global__ __launch_bounds__(256) void gat_agg_bwd_kernel(const int* __restrict_
 // 64/G sub-groups of G lanes stride through the row's edges (a 99-edge hub of Citeseer takes 25 trips instead of
 // 99) and are combined with xor-shuffles; used below 65 536 rows, where one lane group per row leaves the chip idle
 // behind the longest row.
-template <int MAXC>
+template <int MAXC, class ACT>
 __global__ __launch_bounds__(256) void gat_agg_fwd_wave_kernel(const int* __restrict__ rowptr, const int* __restrict__ eid,
                                                                const float* __restrict__ val,
                                                                const int* __restrict__ src, const int* __restrict__ tgt,
@@ -186,7 +224,7 @@ __global__ __launch_bounds__(256) void gat_agg_fwd_wave_kernel(const int* __rest
                                                                const float* __restrict__ bf, const float* __restrict__ a,
                                                                const float* __restrict__ amax, HeadMax hm, float eps, int n_rows, int G,
                                                                float* __restrict__ out, float* __restrict__ w_out,
-                                                               float* __restrict__ s_out) {
+                                                               float* __restrict__ s_out, ACT act) {
     const int v = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (v >= n_rows) return;
     const int l = threadIdx.x & 63, lane = l & (G - 1), sg = l / G, ns = 64 / G;
@@ -207,7 +245,7 @@ __global__ __launch_bounds__(256) void gat_agg_fwd_wave_kernel(const int* __rest
 #pragma unroll
         for (int q = 0; q < MAXC; ++q) {
             const int c = lane + q * G;
-            if (c < o) acc[q] = fmaf(we, fmaxf(ps[c] + pt[c] + bias[q], 0.f), acc[q]);
+            if (c < o) acc[q] = fmaf(we, act.f(ps[c] + pt[c] + bias[q]), acc[q]);
         }
     }
     for (int off = G; off < 64; off <<= 1) {
@@ -229,7 +267,7 @@ __global__ __launch_bounds__(256) void gat_agg_fwd_wave_kernel(const int* __rest
 // Backward, wave per row.  The cotangent is either dout[v, c] or, when cot.n > 0, cot_scale * (sum_j cot_j[v, c])
 // masked by out[v, c] > 0 (the relu that follows the layer inside the ODE function): the solver's stage cotangent
 // is combined and masked here instead of in three elementwise launches.
-template <int MAXC>
+template <int MAXC, class ACT>
 __global__ __launch_bounds__(256) void gat_agg_bwd_wave_kernel(const int* __restrict__ rowptr, const int* __restrict__ eid,
                                                                const float* __restrict__ val,
                                                                const int* __restrict__ src, const int* __restrict__ tgt,
@@ -238,7 +276,7 @@ __global__ __launch_bounds__(256) void gat_agg_bwd_wave_kernel(const int* __rest
                                                                const float* __restrict__ den, const float* __restrict__ out,
                                                                const float* __restrict__ dout, LinComb cot, float cot_scale,
                                                                int n_rows, int G,
-                                                               float* __restrict__ dz, float* __restrict__ da) {
+                                                               float* __restrict__ dz, float* __restrict__ da, ACT act) {
     const int v = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (v >= n_rows) return;
     const int l = threadIdx.x & 63, lane = l & (G - 1), sg = l / G, ns = 64 / G;
@@ -274,8 +312,9 @@ __global__ __launch_bounds__(256) void gat_agg_bwd_wave_kernel(const int* __rest
             const int c = lane + q * G;
             if (c < o) {
                 const float z = ps[c] + pt[c] + bias[q];
-                part += dA[q] * fmaxf(z, 0.f);
-                dz[(int64_t)e * o + c] = z > 0.f ? vv * we * dA[q] : 0.f;
+                const float y = act.f(z);
+                part += dA[q] * y;
+                dz[(int64_t)e * o + c] = act.d(z, y, vv * we * dA[q]);
             }
         }
         for (int off = G >> 1; off > 0; off >>= 1) part += __shfl_xor(part, off, 64);
@@ -295,14 +334,14 @@ __device__ __forceinline__ float4 ldf4(const float* p) { return *reinterpret_cas
 // GW = lanes that share a row: 64 (a wave per row) or 16 (four rows per wave, for narrow rows: eight heads of 8 columns on
 // the H-fold graph are 26 616 virtual rows of ~4 edges - a wave per row left three quarters of the prefetch lanes idle).  A
 // chunk is GW CSR slots; NS = GW / LPR edges are gathered per trip.
-template <int LPR, int GW>
+template <int LPR, int GW, class ACT>
 __global__ __launch_bounds__(256) void gat_agg_fwd_pf_kernel(const int* __restrict__ rowptr, const int* __restrict__ eid,
                                                              const float* __restrict__ val,
                                                              const int* __restrict__ src, const int* __restrict__ tgt,
                                                              Proj pv, const float* __restrict__ bf, const float* __restrict__ a,
                                                              const float* __restrict__ amax, HeadMax hm, float eps, int n_rows,
                                                              float* __restrict__ out, float* __restrict__ w_out,
-                                                             float* __restrict__ s_out) {
+                                                             float* __restrict__ s_out, ACT act) {
     constexpr int O = 4 * LPR, NS = GW / LPR, U = LPR < 4 ? LPR : 4, RPW = 64 / GW;
     const int l = threadIdx.x & 63, gl = l & (GW - 1), q = gl & (LPR - 1), sg = gl / LPR;
     const int v = (blockIdx.x * 4 + (threadIdx.x >> 6)) * RPW + l / GW;
@@ -343,8 +382,8 @@ __global__ __launch_bounds__(256) void gat_agg_fwd_pf_kernel(const int* __restri
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 s += wj[u];
-                acc.x = fmaf(wj[u], fmaxf(xv[u].x + cc[u].x, 0.f), acc.x); acc.y = fmaf(wj[u], fmaxf(xv[u].y + cc[u].y, 0.f), acc.y);
-                acc.z = fmaf(wj[u], fmaxf(xv[u].z + cc[u].z, 0.f), acc.z); acc.w = fmaf(wj[u], fmaxf(xv[u].w + cc[u].w, 0.f), acc.w);
+                acc.x = fmaf(wj[u], act.f(xv[u].x + cc[u].x), acc.x); acc.y = fmaf(wj[u], act.f(xv[u].y + cc[u].y), acc.y);
+                acc.z = fmaf(wj[u], act.f(xv[u].z + cc[u].z), acc.z); acc.w = fmaf(wj[u], act.f(xv[u].w + cc[u].w), acc.w);
             }
         }
     }
@@ -359,14 +398,14 @@ __global__ __launch_bounds__(256) void gat_agg_fwd_pf_kernel(const int* __restri
     if (sg == 0) *reinterpret_cast<float4*>(out + (int64_t)v * O + 4 * q) = make_float4(acc.x / den, acc.y / den, acc.z / den, acc.w / den);
 }
 
-template <int LPR, int GW>
+template <int LPR, int GW, class ACT>
 __global__ __launch_bounds__(256) void gat_agg_bwd_pf_kernel(const int* __restrict__ rowptr, const int* __restrict__ eid,
                                                              const float* __restrict__ val,
                                                              const int* __restrict__ src, const int* __restrict__ tgt,
                                                              Proj pv, const float* __restrict__ bf, const float* __restrict__ w,
                                                              const float* __restrict__ den, const float* __restrict__ out,
                                                              const float* __restrict__ dout, LinComb cot, float cot_scale,
-                                                             int n_rows, float* __restrict__ dz, float* __restrict__ da) {
+                                                             int n_rows, float* __restrict__ dz, float* __restrict__ da, ACT act) {
     constexpr int O = 4 * LPR, NS = GW / LPR, U = LPR < 4 ? LPR : 4, RPW = 64 / GW;
     const int l = threadIdx.x & 63, gl = l & (GW - 1), q = gl & (LPR - 1), sg = gl / LPR;
     const int v = (blockIdx.x * 4 + (threadIdx.x >> 6)) * RPW + l / GW;
@@ -414,14 +453,15 @@ __global__ __launch_bounds__(256) void gat_agg_bwd_pf_kernel(const int* __restri
                 const int ej = __shfl(e, j, GW);
                 const float wej = __shfl(we, j, GW), vj = __shfl(vv, j, GW);
                 const float4 z = make_float4(xv[u].x + cc[u].x, xv[u].y + cc[u].y, xv[u].z + cc[u].z, xv[u].w + cc[u].w);
-                float part = (dA.x * fmaxf(z.x, 0.f) + dA.y * fmaxf(z.y, 0.f)) + (dA.z * fmaxf(z.z, 0.f) + dA.w * fmaxf(z.w, 0.f));
+                const float4 y = act_f4(act, z);
+                float part = (dA.x * y.x + dA.y * y.y) + (dA.z * y.z + dA.w * y.w);
 #pragma unroll
                 for (int off = LPR >> 1; off > 0; off >>= 1) part += __shfl_xor(part, off, 64);
                 if (j < cnt) {
                     const float sc2 = vj * wej;
                     *reinterpret_cast<float4*>(dz + (int64_t)ej * O + 4 * q) =
-                        make_float4(z.x > 0.f ? sc2 * dA.x : 0.f, z.y > 0.f ? sc2 * dA.y : 0.f,
-                                    z.z > 0.f ? sc2 * dA.z : 0.f, z.w > 0.f ? sc2 * dA.w : 0.f);
+                        make_float4(act.d(z.x, y.x, sc2 * dA.x), act.d(z.y, y.y, sc2 * dA.y),
+                                    act.d(z.z, y.z, sc2 * dA.z), act.d(z.w, y.w, sc2 * dA.w));
                     if (q == 0) da[ej] = vj * (part + dsum) * wej;
                 }
             }
@@ -484,13 +524,13 @@ __global__ __launch_bounds__(256) void gat_scatter_pf_kernel(const int* __restri
 // coalesced o*4-byte row per edge with 16 B per lane.  A group of LPR = o/4 lanes owns one record {row, begin, end,
 // slot}; rows longer than the graph's split length are cut into records that write raw partial sums into the slab
 // (row stride o+4: o numerator columns + the denominator) and are finished in slot order by a second small kernel.
-template <int LPR>
+template <int LPR, class ACT>
 __global__ __launch_bounds__(256) void gat_agg_fwd_rec_kernel(const int4* __restrict__ items, int n_items,
                                                               const int* __restrict__ src, const float* __restrict__ val,
                                                               Proj pv, const float* __restrict__ bf,
                                                               const float* __restrict__ a, const float* __restrict__ amax,
                                                               float eps, float* __restrict__ out, float* __restrict__ w_out,
-                                                              float* __restrict__ den_out, float* __restrict__ partial) {
+                                                              float* __restrict__ den_out, float* __restrict__ partial, ACT act) {
     constexpr int U = 4, O = LPR * 4;
     const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int gid = (int)(tid / LPR);
@@ -532,8 +572,8 @@ __global__ __launch_bounds__(256) void gat_agg_fwd_rec_kernel(const int4* __rest
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 s += vv[u];
-                acc.x = fmaf(vv[u], fmaxf(xv[u].x + c.x, 0.f), acc.x); acc.y = fmaf(vv[u], fmaxf(xv[u].y + c.y, 0.f), acc.y);
-                acc.z = fmaf(vv[u], fmaxf(xv[u].z + c.z, 0.f), acc.z); acc.w = fmaf(vv[u], fmaxf(xv[u].w + c.w, 0.f), acc.w);
+                acc.x = fmaf(vv[u], act.f(xv[u].x + c.x), acc.x); acc.y = fmaf(vv[u], act.f(xv[u].y + c.y), acc.y);
+                acc.z = fmaf(vv[u], act.f(xv[u].z + c.z), acc.z); acc.w = fmaf(vv[u], act.f(xv[u].w + c.w), acc.w);
             }
         }
     }
@@ -575,7 +615,7 @@ __global__ __launch_bounds__(256) void gat_agg_fwd_finish_kernel(const int4* __r
 // Backward over records.  Besides dz[k,:] and da[k] it accumulates the target-side sums dpt[v,:] = sum_k dz[k,:]
 // and dat[v] = sum_k da[k] of its record (rows of edge cotangents are contiguous per target in this order), so the
 // caller needs incidence products only for the source side.
-template <int LPR>
+template <int LPR, class ACT>
 __global__ __launch_bounds__(256) void gat_agg_bwd_rec_kernel(const int4* __restrict__ items, int n_items,
                                                               const int* __restrict__ src, const float* __restrict__ val,
                                                               Proj pv, const float* __restrict__ bf,
@@ -584,7 +624,7 @@ __global__ __launch_bounds__(256) void gat_agg_bwd_rec_kernel(const int4* __rest
                                                               LinComb cot, float cot_scale,
                                                               float* __restrict__ dz, float* __restrict__ da,
                                                               float* __restrict__ dpt, int64_t ld_dpt, float* __restrict__ dat,
-                                                              int64_t ld_dat, float* __restrict__ partial) {
+                                                              int64_t ld_dat, float* __restrict__ partial, ACT act) {
     constexpr int U = 4, O = LPR * 4;
     const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int gid = (int)(tid / LPR);
@@ -640,10 +680,11 @@ __global__ __launch_bounds__(256) void gat_agg_bwd_rec_kernel(const int4* __rest
             for (int u = 0; u < U; ++u) {
                 const bool live = k + u < cnt && k + u < LPR;
                 const float4 z = make_float4(xv[u].x + c.x, xv[u].y + c.y, xv[u].z + c.z, xv[u].w + c.w);
-                part[u] = (dA.x * fmaxf(z.x, 0.f) + dA.y * fmaxf(z.y, 0.f)) + (dA.z * fmaxf(z.z, 0.f) + dA.w * fmaxf(z.w, 0.f));
+                const float4 y = act_f4(act, z);
+                part[u] = (dA.x * y.x + dA.y * y.y) + (dA.z * y.z + dA.w * y.w);
                 const float f = vv[u] * ww[u];
-                const float4 t = make_float4(z.x > 0.f ? f * dA.x : 0.f, z.y > 0.f ? f * dA.y : 0.f,
-                                             z.z > 0.f ? f * dA.z : 0.f, z.w > 0.f ? f * dA.w : 0.f);
+                const float4 t = make_float4(act.d(z.x, y.x, f * dA.x), act.d(z.y, y.y, f * dA.y),
+                                             act.d(z.z, y.z, f * dA.z), act.d(z.w, y.w, f * dA.w));
                 if (live) {
                     *reinterpret_cast<float4*>(dz + (int64_t)(b + base + k + u) * O + lane * 4) = t;
                     acc.x += t.x; acc.y += t.y; acc.z += t.z; acc.w += t.w;
@@ -1247,9 +1288,11 @@ int agg_bwd_csr_route(const Proj& pv, int64_t o, int64_t n_rows, const void* out
     return route_code(GODE_GAT_ROUTE_GROUP, maxc_form(o));
 }
 
+template <class ACT>
 int launch_agg_fwd(const int32_t* rowptr, const int32_t* eid, const float* val, const int32_t* src, const int32_t* tgt,
                    const Proj& pv, int64_t o, const float* bf, const float* a, const float* amax, float eps,
-                   int64_t n_rows, float* out, float* w_out, float* den_out, hipStream_t s, int rt, HeadMax hm = HeadMax{nullptr, 0, 0}) {
+                   int64_t n_rows, float* out, float* w_out, float* den_out, hipStream_t s, int rt, ACT act,
+                   HeadMax hm = HeadMax{nullptr, 0, 0}) {
     const int G = pow2_group((int)o);
     const int family = route_family(rt), form = route_form(rt);
     const bool wave = family == GODE_GAT_ROUTE_WAVE;
@@ -1257,8 +1300,8 @@ int launch_agg_fwd(const int32_t* rowptr, const int32_t* eid, const float* val, 
     const int64_t blocks = wave ? (n_rows + 3) / 4 : (n_rows * G + 255) / 256;
     switch (family) {
     case GODE_GAT_ROUTE_PF:
-#define GODE_PF(L, W) hipLaunchKernelGGL((gat_agg_fwd_pf_kernel<L, W>), dim3((unsigned)((n_rows + 4 * (64 / W) - 1) / (4 * (64 / W)))), dim3(256), 0, s, \
-                                         rowptr, eid, val, src, tgt, pv, bf, a, amax, hm, eps, (int)n_rows, out, w_out, den_out)
+#define GODE_PF(L, W) hipLaunchKernelGGL((gat_agg_fwd_pf_kernel<L, W, ACT>), dim3((unsigned)((n_rows + 4 * (64 / W) - 1) / (4 * (64 / W)))), dim3(256), 0, s, \
+                                         rowptr, eid, val, src, tgt, pv, bf, a, amax, hm, eps, (int)n_rows, out, w_out, den_out, act)
         switch (form) { case 1: GODE_PF(1, 16); break; case 2: GODE_PF(2, 16); break; case 4: GODE_PF(4, 64); break; case 8: GODE_PF(8, 64); break;
                         case 16: GODE_PF(16, 64); break; default: return GODE_E_UNSUPPORTED; }
 #undef GODE_PF
@@ -1267,10 +1310,10 @@ int launch_agg_fwd(const int32_t* rowptr, const int32_t* eid, const float* val, 
     case GODE_GAT_ROUTE_GROUP:
 #define GODE_AGG(M)                                                                                              \
     do {                                                                                                         \
-        if (wave) hipLaunchKernelGGL(gat_agg_fwd_wave_kernel<M>, dim3((unsigned)blocks), dim3(256), 0, s, rowptr, eid, val, \
-                                     src, tgt, pv, (int)o, bf, a, amax, hm, eps, (int)n_rows, G, out, w_out, den_out); \
-        else hipLaunchKernelGGL(gat_agg_fwd_kernel<M>, dim3((unsigned)blocks), dim3(256), 0, s, rowptr, eid, val, \
-                                src, tgt, pv, (int)o, bf, a, amax, eps, (int)n_rows, G, out, w_out, den_out);     \
+        if (wave) hipLaunchKernelGGL((gat_agg_fwd_wave_kernel<M, ACT>), dim3((unsigned)blocks), dim3(256), 0, s, rowptr, eid, val, \
+                                     src, tgt, pv, (int)o, bf, a, amax, hm, eps, (int)n_rows, G, out, w_out, den_out, act); \
+        else hipLaunchKernelGGL((gat_agg_fwd_kernel<M, ACT>), dim3((unsigned)blocks), dim3(256), 0, s, rowptr, eid, val, \
+                                src, tgt, pv, (int)o, bf, a, amax, eps, (int)n_rows, G, out, w_out, den_out, act); \
     } while (0)
         switch (form) { case 1: GODE_AGG(1); break; case 2: GODE_AGG(2); break; case 4: GODE_AGG(4); break; case 8: GODE_AGG(8); break;
                         default: return GODE_E_UNSUPPORTED; }
@@ -1282,18 +1325,19 @@ int launch_agg_fwd(const int32_t* rowptr, const int32_t* eid, const float* val, 
     return 0;
 }
 
+template <class ACT>
 int launch_agg_bwd(const int32_t* rowptr, const int32_t* eid, const float* val, const int32_t* src, const int32_t* tgt,
                    const Proj& pv, int64_t o, const float* bf, const float* w, const float* den, const float* out,
                    const float* dout, const LinComb& cot, float cot_scale, int64_t n_rows, float* dz, float* da,
-                   hipStream_t s, int rt) {
+                   hipStream_t s, int rt, ACT act) {
     const int G = pow2_group((int)o);
     const int family = route_family(rt), form = route_form(rt);
     const bool wave = family == GODE_GAT_ROUTE_WAVE;
     const int64_t blocks = wave ? (n_rows + 3) / 4 : (n_rows * G + 255) / 256;
     switch (family) {
     case GODE_GAT_ROUTE_PF:
-#define GODE_PF(L, W) hipLaunchKernelGGL((gat_agg_bwd_pf_kernel<L, W>), dim3((unsigned)((n_rows + 4 * (64 / W) - 1) / (4 * (64 / W)))), dim3(256), 0, s, \
-                                         rowptr, eid, val, src, tgt, pv, bf, w, den, out, dout, cot, cot_scale, (int)n_rows, dz, da)
+#define GODE_PF(L, W) hipLaunchKernelGGL((gat_agg_bwd_pf_kernel<L, W, ACT>), dim3((unsigned)((n_rows + 4 * (64 / W) - 1) / (4 * (64 / W)))), dim3(256), 0, s, \
+                                         rowptr, eid, val, src, tgt, pv, bf, w, den, out, dout, cot, cot_scale, (int)n_rows, dz, da, act)
         switch (form) { case 1: GODE_PF(1, 16); break; case 2: GODE_PF(2, 16); break; case 4: GODE_PF(4, 64); break; case 8: GODE_PF(8, 64); break;
                         case 16: GODE_PF(16, 64); break; default: return GODE_E_UNSUPPORTED; }
 #undef GODE_PF
@@ -1302,10 +1346,10 @@ int launch_agg_bwd(const int32_t* rowptr, const int32_t* eid, const float* val, 
     case GODE_GAT_ROUTE_GROUP:
 #define GODE_AGG(M)                                                                                              \
     do {                                                                                                         \
-        if (wave) hipLaunchKernelGGL(gat_agg_bwd_wave_kernel<M>, dim3((unsigned)blocks), dim3(256), 0, s, rowptr, eid, val, \
-                                     src, tgt, pv, (int)o, bf, w, den, out, dout, cot, cot_scale, (int)n_rows, G, dz, da); \
-        else hipLaunchKernelGGL(gat_agg_bwd_kernel<M>, dim3((unsigned)blocks), dim3(256), 0, s, rowptr, eid, val, \
-                                src, tgt, pv, (int)o, bf, w, den, out, dout, (int)n_rows, G, dz, da);             \
+        if (wave) hipLaunchKernelGGL((gat_agg_bwd_wave_kernel<M, ACT>), dim3((unsigned)blocks), dim3(256), 0, s, rowptr, eid, val, \
+                                     src, tgt, pv, (int)o, bf, w, den, out, dout, cot, cot_scale, (int)n_rows, G, dz, da, act); \
+        else hipLaunchKernelGGL((gat_agg_bwd_kernel<M, ACT>), dim3((unsigned)blocks), dim3(256), 0, s, rowptr, eid, val, \
+                                src, tgt, pv, (int)o, bf, w, den, out, dout, (int)n_rows, G, dz, da, act);        \
     } while (0)
         switch (form) { case 1: GODE_AGG(1); break; case 2: GODE_AGG(2); break; case 4: GODE_AGG(4); break; case 8: GODE_AGG(8); break;
                         default: return GODE_E_UNSUPPORTED; }
@@ -1365,11 +1409,12 @@ extern "C" int gode_gat_agg_f32_fwd_route(const gode_graph_t* mt, const int32_t*
     return agg_fwd_csr_route(pv, o, n_rows, out, bf);
 }
 
-extern "C" int gode_gat_agg_f32_fwd(const gode_graph_t* mt, const int32_t* src, const int32_t* tgt,
-                                    const gode_gat_proj_t* proj, int64_t o, const float* bf, const float* a,
-                                    const float* amax, float eps, float* out, float* w_out, float* den_out, void* stream) {
-    const int rt = gode_gat_agg_f32_fwd_route(mt, src, tgt, proj, o, bf, a, amax, eps, out, w_out, den_out, stream);
-    if (rt <= 0) return rt;
+namespace {
+// the launches of route rt (> 0: the arguments passed gode_gat_agg_f32_fwd_route) with the message activation `act`
+template <class ACT>
+int agg_fwd_launch(int rt, const gode_graph_t* mt, const int32_t* src, const int32_t* tgt, const gode_gat_proj_t* proj, int64_t o,
+                   const float* bf, const float* a, const float* amax, float eps, float* out, float* w_out, float* den_out,
+                   void* stream, ACT act) {
     const int64_t n_rows = mt->n_rows;
     const Proj pv = proj_of(proj);
     hipStream_t s = (hipStream_t)stream;
@@ -1379,8 +1424,8 @@ extern "C" int gode_gat_agg_f32_fwd(const gode_graph_t* mt, const int32_t* src, 
         const int64_t fblocks = (mt->n_long * lpr + 255) / 256;
 #define GODE_REC(L)                                                                                                   \
         do {                                                                                                          \
-            hipLaunchKernelGGL(gat_agg_fwd_rec_kernel<L>, dim3((unsigned)blocks), dim3(256), 0, s, (const int4*)mt->items, \
-                               (int)mt->n_items, src, mt->val, pv, bf, a, amax, eps, out, w_out, den_out, mt->partial); \
+            hipLaunchKernelGGL((gat_agg_fwd_rec_kernel<L, ACT>), dim3((unsigned)blocks), dim3(256), 0, s, (const int4*)mt->items, \
+                               (int)mt->n_items, src, mt->val, pv, bf, a, amax, eps, out, w_out, den_out, mt->partial, act); \
             if (mt->n_long > 0)                                                                                       \
                 hipLaunchKernelGGL(gat_agg_fwd_finish_kernel<L>, dim3((unsigned)fblocks), dim3(256), 0, s,            \
                                    (const int4*)mt->long_rows, (int)mt->n_long, (const float*)mt->partial, eps, out, den_out); \
@@ -1391,7 +1436,47 @@ extern "C" int gode_gat_agg_f32_fwd(const gode_graph_t* mt, const int32_t* src, 
         GODE_LAUNCH_CHECK();
         return 0;
     }
-    return launch_agg_fwd(mt->rowptr, mt->col, mt->val, src, tgt, pv, o, bf, a, amax, eps, n_rows, out, w_out, den_out, s, rt);
+    return launch_agg_fwd(mt->rowptr, mt->col, mt->val, src, tgt, pv, o, bf, a, amax, eps, n_rows, out, w_out, den_out, s, rt, act);
+}
+
+// The checks of the gode_gat_agg_act_* entry points that come before everything else: no pointer but `cot` (whose term
+// count is the question) is looked at.
+int act_check(int32_t act, float act_param, const gode_lincomb_t* cot) {
+    if (act < GODE_GAT_ACT_RELU || act > GODE_GAT_ACT_SIGMOID) return GODE_E_SHAPE;
+    if ((act == GODE_GAT_ACT_LEAKY_RELU || act == GODE_GAT_ACT_ELU) && !std::isfinite(act_param)) return GODE_E_SHAPE;
+    if (act != GODE_GAT_ACT_RELU && cot && cot->n > 0) return GODE_E_UNSUPPORTED;   // the masked cotangent is the ODE function's: relu only
+    return 0;
+}
+}  // namespace
+
+extern "C" int gode_gat_agg_f32_fwd(const gode_graph_t* mt, const int32_t* src, const int32_t* tgt,
+                                    const gode_gat_proj_t* proj, int64_t o, const float* bf, const float* a,
+                                    const float* amax, float eps, float* out, float* w_out, float* den_out, void* stream) {
+    const int rt = gode_gat_agg_f32_fwd_route(mt, src, tgt, proj, o, bf, a, amax, eps, out, w_out, den_out, stream);
+    if (rt <= 0) return rt;
+    return agg_fwd_launch(rt, mt, src, tgt, proj, o, bf, a, amax, eps, out, w_out, den_out, stream, ActRelu{});
+}
+
+// ---- the same aggregation with the message activation as an argument (GODE_GAT_ACT_*) ------------------------------------
+// Dispatch does not depend on the activation: the route is the relu entry point's, and GODE_GAT_ACT_RELU IS the relu
+// entry point (same kernels).  Every other activation runs the ActAny instantiation of the route's kernel.
+extern "C" int gode_gat_agg_act_f32_fwd_route(const gode_graph_t* mt, const int32_t* src, const int32_t* tgt,
+                                              const gode_gat_proj_t* proj, int64_t o, const float* bf, const float* a,
+                                              const float* amax, float eps, float* out, float* w_out, float* den_out,
+                                              int32_t act, float act_param, void* stream) {
+    const int rc = act_check(act, act_param, nullptr); if (rc) return rc;
+    return gode_gat_agg_f32_fwd_route(mt, src, tgt, proj, o, bf, a, amax, eps, out, w_out, den_out, stream);
+}
+
+extern "C" int gode_gat_agg_act_f32_fwd(const gode_graph_t* mt, const int32_t* src, const int32_t* tgt,
+                                        const gode_gat_proj_t* proj, int64_t o, const float* bf, const float* a,
+                                        const float* amax, float eps, float* out, float* w_out, float* den_out,
+                                        int32_t act, float act_param, void* stream) {
+    const int rc = act_check(act, act_param, nullptr); if (rc) return rc;
+    if (act == GODE_GAT_ACT_RELU) return gode_gat_agg_f32_fwd(mt, src, tgt, proj, o, bf, a, amax, eps, out, w_out, den_out, stream);
+    const int rt = gode_gat_agg_f32_fwd_route(mt, src, tgt, proj, o, bf, a, amax, eps, out, w_out, den_out, stream);
+    if (rt <= 0) return rt;
+    return agg_fwd_launch(rt, mt, src, tgt, proj, o, bf, a, amax, eps, out, w_out, den_out, stream, ActAny{act, act_param});
 }
 
 extern "C" int gode_gat_agg_f32_bwd_route(const gode_graph_t* mt, const int32_t* src, const int32_t* tgt,
@@ -1418,15 +1503,13 @@ extern "C" int gode_gat_agg_f32_bwd_route(const gode_graph_t* mt, const int32_t*
     return agg_bwd_csr_route(pv, o, n_rows, out, bf, dout, dz, make_lincomb(use_cot ? cot : nullptr));
 }
 
-extern "C" int gode_gat_agg_f32_bwd(const gode_graph_t* mt, const int32_t* src, const int32_t* tgt,
-                                    const gode_gat_proj_t* proj, int64_t o, const float* bf, const float* w,
-                                    const float* den, const float* out, const float* dout, const gode_lincomb_t* cot,
-                                    float cot_scale, float* dz, float* da, float* dpt, int64_t ld_dpt, float* dat,
-                                    int64_t ld_dat, int32_t* did_target_sums, void* stream) {
-    if (mt && did_target_sums) *did_target_sums = 0;
-    const int rt = gode_gat_agg_f32_bwd_route(mt, src, tgt, proj, o, bf, w, den, out, dout, cot, cot_scale, dz, da, dpt, ld_dpt,
-                                              dat, ld_dat, did_target_sums, stream);
-    if (rt <= 0) return rt;
+namespace {
+// the launches of route rt (> 0: the arguments passed gode_gat_agg_f32_bwd_route) with the message activation `act`
+template <class ACT>
+int agg_bwd_launch(int rt, const gode_graph_t* mt, const int32_t* src, const int32_t* tgt, const gode_gat_proj_t* proj, int64_t o,
+                   const float* bf, const float* w, const float* den, const float* out, const float* dout,
+                   const gode_lincomb_t* cot, float cot_scale, float* dz, float* da, float* dpt, int64_t ld_dpt, float* dat,
+                   int64_t ld_dat, int32_t* did_target_sums, void* stream, ACT act) {
     const int64_t n_rows = mt->n_rows;
     const bool use_cot = cot && cot->n > 0;
     const Proj pv = proj_of(proj);
@@ -1438,9 +1521,9 @@ extern "C" int gode_gat_agg_f32_bwd(const gode_graph_t* mt, const int32_t* src, 
         const int64_t fblocks = (mt->n_long * lpr + 255) / 256;
 #define GODE_REC(L)                                                                                                   \
         do {                                                                                                          \
-            hipLaunchKernelGGL(gat_agg_bwd_rec_kernel<L>, dim3((unsigned)blocks), dim3(256), 0, s, (const int4*)mt->items, \
+            hipLaunchKernelGGL((gat_agg_bwd_rec_kernel<L, ACT>), dim3((unsigned)blocks), dim3(256), 0, s, (const int4*)mt->items, \
                                (int)mt->n_items, src, mt->val, pv, bf, w, den, out, dout, lc, cot_scale, dz, da, dpt,  \
-                               ld_dpt, dat, ld_dat, mt->partial);                                                     \
+                               ld_dpt, dat, ld_dat, mt->partial, act);                                                \
             if (mt->n_long > 0)                                                                                       \
                 hipLaunchKernelGGL(gat_agg_bwd_finish_kernel<L>, dim3((unsigned)fblocks), dim3(256), 0, s,            \
                                    (const int4*)mt->long_rows, (int)mt->n_long, (const float*)mt->partial, dpt, ld_dpt, \
@@ -1454,7 +1537,49 @@ extern "C" int gode_gat_agg_f32_bwd(const gode_graph_t* mt, const int32_t* src, 
         return 0;
     }
     return launch_agg_bwd(mt->rowptr, mt->col, mt->val, src, tgt, pv, o, bf, w, den, out, dout, lc, cot_scale, n_rows,
-                          dz, da, s, rt);
+                          dz, da, s, rt, act);
+}
+}  // namespace
+
+extern "C" int gode_gat_agg_f32_bwd(const gode_graph_t* mt, const int32_t* src, const int32_t* tgt,
+                                    const gode_gat_proj_t* proj, int64_t o, const float* bf, const float* w,
+                                    const float* den, const float* out, const float* dout, const gode_lincomb_t* cot,
+                                    float cot_scale, float* dz, float* da, float* dpt, int64_t ld_dpt, float* dat,
+                                    int64_t ld_dat, int32_t* did_target_sums, void* stream) {
+    if (mt && did_target_sums) *did_target_sums = 0;
+    const int rt = gode_gat_agg_f32_bwd_route(mt, src, tgt, proj, o, bf, w, den, out, dout, cot, cot_scale, dz, da, dpt, ld_dpt,
+                                              dat, ld_dat, did_target_sums, stream);
+    if (rt <= 0) return rt;
+    return agg_bwd_launch(rt, mt, src, tgt, proj, o, bf, w, den, out, dout, cot, cot_scale, dz, da, dpt, ld_dpt, dat, ld_dat,
+                          did_target_sums, stream, ActRelu{});
+}
+
+extern "C" int gode_gat_agg_act_f32_bwd_route(const gode_graph_t* mt, const int32_t* src, const int32_t* tgt,
+                                              const gode_gat_proj_t* proj, int64_t o, const float* bf, const float* w,
+                                              const float* den, const float* out, const float* dout, const gode_lincomb_t* cot,
+                                              float cot_scale, float* dz, float* da, float* dpt, int64_t ld_dpt, float* dat,
+                                              int64_t ld_dat, int32_t* did_target_sums, int32_t act, float act_param,
+                                              void* stream) {
+    const int rc = act_check(act, act_param, cot); if (rc) return rc;
+    return gode_gat_agg_f32_bwd_route(mt, src, tgt, proj, o, bf, w, den, out, dout, cot, cot_scale, dz, da, dpt, ld_dpt, dat,
+                                      ld_dat, did_target_sums, stream);
+}
+
+extern "C" int gode_gat_agg_act_f32_bwd(const gode_graph_t* mt, const int32_t* src, const int32_t* tgt,
+                                        const gode_gat_proj_t* proj, int64_t o, const float* bf, const float* w,
+                                        const float* den, const float* out, const float* dout, const gode_lincomb_t* cot,
+                                        float cot_scale, float* dz, float* da, float* dpt, int64_t ld_dpt, float* dat,
+                                        int64_t ld_dat, int32_t* did_target_sums, int32_t act, float act_param, void* stream) {
+    const int rc = act_check(act, act_param, cot); if (rc) return rc;
+    if (act == GODE_GAT_ACT_RELU)
+        return gode_gat_agg_f32_bwd(mt, src, tgt, proj, o, bf, w, den, out, dout, cot, cot_scale, dz, da, dpt, ld_dpt, dat, ld_dat,
+                                    did_target_sums, stream);
+    if (mt && did_target_sums) *did_target_sums = 0;
+    const int rt = gode_gat_agg_f32_bwd_route(mt, src, tgt, proj, o, bf, w, den, out, dout, cot, cot_scale, dz, da, dpt, ld_dpt,
+                                              dat, ld_dat, did_target_sums, stream);
+    if (rt <= 0) return rt;
+    return agg_bwd_launch(rt, mt, src, tgt, proj, o, bf, w, den, out, dout, cot, cot_scale, dz, da, dpt, ld_dpt, dat, ld_dat,
+                          did_target_sums, stream, ActAny{act, act_param});
 }
 
 extern "C" int64_t gode_gat_maxpath_scratch_bytes(int64_t n_edges) {
@@ -1611,7 +1736,7 @@ extern "C" int gode_gat_agg_heads_f32_fwd(const gode_graph_t* mt, const int32_t*
     HeadMax hm;
     hm.pmax = (const float*)scratch + 2 * (int64_t)kHeadBlocks * heads; hm.n_part = n_edges > 0 ? head_blocks(n_edges) : 0; hm.H = (int)heads;
     return launch_agg_fwd(mt->rowptr, mt->col, mt->val, src, tgt, pv, o, bf, a, nullptr, eps, n_rows, out, w_out, den_out,
-                          (hipStream_t)stream, agg_fwd_csr_route(pv, o, n_rows, out, bf), hm);
+                          (hipStream_t)stream, agg_fwd_csr_route(pv, o, n_rows, out, bf), ActRelu{}, hm);
 }
 
 // the first half only: per-block sums of da and arg-max candidates stay in `scratch`; gode_gat_dense_vjp_small_f32 closes the

@@ -24,7 +24,7 @@ from torch.nn.modules.module import Module
 
 from . import ops
 from . import models as _gcn_models
-from .gat_layers import EdgeGraph, GraphConvolution, edge_graph
+from .gat_layers import EdgeGraph, GraphConvolution, _kernel_act, edge_graph
 from .gat_ode import gat_fields
 from .models import _gn
 
@@ -57,7 +57,7 @@ class _EdgeAttentionHeadsFn(torch.autograd.Function):
     logit part by source and by target, bias folded into the latter)."""
 
     @staticmethod
-    def forward(ctx, egv, heads, Ps, Pt, A2, eps):
+    def forward(ctx, egv, heads, Ps, Pt, A2, eps, act=None):
         Ps, Pt, A2 = Ps.contiguous(), Pt.contiguous(), A2.contiguous()
         n, d = Ps.shape
         o, nv = d // heads, n * heads
@@ -66,8 +66,8 @@ class _EdgeAttentionHeadsFn(torch.autograd.Function):
         out, w, den = torch.empty(n, d, **f), torch.empty(egv.E, **f), torch.empty(nv, **f)
         proj = ops.gat_proj(Ps.view(nv, o), Pt.view(nv, o), A2.view(nv, 2))
         ops.gat_logits_heads(proj, egv.src, egv.tgt, heads, a)
-        ops.gat_agg_fwd(egv, proj, o, torch.zeros(o, **f), a, zero, eps, out.view(nv, o), w, den)
-        ctx.egv, ctx.heads = egv, heads
+        ops.gat_agg_fwd(egv, proj, o, torch.zeros(o, **f), a, zero, eps, out.view(nv, o), w, den, act=act)
+        ctx.egv, ctx.heads, ctx.act = egv, heads, act
         ctx.save_for_backward(Ps, Pt, A2, a, w, den, out)
         return out
 
@@ -82,8 +82,9 @@ class _EdgeAttentionHeadsFn(torch.autograd.Function):
         dPs, dPt, dA2 = torch.empty(n, d, **f), torch.empty(n, d, **f), torch.empty(n, 2 * heads, **f)
         proj = ops.gat_proj(Ps.view(nv, o), Pt.view(nv, o), A2.view(nv, 2))
         ops.gat_vjp(egv, proj, o, torch.zeros(o, **f), a, torch.zeros(1, **f), w, den, out.view(nv, o), dz, da,
-                    dPs.view(nv, o), dPt.view(nv, o), dA2.view(nv, 2), dout=dout.contiguous().view(nv, o), heads=heads)
-        return None, None, dPs, dPt, dA2, None
+                    dPs.view(nv, o), dPt.view(nv, o), dA2.view(nv, 2), dout=dout.contiguous().view(nv, o), heads=heads,
+                    act=ctx.act)
+        return None, None, dPs, dPt, dA2, None, None
 
 
 class MultiHeadGraphConvolution(Module):
@@ -124,15 +125,18 @@ class MultiHeadGraphConvolution(Module):
 
 
 def _heads_forward(layer, x, src, tgt, Mtgt):
-    if layer.act is not F.relu:          # any other activation: every head through the general (unfused) layer path
+    ka = _kernel_act(layer)
+    if ka is False:                      # an activation the kernels do not restate: every head through the general (unfused) layer path
         return torch.cat([hd(x, src, tgt, Mtgt) for hd in layer.heads], 1)
     eg = edge_graph(src, tgt, Mtgt)
+    if not eg.canonical and layer.act is not F.relu:  # no H-fold graph of such an Mtgt: every head through the one-head kernels
+        return torch.cat([hd(x, src, tgt, Mtgt) for hd in layer.heads], 1)
     Wsrc, Wtgt, Wlog, bf, ba = layer.packed()
     from .functional import dense
     Ps, Pt, A2 = dense(x, Wsrc), dense(x, Wtgt, bf), dense(x, Wlog, ba)
     if eg.E == 0:
         return torch.zeros(x.shape[0], layer.out_features, dtype=x.dtype, device=x.device) + 0.0 * (Ps.sum() + Pt.sum() + A2.sum())
-    return _EdgeAttentionHeadsFn.apply(heads_graph(eg, layer.n_heads), layer.n_heads, Ps, Pt, A2, layer.eps)
+    return _EdgeAttentionHeadsFn.apply(heads_graph(eg, layer.n_heads), layer.n_heads, Ps, Pt, A2, layer.eps, ka)
 
 
 class FixedMultiHeadGraphConvolution(MultiHeadGraphConvolution):

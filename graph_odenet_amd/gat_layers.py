@@ -7,11 +7,14 @@
 
 The reference gathers h = [x[src] | x[tgt]] (E x 2i) and applies f and w per edge.  Here f and w are
 applied per NODE (one dense GEMM on N rows, `x @ [Wf_src | Wf_tgt | ww_src | ww_tgt]`), and the
-per-edge work (logit, global-max shift, exp, per-target normalised sum of relu messages) runs in the
+per-edge work (logit, global-max shift, exp, per-target normalised sum of act(message)) runs in the
 HIP kernels of csrc/edge.hip (a wave per target on citation-graph sizes, nnz-balanced records above 65 536
 targets); the backward pass returns the edge cotangents to the nodes with one fused launch (small graphs) or inside
-the record kernel plus source-side SpMMs (large graphs).
+the record kernel plus source-side SpMMs (large graphs).  The message activation (`act=`) is an argument of those kernels
+for relu, identity, leaky_relu, elu, tanh and sigmoid (message_activation); any other callable takes the general path.
 """
+import functools
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -78,12 +81,58 @@ def edge_graph(src, tgt, Mtgt):
     return g
 
 
+def _kw(call, name, default):
+    """Keyword `name` of a functools.partial with no positional arguments; None when the partial cannot be read."""
+    if call.args or set(call.keywords) - {name}:
+        return None
+    return float(call.keywords.get(name, default))
+
+
+def message_activation(act):
+    """(code, param) of the kernels' message activation (ops.GAT_ACT_*; param: slope of leaky_relu / alpha of elu, else
+    0.0) for the callables the kernels restate, recognised by identity or by type; None for anything else (a lambda, a
+    custom module), which keeps the general path."""
+    if act is F.relu or act is torch.relu or type(act) is nn.ReLU:
+        return ops.GAT_ACT_RELU, 0.0
+    if act is F.elu:
+        return ops.GAT_ACT_ELU, 1.0
+    if type(act) is nn.ELU:
+        return ops.GAT_ACT_ELU, float(act.alpha)
+    if act is F.leaky_relu:
+        return ops.GAT_ACT_LEAKY_RELU, 0.01
+    if type(act) is nn.LeakyReLU:
+        return ops.GAT_ACT_LEAKY_RELU, float(act.negative_slope)
+    if act is torch.tanh or act is F.tanh or type(act) is nn.Tanh:
+        return ops.GAT_ACT_TANH, 0.0
+    if act is torch.sigmoid or act is F.sigmoid or type(act) is nn.Sigmoid:
+        return ops.GAT_ACT_SIGMOID, 0.0
+    if type(act) is nn.Identity:
+        return ops.GAT_ACT_IDENTITY, 0.0
+    if type(act) is functools.partial and act.func is F.elu:
+        alpha = _kw(act, "alpha", 1.0)
+        return None if alpha is None else (ops.GAT_ACT_ELU, alpha)
+    if type(act) is functools.partial and act.func is F.leaky_relu:
+        slope = _kw(act, "negative_slope", 0.01)
+        return None if slope is None else (ops.GAT_ACT_LEAKY_RELU, slope)
+    return None
+
+
+def _kernel_act(layer):
+    """The `act=` of the ops wrappers for the layer's activation - None for relu, which keeps the relu entry points - or
+    False when the kernels do not restate it (the general path)."""
+    ma = message_activation(layer.act)
+    if ma is None:
+        return False
+    return None if ma[0] == ops.GAT_ACT_RELU else ma
+
+
 class _EdgeAttentionFn(torch.autograd.Function):
-    """out = per-target softmax-weighted sum of relu messages, from the node-level projections
-    Ps, Pt (N x o: message parts by source / by target) and A2 (N x 2: logit parts)."""
+    """out = per-target softmax-weighted sum of act(messages), from the node-level projections
+    Ps, Pt (N x o: message parts by source / by target) and A2 (N x 2: logit parts).  act: None (relu) or the
+    (code, param) of ops.gat_agg_fwd."""
 
     @staticmethod
-    def forward(ctx, eg, Ps, Pt, A2, bf, bw, eps):
+    def forward(ctx, eg, Ps, Pt, A2, bf, bw, eps, act=None):
         Ps, Pt, A2 = Ps.contiguous(), Pt.contiguous(), A2.contiguous()
         n, o = Ps.shape
         f = dict(dtype=torch.float32, device=Ps.device)
@@ -91,8 +140,8 @@ class _EdgeAttentionFn(torch.autograd.Function):
         out, w, den = torch.empty(n, o, **f), torch.empty(eg.E, **f), torch.empty(n, **f)
         proj = ops.gat_proj(Ps, Pt, A2)
         ops.gat_logits(proj, bw, eg.src, eg.tgt, a, amax)
-        ops.gat_agg_fwd(eg, proj, o, bf, a, amax, eps, out, w, den)
-        ctx.eg = eg
+        ops.gat_agg_fwd(eg, proj, o, bf, a, amax, eps, out, w, den, act=act)
+        ctx.eg, ctx.act = eg, act
         ctx.save_for_backward(Ps, Pt, A2, bf, a, amax, w, den, out)
         return out
 
@@ -105,16 +154,17 @@ class _EdgeAttentionFn(torch.autograd.Function):
         dz, da = torch.empty(eg.E, o, **f), torch.empty(eg.E, **f)
         dPs, dPt, dA2 = torch.empty(n, o, **f), torch.empty(n, o, **f), torch.empty(n, 2, **f)
         proj = ops.gat_proj(Ps, Pt, A2)
-        ops.gat_vjp(eg, proj, o, bf, a, amax, w, den, out, dz, da, dPs, dPt, dA2, dout=dout.contiguous())
+        ops.gat_vjp(eg, proj, o, bf, a, amax, w, den, out, dz, da, dPs, dPt, dA2, dout=dout.contiguous(), act=ctx.act)
         dbf = torch.empty_like(bf)
         ops.colsum_(dbf, dPt)                                    # sum_e dz_e = sum_v (sum over the edges entering v)
         dbw = dA2[:, 1].sum().reshape(1)
-        return None, dPs, dPt, dA2, dbf, dbw, None
+        return None, dPs, dPt, dA2, dbf, dbw, None, None
 
 
 def _gat_forward_general(layer, x, src, tgt, Mtgt):
     """The layer with an arbitrary activation callable (the `act=` constructor argument, GAT/layers.py:16): an
-    activation that is not relu cannot be folded into the aggregation kernels, so the per-edge messages are formed as
+    activation that message_activation does not recognise cannot be folded into the aggregation kernels, so the per-edge
+    messages are formed as
     the reference forms them (GAT/layers.py:40-46: gather both endpoints, two Linear layers, act) with PyTorch ops and
     only the two per-target sums (GAT/layers.py:53,55) run on libgraphode's SpMM."""
     from .functional import graph_aggregate
@@ -131,7 +181,8 @@ def _gat_forward_general(layer, x, src, tgt, Mtgt):
 
 
 def _gat_forward(layer, x, src, tgt, Mtgt):
-    if layer.act is not F.relu:
+    ka = _kernel_act(layer)
+    if ka is False:
         return _gat_forward_general(layer, x, src, tgt, Mtgt)
     eg = edge_graph(src, tgt, Mtgt)
     i, o = layer.in_features, layer.out_features
@@ -142,7 +193,7 @@ def _gat_forward(layer, x, src, tgt, Mtgt):
     A2 = dense(x, torch.stack([ww[0, :i], ww[0, i:]], 1))
     if eg.E == 0:                                                # no edges: every node is 0 / eps = 0
         return torch.zeros(x.shape[0], o, dtype=x.dtype, device=x.device) + 0.0 * (Ps.sum() + Pt.sum() + A2.sum())
-    return _EdgeAttentionFn.apply(eg, Ps, Pt, A2, layer.f.bias, layer.w.bias, layer.eps)
+    return _EdgeAttentionFn.apply(eg, Ps, Pt, A2, layer.f.bias, layer.w.bias, layer.eps, ka)
 
 
 class GraphConvolution(Module):

@@ -739,20 +739,38 @@ def _edge_csr(eg, width):
     return gs
 
 
-def gat_agg_fwd(eg, proj, o, bf, a, amax, eps, out, w, den):
+# Message activations of the aggregation kernels (graphode.h: GODE_GAT_ACT_*).  `act=` of the wrappers below is None (relu
+# through the relu entry points) or (code, param): param is the slope of leaky_relu / alpha of elu, 0.0 otherwise.
+GAT_ACT_RELU, GAT_ACT_IDENTITY, GAT_ACT_LEAKY_RELU, GAT_ACT_ELU, GAT_ACT_TANH, GAT_ACT_SIGMOID = (
+    _lib.CONSTANTS["GODE_GAT_ACT_" + k] for k in ("RELU", "IDENTITY", "LEAKY_RELU", "ELU", "TANH", "SIGMOID"))
+
+
+def _act_args(act):
+    code, param = act
+    return int(code), float(param)
+
+
+def gat_agg_fwd(eg, proj, o, bf, a, amax, eps, out, w, den, act=None):
     lib = _lib.load()
     _need(out, "out"); _need(w, "w"); _need(den, "den"); _need(bf, "bf")
     gs = _edge_csr(eg, o + 4)
-    check(lib.gode_gat_agg_f32_fwd(ctypes.byref(gs), ptr(eg.src), ptr(eg.tgt), ctypes.byref(proj), o, ptr(bf), ptr(a),
-                                   ptr(amax), float(eps), ptr(out), ptr(w), ptr(den), stream_ptr()), "gode_gat_agg_f32_fwd")
+    args = (ctypes.byref(gs), ptr(eg.src), ptr(eg.tgt), ctypes.byref(proj), o, ptr(bf), ptr(a), ptr(amax), float(eps), ptr(out),
+            ptr(w), ptr(den))
+    if act is None:
+        check(lib.gode_gat_agg_f32_fwd(*args, stream_ptr()), "gode_gat_agg_f32_fwd")
+    else:
+        check(lib.gode_gat_agg_act_f32_fwd(*args, *_act_args(act), stream_ptr()), "gode_gat_agg_act_f32_fwd")
 
 
-def gat_agg_fwd_route(eg, proj, o, bf, a, amax, eps, out, w, den):
+def gat_agg_fwd_route(eg, proj, o, bf, a, amax, eps, out, w, den, act=None):
     """The route gat_agg_fwd takes on these arguments (nothing is launched)."""
     lib = _lib.load()
     gs = _edge_csr(eg, o + 4)
-    return lib.gode_gat_agg_f32_fwd_route(ctypes.byref(gs), ptr(eg.src), ptr(eg.tgt), ctypes.byref(proj), o, ptr(bf), ptr(a),
-                                          ptr(amax), float(eps), ptr(out), ptr(w), ptr(den), None)
+    args = (ctypes.byref(gs), ptr(eg.src), ptr(eg.tgt), ctypes.byref(proj), o, ptr(bf), ptr(a), ptr(amax), float(eps), ptr(out),
+            ptr(w), ptr(den))
+    if act is None:
+        return lib.gode_gat_agg_f32_fwd_route(*args, None)
+    return lib.gode_gat_agg_act_f32_fwd_route(*args, *_act_args(act), None)
 
 
 def _agg_bwd_args(eg, proj, o, bf, w, den, out, dz, da, dPt, dA2, dout, cot_terms, cot_scale, did):
@@ -770,7 +788,14 @@ def _agg_bwd_args(eg, proj, o, bf, w, den, out, dz, da, dPt, dA2, dout, cot_term
             ctypes.byref(did)), (gs, lc)
 
 
-def gat_agg_bwd(eg, proj, o, bf, w, den, out, dz, da, dPt=None, dA2=None, dout=None, cot_terms=None, cot_scale=1.0):
+def _agg_bwd_call(lib, args, act, stream):
+    if act is None:
+        check(lib.gode_gat_agg_f32_bwd(*args, stream), "gode_gat_agg_f32_bwd")
+    else:
+        check(lib.gode_gat_agg_act_f32_bwd(*args, *_act_args(act), stream), "gode_gat_agg_act_f32_bwd")
+
+
+def gat_agg_bwd(eg, proj, o, bf, w, den, out, dz, da, dPt=None, dA2=None, dout=None, cot_terms=None, cot_scale=1.0, act=None):
     """The aggregation's backward alone (first piece of gat_vjp): fills dz[E, o] and da[E] WITHOUT the path through the
     maximum.  Returns True when the record route also formed the target-side sums dPt and dA2[:, 1]."""
     lib = _lib.load()
@@ -778,17 +803,21 @@ def gat_agg_bwd(eg, proj, o, bf, w, den, out, dz, da, dPt=None, dA2=None, dout=N
         _need(t, nm)
     did = ctypes.c_int32(0)
     args, keep = _agg_bwd_args(eg, proj, o, bf, w, den, out, dz, da, dPt, dA2, dout, cot_terms, cot_scale, did)
-    check(lib.gode_gat_agg_f32_bwd(*args, stream_ptr()), "gode_gat_agg_f32_bwd")
+    _agg_bwd_call(lib, args, act, stream_ptr())
     del keep
     return bool(did.value)
 
 
-def gat_agg_bwd_route(eg, proj, o, bf, w, den, out, dz, da, dPt=None, dA2=None, dout=None, cot_terms=None, cot_scale=1.0):
+def gat_agg_bwd_route(eg, proj, o, bf, w, den, out, dz, da, dPt=None, dA2=None, dout=None, cot_terms=None, cot_scale=1.0,
+                      act=None):
     """The route gat_agg_bwd (and gat_vjp) takes on these arguments (nothing is launched)."""
     lib = _lib.load()
     did = ctypes.c_int32(0)
     args, keep = _agg_bwd_args(eg, proj, o, bf, w, den, out, dz, da, dPt, dA2, dout, cot_terms, cot_scale, did)
-    rt = lib.gode_gat_agg_f32_bwd_route(*args, None)
+    if act is None:
+        rt = lib.gode_gat_agg_f32_bwd_route(*args, None)
+    else:
+        rt = lib.gode_gat_agg_act_f32_bwd_route(*args, *_act_args(act), None)
     del keep
     return rt
 
@@ -829,18 +858,19 @@ def gat_agg_heads_fwd(eg, proj, o, bf, a, scratch, heads, eps, out, w, den):
 
 
 def gat_vjp(eg, proj, o, bf, a, amax, w, den, out, dz, da, dPs, dPt, dA2, dout=None, cot_terms=None, cot_scale=1.0,
-            heads=1, raw_scratch=None, defer_maxpath=False):
+            heads=1, raw_scratch=None, defer_maxpath=False, act=None):
     """Vector-Jacobian product of the edge-attention aggregation w.r.t. the projections: fills dz[E, o], da[E] (with the
     path through the global maximum folded in), dPs, dPt (N x o) and dA2 (N x 2).  The cotangent is `dout`, or
     cot_scale * (sum cot_terms) masked by out > 0.  heads > 1: `eg` is the H-fold graph, `a` holds logits shifted
-    per head and the path through the maximum is applied per head."""
+    per head and the path through the maximum is applied per head.  act: the message activation (None: relu); only
+    the aggregation's backward depends on it."""
     lib = _lib.load()
     for t, nm in ((out, "out"), (dz, "dz"), (da, "da"), (dout, "dout"), (dPs, "dPs"), (dPt, "dPt"), (dA2, "dA2")):
         _need(t, nm)
     did = ctypes.c_int32(0)
     args, keep = _agg_bwd_args(eg, proj, o, bf, w, den, out, dz, da, dPt, dA2, dout, cot_terms, cot_scale, did)
     at_ptr = ctypes.c_void_p(dA2.data_ptr() + 4)
-    check(lib.gode_gat_agg_f32_bwd(*args, stream_ptr()), "gode_gat_agg_f32_bwd")
+    _agg_bwd_call(lib, args, act, stream_ptr())
     del keep
     if eg.E > 0 and heads > 1 and raw_scratch is not None and defer_maxpath and not did.value:
         # first half only; gat_dense_vjp_small(..., maxfix=(raw_scratch, eg.src, eg.tgt)) closes the step

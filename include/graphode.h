@@ -466,6 +466,36 @@ int gode_gat_agg_f32_bwd_route(const gode_graph_t* mt, const int32_t* src, const
                                const float* out, const float* dout, const gode_lincomb_t* cot, float cot_scale,
                                float* dz, float* da, float* dpt, int64_t ld_dpt, float* dat, int64_t ld_dat,
                                int32_t* did_target_sums, void* stream);
+/* The same aggregation with the message activation as an argument: y_e = act(z_e) in the forward, dz_e = val w_e dA act'(z_e)
+ * and y_e in da in the backward (the layer's `act=` constructor argument, GAT/layers.py:16).  act_param is the slope of
+ * leaky_relu / alpha of elu (ignored otherwise); at z == 0 the derivative is 0 for relu, the slope for leaky_relu, alpha for
+ * elu.  Arguments, validation codes (in the same order) and routes are those of the entry points above: the dispatch does not
+ * depend on act, and GODE_GAT_ACT_RELU runs the very kernels of the entry points above.  Checked before anything else:
+ * act outside the list below, or a non-finite act_param for leaky_relu / elu: GODE_E_SHAPE; another activation than relu
+ * with a cot that has terms (the masked cotangent belongs to the ODE function, which is relu only): GODE_E_UNSUPPORTED. */
+#define GODE_GAT_ACT_RELU 0
+#define GODE_GAT_ACT_IDENTITY 1
+#define GODE_GAT_ACT_LEAKY_RELU 2
+#define GODE_GAT_ACT_ELU 3
+#define GODE_GAT_ACT_TANH 4
+#define GODE_GAT_ACT_SIGMOID 5
+int gode_gat_agg_act_f32_fwd(const gode_graph_t* mt, const int32_t* src, const int32_t* tgt,
+                             const gode_gat_proj_t* proj, int64_t o, const float* bf, const float* a, const float* amax,
+                             float eps, float* out, float* w_out, float* den_out, int32_t act, float act_param, void* stream);
+int gode_gat_agg_act_f32_fwd_route(const gode_graph_t* mt, const int32_t* src, const int32_t* tgt,
+                                   const gode_gat_proj_t* proj, int64_t o, const float* bf, const float* a, const float* amax,
+                                   float eps, float* out, float* w_out, float* den_out, int32_t act, float act_param,
+                                   void* stream);
+int gode_gat_agg_act_f32_bwd(const gode_graph_t* mt, const int32_t* src, const int32_t* tgt,
+                             const gode_gat_proj_t* proj, int64_t o, const float* bf, const float* w, const float* den,
+                             const float* out, const float* dout, const gode_lincomb_t* cot, float cot_scale,
+                             float* dz, float* da, float* dpt, int64_t ld_dpt, float* dat, int64_t ld_dat,
+                             int32_t* did_target_sums, int32_t act, float act_param, void* stream);
+int gode_gat_agg_act_f32_bwd_route(const gode_graph_t* mt, const int32_t* src, const int32_t* tgt,
+                                   const gode_gat_proj_t* proj, int64_t o, const float* bf, const float* w, const float* den,
+                                   const float* out, const float* dout, const gode_lincomb_t* cot, float cot_scale,
+                                   float* dz, float* da, float* dpt, int64_t ld_dpt, float* dat, int64_t ld_dat,
+                                   int32_t* did_target_sums, int32_t act, float act_param, void* stream);
 /* gradient path through the global maximum of the logits (GAT/layers.py:47): da[e*] -= S, S = sum(da), e* = first
  * argmax; when dat (nullable, with tgt) holds target-side sums formed before the correction, dat[tgt[e*]*ld_dat] -= S.
  * scratch: >= gode_gat_maxpath_scratch_bytes(n_edges) bytes (may be NULL for n_edges <= 32 768 without dat). */
