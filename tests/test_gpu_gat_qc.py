@@ -593,7 +593,8 @@ def test_qc_model_zoo_vs_reference_golden(golden, name):
     assert checked >= 4
 
 
-@pytest.mark.parametrize("h,sorted_batch", [(16, True), (73, True), (73, False), (200, False), (1024, True)])
+@pytest.mark.parametrize("h,sorted_batch", [(16, True), (73, True), (73, False), (200, False), (1024, True),
+                                            (257, False), (300, True), (513, True)])     # 257, 300: the MC = 8 instantiation
 def test_segment_attention_vs_oracle(h, sorted_batch):
     """Set2Set's per-graph softmax readout (QC/set2set.py:63-74) through the C ABI against the oracle's restatement of
     the reference loop, forward and backward; graphs of 1..40 nodes, one graph id without nodes, unsorted batch vector."""
