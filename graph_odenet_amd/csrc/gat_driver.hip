@@ -398,3 +398,84 @@ extern "C" int gode_gat_ode_dopri5_step_backprop(const gode_gat_odefunc_t* f, co
     if (live == 0) return 0;
     return gode_gat_small_close_stages_f32(parts, n, d, H, live, ts, theta, stream);
 }
+
+// The rk4 pair above for any fixed-grid method (GODE_RK_*; GODE_RK_RK4_38 calls it): records of (S + 1) n x d floats, S
+// slots of `parts`, one closing launch per swept step.
+extern "C" int gode_gat_ode_fixed_forward_save(int32_t method, const gode_gat_odefunc_t* f, const float* y0, float* y_end,
+                                               float* save, const gode_gat_workspace_t* ws, float t0, float t1,
+                                               int32_t n_steps, int32_t step_begin, int32_t step_end, void* stream)
+{
+    if (!f || !ws || !y0 || !y_end || !save) return GODE_E_NULLPTR;
+    const Tableau* tabp = fixed_tableau(method);
+    if (!tabp) return GODE_E_SHAPE;
+    if (method == GODE_RK_RK4_38)
+        return gode_gat_ode_rk4_forward_save(f, y0, y_end, save, ws, t0, t1, n_steps, step_begin, step_end, stream);
+    int rc = check_steps(n_steps, step_begin, step_end); if (rc) return rc;
+    rc = check_sweep(f, ws); if (rc) return rc;
+    const Tableau& tab = *tabp;
+    const int S = tab.stages;
+    const int64_t nd = f->n * f->d;
+    const double h = ((double)t1 - (double)t0) / n_steps;
+    if (y0 != save) {                                            // record 0 starts with a copy of y0
+        const gode_lincomb_t c = one_term(y0);
+        GODE_TRY(gode_lincomb_f32(save, &c, nd, stream));
+    }
+    for (int i = step_begin; i < step_end; ++i) {
+        float* rec = save + (int64_t)(i - step_begin) * (S + 1) * nd;
+        float* k[4] = {};
+        for (int s = 0; s < S; ++s) k[s] = rec + (int64_t)(s + 1) * nd;
+        float* ynext = (i + 1 < step_end) ? rec + (int64_t)(S + 1) * nd : y_end;      // the next record's y_n, or the result
+        const double t = (double)t0 + i * h;
+        for (int s = 0; s < S; ++s) {
+            gode_lincomb_t yin = tab_stage_terms(tab, rec, k, s, h);
+            GODE_TRY(eval_forward(f, ws, &yin, (float)(t + tab.c[s] * h), k[s], stream));
+        }
+        gode_lincomb_t sol = one_term(rec);
+        for (int s = 0; s < S; ++s)
+            if (tab.b[s] != 0.0) { sol.coef[sol.n] = (float)(h * tab.b[s]); sol.ptr[sol.n] = k[s]; ++sol.n; }
+        GODE_TRY(gode_lincomb_f32(ynext, &sol, nd, stream));
+    }
+    return 0;
+}
+
+extern "C" int gode_gat_ode_fixed_backprop(int32_t method, const gode_gat_odefunc_t* f, const float* save, float* a,
+                                           float* theta, float* const* ybar, float* k_scratch, float* parts,
+                                           const gode_gat_workspace_t* ws, float t0, float t1, int32_t n_steps,
+                                           int32_t step_begin, int32_t step_end, void* stream)
+{
+    if (!f || !ws || !save || !a || !theta || !ybar || !k_scratch || !parts) return GODE_E_NULLPTR;
+    const Tableau* tabp = fixed_tableau(method);
+    if (!tabp) return GODE_E_SHAPE;
+    if (method == GODE_RK_RK4_38)
+        return gode_gat_ode_rk4_backprop(f, save, a, theta, ybar, k_scratch, parts, ws, t0, t1, n_steps, step_begin, step_end, stream);
+    const Tableau& tab = *tabp;
+    const int S = tab.stages;
+    for (int s = 0; s < S; ++s) if (!ybar[s]) return GODE_E_NULLPTR;
+    int rc = check_steps(n_steps, step_begin, step_end); if (rc) return rc;
+    for (int s = 0; s < S; ++s) {
+        if (ybar[s] == a || ybar[s] == k_scratch) return GODE_E_SHAPE;
+        for (int r = s + 1; r < S; ++r) if (ybar[s] == ybar[r]) return GODE_E_SHAPE;
+    }
+    if (k_scratch == a) return GODE_E_SHAPE;
+    rc = check_sweep(f, ws); if (rc) return rc;
+    const int64_t n = f->n, d = f->d, nd = n * d, H = n_heads(f), slot = part_slot(f);
+    const double h = ((double)t1 - (double)t0) / n_steps;
+    for (int i = step_end - 1; i >= step_begin; --i) {
+        float* y = (float*)save + (int64_t)(i - step_begin) * (S + 1) * nd;     // read only
+        float* k[4] = {};
+        for (int s = 0; s < S; ++s) k[s] = y + (int64_t)(s + 1) * nd;
+        const double t = (double)t0 + i * h;
+        float ts[4];
+        // every stage of these methods has a cotangent: b_S is non-zero and each earlier stage feeds a later one
+        for (int s = S - 1; s >= 0; --s) {
+            ts[s] = (float)(t + tab.c[s] * h);
+            const gode_lincomb_t cot = stage_cotangent(tab, a, (float)(h * tab.b[s]), ybar, s, h);
+            gode_lincomb_t yin = tab_stage_terms(tab, y, k, s, h);
+            GODE_TRY(stage_vjp(f, ws, &yin, cot, 1.f, ts[s], k_scratch, ybar[s], nullptr, parts + s * slot, stream));
+        }
+        GODE_TRY(gode_gat_small_close_stages_f32(parts, n, d, H, S, ts, theta, stream));
+        const gode_lincomb_t sum = sweep_pre(tab, a, 1.f, ybar, 0);      // a + Ybar_1 + .. + Ybar_S
+        GODE_TRY(gode_lincomb_f32(a, &sum, nd, stream));
+    }
+    return 0;
+}

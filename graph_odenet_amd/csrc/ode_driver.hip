@@ -836,3 +836,256 @@ extern "C" int gode_gcn_ode_dopri5_step_backprop(const gode_gcn_odefunc_t* f, co
     if (fused) GODE_TRY(gode_gcn_small_finish_multi_f32(f, ws->small_part, live, kt, kt_time, stream));
     return add_stage_parts(theta, kt, live, P, stream);
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// The fixed-grid drivers by method (GODE_RK_*): the rk4 launch sequences above driven by a tableau (rk_driver.h).  The last
+// stage of a step is the closing one; GODE_RK_RK4_38 calls the rk4 entry point itself.
+// ---------------------------------------------------------------------------------------------------------------
+extern "C" int gode_rk_stages(int32_t method)
+{
+    const Tableau* tab = fixed_tableau(method);
+    return tab ? tab->stages : GODE_E_SHAPE;
+}
+
+extern "C" int gode_rk_tableau(int32_t method, double* c, double* a, double* b)
+{
+    const Tableau* tab = fixed_tableau(method);
+    if (!tab) return GODE_E_SHAPE;
+    const int S = tab->stages;
+    for (int s = 0; s < S; ++s) {
+        if (c) c[s] = tab->c[s];
+        if (b) b[s] = tab->b[s];
+        if (a) for (int j = 0; j < S; ++j) a[s * S + j] = j < s ? tab->a[s * tab->lda + j] : 0.0;
+    }
+    return 0;
+}
+
+namespace {
+
+// the closing-combination-once launch needs the last stage's input and the closing combination to name the same arrays in
+// the same order, and saves something only where they are several (the 3/8 rule).  The midpoint rule's differ and explicit
+// Euler's is y alone: both close from their terms - one array, as the once route reads.
+bool same_arrays(const gode_lincomb_t& x, const gode_lincomb_t& p) {
+    if (x.n != p.n || x.n < 2) return false;
+    for (int j = 0; j < x.n; ++j) if (x.ptr[j] != p.ptr[j]) return false;
+    return true;
+}
+
+// rk4_forward_step for any tableau: k_1..k_{S-1} into k[0..S-2], y_{n+1} into ynext (which may be k[S-1]) - or, keep_last,
+// k_S into k[S-1] as well (ynext is then another array)
+int fixed_forward_step(const Tableau& tab, const gode_gcn_odefunc_t* f, const gode_rk4_workspace_t* ws, const float* y,
+                       float* const* k, float* ynext, bool keep_last, double t, double h, bool fused, bool close_once,
+                       void* stream, bool diag_ok = false) {
+    const int S = tab.stages;
+    for (int s = 0; s < S; ++s) {
+        const gode_lincomb_t xin = tab_stage_terms(tab, y, k, s, h);
+        const float ts = (float)(t + tab.c[s] * h);
+        if (s + 1 < S) {
+            if (fused) GODE_TRY(gode_gcn_feval_small_f32(f, &xin, ts, 1.f, nullptr, nullptr, nullptr, k[s], stream));
+            else GODE_TRY(feval_large(f, xin, ts, ws->S, k[s], nullptr, nullptr, stream, diag_ok));
+            continue;
+        }
+        StepClose close = {tab_combine_terms(tab, y, k, h), (float)(h * tab.b[s]), close_once};
+        close.once = close_once && same_arrays(xin, close.pre);
+        float* klast = keep_last ? k[s] : nullptr;
+        if (!fused) GODE_TRY(feval_large(f, xin, ts, ws->S, ynext, &close, klast, stream, diag_ok));
+        else if (keep_last) GODE_TRY(gode_gcn_feval_small_save_f32(f, &xin, ts, close.alpha, &close.pre, ynext, klast, stream));
+        else GODE_TRY(gode_gcn_feval_small_f32(f, &xin, ts, close.alpha, &close.pre, nullptr, nullptr, ynext, stream));
+    }
+    return 0;
+}
+
+// rk4_adjoint_small for any tableau of up to 4 stages
+int fixed_adjoint_small(const Tableau& tab, const gode_gcn_odefunc_t* f, const gode_rk4_workspace_t* ws, float* y, float* a,
+                        float* theta, float** y_result, float** a_result, float t0, double h, int32_t n_steps, void* stream) {
+    const int S = tab.stages, L = S - 1;
+    float* ycur = y; float* acur = a;
+    float* ky[4] = {ws->ky[0], ws->ky[1], ws->ky[2], ws->ky[3]};
+    float* ka[4] = {ws->ka[0], ws->ka[1], ws->ka[2], ws->ka[3]};
+    const int64_t slot = gode_gcn_small_parts(f->n) * gode_gcn_small_part_len(f->d);
+    const float hbl = (float)(h * tab.b[L]);
+    for (int i = 0; i < n_steps; ++i) {
+        float stage_t[4], wb[4];
+        const gode_lincomb_t ypre = tab_combine_terms(tab, ycur, ky, h), apre = tab_combine_terms(tab, acur, ka, h);
+        for (int s = 0; s < S; ++s) {
+            stage_t[s] = (float)((double)t0 + i * h + tab.c[s] * h);
+            wb[s] = (float)(h * tab.b[s]);
+            const gode_lincomb_t yin = tab_stage_terms(tab, ycur, ky, s, h);
+            const gode_lincomb_t cot = negated(tab_stage_terms(tab, acur, ka, s, h));   // cotangent of the VJP is -a
+            GODE_TRY(gode_gcn_feval_small_f32(f, &yin, stage_t[s], s == L ? hbl : 1.f, s == L ? &ypre : nullptr,
+                                              &cot, ws->dZ, ky[s], stream));
+            GODE_TRY(gode_gcn_vjp_small_f32(f, &yin, ws->dZ, s == L ? hbl : 1.f, s == L ? &apre : nullptr,
+                                            ka[s], ws->small_part + s * slot, stream));
+        }
+        GODE_TRY(gode_gcn_small_finish_step_f32(f, ws->small_part, S, theta, wb, stage_t, stream));
+        float* tmp = ycur; ycur = ky[L]; ky[L] = tmp;
+        tmp = acur; acur = ka[L]; ka[L] = tmp;
+    }
+    *y_result = ycur;
+    *a_result = acur;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int gode_gcn_ode_fixed_forward(int32_t method, const gode_gcn_odefunc_t* f, float* y, float** result,
+                                          const gode_rk4_workspace_t* ws, float t0, float t1, int32_t n_steps, void* stream)
+{
+    if (!f || !y || !ws || !result) return GODE_E_NULLPTR;
+    const Tableau* tab = fixed_tableau(method);
+    if (!tab) return GODE_E_SHAPE;
+    if (method == GODE_RK_RK4_38) return gode_gcn_ode_rk4_forward(f, y, result, ws, t0, t1, n_steps, stream);
+    if (n_steps <= 0 || f->n <= 0 || f->d <= 0) return GODE_E_SHAPE;
+    const int S = tab->stages, L = S - 1;
+    if (!ws->S) return GODE_E_NULLPTR;
+    for (int s = 0; s < S; ++s) if (!ws->ky[s]) return GODE_E_NULLPTR;
+    const double h = ((double)t1 - (double)t0) / n_steps;
+    float* cur = y;
+    float* k[4] = {ws->ky[0], ws->ky[1], ws->ky[2], ws->ky[3]};
+    const bool fused = fused_small(f);
+    const bool close_once = close_once_route(f);
+    const bool diag_ok = gode_opt_diag_rows() && !fused && f->n > kMergedFinishMaxRows && f->d == 128 && f->a_core_items &&
+                         f->a_diag && f->at_diag && f->A.items && f->a_n_core > 0 && f->a_n_core <= f->A.n_items;
+    for (int i = 0; i < n_steps; ++i) {
+        GODE_TRY(fixed_forward_step(*tab, f, ws, cur, k, k[L], false, (double)t0 + i * h, h, fused, close_once, stream, diag_ok));
+        float* tmp = cur; cur = k[L]; k[L] = tmp;      // k[L] holds the new solution
+    }
+    *result = cur;
+    return 0;
+}
+
+extern "C" int gode_gcn_ode_fixed_adjoint(int32_t method, const gode_gcn_odefunc_t* f, float* y, float* a, float* theta,
+                                          float** y_result, float** a_result, const gode_rk4_workspace_t* ws,
+                                          float t0, float t1, int32_t n_steps, void* stream)
+{
+    if (!f || !y || !a || !theta || !ws || !y_result || !a_result) return GODE_E_NULLPTR;
+    const Tableau* tab = fixed_tableau(method);
+    if (!tab) return GODE_E_SHAPE;
+    if (method == GODE_RK_RK4_38) return gode_gcn_ode_rk4_adjoint(f, y, a, theta, y_result, a_result, ws, t0, t1, n_steps, stream);
+    if (n_steps <= 0 || f->n <= 0 || f->d <= 0) return GODE_E_SHAPE;
+    if (!(fused_small(f) && ws->small_part != nullptr)) return GODE_E_UNSUPPORTED;      // the launch-bound route only
+    for (int s = 0; s < tab->stages; ++s) if (!ws->ky[s] || !ws->ka[s]) return GODE_E_NULLPTR;
+    if (!ws->dZ) return GODE_E_NULLPTR;
+    const double h = ((double)t1 - (double)t0) / n_steps;
+    return fixed_adjoint_small(*tab, f, ws, y, a, theta, y_result, a_result, t0, h, n_steps, stream);
+}
+
+extern "C" int gode_gcn_ode_fixed_forward_save(int32_t method, const gode_gcn_odefunc_t* f, const float* y0, float* y_end,
+                                               float* save, const gode_rk4_workspace_t* ws, float t0, float t1,
+                                               int32_t n_steps, int32_t step_begin, int32_t step_end, void* stream)
+{
+    if (!f || !y0 || !y_end || !save || !ws) return GODE_E_NULLPTR;
+    const Tableau* tab = fixed_tableau(method);
+    if (!tab) return GODE_E_SHAPE;
+    if (method == GODE_RK_RK4_38)
+        return gode_gcn_ode_rk4_forward_save(f, y0, y_end, save, ws, t0, t1, n_steps, step_begin, step_end, stream);
+    if (n_steps <= 0 || f->n <= 0 || f->d <= 0) return GODE_E_SHAPE;
+    if (step_begin < 0 || step_end > n_steps || step_begin >= step_end) return GODE_E_SHAPE;
+    if (!ws->S) return GODE_E_NULLPTR;
+    const int S = tab->stages;
+    const int64_t nd = f->n * f->d;
+    const double h = ((double)t1 - (double)t0) / n_steps;
+    const bool fused = fused_small(f);
+    const bool close_once = close_once_route(f);
+    if (y0 != save) {                                            // record 0 starts with a copy of y0
+        const gode_lincomb_t c = one_term(y0);
+        GODE_TRY(gode_lincomb_f32(save, &c, nd, stream));
+    }
+    for (int i = step_begin; i < step_end; ++i) {
+        float* rec = save + (int64_t)(i - step_begin) * (S + 1) * nd;
+        float* k[4] = {};
+        for (int s = 0; s < S; ++s) k[s] = rec + (int64_t)(s + 1) * nd;
+        float* ynext = (i + 1 < step_end) ? rec + (int64_t)(S + 1) * nd : y_end;      // the next record's y_n, or the result
+        GODE_TRY(fixed_forward_step(*tab, f, ws, rec, k, ynext, true, (double)t0 + i * h, h, fused, close_once, stream));
+    }
+    return 0;
+}
+
+extern "C" int gode_gcn_ode_fixed_backprop(int32_t method, const gode_gcn_odefunc_t* f, const float* save, float* a,
+                                           float* theta, float** a_result, const gode_rk4_workspace_t* ws,
+                                           float* cot_colpart, float t0, float t1, int32_t n_steps, int32_t step_begin,
+                                           int32_t step_end, void* stream)
+{
+    if (!f || !save || !a || !theta || !a_result || !ws) return GODE_E_NULLPTR;
+    const Tableau* tabp = fixed_tableau(method);
+    if (!tabp) return GODE_E_SHAPE;
+    if (method == GODE_RK_RK4_38)
+        return gode_gcn_ode_rk4_backprop(f, save, a, theta, a_result, ws, cot_colpart, t0, t1, n_steps, step_begin, step_end, stream);
+    if (n_steps <= 0 || f->n <= 0 || f->d <= 0) return GODE_E_SHAPE;
+    if (step_begin < 0 || step_end > n_steps || step_begin >= step_end) return GODE_E_SHAPE;
+    const Tableau& tab = *tabp;
+    const int S = tab.stages, L = S - 1;
+    for (int s = 0; s < S; ++s) if (!ws->ka[s] || !ws->ktheta[s]) return GODE_E_NULLPTR;
+    if (!ws->dZ || !ws->dS || !ws->wpart || !ws->colsum_scratch) return GODE_E_NULLPTR;
+    if (f->groups > 0 && (!ws->gpart || !ws->bpart)) return GODE_E_NULLPTR;
+    const int64_t n = f->n, d = f->d, nd = n * d;
+    const double h = ((double)t1 - (double)t0) / n_steps;
+    float* acur = a;
+    float* yb[4] = {ws->ka[0], ws->ka[1], ws->ka[2], ws->ka[3]};   // yb[1..S-1]: Ybar_2..S; yb[0] receives abar_n
+    auto record = [&](int i) { return save + (int64_t)(i - step_begin) * (S + 1) * nd; };
+    // kbar_S = h b_S abar: b_S is non-zero in every method of the list, so the sweep of a step always opens with one term
+    const float hbl = (float)(h * tab.b[L]);
+    const bool fused = fused_small(f) && ws->small_part != nullptr;
+    if (fused) {
+        // the rk4 sweep's launches: the VJP of stage s also forms the masked cotangent of the stage after it in the sweep
+        const int64_t slot = gode_gcn_small_parts(n) * gode_gcn_small_part_len(d);
+        float* dz[2] = {ws->dZ, ws->dS};
+        int cur = 0;
+        {
+            const float* r = record(step_end - 1);
+            const gode_lincomb_t cl = stage_cotangent(tab, acur, hbl, yb, L, h);
+            GODE_TRY(gode_masked_cot_f32(&cl, r + (int64_t)S * nd, dz[0], n, d, nullptr, stream));
+        }
+        for (int i = step_end - 1; i >= step_begin; --i) {
+            const float* y = record(i);
+            float* k[4] = {};
+            for (int s = 0; s < S; ++s) k[s] = (float*)y + (int64_t)(s + 1) * nd;
+            const double t = (double)t0 + i * h;
+            const gode_lincomb_t pre = sweep_pre(tab, acur, 1.f, yb, 1);
+            float stage_t[4], w1[4];
+            for (int s = L; s >= 0; --s) {
+                stage_t[s] = (float)(t + tab.c[s] * h);
+                w1[s] = 1.f;                                           // h is already inside kbar
+                const gode_lincomb_t yin = tab_stage_terms(tab, y, k, s, h);
+                gode_lincomb_t nxt; nxt.n = 0;
+                const float* knext = nullptr;
+                if (s > 0) {
+                    nxt = stage_cotangent(tab, acur, (float)(h * tab.b[s - 1]), yb, s - 1, h);   // names yb[s]: this launch's rows
+                    knext = k[s - 1];
+                } else if (i > step_begin) {
+                    nxt = one_term(yb[0]); nxt.coef[0] = hbl;                                  // kbar_S of step i - 1
+                    knext = record(i - 1) + (int64_t)S * nd;
+                }
+                float* part = ws->small_part + s * slot;
+                if (knext && nxt.n > 0) {
+                    GODE_TRY(gode_gcn_vjp_small_next_f32(f, &yin, dz[cur], 1.f, s == 0 ? &pre : nullptr, yb[s], part,
+                                                         &nxt, knext, dz[cur ^ 1], stream));
+                    cur ^= 1;
+                } else {
+                    GODE_TRY(gode_gcn_vjp_small_f32(f, &yin, dz[cur], 1.f, s == 0 ? &pre : nullptr, yb[s], part, stream));
+                }
+            }
+            GODE_TRY(gode_gcn_small_finish_step_f32(f, ws->small_part, S, theta, w1, stage_t, stream));
+            float* tmp = acur; acur = yb[0]; yb[0] = tmp;
+        }
+        *a_result = acur;
+        return 0;
+    }
+    const SweepRoute route = sweep_route(f, ws, cot_colpart);
+    for (int i = step_end - 1; i >= step_begin; --i) {
+        const float* y = record(i);
+        float* k[4] = {};
+        for (int s = 0; s < S; ++s) k[s] = (float*)y + (int64_t)(s + 1) * nd;
+        const double t = (double)t0 + i * h;
+        const gode_lincomb_t pre = sweep_pre(tab, acur, 1.f, yb, 1);
+        for (int s = L; s >= 0; --s) {
+            const gode_lincomb_t cot = stage_cotangent(tab, acur, (float)(h * tab.b[s]), yb, s, h);
+            GODE_TRY(sweep_stage(f, ws, route, cot, k[s], tab_stage_terms(tab, y, k, s, h), s == 0 ? &pre : nullptr, yb[s],
+                                 ws->ktheta[s], (float)(t + tab.c[s] * h), stream));
+        }
+        GODE_TRY(add_stage_parts(theta, ws->ktheta, S, gode_gcn_ode_theta_len(d), stream));
+        float* tmp = acur; acur = yb[0]; yb[0] = tmp;
+    }
+    *a_result = acur;
+    return 0;
+}

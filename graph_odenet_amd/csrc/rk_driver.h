@@ -20,6 +20,13 @@ constexpr int64_t kMergedFinishMaxRows = 1 << 16;
 const double C38[4] = {0.0, 1.0 / 3.0, 2.0 / 3.0, 1.0};
 const double A38[4][3] = {{0.0, 0.0, 0.0}, {1.0 / 3.0, 0.0, 0.0}, {-1.0 / 3.0, 1.0, 0.0}, {1.0, -1.0, 1.0}};
 const double B38[4] = {1.0 / 8.0, 3.0 / 8.0, 3.0 / 8.0, 1.0 / 8.0};
+// explicit Euler; the explicit midpoint rule (b_1 = 0: the closing combination never reads k_1)
+const double CEU[1] = {0.0};
+const double AEU[1][1] = {{0.0}};
+const double BEU[1] = {1.0};
+const double CMID[2] = {0.0, 0.5};
+const double AMID[2][1] = {{0.0}, {0.5}};
+const double BMID[2] = {0.0, 1.0};
 // Dormand-Prince 5(4)
 const double DPC[7] = {0.0, 1.0 / 5, 3.0 / 10, 4.0 / 5, 8.0 / 9, 1.0, 1.0};
 const double DPA[7][6] = {
@@ -52,9 +59,32 @@ inline gode_lincomb_t combine_terms(const float* y, float* const* k, double h) {
     return lc;
 }
 // A Butcher matrix as the sweeps read it: a[q * lda + s] = A[q][s] of a method with `stages` stages
-struct Tableau { const double* a; int lda; int stages; };
-const Tableau TAB38 = {&A38[0][0], 3, 4};
-const Tableau TABDP = {&DPA[0][0], 6, 7};
+// (b, c: the weights and abscissae)
+struct Tableau { const double* a; int lda; int stages; const double* b; const double* c; };
+const Tableau TAB38 = {&A38[0][0], 3, 4, B38, C38};
+const Tableau TABDP = {&DPA[0][0], 6, 7, DPB, DPC};
+const Tableau TABEU = {&AEU[0][0], 1, 1, BEU, CEU};
+const Tableau TABMID = {&AMID[0][0], 1, 2, BMID, CMID};
+// the fixed-grid methods by their GODE_RK_* code; nullptr outside the list
+inline const Tableau* fixed_tableau(int method) {
+    return method == GODE_RK_RK4_38 ? &TAB38 : method == GODE_RK_EULER ? &TABEU : method == GODE_RK_MIDPOINT ? &TABMID : nullptr;
+}
+// terms of  y + h * sum_{j<s} A[s][j] * k[j]  of any tableau (zero coefficients dropped; stage_terms is the 3/8 rule's)
+inline gode_lincomb_t tab_stage_terms(const Tableau& tab, const float* y, float* const* k, int s, double h) {
+    gode_lincomb_t lc = one_term(y);
+    for (int j = 0; j < s; ++j) {
+        const double a = tab.a[s * tab.lda + j];
+        if (a != 0.0) { lc.coef[lc.n] = (float)(h * a); lc.ptr[lc.n] = k[j]; ++lc.n; }
+    }
+    return lc;
+}
+// terms of  y + h * sum_{j<stages-1} b_j * k[j]: what the launch that produces the last stage adds h b_last f to
+inline gode_lincomb_t tab_combine_terms(const Tableau& tab, const float* y, float* const* k, double h) {
+    gode_lincomb_t lc = one_term(y);
+    for (int j = 0; j + 1 < tab.stages; ++j)
+        if (tab.b[j] != 0.0) { lc.coef[lc.n] = (float)(h * tab.b[j]); lc.ptr[lc.n] = k[j]; ++lc.n; }
+    return lc;
+}
 
 // kbar_s of a backprop sweep: w abar + h sum_{q > s} A[q][s] Ybar_q  (w = h b_s in a plain step; a zero w, a zero
 // A[q][s] and a stage q with dead[q] set - its cotangent was identically zero, so it has no Ybar_q - add no term:

@@ -373,6 +373,8 @@ struct Finish4 { const float* part[4]; float wb[4]; float ts[4]; };
 // 1 024 threads: 32 part-groups x 32 outputs; a thread has 4 x 8 loads per round of 256 partial rows, all independent and
 // in flight together - the launch is one memory round trip, not a loop of them (8 part-groups took 34 us).  Output
 // out_len is a_t: the sum of the blocks' shares (last column of a partial row).
+// NS: the stages read (4: an rk4 step; fewer: the steps of the methods with fewer stages, or with zero weights)
+template <int NS>
 __global__ __launch_bounds__(1024) void small_finish4_kernel(Finish4 g, int n_part, int plen, int d, float* __restrict__ theta, int out_len)
 {
     __shared__ float sm[32][33];
@@ -381,23 +383,25 @@ __global__ __launch_bounds__(1024) void small_finish4_kernel(Finish4 g, int n_pa
     const int src = j < out_len ? j : (j == out_len ? plen - 1 : -1);
     float v = 0.f;
     if (src >= 0) {
-        float a[4] = {0.f, 0.f, 0.f, 0.f};
-        for (int p0 = qq; p0 < n_part; p0 += 256) {
-            float x[4][8];
+        float a[NS];
 #pragma unroll
-            for (int s = 0; s < 4; ++s)
+        for (int s = 0; s < NS; ++s) a[s] = 0.f;
+        for (int p0 = qq; p0 < n_part; p0 += 256) {
+            float x[NS][8];
+#pragma unroll
+            for (int s = 0; s < NS; ++s)
 #pragma unroll
                 for (int u = 0; u < 8; ++u) {
                     const int p = p0 + 32 * u;
                     x[s][u] = p < n_part ? g.part[s][(int64_t)p * plen + src] : 0.f;
                 }
 #pragma unroll
-            for (int s = 0; s < 4; ++s)
+            for (int s = 0; s < NS; ++s)
 #pragma unroll
                 for (int u = 0; u < 8; ++u) a[s] += x[s][u];
         }
 #pragma unroll
-        for (int s = 0; s < 4; ++s) {
+        for (int s = 0; s < NS; ++s) {
             const float sc = j < d ? g.wb[s] * g.ts[s] : g.wb[s];       // j < d: the time row of W, scaled by the stage time
             v = fmaf(sc, a[s], v);
         }
@@ -695,8 +699,35 @@ extern "C" int gode_gcn_small_finish4_f32(const gode_gcn_odefunc_t* f, const flo
     Finish4 g;
     for (int s = 0; s < 4; ++s) { g.part[s] = part + (int64_t)s * parts * plen; g.wb[s] = wb[s]; g.ts[s] = ts[s]; }
     const int64_t blocks = (out_len + 1 + 31) / 32;
-    hipLaunchKernelGGL(small_finish4_kernel, dim3((unsigned)blocks), dim3(1024), 0, (hipStream_t)stream, g, (int)parts, (int)plen,
+    hipLaunchKernelGGL(small_finish4_kernel<4>, dim3((unsigned)blocks), dim3(1024), 0, (hipStream_t)stream, g, (int)parts, (int)plen,
                        (int)d, theta, (int)out_len);
+    GODE_LAUNCH_CHECK();
+    return 0;
+}
+
+// The same launch over the n_stages <= 4 stages of a step of any fixed-grid method; a stage with a zero weight is left out
+// of the launch (its partial buffer is not read)
+extern "C" int gode_gcn_small_finish_step_f32(const gode_gcn_odefunc_t* f, const float* part, int32_t n_stages, float* theta,
+                                              const float* wb /* host[n_stages] */, const float* ts /* host[n_stages] */,
+                                              void* stream)
+{
+    if (!f || !part || !theta || !wb || !ts) return GODE_E_NULLPTR;
+    if (n_stages < 1 || n_stages > 4) return GODE_E_SHAPE;
+    const int64_t d = f->d, out_len = (d + 1) * d + 3 * d, plen = gode_gcn_small_part_len(d);
+    const int64_t parts = gode_gcn_small_parts(f->n);
+    Finish4 g = {};
+    int live = 0;
+    for (int s = 0; s < n_stages; ++s)
+        if (wb[s] != 0.f) { g.part[live] = part + (int64_t)s * parts * plen; g.wb[live] = wb[s]; g.ts[live] = ts[s]; ++live; }
+    if (live == 0) return GODE_E_SHAPE;
+    const dim3 grid((unsigned)((out_len + 1 + 31) / 32)), block(1024);
+    hipStream_t hs = (hipStream_t)stream;
+    switch (live) {
+    case 1: hipLaunchKernelGGL(small_finish4_kernel<1>, grid, block, 0, hs, g, (int)parts, (int)plen, (int)d, theta, (int)out_len); break;
+    case 2: hipLaunchKernelGGL(small_finish4_kernel<2>, grid, block, 0, hs, g, (int)parts, (int)plen, (int)d, theta, (int)out_len); break;
+    case 3: hipLaunchKernelGGL(small_finish4_kernel<3>, grid, block, 0, hs, g, (int)parts, (int)plen, (int)d, theta, (int)out_len); break;
+    default: hipLaunchKernelGGL(small_finish4_kernel<4>, grid, block, 0, hs, g, (int)parts, (int)plen, (int)d, theta, (int)out_len); break;
+    }
     GODE_LAUNCH_CHECK();
     return 0;
 }

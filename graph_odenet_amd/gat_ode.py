@@ -36,7 +36,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib, ops
-from .solver import Field
+from .solver import Field, method_code
 
 
 # launch-bound graphs: the reduction launches that close an adjoint stage run as one (ops.reduce_segments_); larger graphs
@@ -203,6 +203,7 @@ class GatOdeField(Field):
         if order is not None and self.BACKPROP_FUSED and not spec.pad_logits and self.small():
             self.order = order
             self.rk4_forward_save, self.rk4_backprop = self._rk4_forward_save, self._rk4_backprop
+            self.fixed_forward_save, self.fixed_backprop = self._fixed_forward_save, self._fixed_backprop
             self.dopri5_step_backprop, self.dopri5_backprop_work = self._dopri5_step_backprop, self._dopri5_backprop_work
             self.packed_grads, self.packed_param_grads = self._packed_grads, self._packed_param_grads
 
@@ -300,6 +301,25 @@ class GatOdeField(Field):
             ctypes.byref(fs), _lib.ptr(save), _lib.ptr(a), _lib.ptr(theta), ybar, _lib.ptr(sw.k_scratch), _lib.ptr(sw.parts),
             ctypes.byref(ws), float(t0), float(t1), int(n_steps), int(i0), int(i1), _lib.stream_ptr()),
             "gode_gat_ode_rk4_backprop")
+        return a
+
+    def _fixed_forward_save(self, method, y0, y_end, save, t0, t1, n_steps, i0, i1):
+        """_rk4_forward_save for any fixed-grid method (the launches of solver.integrate_fixed on this field); save[r] =
+        [y_n, k_1..k_S]."""
+        fs, ws = self._structs(True)
+        _lib.check(_lib.load().gode_gat_ode_fixed_forward_save(
+            method_code(method), ctypes.byref(fs), _lib.ptr(y0), _lib.ptr(y_end), _lib.ptr(save), ctypes.byref(ws), float(t0),
+            float(t1), int(n_steps), int(i0), int(i1), _lib.stream_ptr()), "gode_gat_ode_fixed_forward_save")
+
+    def _fixed_backprop(self, method, save, a, theta, t0, t1, n_steps, i0, i1):
+        """_rk4_backprop for any fixed-grid method, over the records of _fixed_forward_save."""
+        fs, ws = self._structs(True)
+        sw = self._sweep_work()
+        ybar = (ctypes.c_void_p * 4)(*[b.data_ptr() for b in sw.ybar[:4]])
+        _lib.check(_lib.load().gode_gat_ode_fixed_backprop(
+            method_code(method), ctypes.byref(fs), _lib.ptr(save), _lib.ptr(a), _lib.ptr(theta), ybar, _lib.ptr(sw.k_scratch),
+            _lib.ptr(sw.parts), ctypes.byref(ws), float(t0), float(t1), int(n_steps), int(i0), int(i1), _lib.stream_ptr()),
+            "gode_gat_ode_fixed_backprop")
         return a
 
     def _dopri5_backprop_work(self, like):

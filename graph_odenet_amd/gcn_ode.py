@@ -16,7 +16,7 @@ import torch
 
 from . import _lib, ops
 from .graph import as_graph
-from .solver import Field
+from .solver import Field, method_code, n_stages
 
 
 def _graph_struct(g, d):
@@ -145,6 +145,9 @@ def _func_struct(spec):
         a = spec.graph.__dict__["_a_core"]
         fs.a_core_items, fs.a_n_core, fs.a_diag = a.items.data_ptr(), a.n_items, a.diag.data_ptr()
     return fs
+
+
+E_UNSUPPORTED = -5        # include/graphode.h: GODE_E_UNSUPPORTED
 
 
 def _by_ptr(ptr_value, candidates):
@@ -430,6 +433,43 @@ class GcnOdeField(_PackedParams, Field):
             comps[0].copy_(out)
         return 4 * n_steps
 
+    def fixed_native(self, comps, t0, t1, n_steps, method):
+        """rk4_native for any fixed-grid method (gode_gcn_ode_fixed_forward)."""
+        lib = _lib.load()
+        s, w = self.s, self.w
+        ky = w.stage_buffers(False)[0]
+        fs, ws = _func_struct(s), w.workspace_struct(False, s.groups)
+        res = ctypes.c_void_p()
+        _lib.check(lib.gode_gcn_ode_fixed_forward(method_code(method), ctypes.byref(fs), _lib.ptr(comps[0]), ctypes.byref(res),
+                                                  ctypes.byref(ws), float(t0), float(t1), int(n_steps), _lib.stream_ptr()),
+                   "gode_gcn_ode_fixed_forward")
+        out = _by_ptr(res.value, [comps[0]] + ky)
+        if out is not comps[0]:
+            comps[0].copy_(out)
+        return n_stages(method) * n_steps
+
+    def fixed_forward_save(self, method, y0, y_end, save, t0, t1, n_steps, i0, i1):
+        """rk4_forward_save for any fixed-grid method: save[r] = [y_n, k_1..k_S] of step i0 + r."""
+        lib = _lib.load()
+        s, w = self.s, self.w
+        fs, ws = _func_struct(s), w.workspace_struct(False, s.groups)
+        _lib.check(lib.gode_gcn_ode_fixed_forward_save(method_code(method), ctypes.byref(fs), _lib.ptr(y0), _lib.ptr(y_end),
+                                                       _lib.ptr(save), ctypes.byref(ws), float(t0), float(t1), int(n_steps),
+                                                       int(i0), int(i1), _lib.stream_ptr()), "gode_gcn_ode_fixed_forward_save")
+
+    def fixed_backprop(self, method, save, a, theta, t0, t1, n_steps, i0, i1):
+        """rk4_backprop for any fixed-grid method, over the records of fixed_forward_save."""
+        lib = _lib.load()
+        s, w = self.s, self.w
+        ka = w.stage_buffers(True)[1]
+        fs, ws = _func_struct(s), w.workspace_struct(True, s.groups)
+        res = ctypes.c_void_p()
+        _lib.check(lib.gode_gcn_ode_fixed_backprop(method_code(method), ctypes.byref(fs), _lib.ptr(save), _lib.ptr(a),
+                                                   _lib.ptr(theta), ctypes.byref(res), ctypes.byref(ws),
+                                                   _lib.ptr(w.cot_colpart()), float(t0), float(t1), int(n_steps), int(i0),
+                                                   int(i1), _lib.stream_ptr()), "gode_gcn_ode_fixed_backprop")
+        return _by_ptr(res.value, [a] + ka)
+
     # ---- backprop through a fixed-grid solve (odeint._OdeintBackprop under rk4; csrc/ode_driver.hip) -----------
     def rk4_forward_save(self, y0, y_end, save, t0, t1, n_steps, i0, i1):
         """Steps i0 .. i1-1 of the n_steps-step rk4 solve from t0 to t1, bit for bit rk4_native's launches; save[r] =
@@ -511,6 +551,7 @@ class GcnOdeField(_PackedParams, Field):
 class _PartMixin:
     """Row-partitioned state (partition.py): hooks the adaptive solver uses to see global error norms."""
     rk4_native = None
+    fixed_native = None
     dopri5_step_native = None
     adaptive = False                # set by odeint when the method is adaptive
 
@@ -547,6 +588,8 @@ class GcnOdePartField(_PartMixin, GcnOdeField):
     big_components = (0,)
     rk4_forward_save = None
     rk4_backprop = None
+    fixed_forward_save = None
+    fixed_backprop = None
     dopri5_step_backprop = None
 
     def __init__(self, spec, shared, params_order):
@@ -587,6 +630,30 @@ class GcnOdeAdjointField(_PackedParams, Field):
         if ao is not comps[1]:
             comps[1].copy_(ao)
         return 4 * n_steps
+
+    def fixed_native(self, comps, t0, t1, n_steps, method):
+        """The whole adjoint solve of any fixed-grid method on the launch-bound route (gode_gcn_ode_fixed_adjoint); None
+        off that route: the per-stage driver then runs it (the two-chain schedule of large graphs is rk4's alone)."""
+        if method == "rk4":
+            return self.rk4_native(comps, t0, t1, n_steps)
+        lib = _lib.load()
+        s, w = self.s, self.w
+        ky, ka, _, _ = w.stage_buffers(True)
+        fs, ws = _func_struct(s), w.workspace_struct(True, s.groups)
+        yr, ar = ctypes.c_void_p(), ctypes.c_void_p()
+        rc = lib.gode_gcn_ode_fixed_adjoint(method_code(method), ctypes.byref(fs), _lib.ptr(comps[0]), _lib.ptr(comps[1]),
+                                            _lib.ptr(self.theta), ctypes.byref(yr), ctypes.byref(ar), ctypes.byref(ws),
+                                            float(t0), float(t1), int(n_steps), _lib.stream_ptr())
+        if rc == E_UNSUPPORTED:
+            return None
+        _lib.check(rc, "gode_gcn_ode_fixed_adjoint")
+        yo = _by_ptr(yr.value, [comps[0]] + ky)
+        ao = _by_ptr(ar.value, [comps[1]] + ka)
+        if yo is not comps[0]:
+            comps[0].copy_(yo)
+        if ao is not comps[1]:
+            comps[1].copy_(ao)
+        return n_stages(method) * n_steps
 
     def param_grads(self, comps):
         return self._in_params_order(comps)

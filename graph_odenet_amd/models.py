@@ -184,13 +184,17 @@ class ODEfunc2(nn.Module):
 
 
 class ODEBlock(nn.Module):
-    """y(1) of y' = odefunc(t, y), y(0) = x (reference: GCN/models.py:181-201)."""
+    """y(1) of y' = odefunc(t, y), y(0) = x (reference: GCN/models.py:181-201).
+
+    method: None / 'dopri5' (adaptive, rtol = atol = tol), or a fixed-grid method on steps of step_size (one step over
+    [0, 1] without it): 'rk4' (3/8 rule, 4 evaluations per step), 'midpoint' (2) or 'euler' (1).  Euler at step_size 1/K is
+    the weight-tied K-layer residual stack x <- x + odefunc(k/K, x) / K."""
 
     def __init__(self, odefunc, tol=1e-5, method=None, step_size=None, node_order=None, adjoint=True):
         super(ODEBlock, self).__init__()
         self.odefunc = odefunc
         # True (the reference): odeint_adjoint.  False: odeint, differentiable by backprop through the solve
-        # (odeint._OdeintBackprop, under rk4 and under the adaptive default)
+        # (odeint._OdeintBackprop, under every method)
         self.adjoint = bool(adjoint)
         if node_order is not None:            # extension: "auto" (default rule) | "given" | "degree" (gcn_ode.tuned_graph)
             from .gcn_ode import NODE_ORDERS

@@ -11,7 +11,9 @@ RK arithmetic still in the HIP kernels.
 
 `odeint` is differentiable as torchdiffeq's is (backprop through the solver's operations, not the adjoint): with grad
 mode on and y0 or a parameter of func requiring grad it returns a tensor with a grad_fn whose gradient is the exact
-derivative of the computed discrete solution w.r.t. y0 and func's parameters (t gets None).  Under adaptive dopri5 the
+derivative of the computed discrete solution w.r.t. y0 and func's parameters (t gets None).  Methods: adaptive `dopri5`
+(the default) and the fixed-grid `rk4` (3/8 rule), `midpoint` and `euler` on the grid options['step_size'] gives (one step
+per interval of t without it); euler at step_size 1/K is the weight-tied K-layer residual stack.  Under adaptive dopri5 the
 accepted step sizes are constants of that derivative: rejected attempts, the initial-step heuristic and the controller
 contribute nothing (what autograd through a solver whose step sizes are Python floats gives).  Row-partitioned fields
 stay forward-only.
@@ -22,11 +24,11 @@ import torch
 
 from . import ops
 from . import solver
-from .solver import (DP_A, DP_B, DP_C, Dopri5Record, Dopri5Stats, Field, integrate_dopri5, integrate_dopri5_inplace,
-                     integrate_rk4, interp_weights, uniform_grid)
+from .solver import (DP_A, DP_B, DP_C, FIXED_METHODS, FIXED_TABLEAUS, Dopri5Record, Dopri5Stats, Field, integrate_dopri5,
+                     integrate_dopri5_inplace, integrate_fixed, integrate_rk4, interp_weights, n_stages, uniform_grid)
 
 
-NATIVE_RK4 = True      # fused fields: issue a whole rk4 solve from one C-ABI call (False: per-stage Python driver)
+NATIVE_RK4 = True      # fused fields: issue a whole fixed-grid solve from one C-ABI call (False: per-stage Python driver)
 # Fixed-grid solves of fused fields on launch-bound sizes (state of at most this many elements) are captured into a
 # HIP graph the second time the same solve is requested and replayed afterwards; 0 turns the capture off.
 GRAPH_CAPTURE_MAX_ELEMS = 1 << 21
@@ -137,34 +139,43 @@ def _times(t):
     return tl
 
 
+METHODS = ("dopri5",) + FIXED_METHODS       # adaptive dopri5; fixed-grid rk4 (3/8 rule), euler, midpoint
+
+
 def _method(method):
     m = "dopri5" if method is None else method
-    if m not in ("dopri5", "rk4"):
-        raise ValueError("odeint: unsupported method %r (supported: dopri5, rk4)" % (method,))
+    if m not in METHODS:
+        raise ValueError("odeint: unsupported method %r (supported: %s)" % (method, ", ".join(METHODS)))
     return m
 
 
 def _integrate(field, comps, t0, t1, rtol, atol, method, options, stats):
     if method == "rk4":
         stats.nfe += _run_rk4(field, comps, t0, t1, uniform_grid(t0, t1, (options or {}).get("step_size")))
+    elif method in FIXED_METHODS:
+        stats.nfe += _run_fixed(field, comps, t0, t1, uniform_grid(t0, t1, (options or {}).get("step_size")), method)
     else:
         if field.fixed_grid_only:
-            raise NotImplementedError("odeint: this field supports the fixed-grid method only (method='rk4')")
+            raise NotImplementedError(_FIXED_ONLY)
         if field.big_components is not None:
             field.adaptive = True                  # row-partitioned fields: keep the small components global
         _prepare(field)
         integrate_dopri5_inplace(field, comps, t0, t1, rtol, atol, stats)
 
 
+_FIXED_ONLY = "odeint: this field supports the fixed-grid methods only (method=%s)" % " / ".join(
+    repr(m) for m in FIXED_METHODS)
+
+
 class _GraphedSolve:
     """One captured fixed-grid solve: static input components, the HIP graph, and the components holding the result."""
 
-    def __init__(self, field, comps, t0, t1, n_steps):
+    def __init__(self, field, comps, t0, t1, n_steps, method="rk4"):
         from . import _lib
         lib = _lib.load()
         self.field = field
         self.inputs = list(comps)
-        self.nfe = 4 * n_steps
+        self.nfe = n_stages(method) * n_steps
         work = list(comps)
         overlap = lib.gode_get_option(b"overlap")
         lib.gode_set_option(b"overlap", 0)           # launch-bound sizes gain nothing from the second stream
@@ -172,7 +183,7 @@ class _GraphedSolve:
             torch.cuda.synchronize()
             self.graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.graph):
-                _run_rk4(field, work, t0, t1, n_steps)
+                _run_fixed(field, work, t0, t1, n_steps, method)
         finally:
             lib.gode_set_option(b"overlap", overlap)
         self.outputs = work
@@ -214,7 +225,7 @@ def plans_of(func):
 def _try_capture(plan, field, comps, t0, t1):
     """A captured solve, or None (and the plan switched to the eager path for good) when the capture fails."""
     try:
-        return _GraphedSolve(field, comps, t0, t1, plan.n_steps)
+        return _GraphedSolve(field, comps, t0, t1, plan.n_steps, plan.method)
     except RuntimeError as exc:
         import warnings
         plan.no_capture = True
@@ -229,7 +240,7 @@ def _plan_for(func, y0, tl, method, options, params):
     shape and the parameter storage (i.e. the graph)."""
     tok = getattr(func, "gode_plan_token", None)
     token = None
-    if (tok is not None and GRAPH_CAPTURE_MAX_ELEMS > 0 and method == "rk4" and len(tl) == 2
+    if (tok is not None and GRAPH_CAPTURE_MAX_ELEMS > 0 and method in FIXED_METHODS and len(tl) == 2
             and y0.numel() <= GRAPH_CAPTURE_MAX_ELEMS and not torch.cuda.is_current_stream_capturing()):
         token = tok(y0)
     if token is None:
@@ -237,7 +248,8 @@ def _plan_for(func, y0, tl, method, options, params):
     n = uniform_grid(tl[0], tl[1], (options or {}).get("step_size"))
     # the hook's identity is part of the key: a func whose gode_fields was swapped (e.g. to force the autograd path)
     # must not be served the fused fields of an earlier plan
-    key = (tuple(y0.shape), y0.device.index, tl[0], tl[1], n, token, tuple(p.data_ptr() for p in params), NATIVE_RK4,
+    # ... and the method: an euler solve after an rk4 solve of the same func must not replay the rk4 graph
+    key = (tuple(y0.shape), y0.device.index, tl[0], tl[1], n, method, token, tuple(p.data_ptr() for p in params), NATIVE_RK4,
            id(getattr(func, "gode_fields", None).__func__) if hasattr(getattr(func, "gode_fields", None), "__func__") else None)
     plans = plans_of(func)
     plan = plans.get(key)
@@ -248,7 +260,7 @@ def _plan_for(func, y0, tl, method, options, params):
         if len(plans) >= 4:
             plans.clear()                       # a func that keeps changing graphs / shapes: start over
         plan = plans[key] = _Plan(*fields)
-        plan.n_steps = n
+        plan.n_steps, plan.method = n, method
     return plan, (plan.fwd, plan.mk_adj, plan.plist)
 
 
@@ -257,6 +269,18 @@ def _run_rk4(field, comps, t0, t1, n):
     if field.rk4_native is not None and NATIVE_RK4:
         return field.rk4_native(comps, t0, t1, n)          # whole solve issued from C (csrc/ode_driver.hip)
     return integrate_rk4(field, comps, t0, t1, n)
+
+
+def _run_fixed(field, comps, t0, t1, n, method):
+    """A fixed-grid solve by any method of solver.FIXED_TABLEAUS; rk4 takes _run_rk4's launches exactly."""
+    if method == "rk4":
+        return _run_rk4(field, comps, t0, t1, n)
+    _prepare(field)
+    if field.fixed_native is not None and NATIVE_RK4:
+        nfe = field.fixed_native(comps, t0, t1, n, method)     # whole solve issued from C; None: not on that route
+        if nfe is not None:
+            return nfe
+    return integrate_fixed(field, comps, t0, t1, n, method)
 
 
 def _extra_inputs(func):
@@ -320,6 +344,22 @@ def _rk4_torch(func, y, t0, t1, n):
     return y
 
 
+def _fixed_torch(func, y, t0, t1, n, method):
+    """n steps of a fixed-grid method from t0 to t1 as differentiable torch ops through func; rk4 is _rk4_torch."""
+    if method == "rk4":
+        return _rk4_torch(func, y, t0, t1, n)
+    C, A, B = FIXED_TABLEAUS[method]
+    h = (t1 - t0) / n
+    tt = lambda v: torch.tensor(v, dtype=y.dtype, device=y.device)      # noqa: E731
+    for i in range(n):
+        t = t0 + i * h
+        ks = []
+        for s in range(len(C)):
+            ks.append(func(tt(t + C[s] * h), y + sum((h * a) * k for a, k in zip(A[s], ks) if a != 0.0)))
+        y = y + sum((h * b) * k for b, k in zip(B, ks) if b != 0.0)
+    return y
+
+
 def _dopri5_step_torch(func, y, t, h, x):
     """One Dormand-Prince step from y at t as differentiable torch ops through func; x: the interpolation abscissa of a
     last step that overshot the end time (None: the step's own end state is returned)."""
@@ -334,63 +374,80 @@ def _dopri5_step_torch(func, y, t, h, x):
     return cy0 * y + cy1 * y1 + sum((h * c) * k for c, k in zip(kc, ks) if c != 0.0)
 
 
+def _fixed_sweep(fwd, method):
+    """(forward_save, backprop) of a field under a fixed-grid method, both taking (.., t0, t1, n, i0, i1) - or None.  rk4
+    keeps the members it has always used."""
+    if method == "rk4":
+        if fwd.rk4_forward_save is None:
+            return None
+        return fwd.rk4_forward_save, fwd.rk4_backprop
+    if fwd.fixed_forward_save is None:
+        return None
+    return (lambda *args: fwd.fixed_forward_save(method, *args)), (lambda *args: fwd.fixed_backprop(method, *args))
+
+
 class _Rk4Backprop:
-    """What _OdeintBackprop does per interval under fixed-grid rk4.  Fused (a field offering rk4_forward_save /
-    rk4_backprop: GcnOdeField): the record is [y_n, k_1..k_4] of every step, swept in reverse by one C call per interval
-    (csrc/ode_driver.hip) - or, when the whole solve outgrows BACKPROP_SAVE_MAX_BYTES, y_n alone, each step then re-run
-    into a one-step record just before its sweep.  Generic: the record is the interval's start state, from which the
-    interval is re-run as torch ops through func (what torchdiffeq does)."""
+    """What _OdeintBackprop does per interval under a fixed-grid method of S stages (rk4, euler, midpoint).  Fused (a field
+    offering rk4_forward_save / rk4_backprop, for the other methods fixed_forward_save / fixed_backprop: GcnOdeField): the
+    record is [y_n, k_1..k_S] of every step, swept in reverse by one C call per interval (csrc/ode_driver.hip) - or, when
+    the whole solve outgrows BACKPROP_SAVE_MAX_BYTES, y_n alone, each step then re-run into a one-step record just before
+    its sweep.  Generic: the record is the interval's start state, from which the interval is re-run as torch ops through
+    func (what torchdiffeq does)."""
     own_cotangent = True              # fused_reverse hands back the tensor it was given
 
-    def __init__(self, func, fwd, tl, rtol, atol, options, y0c):
+    def __init__(self, func, fwd, tl, rtol, atol, options, y0c, method="rk4"):
         self.func, self.fwd, self.tl, self.tols, self.options = func, fwd, tl, (rtol, atol), options
+        self.method, self.S = method, n_stages(method)
         step_size = (options or {}).get("step_size")
         self.steps = [uniform_grid(tl[i - 1], tl[i], step_size) for i in range(1, len(tl))]
-        self.fused = fwd.rk4_forward_save is not None and NATIVE_RK4
+        sweep = _fixed_sweep(fwd, method) if NATIVE_RK4 else None
+        self.fused = sweep is not None
         self.stats = Dopri5Stats()
         if self.fused:
+            self.forward_save, self.backprop = sweep
             _prepare(fwd)
-            self.save_all = 5 * sum(self.steps) * y0c.numel() * 4 <= BACKPROP_SAVE_MAX_BYTES
+            self.save_all = (self.S + 1) * sum(self.steps) * y0c.numel() * 4 <= BACKPROP_SAVE_MAX_BYTES
 
     def forward(self, i, cur, start):
         fwd, t0, t1, n = self.fwd, self.tl[i - 1], self.tl[i], self.steps[i - 1]
         if not self.fused:
             ys = [cur]
-            _integrate(fwd, ys, t0, t1, *self.tols, "rk4", self.options, self.stats)
+            _integrate(fwd, ys, t0, t1, *self.tols, self.method, self.options, self.stats)
             return start, ys[0]
         shape, like = tuple(cur.shape), dict(dtype=cur.dtype, device=cur.device)
         y_end = torch.empty_like(cur)
         if self.save_all:
-            rec = torch.empty((n, 5) + shape, **like)
+            rec = torch.empty((n, self.S + 1) + shape, **like)
             rec[0, 0].copy_(cur)
-            fwd.rk4_forward_save(rec[0, 0], y_end, rec, t0, t1, n, 0, n)
+            self.forward_save(rec[0, 0], y_end, rec, t0, t1, n, 0, n)
         else:
             rec = torch.empty((n,) + shape, **like)
             rec[0].copy_(cur)
-            one = torch.empty((1, 5) + shape, **like)
+            one = torch.empty((1, self.S + 1) + shape, **like)
             for j in range(n):
-                fwd.rk4_forward_save(rec[j], rec[j + 1] if j + 1 < n else y_end, one, t0, t1, n, j, j + 1)
-        self.stats.nfe += 4 * n
+                self.forward_save(rec[j], rec[j + 1] if j + 1 < n else y_end, one, t0, t1, n, j, j + 1)
+        self.stats.nfe += self.S * n
         return rec, y_end
 
     def fused_reverse(self, i, rec, a, theta, work):
-        fwd, t0, t1, n = self.fwd, self.tl[i - 1], self.tl[i], self.steps[i - 1]
+        t0, t1, n = self.tl[i - 1], self.tl[i], self.steps[i - 1]
         if self.save_all:
-            res = fwd.rk4_backprop(rec, a, theta, t0, t1, n, 0, n)
+            res = self.backprop(rec, a, theta, t0, t1, n, 0, n)
             if res is not a:
                 a.copy_(res)
             return a
         if not work:
-            work.update(one=torch.empty((1, 5) + tuple(a.shape), dtype=a.dtype, device=a.device), y=torch.empty_like(a))
+            work.update(one=torch.empty((1, self.S + 1) + tuple(a.shape), dtype=a.dtype, device=a.device),
+                        y=torch.empty_like(a))
         for j in range(n - 1, -1, -1):          # re-run the step into a one-step record, then sweep it
-            fwd.rk4_forward_save(rec[j], work["y"], work["one"], t0, t1, n, j, j + 1)
-            res = fwd.rk4_backprop(work["one"], a, theta, t0, t1, n, j, j + 1)
+            self.forward_save(rec[j], work["y"], work["one"], t0, t1, n, j, j + 1)
+            res = self.backprop(work["one"], a, theta, t0, t1, n, j, j + 1)
             if res is not a:
                 a.copy_(res)
         return a
 
     def generic_reverse(self, i, rec):
-        yield rec, lambda y: _rk4_torch(self.func, y, self.tl[i - 1], self.tl[i], self.steps[i - 1])
+        yield rec, lambda y: _fixed_torch(self.func, y, self.tl[i - 1], self.tl[i], self.steps[i - 1], self.method)
 
 
 class _Dopri5Backprop:
@@ -405,7 +462,7 @@ class _Dopri5Backprop:
 
     def __init__(self, func, fwd, tl, rtol, atol, options, y0c):
         if fwd.fixed_grid_only:
-            raise NotImplementedError("odeint: this field supports the fixed-grid method only (method='rk4')")
+            raise NotImplementedError(_FIXED_ONLY)
         self.func, self.fwd, self.tl, self.tols = func, fwd, tl, (rtol, atol)
         self.fused = fwd.dopri5_step_backprop is not None and solver.DOPRI5_NATIVE
         self.stats = Dopri5Stats()
@@ -467,7 +524,10 @@ class _OdeintBackprop(torch.autograd.Function):
         outs = [y0c.clone()]
         records = []
         with torch.no_grad():
-            sweep = (_Rk4Backprop if method == "rk4" else _Dopri5Backprop)(func, fwd, tl, rtol, atol, options, y0c)
+            if method in FIXED_METHODS:
+                sweep = _Rk4Backprop(func, fwd, tl, rtol, atol, options, y0c, method)
+            else:
+                sweep = _Dopri5Backprop(func, fwd, tl, rtol, atol, options, y0c)
             cur = _gather(y0c, fwd.row_order)
             for i in range(1, len(tl)):
                 rec, cur = sweep.forward(i, cur, outs[-1])
@@ -528,7 +588,7 @@ def odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None):
         if y0.requires_grad or params:
             covered = tuple(fields[2]) + _extra_inputs(func)       # a field with a sweep returns the extra inputs' gradients too
             same = len(covered) == len(params) and all(p is q for p, q in zip(covered, params))
-            sweep = fwd.rk4_forward_save if method == "rk4" else fwd.dopri5_step_backprop
+            sweep = _fixed_sweep(fwd, method) if method in FIXED_METHODS else fwd.dopri5_step_backprop
             if sweep is not None and not same:
                 fwd = AutogradField(func, y0)         # the fused field does not cover these parameters
             return _OdeintBackprop.apply(func, fwd, tl, float(rtol), float(atol), method, options, y0, *params)
@@ -638,9 +698,9 @@ class _OdeintAdjoint(torch.autograd.Function):
             _gather(g_raw(-1), order, out=comps[1])
             for i in range(len(tl) - 1, 0, -1):
                 comps[0].copy_(ans[i])
-                if ctx.method != "rk4":
+                if ctx.method not in FIXED_METHODS:
                     # dL/dt at the output time enters the adaptive error control (torchdiffeq evaluates
-                    # func once more here); a fixed grid never looks at it, so rk4 skips the eval.
+                    # func once more here); a fixed grid never looks at it, so the fixed-grid methods skip the eval.
                     fwd.eval(tl[i], [[(1.0, ans[i])]], [ctx_tmp])
                     stats.nfe += 1
                     gi = g_at(i)
@@ -655,13 +715,13 @@ class _OdeintAdjoint(torch.autograd.Function):
             # the cotangent of the start state is added after the rows are back in the caller's order: one pass, and
             # no gather of a slice that is all zeros whenever the loss only looks at the end state
             gy0 = add_start(back(comps[1]))
-        skipped = (n_t - 1) if (ctx.method == "rk4" and NFE_COUNTS_SKIPPED_DLDT_EVAL) else 0
+        skipped = (n_t - 1) if (ctx.method in FIXED_METHODS and NFE_COUNTS_SKIPPED_DLDT_EVAL) else 0
         _bump_nfe(func, adj, stats.nfe, skipped)
         return (None, None, None, None, None, None, None, gy0, *adj.param_grads(comps))
 
 
 def odeint_adjoint(func, y0, t, rtol=1e-6, atol=1e-12, method=None, options=None, _last_only=False):
-    """torchdiffeq's odeint_adjoint for the two solvers of the hot path.  `_last_only=True` (not part of the reference
+    """torchdiffeq's odeint_adjoint for dopri5 and the fixed-grid methods (rk4, midpoint, euler).  `_last_only=True` (not part of the reference
     API; used by models.ODEBlock, which keeps `out[1]` only) returns y(t[-1]) instead of the stack over t."""
     _check_state(y0)
     tl = _times(t)

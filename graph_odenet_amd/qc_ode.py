@@ -49,7 +49,7 @@ import torch.nn.functional as F
 from . import _lib, ops
 from .functional import GroupNorm
 from .qc_layers import EdgeGraphConvolution, _edges, _EdgeSet
-from .solver import DP_A, DP_C, RK38_A, RK38_B, RK38_C, Field, _stage_terms
+from .solver import DP_A, DP_C, FIXED_METHODS, FIXED_TABLEAUS, Field, _stage_terms
 
 
 def _edge_index(Esrc, Etgt):
@@ -206,6 +206,7 @@ class EdgeOdeField(Field):
                 ops.edge_ode_stage_bwd_supported(spec.n, spec.d, spec.groups):
             self.order, self.want_A, self._bwork = order, bool(want_A), None
             self.rk4_forward_save, self.rk4_backprop = self._rk4_forward_save, self._rk4_backprop
+            self.fixed_forward_save, self.fixed_backprop = self._fixed_forward_save, self._fixed_backprop
             self.dopri5_step_backprop, self.dopri5_backprop_work = self._dopri5_step_backprop, self._dopri5_backprop_work
             self.packed_grads, self.packed_param_grads = self._packed_grads, self._packed_param_grads
 
@@ -244,36 +245,46 @@ class EdgeOdeField(Field):
                                    [1.0] * len(stages), theta[s.n_theta:].view_as(s.A), True)
 
     def _rk4_forward_save(self, y0, y_end, save, t0, t1, n_steps, i0, i1):
-        """Steps i0 .. i1-1 with the launches of solver.integrate_rk4 on this field (the same bits); save[r] = [y_n, k_1..k_4]
-        of step i0 + r, k_4 stored by the launch that folds the last stage into the solution."""
+        self._fixed_forward_save("rk4", y0, y_end, save, t0, t1, n_steps, i0, i1)
+
+    def _rk4_backprop(self, save, a, theta, t0, t1, n_steps, i0, i1):
+        return self._fixed_backprop("rk4", save, a, theta, t0, t1, n_steps, i0, i1)
+
+    def _fixed_forward_save(self, method, y0, y_end, save, t0, t1, n_steps, i0, i1):
+        """Steps i0 .. i1-1 with the launches of solver.integrate_fixed on this field (the same bits; rk4: integrate_rk4's);
+        save[r] = [y_n, k_1..k_S] of step i0 + r, k_S stored by the launch that folds the last stage into the solution."""
+        C, A, B = FIXED_TABLEAUS[method]
+        L = len(C) - 1
         if y0.data_ptr() != save[0, 0].data_ptr():
             save[0, 0].copy_(y0)
         h = (t1 - t0) / n_steps
         for i in range(i0, i1):
             rec = save[i - i0]
-            y, ks = [rec[0]], [[rec[1 + q]] for q in range(4)]
+            y, ks = [rec[0]], [[rec[1 + q]] for q in range(L + 1)]
             t = t0 + i * h
-            for q in range(3):
-                self.eval(t + RK38_C[q] * h, _stage_terms(y, ks, RK38_A[q], h), ks[q])
-            pre = [(1.0, y[0])] + [(h * RK38_B[q], ks[q][0]) for q in range(3)]
+            for q in range(L):
+                self.eval(t + C[q] * h, _stage_terms(y, ks, A[q], h), ks[q])
+            pre = [(1.0, y[0])] + [(h * B[q], ks[q][0]) for q in range(L) if B[q] != 0.0]
             y_next = save[i - i0 + 1, 0] if i + 1 < i1 else y_end
-            self._forward(t + RK38_C[3] * h, _stage_terms(y, ks, RK38_A[3], h)[0], y_next, pre=pre, alpha=h * RK38_B[3],
-                          k_out=ks[3][0])
+            self._forward(t + C[L] * h, _stage_terms(y, ks, A[L], h)[0], y_next, pre=pre, alpha=h * B[L], k_out=ks[L][0])
 
-    def _rk4_backprop(self, save, a, theta, t0, t1, n_steps, i0, i1):
-        """Reverse sweep over the records of steps i0 .. i1-1: kbar_s = h b_s a + h sum_{r > s} a_rs Ybar_r, Ybar_s through
-        the stage, a += sum_s Ybar_s.  `a` is advanced in place and returned."""
+    def _fixed_backprop(self, method, save, a, theta, t0, t1, n_steps, i0, i1):
+        """Reverse sweep over the records of steps i0 .. i1-1: kbar_s = h b_s a + h sum_{r > s} a_rs Ybar_r (zero coefficients
+        dropped), Ybar_s through the stage, a += sum_s Ybar_s.  `a` is advanced in place and returned."""
+        C, A, B = FIXED_TABLEAUS[method]
+        S = len(C)
         h = (t1 - t0) / n_steps
-        yb = self._bw(a.device).ybar
+        yb = self._bw(a.device).ybar[:S]
         for i in range(i1 - 1, i0 - 1, -1):
             rec = save[i - i0]
-            y, ks = [rec[0]], [[rec[1 + q]] for q in range(4)]
+            y, ks = [rec[0]], [[rec[1 + q]] for q in range(S)]
             t = t0 + i * h
             stages = []
-            for q in range(3, -1, -1):
-                cot = [(h * RK38_B[q], a)] + [(h * RK38_A[r][q], yb[r]) for r in range(q + 1, 4) if RK38_A[r][q] != 0.0]
-                stages.append(self._stage_bwd(len(stages), cot, ks[q][0], _stage_terms(y, ks, RK38_A[q], h)[0],
-                                              t + RK38_C[q] * h, yb[q]))
+            for q in range(S - 1, -1, -1):
+                cot = ([(h * B[q], a)] if B[q] != 0.0 else []) + \
+                      [(h * A[r][q], yb[r]) for r in range(q + 1, S) if A[r][q] != 0.0]
+                stages.append(self._stage_bwd(len(stages), cot, ks[q][0], _stage_terms(y, ks, A[q], h)[0],
+                                              t + C[q] * h, yb[q]))
             self._close_step(stages, theta)
             ops.lincomb_(a, [(1.0, a)] + [(1.0, b) for b in yb])
         return a
@@ -423,7 +434,7 @@ class EdgeODEBlock(nn.Module):
     def __init__(self, odefunc, tol=1e-5, method=None, step_size=None, adjoint=True):
         super().__init__()
         self.odefunc = odefunc
-        self.adjoint = bool(adjoint)       # False: odeint, differentiable by backprop through the solve (rk4 and dopri5)
+        self.adjoint = bool(adjoint)       # False: odeint, differentiable by backprop through the solve (every method)
         self.integration_time = torch.tensor([0, 1]).float()
         self.tol, self.method, self.step_size = tol, method, step_size
 
@@ -431,7 +442,7 @@ class EdgeODEBlock(nn.Module):
         from .odeint import odeint, odeint_adjoint
         self.integration_time = self.integration_time.type_as(x)
         self.odefunc.set_edges(Esrc, Etgt, edge_data)
-        self.odefunc.fixed_grid = self.method == "rk4"
+        self.odefunc.fixed_grid = self.method in FIXED_METHODS
         options = None if self.step_size is None else {"step_size": self.step_size}
         if not self.adjoint:
             return odeint(self.odefunc, x, self.integration_time, rtol=self.tol, atol=self.tol, method=self.method,

@@ -5,6 +5,8 @@ module re-creates the two methods the hot path needs from the published algorith
 (see oracle/solver_ref.py for the restatement and its sources):
 
   * fixed-grid `rk4`  : 3/8-rule steps on a uniform grid (options['step_size']);
+  * fixed-grid `euler`, `midpoint` : torchdiffeq's one- and two-stage methods on the same grid, run by the same driver from
+                        their tableaus (FIXED_TABLEAUS, integrate_fixed);
   * adaptive `dopri5` : Dormand-Prince 5(4), FSAL, RMS mixed-tolerance error ratio per
                         state tensor, safety 0.9 / ifactor 10 / dfactor 0.2, 4th-order
                         interpolation to the end time (the reference's default: no
@@ -27,6 +29,24 @@ from . import ops
 RK38_C = [0.0, 1.0 / 3.0, 2.0 / 3.0, 1.0]
 RK38_A = [[], [1.0 / 3.0], [-1.0 / 3.0, 1.0], [1.0, -1.0, 1.0]]
 RK38_B = [1.0 / 8.0, 3.0 / 8.0, 3.0 / 8.0, 1.0 / 8.0]
+
+# explicit Euler, and the explicit midpoint rule as torchdiffeq states it (b_1 = 0: the result never reads k_1)
+EULER_C, EULER_A, EULER_B = [0.0], [[]], [1.0]
+MIDPOINT_C, MIDPOINT_A, MIDPOINT_B = [0.0, 0.5], [[], [0.5]], [0.0, 1.0]
+# the fixed-grid methods by name: (c, a, b); the order is that of the GODE_RK_* codes of include/graphode.h
+FIXED_TABLEAUS = {"rk4": (RK38_C, RK38_A, RK38_B), "euler": (EULER_C, EULER_A, EULER_B),
+                  "midpoint": (MIDPOINT_C, MIDPOINT_A, MIDPOINT_B)}
+FIXED_METHODS = tuple(FIXED_TABLEAUS)
+
+
+def method_code(method):
+    """The GODE_RK_* code of a fixed-grid method name."""
+    return FIXED_METHODS.index(method)
+
+
+def n_stages(method):
+    return len(FIXED_TABLEAUS[method][0])
+
 
 DP_C = [0.0, 1 / 5, 3 / 10, 4 / 5, 8 / 9, 1.0, 1.0]
 DP_A = [
@@ -91,6 +111,11 @@ class Field:
     finish_rk4_step = None        # ... deferred_components are advanced in place by finish_rk4_step(weights, y) after them
     deferred_components = ()
     fixed_grid_only = False       # odeint refuses the adaptive method on this field
+    # ---- every fixed-grid method (a name of FIXED_TABLEAUS; S stages) ---------------------------------------------------
+    #                               eval_combine / begin_rk4_step / finish_rk4_step serve integrate_fixed as they serve
+    #                               integrate_rk4: the last stage closes the step, finish_rk4_step receives S weights
+    fixed_native = None           # fixed_native(comps, t0, t1, n, method) -> nfe: odeint, the whole solve as one C call;
+    #                               None from the call itself = not on this route, take the per-stage driver
     # ---- adaptive dopri5 ------------------------------------------------------------------------------------------
     dopri5_step_native = None     # dopri5_step_native(y, kk, y1, t, h, rtol, atol) -> error sums per ratio group (fp64,
     #                               on the device): integrate_dopri5, one attempted step as one C call
@@ -107,6 +132,9 @@ class Field:
     # ---- backprop through the solve (odeint._OdeintBackprop); a field offering a sweep offers the packed pair too ----------
     rk4_forward_save = None       # rk4_forward_save(y0, y_end, save, t0, t1, n, i0, i1): steps i0..i1-1, stages recorded
     rk4_backprop = None           # rk4_backprop(save, a, theta, t0, t1, n, i0, i1) -> tensor holding dL/dy before step i0
+    fixed_forward_save = None     # fixed_forward_save(method, y0, y_end, save, t0, t1, n, i0, i1): the same for any fixed-grid
+    #                               method; a step's record is [y_n, k_1..k_S]
+    fixed_backprop = None         # fixed_backprop(method, save, a, theta, t0, t1, n, i0, i1) -> as rk4_backprop
     dopri5_step_backprop = None   # dopri5_step_backprop(y, k, g, kbar7, wy, wk, t, h, first, work, turn, theta); a field
     #                               offering it without dopri5_step_native gets all seven k_s of every step, whatever the
     #                               byte bound (there is nothing to re-run a step with)
@@ -187,6 +215,53 @@ def integrate_rk4(field, y, t0, t1, n_steps, work=None):
         for g0 in range(0, len(todo), 4):
             grp = todo[g0:g0 + 4]
             terms = [[(1.0, y[c])] + [(h * RK38_B[s], ks[s][c]) for s in range(4)] for c in grp]
+            if len(grp) == 1:
+                ops.lincomb_(y[grp[0]], terms[0])
+            else:
+                ops.lincomb_multi_([y[c] for c in grp], terms)
+    return nfe
+
+
+def integrate_fixed(field, y, t0, t1, n_steps, method, work=None):
+    """integrate_rk4 for any method of FIXED_TABLEAUS, the same protocol: `eval` for every stage but the last,
+    `eval_combine` for the last - its pre is y + h * sum of the earlier stages with a non-zero b, its coefficient h * b_last -
+    begin_rk4_step / finish_rk4_step around the stages (S weights), and the remaining components in lincomb_multi_ launches of
+    four.  Terms with a zero coefficient are dropped.  Returns nfe; read the result from `y[c]`."""
+    C, A, B = FIXED_TABLEAUS[method]
+    S = len(C)
+    L = S - 1
+    alloc = field.alloc_like or _alloc_like
+    ks = work if work is not None else alloc(y, S)
+    h = (t1 - t0) / n_steps
+    nfe = 0
+    nc = len(y)
+    fused = field.eval_combine
+    begin, finish = field.begin_rk4_step, field.finish_rk4_step
+    for i in range(n_steps):
+        t = t0 + i * h
+        deferred = begin is not None and begin()
+        for s in range(L):
+            field.eval(t + C[s] * h, _stage_terms(y, ks, A[s], h), ks[s])
+        done = ()
+        if fused is not None:
+            pre = [[(1.0, y[c])] + [(h * B[s], ks[s][c]) for s in range(L) if B[s] != 0.0] for c in range(nc)]
+            done = fused(t + C[L] * h, _stage_terms(y, ks, A[L], h), pre, h * B[L], ks[L])
+        else:
+            field.eval(t + C[L] * h, _stage_terms(y, ks, A[L], h), ks[L])
+        nfe += S
+        if deferred:
+            done = tuple(done) + tuple(finish([h * b for b in B], y))
+        todo = []
+        for c in range(nc):
+            if c in done:
+                if deferred and c in field.deferred_components:
+                    continue                           # advanced in place by finish_rk4_step
+                y[c], ks[L][c] = ks[L][c], y[c]        # ks[L][c] already holds the new solution
+            else:
+                todo.append(c)
+        for g0 in range(0, len(todo), 4):
+            grp = todo[g0:g0 + 4]
+            terms = [[(1.0, y[c])] + [(h * B[s], ks[s][c]) for s in range(S) if B[s] != 0.0] for c in grp]
             if len(grp) == 1:
                 ops.lincomb_(y[grp[0]], terms[0])
             else:

@@ -741,6 +741,47 @@ int gode_gcn_ode_rk4_backprop(const gode_gcn_odefunc_t* f, const float* save, fl
                               const gode_rk4_workspace_t* ws, float* cot_colpart /* nullable */, float t0, float t1,
                               int32_t n_steps, int32_t step_begin, int32_t step_end, void* stream);
 
+/* The fixed-grid methods of the drivers by code, and their Butcher tableaus (host queries: no device is touched).
+ * gode_rk_stages: the number of stages S, or GODE_E_SHAPE for a code outside the list.  gode_rk_tableau: c (S), a (S x S,
+ * row-major, strictly lower triangular) and b (S) as the drivers hold them; any of the three may be NULL.
+ *   GODE_RK_RK4_38    Kutta's 3/8 rule (what the gode_*_rk4_* entry points run)
+ *   GODE_RK_EULER     explicit Euler: c = [0], b = [1]
+ *   GODE_RK_MIDPOINT  explicit midpoint rule: c = [0, 1/2], a21 = 1/2, b = [0, 1] */
+#define GODE_RK_RK4_38   0
+#define GODE_RK_EULER    1
+#define GODE_RK_MIDPOINT 2
+int gode_rk_stages(int32_t method);
+int gode_rk_tableau(int32_t method, double* c, double* a, double* b);
+
+/* One launch per step of an S-stage fixed-grid adjoint solve on launch-bound graphs, S <= 4: gode_gcn_small_finish4_f32 over
+ * n_stages partial buffers (stage s at part + s * parts * part_len; wb, ts: host arrays of n_stages).  A stage whose wb is
+ * zero is not read.  With four non-zero weights the result is bit for bit gode_gcn_small_finish4_f32's.  GODE_E_SHAPE:
+ * n_stages outside 1..4, or every weight zero. */
+int gode_gcn_small_finish_step_f32(const gode_gcn_odefunc_t* f, const float* part, int32_t n_stages, float* theta,
+                                   const float* wb /* host */, const float* ts /* host */, void* stream);
+
+/* The four rk4 drivers above with the method as an argument (GODE_RK_*); GODE_RK_RK4_38 calls the rk4 entry point itself.
+ * h, the stage times and every h * coefficient product are formed in double and rounded once; a term with a zero
+ * coefficient is not read (the midpoint rule's closing combination never names k_1).  The last stage of a step is the
+ * closing one, and every option of the rk4 drivers applies to it as it does there; explicit Euler's only stage closes the
+ * step with pre = y and alpha = h.
+ * Validation: null pointers, then a method outside the list (GODE_E_SHAPE), then the rk4 counterpart's checks in its order.
+ * fixed_adjoint: the launch-bound route only (the fused one-launch stages with ws->small_part given); elsewhere
+ *   GODE_E_UNSUPPORTED before any launch, and the caller runs the stages itself.
+ * fixed_forward_save / fixed_backprop: a record is [ y_n | k_1 .. k_S ], (S + 1) n x d floats; ws->ka / ktheta /
+ *   small_part are used per stage, slots 0 .. S - 1. */
+int gode_gcn_ode_fixed_forward(int32_t method, const gode_gcn_odefunc_t* f, float* y, float** result,
+                               const gode_rk4_workspace_t* ws, float t0, float t1, int32_t n_steps, void* stream);
+int gode_gcn_ode_fixed_adjoint(int32_t method, const gode_gcn_odefunc_t* f, float* y, float* a, float* theta,
+                               float** y_result, float** a_result,
+                               const gode_rk4_workspace_t* ws, float t0, float t1, int32_t n_steps, void* stream);
+int gode_gcn_ode_fixed_forward_save(int32_t method, const gode_gcn_odefunc_t* f, const float* y0, float* y_end, float* save,
+                                    const gode_rk4_workspace_t* ws, float t0, float t1, int32_t n_steps,
+                                    int32_t step_begin, int32_t step_end, void* stream);
+int gode_gcn_ode_fixed_backprop(int32_t method, const gode_gcn_odefunc_t* f, const float* save, float* a, float* theta,
+                                float** a_result, const gode_rk4_workspace_t* ws, float* cot_colpart /* nullable */,
+                                float t0, float t1, int32_t n_steps, int32_t step_begin, int32_t step_end, void* stream);
+
 /* One Dormand-Prince 5(4) step of the same ODE function per call (adaptive solves on launch-bound sizes; the controller
  * - step-size selection, accept / reject, interpolation - stays with the caller, as in torchdiffeq).
  * forward: k[0] = f(t, y) on entry (FSAL); on return k[1..6] hold the other stages, y1 the 5th-order solution and
@@ -909,6 +950,15 @@ int gode_gat_ode_rk4_forward_save(const gode_gat_odefunc_t* f, const float* y0, 
 int gode_gat_ode_rk4_backprop(const gode_gat_odefunc_t* f, const float* save, float* a, float* theta,
                               float* const* ybar /* 4 */, float* k_scratch, float* parts, const gode_gat_workspace_t* ws,
                               float t0, float t1, int32_t n_steps, int32_t step_begin, int32_t step_end, void* stream);
+/* The rk4 pair for any fixed-grid method (GODE_RK_*; GODE_RK_RK4_38 calls it): records of (S + 1) n x d floats, ybar and
+ * the slots of `parts` counted per stage (S of each), one gode_gat_small_close_stages_f32 launch per swept step.
+ * Validation: null pointers, a method outside the list (GODE_E_SHAPE), then the rk4 pair's checks in their order. */
+int gode_gat_ode_fixed_forward_save(int32_t method, const gode_gat_odefunc_t* f, const float* y0, float* y_end, float* save,
+                                    const gode_gat_workspace_t* ws, float t0, float t1, int32_t n_steps,
+                                    int32_t step_begin, int32_t step_end, void* stream);
+int gode_gat_ode_fixed_backprop(int32_t method, const gode_gat_odefunc_t* f, const float* save, float* a, float* theta,
+                                float* const* ybar /* S */, float* k_scratch, float* parts, const gode_gat_workspace_t* ws,
+                                float t0, float t1, int32_t n_steps, int32_t step_begin, int32_t step_end, void* stream);
 int gode_gat_ode_dopri5_step_backprop(const gode_gat_odefunc_t* f, const float* y, float* const* k /* 7 */, const float* g,
                                       const float* kbar7 /* nullable */, double wy, const double* wk /* host, 7 */,
                                       double t, double h, int32_t first, float* const* ybar /* 7 */, float* ybar_n,
