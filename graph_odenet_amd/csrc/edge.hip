@@ -74,16 +74,26 @@ __global__ __launch_bounds__(256) void final_max_kernel(const float* pmax, int n
 
 // ---- the message activation -----------------------------------------------------------------------------------------------
 // y_e = act(z_e) in the forward; the backward needs y (for da) and g * act'(z) (dz, g = val * w * dA).  The aggregation
-// kernels take the activation as a type: ActRelu is the reference's default (GAT/layers.py:16) and the only form the ODE
-// function uses; ActAny is every GODE_GAT_ACT_* behind ONE further instantiation per kernel form, chosen by a switch on a
-// kernel argument (wave-uniform: a scalar branch).  Accurate expf / expm1f / tanhf only.  At z == 0 the derivative is the
-// one torch's autograd gives: 0 for relu, the slope for leaky_relu, alpha for elu.
+// kernels take the activation as a type: ActRelu is the reference's default (GAT/layers.py:16); ActAny is every
+// GODE_GAT_ACT_* behind ONE further instantiation per kernel form, chosen by a switch on a kernel argument (wave-uniform: a
+// scalar branch).  Accurate expf / expm1f / tanhf only.  At z == 0 the derivative is the one torch's autograd gives: 0 for
+// relu, the slope for leaky_relu, alpha for elu.
+// The ODE function is relu(layer(.)) (GAT/models.py:178).  Under relu messages that outer relu is the identity on a
+// weighted mean of relu's and ActRelu stores the mean as it is.  Under a signed activation the forward kernels apply it
+// where they store `out` (ActAny::post, wave-uniform as well: the gode_gat_agg_ode_* entry points set it).  The backward
+// needs no further arithmetic for it: it reads `out` as the mask of the combined cotangent (ov > 0) and as the mean in
+// dot += g * ov, and where the mask is open relu(m) = m while where it is closed g = 0 - the stored relu(m) gives exactly
+// the numbers the stored m would.
 struct ActRelu {
+    static constexpr int post = 0;
+    __device__ __forceinline__ float out(float m) const { return m; }
     __device__ __forceinline__ float f(float z) const { return fmaxf(z, 0.f); }
     __device__ __forceinline__ float d(float z, float, float g) const { return z > 0.f ? g : 0.f; }
 };
 struct ActAny {
     int code; float p;                  // GODE_GAT_ACT_*; slope of leaky_relu / alpha of elu
+    int post;                           // != 0: out = relu(mean) (the ODE function's outer relu)
+    __device__ __forceinline__ float out(float m) const { return (post && m < 0.f) ? 0.f : m; }
     __device__ __forceinline__ float f(float z) const {
         switch (code) {
         case GODE_GAT_ACT_IDENTITY: return z;
@@ -151,7 +161,7 @@ __global__ __launch_bounds__(256) void gat_agg_fwd_kernel(const int* __restrict_
 #pragma unroll
     for (int q = 0; q < MAXC; ++q) {
         const int c = lane + q * G;
-        if (c < o) out[(int64_t)v * o + c] = acc[q] / den;
+        if (c < o) out[(int64_t)v * o + c] = act.out(acc[q] / den);
     }
 }
 
@@ -259,7 +269,7 @@ __global__ __launch_bounds__(256) void gat_agg_fwd_wave_kernel(const int* __rest
 #pragma unroll
         for (int q = 0; q < MAXC; ++q) {
             const int c = lane + q * G;
-            if (c < o) out[(int64_t)v * o + c] = acc[q] / den;
+            if (c < o) out[(int64_t)v * o + c] = act.out(acc[q] / den);
         }
     }
 }
@@ -395,7 +405,8 @@ __global__ __launch_bounds__(256) void gat_agg_fwd_pf_kernel(const int* __restri
     }
     const float den = s + eps;
     if (gl == 0) s_out[v] = den;
-    if (sg == 0) *reinterpret_cast<float4*>(out + (int64_t)v * O + 4 * q) = make_float4(acc.x / den, acc.y / den, acc.z / den, acc.w / den);
+    if (sg == 0) *reinterpret_cast<float4*>(out + (int64_t)v * O + 4 * q) =
+        make_float4(act.out(acc.x / den), act.out(acc.y / den), act.out(acc.z / den), act.out(acc.w / den));
 }
 
 template <int LPR, int GW, class ACT>
@@ -581,7 +592,8 @@ __global__ __launch_bounds__(256) void gat_agg_fwd_rec_kernel(const int4* __rest
     if (slot < 0) {
         const float den = s + eps;
         if (lane == 0) den_out[row] = den;
-        *reinterpret_cast<float4*>(out + (int64_t)row * O + lane * 4) = make_float4(acc.x / den, acc.y / den, acc.z / den, acc.w / den);
+        *reinterpret_cast<float4*>(out + (int64_t)row * O + lane * 4) =
+            make_float4(act.out(acc.x / den), act.out(acc.y / den), act.out(acc.z / den), act.out(acc.w / den));
     } else {
         float* p = partial + (int64_t)slot * (O + 4);
         *reinterpret_cast<float4*>(p + lane * 4) = acc;
@@ -592,7 +604,8 @@ __global__ __launch_bounds__(256) void gat_agg_fwd_rec_kernel(const int4* __rest
 template <int LPR>
 __global__ __launch_bounds__(256) void gat_agg_fwd_finish_kernel(const int4* __restrict__ long_rows, int n_long,
                                                                  const float* __restrict__ partial, float eps,
-                                                                 float* __restrict__ out, float* __restrict__ den_out) {
+                                                                 float* __restrict__ out, float* __restrict__ den_out,
+                                                                 int post /* ActAny::post: split rows close here */) {
     constexpr int O = LPR * 4;
     const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int gid = (int)(tid / LPR);
@@ -609,7 +622,9 @@ __global__ __launch_bounds__(256) void gat_agg_fwd_finish_kernel(const int4* __r
     }
     const float den = s + eps;
     if (lane == 0) den_out[lr.x] = den;
-    *reinterpret_cast<float4*>(out + (int64_t)lr.x * O + lane * 4) = make_float4(acc.x / den, acc.y / den, acc.z / den, acc.w / den);
+    float4 r = make_float4(acc.x / den, acc.y / den, acc.z / den, acc.w / den);
+    if (post) { r.x = r.x < 0.f ? 0.f : r.x; r.y = r.y < 0.f ? 0.f : r.y; r.z = r.z < 0.f ? 0.f : r.z; r.w = r.w < 0.f ? 0.f : r.w; }
+    *reinterpret_cast<float4*>(out + (int64_t)lr.x * O + lane * 4) = r;
 }
 
 // Backward over records.  Besides dz[k,:] and da[k] it accumulates the target-side sums dpt[v,:] = sum_k dz[k,:]
@@ -1428,7 +1443,8 @@ int agg_fwd_launch(int rt, const gode_graph_t* mt, const int32_t* src, const int
                                (int)mt->n_items, src, mt->val, pv, bf, a, amax, eps, out, w_out, den_out, mt->partial, act); \
             if (mt->n_long > 0)                                                                                       \
                 hipLaunchKernelGGL(gat_agg_fwd_finish_kernel<L>, dim3((unsigned)fblocks), dim3(256), 0, s,            \
-                                   (const int4*)mt->long_rows, (int)mt->n_long, (const float*)mt->partial, eps, out, den_out); \
+                                   (const int4*)mt->long_rows, (int)mt->n_long, (const float*)mt->partial, eps, out, den_out, \
+                                   (int)act.post);                                                                    \
         } while (0)
         switch (lpr) { case 4: GODE_REC(4); break; case 8: GODE_REC(8); break; case 16: GODE_REC(16); break;
                        case 32: GODE_REC(32); break; case 64: GODE_REC(64); break; default: return GODE_E_UNSUPPORTED; }
@@ -1444,7 +1460,8 @@ int agg_fwd_launch(int rt, const gode_graph_t* mt, const int32_t* src, const int
 int act_check(int32_t act, float act_param, const gode_lincomb_t* cot) {
     if (act < GODE_GAT_ACT_RELU || act > GODE_GAT_ACT_SIGMOID) return GODE_E_SHAPE;
     if ((act == GODE_GAT_ACT_LEAKY_RELU || act == GODE_GAT_ACT_ELU) && !std::isfinite(act_param)) return GODE_E_SHAPE;
-    if (act != GODE_GAT_ACT_RELU && cot && cot->n > 0) return GODE_E_UNSUPPORTED;   // the masked cotangent is the ODE function's: relu only
+    // the masked cotangent is the ODE function's (gode_gat_agg_ode_*): the plain layer's `out` is not behind a relu
+    if (act != GODE_GAT_ACT_RELU && cot && cot->n > 0) return GODE_E_UNSUPPORTED;
     return 0;
 }
 }  // namespace
@@ -1476,7 +1493,7 @@ extern "C" int gode_gat_agg_act_f32_fwd(const gode_graph_t* mt, const int32_t* s
     if (act == GODE_GAT_ACT_RELU) return gode_gat_agg_f32_fwd(mt, src, tgt, proj, o, bf, a, amax, eps, out, w_out, den_out, stream);
     const int rt = gode_gat_agg_f32_fwd_route(mt, src, tgt, proj, o, bf, a, amax, eps, out, w_out, den_out, stream);
     if (rt <= 0) return rt;
-    return agg_fwd_launch(rt, mt, src, tgt, proj, o, bf, a, amax, eps, out, w_out, den_out, stream, ActAny{act, act_param});
+    return agg_fwd_launch(rt, mt, src, tgt, proj, o, bf, a, amax, eps, out, w_out, den_out, stream, ActAny{act, act_param, 0});
 }
 
 extern "C" int gode_gat_agg_f32_bwd_route(const gode_graph_t* mt, const int32_t* src, const int32_t* tgt,
@@ -1579,7 +1596,57 @@ extern "C" int gode_gat_agg_act_f32_bwd(const gode_graph_t* mt, const int32_t* s
                                               dat, ld_dat, did_target_sums, stream);
     if (rt <= 0) return rt;
     return agg_bwd_launch(rt, mt, src, tgt, proj, o, bf, w, den, out, dout, cot, cot_scale, dz, da, dpt, ld_dpt, dat, ld_dat,
-                          did_target_sums, stream, ActAny{act, act_param});
+                          did_target_sums, stream, ActAny{act, act_param, 0});
+}
+
+// ---- the ODE function's aggregation: message activation inside, relu outside ----------------------------------------------
+// out = relu(m), m the layer's aggregate under `act` (ActAny::post).  Routes, validation order and - with GODE_GAT_ACT_RELU -
+// the kernels are those of the entry points above; a cot with terms is taken under every activation (masked by out > 0).
+extern "C" int gode_gat_agg_ode_f32_fwd_route(const gode_graph_t* mt, const int32_t* src, const int32_t* tgt,
+                                              const gode_gat_proj_t* proj, int64_t o, const float* bf, const float* a,
+                                              const float* amax, float eps, float* out, float* w_out, float* den_out,
+                                              int32_t act, float act_param, void* stream) {
+    const int rc = act_check(act, act_param, nullptr); if (rc) return rc;
+    return gode_gat_agg_f32_fwd_route(mt, src, tgt, proj, o, bf, a, amax, eps, out, w_out, den_out, stream);
+}
+
+extern "C" int gode_gat_agg_ode_f32_fwd(const gode_graph_t* mt, const int32_t* src, const int32_t* tgt,
+                                        const gode_gat_proj_t* proj, int64_t o, const float* bf, const float* a,
+                                        const float* amax, float eps, float* out, float* w_out, float* den_out,
+                                        int32_t act, float act_param, void* stream) {
+    const int rc = act_check(act, act_param, nullptr); if (rc) return rc;
+    if (act == GODE_GAT_ACT_RELU) return gode_gat_agg_f32_fwd(mt, src, tgt, proj, o, bf, a, amax, eps, out, w_out, den_out, stream);
+    const int rt = gode_gat_agg_f32_fwd_route(mt, src, tgt, proj, o, bf, a, amax, eps, out, w_out, den_out, stream);
+    if (rt <= 0) return rt;
+    return agg_fwd_launch(rt, mt, src, tgt, proj, o, bf, a, amax, eps, out, w_out, den_out, stream, ActAny{act, act_param, 1});
+}
+
+extern "C" int gode_gat_agg_ode_f32_bwd_route(const gode_graph_t* mt, const int32_t* src, const int32_t* tgt,
+                                              const gode_gat_proj_t* proj, int64_t o, const float* bf, const float* w,
+                                              const float* den, const float* out, const float* dout, const gode_lincomb_t* cot,
+                                              float cot_scale, float* dz, float* da, float* dpt, int64_t ld_dpt, float* dat,
+                                              int64_t ld_dat, int32_t* did_target_sums, int32_t act, float act_param,
+                                              void* stream) {
+    const int rc = act_check(act, act_param, nullptr); if (rc) return rc;
+    return gode_gat_agg_f32_bwd_route(mt, src, tgt, proj, o, bf, w, den, out, dout, cot, cot_scale, dz, da, dpt, ld_dpt, dat,
+                                      ld_dat, did_target_sums, stream);
+}
+
+extern "C" int gode_gat_agg_ode_f32_bwd(const gode_graph_t* mt, const int32_t* src, const int32_t* tgt,
+                                        const gode_gat_proj_t* proj, int64_t o, const float* bf, const float* w,
+                                        const float* den, const float* out, const float* dout, const gode_lincomb_t* cot,
+                                        float cot_scale, float* dz, float* da, float* dpt, int64_t ld_dpt, float* dat,
+                                        int64_t ld_dat, int32_t* did_target_sums, int32_t act, float act_param, void* stream) {
+    const int rc = act_check(act, act_param, nullptr); if (rc) return rc;
+    if (act == GODE_GAT_ACT_RELU)
+        return gode_gat_agg_f32_bwd(mt, src, tgt, proj, o, bf, w, den, out, dout, cot, cot_scale, dz, da, dpt, ld_dpt, dat, ld_dat,
+                                    did_target_sums, stream);
+    if (mt && did_target_sums) *did_target_sums = 0;
+    const int rt = gode_gat_agg_f32_bwd_route(mt, src, tgt, proj, o, bf, w, den, out, dout, cot, cot_scale, dz, da, dpt, ld_dpt,
+                                              dat, ld_dat, did_target_sums, stream);
+    if (rt <= 0) return rt;
+    return agg_bwd_launch(rt, mt, src, tgt, proj, o, bf, w, den, out, dout, cot, cot_scale, dz, da, dpt, ld_dpt, dat, ld_dat,
+                          did_target_sums, stream, ActAny{act, act_param, 1});
 }
 
 extern "C" int64_t gode_gat_maxpath_scratch_bytes(int64_t n_edges) {
@@ -1719,10 +1786,11 @@ extern "C" int gode_gat_logits_heads_raw_f32(const gode_gat_proj_t* proj, const 
     return 0;
 }
 
-extern "C" int gode_gat_agg_heads_f32_fwd(const gode_graph_t* mt, const int32_t* src, const int32_t* tgt,
-                                          const gode_gat_proj_t* proj, int64_t o, const float* bf, const float* a,
-                                          const void* scratch, int64_t n_edges, int64_t heads, float eps, float* out,
-                                          float* w_out, float* den_out, void* stream) {
+namespace {
+template <class ACT>
+int agg_heads_fwd(const gode_graph_t* mt, const int32_t* src, const int32_t* tgt, const gode_gat_proj_t* proj, int64_t o,
+                  const float* bf, const float* a, const void* scratch, int64_t n_edges, int64_t heads, float eps, float* out,
+                  float* w_out, float* den_out, void* stream, ACT act) {
     if (!mt || !proj || !scratch) return GODE_E_NULLPTR;
     const int64_t n_rows = mt->n_rows;
     if (n_rows < 0 || o <= 0 || heads < 1 || n_edges < 0) return GODE_E_SHAPE;
@@ -1736,7 +1804,27 @@ extern "C" int gode_gat_agg_heads_f32_fwd(const gode_graph_t* mt, const int32_t*
     HeadMax hm;
     hm.pmax = (const float*)scratch + 2 * (int64_t)kHeadBlocks * heads; hm.n_part = n_edges > 0 ? head_blocks(n_edges) : 0; hm.H = (int)heads;
     return launch_agg_fwd(mt->rowptr, mt->col, mt->val, src, tgt, pv, o, bf, a, nullptr, eps, n_rows, out, w_out, den_out,
-                          (hipStream_t)stream, agg_fwd_csr_route(pv, o, n_rows, out, bf), ActRelu{}, hm);
+                          (hipStream_t)stream, agg_fwd_csr_route(pv, o, n_rows, out, bf), act, hm);
+}
+}  // namespace
+
+extern "C" int gode_gat_agg_heads_f32_fwd(const gode_graph_t* mt, const int32_t* src, const int32_t* tgt,
+                                          const gode_gat_proj_t* proj, int64_t o, const float* bf, const float* a,
+                                          const void* scratch, int64_t n_edges, int64_t heads, float eps, float* out,
+                                          float* w_out, float* den_out, void* stream) {
+    return agg_heads_fwd(mt, src, tgt, proj, o, bf, a, scratch, n_edges, heads, eps, out, w_out, den_out, stream, ActRelu{});
+}
+
+// the ODE function's form: message activation inside, relu outside (GODE_GAT_ACT_RELU: the entry point above)
+extern "C" int gode_gat_agg_heads_ode_f32_fwd(const gode_graph_t* mt, const int32_t* src, const int32_t* tgt,
+                                              const gode_gat_proj_t* proj, int64_t o, const float* bf, const float* a,
+                                              const void* scratch, int64_t n_edges, int64_t heads, float eps, float* out,
+                                              float* w_out, float* den_out, int32_t act, float act_param, void* stream) {
+    const int rc = act_check(act, act_param, nullptr); if (rc) return rc;
+    if (act == GODE_GAT_ACT_RELU)
+        return agg_heads_fwd(mt, src, tgt, proj, o, bf, a, scratch, n_edges, heads, eps, out, w_out, den_out, stream, ActRelu{});
+    return agg_heads_fwd(mt, src, tgt, proj, o, bf, a, scratch, n_edges, heads, eps, out, w_out, den_out, stream,
+                         ActAny{act, act_param, 1});
 }
 
 // the first half only: per-block sums of da and arg-max candidates stay in `scratch`; gode_gat_dense_vjp_small_f32 closes the

@@ -24,7 +24,7 @@ from torch.nn.modules.module import Module
 
 from . import ops
 from . import models as _gcn_models
-from .gat_layers import EdgeGraph, GraphConvolution, _kernel_act, edge_graph
+from .gat_layers import EdgeGraph, GraphConvolution, _kernel_act, edge_graph, message_activation
 from .gat_ode import gat_fields
 from .models import _gn
 
@@ -155,14 +155,14 @@ class FixedMultiHeadGraphConvolution(MultiHeadGraphConvolution):
 
 class ODEfunc(nn.Module):
     """relu(gc1([t | norm1(x)])) with an H-head layer: GAT/models.py:161-179 with `heads` reference layers side by
-    side (dim must be a multiple of heads)."""
+    side (dim must be a multiple of heads).  act: the message activation of every head (gc1.act is the one that counts)."""
 
     _gode_counts_nfe = True
 
-    def __init__(self, dim, heads=8):
+    def __init__(self, dim, heads=8, act=F.relu):
         super(ODEfunc, self).__init__()
         self.norm1 = _gn(dim)
-        self.gc1 = FixedMultiHeadGraphConvolution(dim + 1, dim, heads)
+        self.gc1 = FixedMultiHeadGraphConvolution(dim + 1, dim, heads, act=act)
         self.nfe = 0
 
     def set_adj(self, src, tgt, Mtgt):
@@ -182,7 +182,8 @@ class ODEfunc(nn.Module):
 
     def gode_plan_token(self, y0):
         egv = self._egv()
-        return None if egv is None else ("gat-heads", id(egv))
+        # the activation's (code, param) are kernel arguments of a captured solve: a changed gc1.act is another plan
+        return None if egv is None else ("gat-heads", id(egv), message_activation(self.gc1.act))
 
     def gode_fields(self, y0):
         """Hook for graph_odenet_amd.odeint: fused forward / adjoint kernel sequences (gat_ode.py)."""
@@ -194,7 +195,7 @@ class ODEfunc(nn.Module):
         if layer.n_heads == 1:           # the reference's layer: the one-head sequence on the base graph
             hd = layer.heads[0]
             names.update({id(hd.f.weight): "Wf", id(hd.f.bias): "bf", id(hd.w.weight): "ww", id(hd.w.bias): "bw"})
-            return gat_fields(self, hd, egv.base, egv.base.n, names, y0)
+            return gat_fields(self, hd, egv.base, egv.base.n, names, y0, act_layer=layer)
         for h, hd in enumerate(layer.heads):
             names.update({id(hd.f.weight): "Wf%d" % h, id(hd.f.bias): "bf%d" % h, id(hd.w.weight): "ww%d" % h,
                           id(hd.w.bias): "bw%d" % h})

@@ -12,12 +12,13 @@ from .models import ODEBlock, _gn
 
 
 class ODEfunc(nn.Module):
-    """relu(gc1([t | norm1(x)])) with the edge-attention layer (reference: GAT/models.py:161-179)."""
+    """relu(gc1([t | norm1(x)])) with the edge-attention layer (reference: GAT/models.py:161-179).  act: the layer's message
+    activation (the reference's layer default; no parameter of its own, so the state_dict is the reference's)."""
 
-    def __init__(self, dim):
+    def __init__(self, dim, act=F.relu):
         super(ODEfunc, self).__init__()
         self.norm1 = _gn(dim)
-        self.gc1 = FixedGraphConvolution(dim + 1, dim)
+        self.gc1 = FixedGraphConvolution(dim + 1, dim, act=act)
         self.nfe = 0
 
     def set_adj(self, src, tgt, Mtgt):
@@ -32,11 +33,12 @@ class ODEfunc(nn.Module):
         return F.relu(self.gc1(ttx))
 
     def gode_plan_token(self, y0):
-        from .gat_layers import edge_graph
+        from .gat_layers import edge_graph, message_activation
         layer = self.gc1
         if not torch.is_tensor(layer.src) or layer.src.dim() != 1:
             return None
-        return ("gat", id(edge_graph(layer.src, layer.tgt, layer.Mtgt)))
+        # the activation's (code, param) are kernel arguments of a captured solve: a changed gc1.act is another plan
+        return ("gat", id(edge_graph(layer.src, layer.tgt, layer.Mtgt)), message_activation(layer.act))
 
     def gode_fields(self, y0):
         """Hook for graph_odenet_amd.odeint: fused forward / adjoint kernel sequences (gat_ode.py)."""

@@ -10,8 +10,9 @@ MFMA kernels and only the two logit columns take the generic path:
   Pt = [t|xn] Wtgt   (Wtgt = Wf[:, i:]^T, i x o)      At = [t|xn] ww[:, i:]^T     a_e = As[src_e] + At[tgt_e] + bw
 
   forward : 3 x gode_gn_time_gemm_f32 (GroupNorm + time column fused; a multi-term stage input is combined once and
-            written out by the first launch), gode_gat_logits_f32, gode_gat_agg_f32_fwd
-  adjoint : + gode_gat_agg_f32_bwd (stage cotangent combined and relu-masked inside), gode_gat_maxpath_f32,
+            written out by the first launch), gode_gat_logits_f32, gode_gat_agg_f32_fwd (a message activation other than
+            relu: gode_gat_agg_ode_f32_fwd, which applies the function's outer relu as well)
+  adjoint : + gode_gat_agg_f32_bwd / gode_gat_agg_ode_f32_bwd (stage cotangent combined and relu-masked inside), gode_gat_maxpath_f32,
             gode_gat_scatter_f32 (all four incidence sums in one launch), 3 x gode_gn_time_gemm_bwd_f32 (accumulating
             into k_a), 3 x gode_wgrad_f32 + reductions, gode_time_row_fixup_f32, column sums for the biases.
 
@@ -33,9 +34,9 @@ None and odeint re-runs each interval as torch ops under autograd.
 import ctypes
 
 import torch
-import torch.nn.functional as F
 
 from . import _lib, ops
+from .gat_layers import message_activation
 from .solver import Field, method_code
 
 
@@ -53,7 +54,7 @@ class GatOdeSpec:
     with Wsrc, Wtgt (d+1) x d (head h in columns h*o..), Wlog (d+1) x 2H, bf d, bw H.  eg is the graph the kernels see
     (the H-fold graph with H > 1 heads); layer is the reference's layer, or a MultiHeadGraphConvolution."""
 
-    def __init__(self, eg, n, layer, norm):
+    def __init__(self, eg, n, layer, norm, act_layer=None):
         self.eg, self.n, self.layer, self.norm = eg, n, layer, norm
         self.heads = H = getattr(layer, "n_heads", 1)
         self.d, self.i = d, i = layer.out_features, layer.in_features
@@ -61,6 +62,7 @@ class GatOdeSpec:
             raise ValueError("GatOdeSpec: the ODE layer maps d+1 -> d features")
         self.o = d // H
         self.groups, self.eps_gn, self.eps = int(norm.num_groups), float(norm.eps), float(layer.eps)
+        self.act = message_activation(layer.act if act_layer is None else act_layer.act)       # (code, param); None: no kernel form
         f = dict(dtype=torch.float32, device=norm.weight.device)
         self.Wsrc, self.Wtgt, self.Wlog = torch.empty(i, d, **f), torch.empty(i, d, **f), torch.empty(i, 2 * H, **f)
         self.pad_logits = n >= PAD_LOGITS_MIN_ROWS and d in (16, 32, 64, 128) and 4 < 2 * H <= d
@@ -241,6 +243,7 @@ class GatOdeField(Field):
         fs.Wsrc, fs.Wtgt, fs.Wlog = s.Wsrc.data_ptr(), s.Wtgt.data_ptr(), s.Wlog.data_ptr()
         fs.bf, fs.bw, fs.gamma, fs.beta = s.bf.data_ptr(), s.bw.data_ptr(), s.gamma.data_ptr(), s.beta.data_ptr()
         fs.Wpacked = s.Wpacked.data_ptr() if s.Wpacked is not None else None
+        fs.act, fs.act_param = int(s.act[0]), float(s.act[1])
         ws = _lib.GatWorkspace()
         for k in ("X", "Ps", "Pt", "A2", "a", "wgt", "den"):
             setattr(ws, k, p(getattr(w, k)))
@@ -364,17 +367,28 @@ class GatOdeField(Field):
     def _forward(self, t, y_terms, out):
         s, w, eg = self.s, self.w, self.s.eg
         terms = self._project(t, y_terms)
+        # The outer relu of ODEfunc is the identity on a weighted mean of relu's: relu messages run the relu entry points.
+        # Under any other message activation the aggregation applies it where it stores `out` (the gode_gat_agg_ode_* forms;
+        # csrc/gat_driver.hip: eval_forward branches the same way).
+        act, ode = self._kernel_act()
         if s.heads == 1:
             ops.gat_logits(w.proj, s.bw, eg.src, eg.tgt, w.a, w.amax)
-            ops.gat_agg_fwd(eg, w.proj, s.d, s.bf, w.a, w.amax, s.eps, out, w.wgt, w.den)
+            ops.gat_agg_fwd(eg, w.proj, s.d, s.bf, w.a, w.amax, s.eps, out, w.wgt, w.den, act=act, ode=ode)
         elif self.raw_logits():
             ops.gat_logits_heads_raw(w.proj, eg.src, eg.tgt, s.heads, w.a, w.heads_scratch, bw=s.bw)
             ops.gat_agg_heads_fwd(eg, w.proj, s.o, w.bf0, w.a, w.heads_scratch, s.heads, s.eps, out.view(s.n * s.heads, s.o),
-                                  w.wgt, w.den)
+                                  w.wgt, w.den, act=act)
         else:
             ops.gat_logits_heads(w.proj, eg.src, eg.tgt, s.heads, w.a, bw=s.bw)
-            ops.gat_agg_fwd(eg, w.proj, s.o, w.bf0, w.a, w.zero, s.eps, out.view(s.n * s.heads, s.o), w.wgt, w.den)
-        return terms                 # the outer relu of ODEfunc is the identity on a weighted mean of relu's
+            ops.gat_agg_fwd(eg, w.proj, s.o, w.bf0, w.a, w.zero, s.eps, out.view(s.n * s.heads, s.o), w.wgt, w.den, act=act,
+                            ode=ode)
+        return terms
+
+    def _kernel_act(self):
+        """(act, ode) of the ops wrappers: (None, False) - the relu entry points - under relu messages."""
+        if self.s.act[0] == ops.GAT_ACT_RELU:
+            return None, False
+        return self.s.act, True
 
     def eval(self, t, terms, out):
         self._forward(t, terms[0], out[0])
@@ -446,14 +460,15 @@ class GatOdeAdjointField(GatOdeField):
         g = s.views(out[3])
         raw = self.raw_logits()
         # cotangent -a of the VJP, masked by the outer relu, is formed inside the kernel
+        act, ode = self._kernel_act()
         if H == 1:
             ops.gat_vjp(eg, w.proj, o, s.bf, w.a, w.amax, w.wgt, w.den, out[0], w.dz, w.da, w.dPs, w.dPt, w.dA2,
-                        cot_terms=terms[1], cot_scale=-1.0)
+                        cot_terms=terms[1], cot_scale=-1.0, act=act, ode=ode)
         else:
             nv = n * H
             ops.gat_vjp(eg, w.proj, o, w.bf0, w.a, w.zero, w.wgt, w.den, out[0].view(nv, o), w.dz, w.da, w.dPs.view(nv, o),
                         w.dPt.view(nv, o), w.dA2.view(nv, 2), cot_terms=terms[1], cot_scale=-1.0, heads=H,
-                        raw_scratch=w.heads_scratch if raw else None, defer_maxpath=raw)
+                        raw_scratch=w.heads_scratch if raw else None, defer_maxpath=raw, act=act, ode=ode)
         if self.small():
             # launch-bound graphs: k_a and the partials of every parameter gradient in one launch, one more to close (on the
             # raw-logit route the per-head max-path sums are taken off dA2 inside the first)
@@ -514,16 +529,17 @@ class GatOdeAdjointField(GatOdeField):
         ops.time_row_fixup3_([g["Wsrc"][0], g["Wtgt"][0], g["Wlog"][0]], [s.Wsrc[0], s.Wtgt[0], s.Wlog[0]], t, out[2])
 
 
-def gat_fields(odefunc, layer, eg, n, names, y0):
+def gat_fields(odefunc, layer, eg, n, names, y0, act_layer=None):
     """Hook body of gat_models.ODEfunc.gode_fields and gat_heads.ODEfunc.gode_fields, after their own checks of the
     graph: the fused fields of relu(layer([t | odefunc.norm1(x)])) on n nodes, or None.  eg is the graph the kernels see
-    (the H-fold graph with H heads); names maps id(parameter) -> its name in param_grads."""
-    if layer.act is not F.relu or y0.dim() != 2 or n != y0.shape[0]:
+    (the H-fold graph with H heads); names maps id(parameter) -> its name in param_grads.  The message activation is
+    act_layer.act (default: layer.act); one the kernels do not restate (a lambda, a custom module) has no fused field."""
+    if message_activation((layer if act_layer is None else act_layer).act) is None or y0.dim() != 2 or n != y0.shape[0]:
         return None
     plist = [p for p in odefunc.parameters() if p.requires_grad]
     if len(plist) != len(names) or any(id(p) not in names for p in plist):
         return None
-    spec = GatOdeSpec(eg, n, layer, odefunc.norm1)
+    spec = GatOdeSpec(eg, n, layer, odefunc.norm1, act_layer)
     # a one-head and an H-head function on the same edge list keep their own buffers
     key = ("heads", spec.d, y0.device) if spec.heads > 1 else (spec.d, y0.device)
     cache = eg.__dict__.setdefault("_ode_work", {})

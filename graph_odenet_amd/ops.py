@@ -750,24 +750,35 @@ def _act_args(act):
     return int(code), float(param)
 
 
-def gat_agg_fwd(eg, proj, o, bf, a, amax, eps, out, w, den, act=None):
+# ode=True on the aggregation wrappers: the ODE function's form (gode_gat_agg_ode_*) - message activation inside, relu
+# outside, and the masked cotangent (cot_terms) under every activation.  act=None is (GAT_ACT_RELU, 0.0) there, which runs
+# the kernels of the relu entry points.
+def _ode_act(act):
+    return (GAT_ACT_RELU, 0.0) if act is None else act
+
+
+def gat_agg_fwd(eg, proj, o, bf, a, amax, eps, out, w, den, act=None, ode=False):
     lib = _lib.load()
     _need(out, "out"); _need(w, "w"); _need(den, "den"); _need(bf, "bf")
     gs = _edge_csr(eg, o + 4)
     args = (ctypes.byref(gs), ptr(eg.src), ptr(eg.tgt), ctypes.byref(proj), o, ptr(bf), ptr(a), ptr(amax), float(eps), ptr(out),
             ptr(w), ptr(den))
-    if act is None:
+    if ode:
+        check(lib.gode_gat_agg_ode_f32_fwd(*args, *_act_args(_ode_act(act)), stream_ptr()), "gode_gat_agg_ode_f32_fwd")
+    elif act is None:
         check(lib.gode_gat_agg_f32_fwd(*args, stream_ptr()), "gode_gat_agg_f32_fwd")
     else:
         check(lib.gode_gat_agg_act_f32_fwd(*args, *_act_args(act), stream_ptr()), "gode_gat_agg_act_f32_fwd")
 
 
-def gat_agg_fwd_route(eg, proj, o, bf, a, amax, eps, out, w, den, act=None):
+def gat_agg_fwd_route(eg, proj, o, bf, a, amax, eps, out, w, den, act=None, ode=False):
     """The route gat_agg_fwd takes on these arguments (nothing is launched)."""
     lib = _lib.load()
     gs = _edge_csr(eg, o + 4)
     args = (ctypes.byref(gs), ptr(eg.src), ptr(eg.tgt), ctypes.byref(proj), o, ptr(bf), ptr(a), ptr(amax), float(eps), ptr(out),
             ptr(w), ptr(den))
+    if ode:
+        return lib.gode_gat_agg_ode_f32_fwd_route(*args, *_act_args(_ode_act(act)), None)
     if act is None:
         return lib.gode_gat_agg_f32_fwd_route(*args, None)
     return lib.gode_gat_agg_act_f32_fwd_route(*args, *_act_args(act), None)
@@ -788,14 +799,17 @@ def _agg_bwd_args(eg, proj, o, bf, w, den, out, dz, da, dPt, dA2, dout, cot_term
             ctypes.byref(did)), (gs, lc)
 
 
-def _agg_bwd_call(lib, args, act, stream):
-    if act is None:
+def _agg_bwd_call(lib, args, act, stream, ode=False):
+    if ode:
+        check(lib.gode_gat_agg_ode_f32_bwd(*args, *_act_args(_ode_act(act)), stream), "gode_gat_agg_ode_f32_bwd")
+    elif act is None:
         check(lib.gode_gat_agg_f32_bwd(*args, stream), "gode_gat_agg_f32_bwd")
     else:
         check(lib.gode_gat_agg_act_f32_bwd(*args, *_act_args(act), stream), "gode_gat_agg_act_f32_bwd")
 
 
-def gat_agg_bwd(eg, proj, o, bf, w, den, out, dz, da, dPt=None, dA2=None, dout=None, cot_terms=None, cot_scale=1.0, act=None):
+def gat_agg_bwd(eg, proj, o, bf, w, den, out, dz, da, dPt=None, dA2=None, dout=None, cot_terms=None, cot_scale=1.0, act=None,
+                ode=False):
     """The aggregation's backward alone (first piece of gat_vjp): fills dz[E, o] and da[E] WITHOUT the path through the
     maximum.  Returns True when the record route also formed the target-side sums dPt and dA2[:, 1]."""
     lib = _lib.load()
@@ -803,18 +817,20 @@ def gat_agg_bwd(eg, proj, o, bf, w, den, out, dz, da, dPt=None, dA2=None, dout=N
         _need(t, nm)
     did = ctypes.c_int32(0)
     args, keep = _agg_bwd_args(eg, proj, o, bf, w, den, out, dz, da, dPt, dA2, dout, cot_terms, cot_scale, did)
-    _agg_bwd_call(lib, args, act, stream_ptr())
+    _agg_bwd_call(lib, args, act, stream_ptr(), ode)
     del keep
     return bool(did.value)
 
 
 def gat_agg_bwd_route(eg, proj, o, bf, w, den, out, dz, da, dPt=None, dA2=None, dout=None, cot_terms=None, cot_scale=1.0,
-                      act=None):
+                      act=None, ode=False):
     """The route gat_agg_bwd (and gat_vjp) takes on these arguments (nothing is launched)."""
     lib = _lib.load()
     did = ctypes.c_int32(0)
     args, keep = _agg_bwd_args(eg, proj, o, bf, w, den, out, dz, da, dPt, dA2, dout, cot_terms, cot_scale, did)
-    if act is None:
+    if ode:
+        rt = lib.gode_gat_agg_ode_f32_bwd_route(*args, *_act_args(_ode_act(act)), None)
+    elif act is None:
         rt = lib.gode_gat_agg_f32_bwd_route(*args, None)
     else:
         rt = lib.gode_gat_agg_act_f32_bwd_route(*args, *_act_args(act), None)
@@ -846,31 +862,35 @@ def gat_logits_heads_raw(proj, src, tgt, heads, a, scratch, bw=None):
                                             stream_ptr()), "gode_gat_logits_heads_raw_f32")
 
 
-def gat_agg_heads_fwd(eg, proj, o, bf, a, scratch, heads, eps, out, w, den):
+def gat_agg_heads_fwd(eg, proj, o, bf, a, scratch, heads, eps, out, w, den, act=None):
     """gat_agg_fwd on the H-fold graph with every row shifted by its head's maximum (reduced in the kernel from the partial
-    maxima gat_logits_heads_raw left in `scratch`)."""
+    maxima gat_logits_heads_raw left in `scratch`).  act (code, param): the ODE function's form, as gat_agg_fwd(ode=True)."""
     lib = _lib.load()
     _need(out, "out"); _need(w, "w"); _need(den, "den"); _need(bf, "bf"); _need(scratch, "scratch", torch.uint8)
     gs = _edge_csr(eg, o + 4)
-    check(lib.gode_gat_agg_heads_f32_fwd(ctypes.byref(gs), ptr(eg.src), ptr(eg.tgt), ctypes.byref(proj), o, ptr(bf), ptr(a),
-                                         ptr(scratch), eg.E, int(heads), float(eps), ptr(out), ptr(w), ptr(den), stream_ptr()),
-          "gode_gat_agg_heads_f32_fwd")
+    args = (ctypes.byref(gs), ptr(eg.src), ptr(eg.tgt), ctypes.byref(proj), o, ptr(bf), ptr(a), ptr(scratch), eg.E, int(heads),
+            float(eps), ptr(out), ptr(w), ptr(den))
+    if act is None:
+        check(lib.gode_gat_agg_heads_f32_fwd(*args, stream_ptr()), "gode_gat_agg_heads_f32_fwd")
+    else:
+        check(lib.gode_gat_agg_heads_ode_f32_fwd(*args, *_act_args(act), stream_ptr()), "gode_gat_agg_heads_ode_f32_fwd")
 
 
 def gat_vjp(eg, proj, o, bf, a, amax, w, den, out, dz, da, dPs, dPt, dA2, dout=None, cot_terms=None, cot_scale=1.0,
-            heads=1, raw_scratch=None, defer_maxpath=False, act=None):
+            heads=1, raw_scratch=None, defer_maxpath=False, act=None, ode=False):
     """Vector-Jacobian product of the edge-attention aggregation w.r.t. the projections: fills dz[E, o], da[E] (with the
     path through the global maximum folded in), dPs, dPt (N x o) and dA2 (N x 2).  The cotangent is `dout`, or
     cot_scale * (sum cot_terms) masked by out > 0.  heads > 1: `eg` is the H-fold graph, `a` holds logits shifted
     per head and the path through the maximum is applied per head.  act: the message activation (None: relu); only
-    the aggregation's backward depends on it."""
+    the aggregation's backward depends on it.  ode=True: `out` is the ODE function's relu(aggregate) and cot_terms are
+    taken under every activation."""
     lib = _lib.load()
     for t, nm in ((out, "out"), (dz, "dz"), (da, "da"), (dout, "dout"), (dPs, "dPs"), (dPt, "dPt"), (dA2, "dA2")):
         _need(t, nm)
     did = ctypes.c_int32(0)
     args, keep = _agg_bwd_args(eg, proj, o, bf, w, den, out, dz, da, dPt, dA2, dout, cot_terms, cot_scale, did)
     at_ptr = ctypes.c_void_p(dA2.data_ptr() + 4)
-    _agg_bwd_call(lib, args, act, stream_ptr())
+    _agg_bwd_call(lib, args, act, stream_ptr(), ode)
     del keep
     if eg.E > 0 and heads > 1 and raw_scratch is not None and defer_maxpath and not did.value:
         # first half only; gat_dense_vjp_small(..., maxfix=(raw_scratch, eg.src, eg.tgt)) closes the step

@@ -64,6 +64,8 @@ def build_parser():
     p.add_argument('--heads', type=int, default=1,
                    help="gat variant: H reference attention heads side by side in every layer whose width H divides "
                         "(gat_heads.py; --hidden must be a multiple of H)")
+    p.add_argument('--act', choices=sorted(ODE_ACTS), default="relu",
+                   help="gat variant: message activation of the ODE function's attention layer (relu: the reference)")
     p.add_argument('--adjoint', type=int, choices=[0, 1], default=1,
                    help="1: every ODE block trains through odeint_adjoint (the reference); 0: through odeint, "
                         "differentiated by backprop through the solve (rk4 or dopri5)")
@@ -71,6 +73,21 @@ def build_parser():
                    help="gcn: models over a normalised adjacency (GCN/train_res.py); gat: edge attention over "
                         "(src, tgt, Mtgt) (GAT/train_res.py)")
     return p
+
+
+# --act: message activations the fused GAT ODE function restates (gat_layers.message_activation)
+ODE_ACTS = {"relu": F.relu, "elu": F.elu, "leaky_relu": F.leaky_relu, "tanh": torch.tanh, "sigmoid": torch.sigmoid,
+            "identity": torch.nn.Identity()}
+
+
+def set_ode_act(model, act):
+    """Set the message activation of the attention layer of every one-layer GAT ODE function (ODEfunc.gc1) of `model`."""
+    from . import gat_heads, gat_models
+    for m in model.modules():
+        if isinstance(m, (gat_models.ODEfunc, gat_heads.ODEfunc)):
+            m.gc1.act = act
+            for hd in getattr(m.gc1, "heads", ()):
+                hd.act = act
 
 
 class Trainer:
@@ -92,6 +109,11 @@ class Trainer:
             from . import gat_heads
             table = _model_dict(gat_heads.zoo(a.heads))
         model = table[a.model](**kw).to(self.device)
+        act = getattr(a, "act", "relu")
+        if act != "relu":
+            if a.variant != "gat":
+                raise SystemExit("--act applies to --variant gat")
+            set_ode_act(model, ODE_ACTS[act])
         for m in model.modules():
             if isinstance(m, models.ODEBlock):
                 m.adjoint = bool(getattr(a, "adjoint", 1))

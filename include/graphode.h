@@ -472,7 +472,7 @@ int gode_gat_agg_f32_bwd_route(const gode_graph_t* mt, const int32_t* src, const
  * elu.  Arguments, validation codes (in the same order) and routes are those of the entry points above: the dispatch does not
  * depend on act, and GODE_GAT_ACT_RELU runs the very kernels of the entry points above.  Checked before anything else:
  * act outside the list below, or a non-finite act_param for leaky_relu / elu: GODE_E_SHAPE; another activation than relu
- * with a cot that has terms (the masked cotangent belongs to the ODE function, which is relu only): GODE_E_UNSUPPORTED. */
+ * with a cot that has terms (the masked cotangent belongs to the ODE function: gode_gat_agg_ode_* below): GODE_E_UNSUPPORTED. */
 #define GODE_GAT_ACT_RELU 0
 #define GODE_GAT_ACT_IDENTITY 1
 #define GODE_GAT_ACT_LEAKY_RELU 2
@@ -492,6 +492,29 @@ int gode_gat_agg_act_f32_bwd(const gode_graph_t* mt, const int32_t* src, const i
                              float* dz, float* da, float* dpt, int64_t ld_dpt, float* dat, int64_t ld_dat,
                              int32_t* did_target_sums, int32_t act, float act_param, void* stream);
 int gode_gat_agg_act_f32_bwd_route(const gode_graph_t* mt, const int32_t* src, const int32_t* tgt,
+                                   const gode_gat_proj_t* proj, int64_t o, const float* bf, const float* w, const float* den,
+                                   const float* out, const float* dout, const gode_lincomb_t* cot, float cot_scale,
+                                   float* dz, float* da, float* dpt, int64_t ld_dpt, float* dat, int64_t ld_dat,
+                                   int32_t* did_target_sums, int32_t act, float act_param, void* stream);
+/* The ODE function's aggregation (GAT/models.py:178: relu(layer(.))): message activation inside, relu outside -
+ * out = relu(m), m[v] = sum_e val w_e act(z_e) / den_v.  Arguments, validation order (act and act_param first) and routes are
+ * those of gode_gat_agg_act_f32_*; GODE_GAT_ACT_RELU runs the very kernels of gode_gat_agg_f32_* (the outer relu is the
+ * identity there).  The backward takes a cot with terms under EVERY activation: cot_scale * (sum_j cot_j) masked by out > 0.
+ * The stored relu(m) serves it exactly - where the mask is open relu(m) = m, where it is closed the cotangent is 0.  With dout
+ * instead of cot no mask is applied (the caller has applied it). */
+int gode_gat_agg_ode_f32_fwd(const gode_graph_t* mt, const int32_t* src, const int32_t* tgt,
+                             const gode_gat_proj_t* proj, int64_t o, const float* bf, const float* a, const float* amax,
+                             float eps, float* out, float* w_out, float* den_out, int32_t act, float act_param, void* stream);
+int gode_gat_agg_ode_f32_fwd_route(const gode_graph_t* mt, const int32_t* src, const int32_t* tgt,
+                                   const gode_gat_proj_t* proj, int64_t o, const float* bf, const float* a, const float* amax,
+                                   float eps, float* out, float* w_out, float* den_out, int32_t act, float act_param,
+                                   void* stream);
+int gode_gat_agg_ode_f32_bwd(const gode_graph_t* mt, const int32_t* src, const int32_t* tgt,
+                             const gode_gat_proj_t* proj, int64_t o, const float* bf, const float* w, const float* den,
+                             const float* out, const float* dout, const gode_lincomb_t* cot, float cot_scale,
+                             float* dz, float* da, float* dpt, int64_t ld_dpt, float* dat, int64_t ld_dat,
+                             int32_t* did_target_sums, int32_t act, float act_param, void* stream);
+int gode_gat_agg_ode_f32_bwd_route(const gode_graph_t* mt, const int32_t* src, const int32_t* tgt,
                                    const gode_gat_proj_t* proj, int64_t o, const float* bf, const float* w, const float* den,
                                    const float* out, const float* dout, const gode_lincomb_t* cot, float cot_scale,
                                    float* dz, float* da, float* dpt, int64_t ld_dpt, float* dat, int64_t ld_dat,
@@ -529,6 +552,12 @@ int gode_gat_logits_heads_raw_f32(const gode_gat_proj_t* proj, const float* bw, 
 int gode_gat_agg_heads_f32_fwd(const gode_graph_t* mt, const int32_t* src, const int32_t* tgt, const gode_gat_proj_t* proj,
                                int64_t o, const float* bf, const float* a, const void* scratch, int64_t n_edges,
                                int64_t heads, float eps, float* out, float* w_out, float* den_out, void* stream);
+/* agg_heads_fwd as the ODE function's aggregation (gode_gat_agg_ode_f32_fwd: act inside, relu outside; act and act_param are
+ * checked first, then the checks above; GODE_GAT_ACT_RELU is the entry point above) */
+int gode_gat_agg_heads_ode_f32_fwd(const gode_graph_t* mt, const int32_t* src, const int32_t* tgt, const gode_gat_proj_t* proj,
+                                   int64_t o, const float* bf, const float* a, const void* scratch, int64_t n_edges,
+                                   int64_t heads, float eps, float* out, float* w_out, float* den_out, int32_t act,
+                                   float act_param, void* stream);
 int gode_gat_maxpath_heads_raw_f32(const float* a, float* da, int64_t n_edges, int64_t heads, const int32_t* tgt,
                                    float* dat, int64_t ld_dat, void* scratch, void* stream);
 /* the first half of maxpath_heads_raw only (per-block sums and arg-max candidates left in `scratch`): the step is closed by
@@ -823,7 +852,7 @@ int gode_gcn_ode_dopri5_step_backprop(const gode_gcn_odefunc_t* f, const float* 
                                       float* cot_colpart /* nullable */, void* stream);
 
 /* The same for the GAT ODE function  f(t, x) = relu(EdgeAttention([t | GroupNorm(x)]))  (GAT/models.py:172-179 ->
- * GAT/layers.py:95-122), with the two Linear layers packed by role: Wsrc, Wtgt ((d+1) x d: message parts by source /
+ * GAT/layers.py:95-122; the layer's message activation is any GODE_GAT_ACT_*: `act` below), with the two Linear layers packed by role: Wsrc, Wtgt ((d+1) x d: message parts by source /
  * target, time row first) and Wlog ((d+1) x 2: the two logit columns).  Adjoint state: (y, a, a_t, theta) with
  * theta = [Wsrc | Wtgt | Wlog | bf | bw | gamma | beta]  (gode_gat_ode_theta_len floats). */
 typedef struct gode_gat_odefunc {
@@ -840,6 +869,11 @@ typedef struct gode_gat_odefunc {
     int32_t heads;
     /* nullable: gode_gat_small_pack_f32 of (Wsrc, Wtgt, Wlog), refreshed with them - launch-bound graphs only */
     const float* Wpacked;
+    /* the layer's message activation (GODE_GAT_ACT_*; act_param: slope of leaky_relu / alpha of elu).  A zeroed struct is
+     * relu: the launches of the relu entry points.  Any other runs the aggregation through gode_gat_agg_ode_* (message
+     * activation inside, the function's relu outside).  Outside the list, or a non-finite act_param for leaky_relu / elu:
+     * GODE_E_SHAPE from every gode_gat_ode_* entry point - the first check of the struct, before any launch. */
+    int32_t act; float act_param;
 } gode_gat_odefunc_t;
 
 typedef struct gode_gat_workspace {
@@ -930,7 +964,7 @@ int gode_gat_ode_dopri5_step_adjoint(const gode_gat_odefunc_t* f, const float* y
  * GODE_E_UNSUPPORTED, before any launch.  The entry points mirror gode_gcn_ode_rk4_forward_save / _rk4_backprop /
  * _dopri5_step_backprop (records, step ranges, the algebra of the sweeps: see there).  ws as for the adjoint step.
  * The reverse of a stage k_s = f(t_s, Y_s) with cotangent kbar_s: f is evaluated again at Y_s (into k_scratch, n x d, which
- * masks kbar_s: the relu), then the launches of an adjoint stage with cotangent scale +1 - Ybar_s = J_s^T kbar_s into its
+ * masks kbar_s: the function's outer relu, under every message activation), then the launches of an adjoint stage with cotangent scale +1 - Ybar_s = J_s^T kbar_s into its
  * own array and the partials of (df/dtheta)_s^T kbar_s into a slot of `parts` (slots of gode_gat_small_parts(n, d) *
  * gode_gat_small_part_len(d, heads) floats, one after the other); ONE gode_gat_small_close_stages_f32 launch per step adds
  * the swept stages' parameter parts to theta (gode_gat_ode_theta_len_heads floats, incremented).  One stream.
