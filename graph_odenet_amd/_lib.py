@@ -39,6 +39,7 @@ SpmmEpilogue = STRUCTS["gode_spmm_epilogue_t"]
 Graph = STRUCTS["gode_graph_t"]
 GcnOdeFunc = STRUCTS["gode_gcn_odefunc_t"]
 GatProj = STRUCTS["gode_gat_proj_t"]                 # member `as` is `as_` here (Python keyword)
+GatAct = STRUCTS["gode_gat_act_t"]
 Rk4Workspace = STRUCTS["gode_rk4_workspace_t"]
 ReduceSeg = STRUCTS["gode_reduce_seg_t"]
 GatOdeFunc = STRUCTS["gode_gat_odefunc_t"]

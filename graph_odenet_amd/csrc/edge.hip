@@ -1405,12 +1405,33 @@ bool rec_ok(const gode_graph_t* mt, const Proj& pv, int64_t o, const void* p0, c
     const uintptr_t al = (uintptr_t)pv.ps | (uintptr_t)pv.pt | (uintptr_t)p0 | (uintptr_t)p1;
     return !(al & 15);
 }
+
+// The checks of gode_gat_act_t (NULL: zeroed), which come before everything else in every aggregation entry point: no
+// pointer but `cot` (the backward's; its term count is the question) is looked at.
+int act_check(const gode_gat_act_t* act, const gode_lincomb_t* cot) {
+    if (!act) return 0;
+    if (act->act < GODE_GAT_ACT_RELU || act->act > GODE_GAT_ACT_SIGMOID) return GODE_E_SHAPE;
+    if ((act->act == GODE_GAT_ACT_LEAKY_RELU || act->act == GODE_GAT_ACT_ELU) && !std::isfinite(act->act_param)) return GODE_E_SHAPE;
+    // the combined cotangent is masked by out > 0, a relu's mask: `out` must be behind one
+    if (act->act != GODE_GAT_ACT_RELU && !act->outer_relu && cot && cot->n > 0) return GODE_E_UNSUPPORTED;
+    return 0;
+}
+
+// f(ActRelu{}) under relu messages - with or without the outer relu, which is the identity there - and f(ActAny{...}) under
+// every other activation: the dispatch does not depend on the activation, only the instantiation of the route's kernel does
+template <class F>
+int with_act(const gode_gat_act_t* act, F&& f) {
+    if (!act || act->act == GODE_GAT_ACT_RELU) return f(ActRelu{});
+    return f(ActAny{act->act, act->act_param, act->outer_relu != 0});
+}
 }  // namespace
 
 extern "C" int gode_gat_agg_f32_fwd_route(const gode_graph_t* mt, const int32_t* src, const int32_t* tgt,
                                           const gode_gat_proj_t* proj, int64_t o, const float* bf, const float* a,
-                                          const float* amax, float eps, float* out, float* w_out, float* den_out, void* stream) {
+                                          const float* amax, float eps, float* out, float* w_out, float* den_out,
+                                          const gode_gat_act_t* act, void* stream) {
     (void)eps; (void)stream;
+    if (const int rc = act_check(act, nullptr)) return rc;
     if (!mt) return GODE_E_NULLPTR;
     const int64_t n_rows = mt->n_rows;
     if (n_rows < 0 || o <= 0) return GODE_E_SHAPE;
@@ -1454,54 +1475,26 @@ int agg_fwd_launch(int rt, const gode_graph_t* mt, const int32_t* src, const int
     }
     return launch_agg_fwd(mt->rowptr, mt->col, mt->val, src, tgt, pv, o, bf, a, amax, eps, n_rows, out, w_out, den_out, s, rt, act);
 }
-
-// The checks of the gode_gat_agg_act_* entry points that come before everything else: no pointer but `cot` (whose term
-// count is the question) is looked at.
-int act_check(int32_t act, float act_param, const gode_lincomb_t* cot) {
-    if (act < GODE_GAT_ACT_RELU || act > GODE_GAT_ACT_SIGMOID) return GODE_E_SHAPE;
-    if ((act == GODE_GAT_ACT_LEAKY_RELU || act == GODE_GAT_ACT_ELU) && !std::isfinite(act_param)) return GODE_E_SHAPE;
-    // the masked cotangent is the ODE function's (gode_gat_agg_ode_*): the plain layer's `out` is not behind a relu
-    if (act != GODE_GAT_ACT_RELU && cot && cot->n > 0) return GODE_E_UNSUPPORTED;
-    return 0;
-}
 }  // namespace
 
 extern "C" int gode_gat_agg_f32_fwd(const gode_graph_t* mt, const int32_t* src, const int32_t* tgt,
                                     const gode_gat_proj_t* proj, int64_t o, const float* bf, const float* a,
-                                    const float* amax, float eps, float* out, float* w_out, float* den_out, void* stream) {
-    const int rt = gode_gat_agg_f32_fwd_route(mt, src, tgt, proj, o, bf, a, amax, eps, out, w_out, den_out, stream);
+                                    const float* amax, float eps, float* out, float* w_out, float* den_out,
+                                    const gode_gat_act_t* act, void* stream) {
+    const int rt = gode_gat_agg_f32_fwd_route(mt, src, tgt, proj, o, bf, a, amax, eps, out, w_out, den_out, act, stream);
     if (rt <= 0) return rt;
-    return agg_fwd_launch(rt, mt, src, tgt, proj, o, bf, a, amax, eps, out, w_out, den_out, stream, ActRelu{});
-}
-
-// ---- the same aggregation with the message activation as an argument (GODE_GAT_ACT_*) ------------------------------------
-// Dispatch does not depend on the activation: the route is the relu entry point's, and GODE_GAT_ACT_RELU IS the relu
-// entry point (same kernels).  Every other activation runs the ActAny instantiation of the route's kernel.
-extern "C" int gode_gat_agg_act_f32_fwd_route(const gode_graph_t* mt, const int32_t* src, const int32_t* tgt,
-                                              const gode_gat_proj_t* proj, int64_t o, const float* bf, const float* a,
-                                              const float* amax, float eps, float* out, float* w_out, float* den_out,
-                                              int32_t act, float act_param, void* stream) {
-    const int rc = act_check(act, act_param, nullptr); if (rc) return rc;
-    return gode_gat_agg_f32_fwd_route(mt, src, tgt, proj, o, bf, a, amax, eps, out, w_out, den_out, stream);
-}
-
-extern "C" int gode_gat_agg_act_f32_fwd(const gode_graph_t* mt, const int32_t* src, const int32_t* tgt,
-                                        const gode_gat_proj_t* proj, int64_t o, const float* bf, const float* a,
-                                        const float* amax, float eps, float* out, float* w_out, float* den_out,
-                                        int32_t act, float act_param, void* stream) {
-    const int rc = act_check(act, act_param, nullptr); if (rc) return rc;
-    if (act == GODE_GAT_ACT_RELU) return gode_gat_agg_f32_fwd(mt, src, tgt, proj, o, bf, a, amax, eps, out, w_out, den_out, stream);
-    const int rt = gode_gat_agg_f32_fwd_route(mt, src, tgt, proj, o, bf, a, amax, eps, out, w_out, den_out, stream);
-    if (rt <= 0) return rt;
-    return agg_fwd_launch(rt, mt, src, tgt, proj, o, bf, a, amax, eps, out, w_out, den_out, stream, ActAny{act, act_param, 0});
+    return with_act(act, [&](auto m) {
+        return agg_fwd_launch(rt, mt, src, tgt, proj, o, bf, a, amax, eps, out, w_out, den_out, stream, m);
+    });
 }
 
 extern "C" int gode_gat_agg_f32_bwd_route(const gode_graph_t* mt, const int32_t* src, const int32_t* tgt,
                                           const gode_gat_proj_t* proj, int64_t o, const float* bf, const float* w,
                                           const float* den, const float* out, const float* dout, const gode_lincomb_t* cot,
                                           float cot_scale, float* dz, float* da, float* dpt, int64_t ld_dpt, float* dat,
-                                          int64_t ld_dat, int32_t* did_target_sums, void* stream) {
+                                          int64_t ld_dat, int32_t* did_target_sums, const gode_gat_act_t* act, void* stream) {
     (void)cot_scale; (void)stream;
+    if (const int rc = act_check(act, cot)) return rc;
     if (!mt) return GODE_E_NULLPTR;
     const int64_t n_rows = mt->n_rows;
     if (n_rows < 0 || o <= 0) return GODE_E_SHAPE;
@@ -1562,91 +1555,16 @@ extern "C" int gode_gat_agg_f32_bwd(const gode_graph_t* mt, const int32_t* src, 
                                     const gode_gat_proj_t* proj, int64_t o, const float* bf, const float* w,
                                     const float* den, const float* out, const float* dout, const gode_lincomb_t* cot,
                                     float cot_scale, float* dz, float* da, float* dpt, int64_t ld_dpt, float* dat,
-                                    int64_t ld_dat, int32_t* did_target_sums, void* stream) {
+                                    int64_t ld_dat, int32_t* did_target_sums, const gode_gat_act_t* act, void* stream) {
+    if (const int rc = act_check(act, cot)) return rc;          // a call the activation checks refuse writes no flag
     if (mt && did_target_sums) *did_target_sums = 0;
     const int rt = gode_gat_agg_f32_bwd_route(mt, src, tgt, proj, o, bf, w, den, out, dout, cot, cot_scale, dz, da, dpt, ld_dpt,
-                                              dat, ld_dat, did_target_sums, stream);
+                                              dat, ld_dat, did_target_sums, act, stream);
     if (rt <= 0) return rt;
-    return agg_bwd_launch(rt, mt, src, tgt, proj, o, bf, w, den, out, dout, cot, cot_scale, dz, da, dpt, ld_dpt, dat, ld_dat,
-                          did_target_sums, stream, ActRelu{});
-}
-
-extern "C" int gode_gat_agg_act_f32_bwd_route(const gode_graph_t* mt, const int32_t* src, const int32_t* tgt,
-                                              const gode_gat_proj_t* proj, int64_t o, const float* bf, const float* w,
-                                              const float* den, const float* out, const float* dout, const gode_lincomb_t* cot,
-                                              float cot_scale, float* dz, float* da, float* dpt, int64_t ld_dpt, float* dat,
-                                              int64_t ld_dat, int32_t* did_target_sums, int32_t act, float act_param,
-                                              void* stream) {
-    const int rc = act_check(act, act_param, cot); if (rc) return rc;
-    return gode_gat_agg_f32_bwd_route(mt, src, tgt, proj, o, bf, w, den, out, dout, cot, cot_scale, dz, da, dpt, ld_dpt, dat,
-                                      ld_dat, did_target_sums, stream);
-}
-
-extern "C" int gode_gat_agg_act_f32_bwd(const gode_graph_t* mt, const int32_t* src, const int32_t* tgt,
-                                        const gode_gat_proj_t* proj, int64_t o, const float* bf, const float* w,
-                                        const float* den, const float* out, const float* dout, const gode_lincomb_t* cot,
-                                        float cot_scale, float* dz, float* da, float* dpt, int64_t ld_dpt, float* dat,
-                                        int64_t ld_dat, int32_t* did_target_sums, int32_t act, float act_param, void* stream) {
-    const int rc = act_check(act, act_param, cot); if (rc) return rc;
-    if (act == GODE_GAT_ACT_RELU)
-        return gode_gat_agg_f32_bwd(mt, src, tgt, proj, o, bf, w, den, out, dout, cot, cot_scale, dz, da, dpt, ld_dpt, dat, ld_dat,
-                                    did_target_sums, stream);
-    if (mt && did_target_sums) *did_target_sums = 0;
-    const int rt = gode_gat_agg_f32_bwd_route(mt, src, tgt, proj, o, bf, w, den, out, dout, cot, cot_scale, dz, da, dpt, ld_dpt,
-                                              dat, ld_dat, did_target_sums, stream);
-    if (rt <= 0) return rt;
-    return agg_bwd_launch(rt, mt, src, tgt, proj, o, bf, w, den, out, dout, cot, cot_scale, dz, da, dpt, ld_dpt, dat, ld_dat,
-                          did_target_sums, stream, ActAny{act, act_param, 0});
-}
-
-// ---- the ODE function's aggregation: message activation inside, relu outside ----------------------------------------------
-// out = relu(m), m the layer's aggregate under `act` (ActAny::post).  Routes, validation order and - with GODE_GAT_ACT_RELU -
-// the kernels are those of the entry points above; a cot with terms is taken under every activation (masked by out > 0).
-extern "C" int gode_gat_agg_ode_f32_fwd_route(const gode_graph_t* mt, const int32_t* src, const int32_t* tgt,
-                                              const gode_gat_proj_t* proj, int64_t o, const float* bf, const float* a,
-                                              const float* amax, float eps, float* out, float* w_out, float* den_out,
-                                              int32_t act, float act_param, void* stream) {
-    const int rc = act_check(act, act_param, nullptr); if (rc) return rc;
-    return gode_gat_agg_f32_fwd_route(mt, src, tgt, proj, o, bf, a, amax, eps, out, w_out, den_out, stream);
-}
-
-extern "C" int gode_gat_agg_ode_f32_fwd(const gode_graph_t* mt, const int32_t* src, const int32_t* tgt,
-                                        const gode_gat_proj_t* proj, int64_t o, const float* bf, const float* a,
-                                        const float* amax, float eps, float* out, float* w_out, float* den_out,
-                                        int32_t act, float act_param, void* stream) {
-    const int rc = act_check(act, act_param, nullptr); if (rc) return rc;
-    if (act == GODE_GAT_ACT_RELU) return gode_gat_agg_f32_fwd(mt, src, tgt, proj, o, bf, a, amax, eps, out, w_out, den_out, stream);
-    const int rt = gode_gat_agg_f32_fwd_route(mt, src, tgt, proj, o, bf, a, amax, eps, out, w_out, den_out, stream);
-    if (rt <= 0) return rt;
-    return agg_fwd_launch(rt, mt, src, tgt, proj, o, bf, a, amax, eps, out, w_out, den_out, stream, ActAny{act, act_param, 1});
-}
-
-extern "C" int gode_gat_agg_ode_f32_bwd_route(const gode_graph_t* mt, const int32_t* src, const int32_t* tgt,
-                                              const gode_gat_proj_t* proj, int64_t o, const float* bf, const float* w,
-                                              const float* den, const float* out, const float* dout, const gode_lincomb_t* cot,
-                                              float cot_scale, float* dz, float* da, float* dpt, int64_t ld_dpt, float* dat,
-                                              int64_t ld_dat, int32_t* did_target_sums, int32_t act, float act_param,
-                                              void* stream) {
-    const int rc = act_check(act, act_param, nullptr); if (rc) return rc;
-    return gode_gat_agg_f32_bwd_route(mt, src, tgt, proj, o, bf, w, den, out, dout, cot, cot_scale, dz, da, dpt, ld_dpt, dat,
-                                      ld_dat, did_target_sums, stream);
-}
-
-extern "C" int gode_gat_agg_ode_f32_bwd(const gode_graph_t* mt, const int32_t* src, const int32_t* tgt,
-                                        const gode_gat_proj_t* proj, int64_t o, const float* bf, const float* w,
-                                        const float* den, const float* out, const float* dout, const gode_lincomb_t* cot,
-                                        float cot_scale, float* dz, float* da, float* dpt, int64_t ld_dpt, float* dat,
-                                        int64_t ld_dat, int32_t* did_target_sums, int32_t act, float act_param, void* stream) {
-    const int rc = act_check(act, act_param, nullptr); if (rc) return rc;
-    if (act == GODE_GAT_ACT_RELU)
-        return gode_gat_agg_f32_bwd(mt, src, tgt, proj, o, bf, w, den, out, dout, cot, cot_scale, dz, da, dpt, ld_dpt, dat, ld_dat,
-                                    did_target_sums, stream);
-    if (mt && did_target_sums) *did_target_sums = 0;
-    const int rt = gode_gat_agg_f32_bwd_route(mt, src, tgt, proj, o, bf, w, den, out, dout, cot, cot_scale, dz, da, dpt, ld_dpt,
-                                              dat, ld_dat, did_target_sums, stream);
-    if (rt <= 0) return rt;
-    return agg_bwd_launch(rt, mt, src, tgt, proj, o, bf, w, den, out, dout, cot, cot_scale, dz, da, dpt, ld_dpt, dat, ld_dat,
-                          did_target_sums, stream, ActAny{act, act_param, 1});
+    return with_act(act, [&](auto m) {
+        return agg_bwd_launch(rt, mt, src, tgt, proj, o, bf, w, den, out, dout, cot, cot_scale, dz, da, dpt, ld_dpt, dat, ld_dat,
+                              did_target_sums, stream, m);
+    });
 }
 
 extern "C" int64_t gode_gat_maxpath_scratch_bytes(int64_t n_edges) {
@@ -1811,20 +1729,11 @@ int agg_heads_fwd(const gode_graph_t* mt, const int32_t* src, const int32_t* tgt
 extern "C" int gode_gat_agg_heads_f32_fwd(const gode_graph_t* mt, const int32_t* src, const int32_t* tgt,
                                           const gode_gat_proj_t* proj, int64_t o, const float* bf, const float* a,
                                           const void* scratch, int64_t n_edges, int64_t heads, float eps, float* out,
-                                          float* w_out, float* den_out, void* stream) {
-    return agg_heads_fwd(mt, src, tgt, proj, o, bf, a, scratch, n_edges, heads, eps, out, w_out, den_out, stream, ActRelu{});
-}
-
-// the ODE function's form: message activation inside, relu outside (GODE_GAT_ACT_RELU: the entry point above)
-extern "C" int gode_gat_agg_heads_ode_f32_fwd(const gode_graph_t* mt, const int32_t* src, const int32_t* tgt,
-                                              const gode_gat_proj_t* proj, int64_t o, const float* bf, const float* a,
-                                              const void* scratch, int64_t n_edges, int64_t heads, float eps, float* out,
-                                              float* w_out, float* den_out, int32_t act, float act_param, void* stream) {
-    const int rc = act_check(act, act_param, nullptr); if (rc) return rc;
-    if (act == GODE_GAT_ACT_RELU)
-        return agg_heads_fwd(mt, src, tgt, proj, o, bf, a, scratch, n_edges, heads, eps, out, w_out, den_out, stream, ActRelu{});
-    return agg_heads_fwd(mt, src, tgt, proj, o, bf, a, scratch, n_edges, heads, eps, out, w_out, den_out, stream,
-                         ActAny{act, act_param, 1});
+                                          float* w_out, float* den_out, const gode_gat_act_t* act, void* stream) {
+    if (const int rc = act_check(act, nullptr)) return rc;
+    return with_act(act, [&](auto m) {
+        return agg_heads_fwd(mt, src, tgt, proj, o, bf, a, scratch, n_edges, heads, eps, out, w_out, den_out, stream, m);
+    });
 }
 
 // the first half only: per-block sums of da and arg-max candidates stay in `scratch`; gode_gat_dense_vjp_small_f32 closes the

@@ -1,9 +1,8 @@
 // gat_driver.hip — one Dormand-Prince 5(4) step of the GAT ODE function per C-ABI call.
 //
 // f(t, x) = relu(EdgeAttention([t | GroupNorm(x)]))  (reference: GAT/models.py:172-179 -> GAT/layers.py:95-122).
-// The layer's message activation is f->act (GODE_GAT_ACT_*).  relu - a zeroed field - issues the relu entry points of
-// csrc/edge.hip, where the outer relu is the identity; any other goes through gode_gat_agg_ode_* (message activation
-// inside, relu outside) in the same places: eval_forward and stage_vjp are the only functions that look at it.
+// The layer's message activation is f->act (GODE_GAT_ACT_*; zeroed: relu): eval_forward and stage_vjp hand it to the
+// aggregation of csrc/edge.hip as gode_gat_act_t{f->act, f->act_param, 1}; check_common refuses a bad one before any launch.
 // The adaptive controller (step-size choice, accept / reject, interpolation) stays with the caller, as for the GCN
 // function in ode_driver.hip; this file only sequences the launches of six stage evaluations, the solution combine
 // and the error-ratio sums, so that an adaptive step on a citation-size graph is one call instead of ~200.
@@ -77,33 +76,19 @@ int eval_forward(const gode_gat_odefunc_t* f, const gode_gat_workspace_t* w, god
     GODE_TRY(project(f, w, yin, t, stream));
     const gode_gat_proj_t pr = proj_of(f, w);
     const int64_t H = n_heads(f);
-    if (f->act != GODE_GAT_ACT_RELU) {     // the same three branches; the aggregation applies the outer relu itself
-        if (H > 1 && raw_logits(f)) {
-            GODE_TRY(gode_gat_logits_heads_raw_f32(&pr, f->bw, f->src, f->tgt, f->n_edges, H, w->a, w->heads_scratch, stream));
-            return gode_gat_agg_heads_ode_f32_fwd(&f->mt, f->src, f->tgt, &pr, f->d / H, w->zeros, w->a, w->heads_scratch, f->n_edges,
-                                                  H, f->eps, ky, w->wgt, w->den, f->act, f->act_param, stream);
-        }
-        if (H > 1) {
-            GODE_TRY(gode_gat_logits_heads_f32(&pr, f->bw, f->src, f->tgt, f->n_edges, H, w->a, nullptr, w->heads_scratch, stream));
-            return gode_gat_agg_ode_f32_fwd(&f->mt, f->src, f->tgt, &pr, f->d / H, w->zeros, w->a, w->zeros, f->eps, ky, w->wgt,
-                                            w->den, f->act, f->act_param, stream);
-        }
-        GODE_TRY(gode_gat_logits_f32(&pr, f->bw, f->src, f->tgt, f->n_edges, w->a, w->amax, (float*)w->logits_scratch, stream));
-        return gode_gat_agg_ode_f32_fwd(&f->mt, f->src, f->tgt, &pr, f->d, f->bf, w->a, w->amax, f->eps, ky, w->wgt, w->den, f->act,
-                                        f->act_param, stream);
-    }
-    if (H > 1) {     // logits shifted by their head's maximum (so the aggregation runs with amax = 0), biases in Pt
+    const gode_gat_act_t mode = {f->act, f->act_param, 1};     // message activation inside, the function's relu outside
+    if (H > 1) {   // logits shifted by their head's maximum (so the aggregation runs with amax = 0), biases in Pt
         if (raw_logits(f)) {     // launch-bound graphs: no launch that shifts the logits (csrc/edge.hip, HeadMax)
             GODE_TRY(gode_gat_logits_heads_raw_f32(&pr, f->bw, f->src, f->tgt, f->n_edges, H, w->a, w->heads_scratch, stream));
             return gode_gat_agg_heads_f32_fwd(&f->mt, f->src, f->tgt, &pr, f->d / H, w->zeros, w->a, w->heads_scratch, f->n_edges, H,
-                                              f->eps, ky, w->wgt, w->den, stream);
+                                              f->eps, ky, w->wgt, w->den, &mode, stream);
         }
         GODE_TRY(gode_gat_logits_heads_f32(&pr, f->bw, f->src, f->tgt, f->n_edges, H, w->a, nullptr, w->heads_scratch, stream));
         return gode_gat_agg_f32_fwd(&f->mt, f->src, f->tgt, &pr, f->d / H, w->zeros, w->a, w->zeros, f->eps, ky, w->wgt, w->den,
-                                    stream);
+                                    &mode, stream);
     }
     GODE_TRY(gode_gat_logits_f32(&pr, f->bw, f->src, f->tgt, f->n_edges, w->a, w->amax, (float*)w->logits_scratch, stream));
-    return gode_gat_agg_f32_fwd(&f->mt, f->src, f->tgt, &pr, f->d, f->bf, w->a, w->amax, f->eps, ky, w->wgt, w->den, stream);
+    return gode_gat_agg_f32_fwd(&f->mt, f->src, f->tgt, &pr, f->d, f->bf, w->a, w->amax, f->eps, ky, w->wgt, w->den, &mode, stream);
 }
 
 // The reverse of one evaluation k = f(t, sum yin) with cotangent cot_scale * (sum cot), shared by the adjoint step (cot = a,
@@ -118,12 +103,9 @@ int stage_vjp(const gode_gat_odefunc_t* f, const gode_gat_workspace_t* w, gode_l
     GODE_TRY(eval_forward(f, w, yin, t, ky, stream));                  // yin now names the combined input
     const gode_gat_proj_t pr = proj_of(f, w);
     int32_t did = 0;
-    if (f->act != GODE_GAT_ACT_RELU)
-        GODE_TRY(gode_gat_agg_ode_f32_bwd(&f->mt, f->src, f->tgt, &pr, o, H > 1 ? w->zeros : f->bf, w->wgt, w->den, ky, nullptr, &cot,
-                                          cot_scale, w->dz, w->da, w->dPt, o, w->dA2 + 1, 2, &did, f->act, f->act_param, stream));
-    else
-        GODE_TRY(gode_gat_agg_f32_bwd(&f->mt, f->src, f->tgt, &pr, o, H > 1 ? w->zeros : f->bf, w->wgt, w->den, ky, nullptr, &cot,
-                                      cot_scale, w->dz, w->da, w->dPt, o, w->dA2 + 1, 2, &did, stream));
+    const gode_gat_act_t mode = {f->act, f->act_param, 1};
+    GODE_TRY(gode_gat_agg_f32_bwd(&f->mt, f->src, f->tgt, &pr, o, H > 1 ? w->zeros : f->bf, w->wgt, w->den, ky, nullptr, &cot,
+                                  cot_scale, w->dz, w->da, w->dPt, o, w->dA2 + 1, 2, &did, &mode, stream));
     if (f->n_edges > 0) {
         if (H > 1 && raw_logits(f) && !did && part)     // first half; the dense VJP launch below closes the step
             GODE_TRY(gode_gat_maxpath_heads_part_f32(w->a, w->da, f->n_edges, H, f->tgt, w->heads_scratch, stream));

@@ -118,7 +118,7 @@ def message_activation(act):
 
 
 def _kernel_act(layer):
-    """The `act=` of the ops wrappers for the layer's activation - None for relu, which keeps the relu entry points - or
+    """The `act=` of the ops wrappers for the layer's activation - None for relu, which keeps the relu instantiations - or
     False when the kernels do not restate it (the general path)."""
     ma = message_activation(layer.act)
     if ma is None:

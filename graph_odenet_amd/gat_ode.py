@@ -11,8 +11,8 @@ MFMA kernels and only the two logit columns take the generic path:
 
   forward : 3 x gode_gn_time_gemm_f32 (GroupNorm + time column fused; a multi-term stage input is combined once and
             written out by the first launch), gode_gat_logits_f32, gode_gat_agg_f32_fwd (a message activation other than
-            relu: gode_gat_agg_ode_f32_fwd, which applies the function's outer relu as well)
-  adjoint : + gode_gat_agg_f32_bwd / gode_gat_agg_ode_f32_bwd (stage cotangent combined and relu-masked inside), gode_gat_maxpath_f32,
+            relu: its gode_gat_act_t with outer_relu, so that it applies the function's outer relu as well)
+  adjoint : + gode_gat_agg_f32_bwd (stage cotangent combined and relu-masked inside), gode_gat_maxpath_f32,
             gode_gat_scatter_f32 (all four incidence sums in one launch), 3 x gode_gn_time_gemm_bwd_f32 (accumulating
             into k_a), 3 x gode_wgrad_f32 + reductions, gode_time_row_fixup_f32, column sums for the biases.
 
@@ -367,9 +367,9 @@ class GatOdeField(Field):
     def _forward(self, t, y_terms, out):
         s, w, eg = self.s, self.w, self.s.eg
         terms = self._project(t, y_terms)
-        # The outer relu of ODEfunc is the identity on a weighted mean of relu's: relu messages run the relu entry points.
-        # Under any other message activation the aggregation applies it where it stores `out` (the gode_gat_agg_ode_* forms;
-        # csrc/gat_driver.hip: eval_forward branches the same way).
+        # The outer relu of ODEfunc is the identity on a weighted mean of relu's: relu messages pass no gode_gat_act_t.
+        # Under any other message activation the aggregation applies it where it stores `out` (outer_relu; csrc/gat_driver.hip:
+        # eval_forward sets it under every activation, which runs the same kernels).
         act, ode = self._kernel_act()
         if s.heads == 1:
             ops.gat_logits(w.proj, s.bw, eg.src, eg.tgt, w.a, w.amax)
@@ -385,7 +385,7 @@ class GatOdeField(Field):
         return terms
 
     def _kernel_act(self):
-        """(act, ode) of the ops wrappers: (None, False) - the relu entry points - under relu messages."""
+        """(act, ode) of the ops wrappers: (None, False) under relu messages."""
         if self.s.act[0] == ops.GAT_ACT_RELU:
             return None, False
         return self.s.act, True

@@ -739,52 +739,50 @@ def _edge_csr(eg, width):
     return gs
 
 
-# Message activations of the aggregation kernels (graphode.h: GODE_GAT_ACT_*).  `act=` of the wrappers below is None (relu
-# through the relu entry points) or (code, param): param is the slope of leaky_relu / alpha of elu, 0.0 otherwise.
+# Message activations of the aggregation kernels (graphode.h: GODE_GAT_ACT_*).  `act=` of the wrappers below is None (relu)
+# or (code, param): param is the slope of leaky_relu / alpha of elu, 0.0 otherwise.  ode=True is the ODE function's form:
+# message activation inside, relu outside, and the masked cotangent (cot_terms) under every activation.
 GAT_ACT_RELU, GAT_ACT_IDENTITY, GAT_ACT_LEAKY_RELU, GAT_ACT_ELU, GAT_ACT_TANH, GAT_ACT_SIGMOID = (
     _lib.CONSTANTS["GODE_GAT_ACT_" + k] for k in ("RELU", "IDENTITY", "LEAKY_RELU", "ELU", "TANH", "SIGMOID"))
 
 
-def _act_args(act):
-    code, param = act
-    return int(code), float(param)
+def _gat_act(act, ode):
+    """gode_gat_act_t of the wrappers' act= and ode=: None (NULL: relu, no outer relu) or a filled struct, which the caller
+    keeps alive across the call."""
+    if act is None and not ode:
+        return None
+    code, param = (GAT_ACT_RELU, 0.0) if act is None else act
+    return _lib.GatAct(int(code), float(param), int(bool(ode)))
 
 
-# ode=True on the aggregation wrappers: the ODE function's form (gode_gat_agg_ode_*) - message activation inside, relu
-# outside, and the masked cotangent (cot_terms) under every activation.  act=None is (GAT_ACT_RELU, 0.0) there, which runs
-# the kernels of the relu entry points.
-def _ode_act(act):
-    return (GAT_ACT_RELU, 0.0) if act is None else act
+def _byref(s):
+    return ctypes.byref(s) if s is not None else None
+
+
+def _agg_fwd_args(eg, proj, o, bf, a, amax, eps, out, w, den, act, ode):
+    gs, mode = _edge_csr(eg, o + 4), _gat_act(act, ode)
+    return (ctypes.byref(gs), ptr(eg.src), ptr(eg.tgt), ctypes.byref(proj), o, ptr(bf), ptr(a), ptr(amax), float(eps), ptr(out),
+            ptr(w), ptr(den), _byref(mode)), (gs, mode)
 
 
 def gat_agg_fwd(eg, proj, o, bf, a, amax, eps, out, w, den, act=None, ode=False):
     lib = _lib.load()
     _need(out, "out"); _need(w, "w"); _need(den, "den"); _need(bf, "bf")
-    gs = _edge_csr(eg, o + 4)
-    args = (ctypes.byref(gs), ptr(eg.src), ptr(eg.tgt), ctypes.byref(proj), o, ptr(bf), ptr(a), ptr(amax), float(eps), ptr(out),
-            ptr(w), ptr(den))
-    if ode:
-        check(lib.gode_gat_agg_ode_f32_fwd(*args, *_act_args(_ode_act(act)), stream_ptr()), "gode_gat_agg_ode_f32_fwd")
-    elif act is None:
-        check(lib.gode_gat_agg_f32_fwd(*args, stream_ptr()), "gode_gat_agg_f32_fwd")
-    else:
-        check(lib.gode_gat_agg_act_f32_fwd(*args, *_act_args(act), stream_ptr()), "gode_gat_agg_act_f32_fwd")
+    args, keep = _agg_fwd_args(eg, proj, o, bf, a, amax, eps, out, w, den, act, ode)
+    check(lib.gode_gat_agg_f32_fwd(*args, stream_ptr()), "gode_gat_agg_f32_fwd")
+    del keep
 
 
 def gat_agg_fwd_route(eg, proj, o, bf, a, amax, eps, out, w, den, act=None, ode=False):
     """The route gat_agg_fwd takes on these arguments (nothing is launched)."""
     lib = _lib.load()
-    gs = _edge_csr(eg, o + 4)
-    args = (ctypes.byref(gs), ptr(eg.src), ptr(eg.tgt), ctypes.byref(proj), o, ptr(bf), ptr(a), ptr(amax), float(eps), ptr(out),
-            ptr(w), ptr(den))
-    if ode:
-        return lib.gode_gat_agg_ode_f32_fwd_route(*args, *_act_args(_ode_act(act)), None)
-    if act is None:
-        return lib.gode_gat_agg_f32_fwd_route(*args, None)
-    return lib.gode_gat_agg_act_f32_fwd_route(*args, *_act_args(act), None)
+    args, keep = _agg_fwd_args(eg, proj, o, bf, a, amax, eps, out, w, den, act, ode)
+    rt = lib.gode_gat_agg_f32_fwd_route(*args, None)
+    del keep
+    return rt
 
 
-def _agg_bwd_args(eg, proj, o, bf, w, den, out, dz, da, dPt, dA2, dout, cot_terms, cot_scale, did):
+def _agg_bwd_args(eg, proj, o, bf, w, den, out, dz, da, dPt, dA2, dout, cot_terms, cot_scale, did, act, ode):
     lc = None
     if cot_terms is not None:
         if _need_terms(cot_terms, "cot") != out.numel():
@@ -792,20 +790,10 @@ def _agg_bwd_args(eg, proj, o, bf, w, den, out, dz, da, dPt, dA2, dout, cot_term
         lc = lincomb(cot_terms)
     elif dout is None:
         raise ValueError("gat_agg_bwd: dout or cot_terms required")
-    gs = _edge_csr(eg, o + 4)
+    gs, mode = _edge_csr(eg, o + 4), _gat_act(act, ode)
     at_ptr = ctypes.c_void_p(dA2.data_ptr() + 4) if dA2 is not None else None
     return (ctypes.byref(gs), ptr(eg.src), ptr(eg.tgt), ctypes.byref(proj), o, ptr(bf), ptr(w), ptr(den), ptr(out), ptr(dout),
-            ctypes.byref(lc) if lc is not None else None, float(cot_scale), ptr(dz), ptr(da), ptr(dPt), o, at_ptr, 2,
-            ctypes.byref(did)), (gs, lc)
-
-
-def _agg_bwd_call(lib, args, act, stream, ode=False):
-    if ode:
-        check(lib.gode_gat_agg_ode_f32_bwd(*args, *_act_args(_ode_act(act)), stream), "gode_gat_agg_ode_f32_bwd")
-    elif act is None:
-        check(lib.gode_gat_agg_f32_bwd(*args, stream), "gode_gat_agg_f32_bwd")
-    else:
-        check(lib.gode_gat_agg_act_f32_bwd(*args, *_act_args(act), stream), "gode_gat_agg_act_f32_bwd")
+            _byref(lc), float(cot_scale), ptr(dz), ptr(da), ptr(dPt), o, at_ptr, 2, ctypes.byref(did), _byref(mode)), (gs, lc, mode)
 
 
 def gat_agg_bwd(eg, proj, o, bf, w, den, out, dz, da, dPt=None, dA2=None, dout=None, cot_terms=None, cot_scale=1.0, act=None,
@@ -816,8 +804,8 @@ def gat_agg_bwd(eg, proj, o, bf, w, den, out, dz, da, dPt=None, dA2=None, dout=N
     for t, nm in ((out, "out"), (dz, "dz"), (da, "da"), (dout, "dout"), (dPt, "dPt"), (dA2, "dA2")):
         _need(t, nm)
     did = ctypes.c_int32(0)
-    args, keep = _agg_bwd_args(eg, proj, o, bf, w, den, out, dz, da, dPt, dA2, dout, cot_terms, cot_scale, did)
-    _agg_bwd_call(lib, args, act, stream_ptr(), ode)
+    args, keep = _agg_bwd_args(eg, proj, o, bf, w, den, out, dz, da, dPt, dA2, dout, cot_terms, cot_scale, did, act, ode)
+    check(lib.gode_gat_agg_f32_bwd(*args, stream_ptr()), "gode_gat_agg_f32_bwd")
     del keep
     return bool(did.value)
 
@@ -827,13 +815,8 @@ def gat_agg_bwd_route(eg, proj, o, bf, w, den, out, dz, da, dPt=None, dA2=None, 
     """The route gat_agg_bwd (and gat_vjp) takes on these arguments (nothing is launched)."""
     lib = _lib.load()
     did = ctypes.c_int32(0)
-    args, keep = _agg_bwd_args(eg, proj, o, bf, w, den, out, dz, da, dPt, dA2, dout, cot_terms, cot_scale, did)
-    if ode:
-        rt = lib.gode_gat_agg_ode_f32_bwd_route(*args, *_act_args(_ode_act(act)), None)
-    elif act is None:
-        rt = lib.gode_gat_agg_f32_bwd_route(*args, None)
-    else:
-        rt = lib.gode_gat_agg_act_f32_bwd_route(*args, *_act_args(act), None)
+    args, keep = _agg_bwd_args(eg, proj, o, bf, w, den, out, dz, da, dPt, dA2, dout, cot_terms, cot_scale, did, act, ode)
+    rt = lib.gode_gat_agg_f32_bwd_route(*args, None)
     del keep
     return rt
 
@@ -867,13 +850,10 @@ def gat_agg_heads_fwd(eg, proj, o, bf, a, scratch, heads, eps, out, w, den, act=
     maxima gat_logits_heads_raw left in `scratch`).  act (code, param): the ODE function's form, as gat_agg_fwd(ode=True)."""
     lib = _lib.load()
     _need(out, "out"); _need(w, "w"); _need(den, "den"); _need(bf, "bf"); _need(scratch, "scratch", torch.uint8)
-    gs = _edge_csr(eg, o + 4)
-    args = (ctypes.byref(gs), ptr(eg.src), ptr(eg.tgt), ctypes.byref(proj), o, ptr(bf), ptr(a), ptr(scratch), eg.E, int(heads),
-            float(eps), ptr(out), ptr(w), ptr(den))
-    if act is None:
-        check(lib.gode_gat_agg_heads_f32_fwd(*args, stream_ptr()), "gode_gat_agg_heads_f32_fwd")
-    else:
-        check(lib.gode_gat_agg_heads_ode_f32_fwd(*args, *_act_args(act), stream_ptr()), "gode_gat_agg_heads_ode_f32_fwd")
+    gs, mode = _edge_csr(eg, o + 4), _gat_act(act, act is not None)
+    check(lib.gode_gat_agg_heads_f32_fwd(ctypes.byref(gs), ptr(eg.src), ptr(eg.tgt), ctypes.byref(proj), o, ptr(bf), ptr(a),
+                                         ptr(scratch), eg.E, int(heads), float(eps), ptr(out), ptr(w), ptr(den), _byref(mode),
+                                         stream_ptr()), "gode_gat_agg_heads_f32_fwd")
 
 
 def gat_vjp(eg, proj, o, bf, a, amax, w, den, out, dz, da, dPs, dPt, dA2, dout=None, cot_terms=None, cot_scale=1.0,
@@ -888,9 +868,9 @@ def gat_vjp(eg, proj, o, bf, a, amax, w, den, out, dz, da, dPs, dPt, dA2, dout=N
     for t, nm in ((out, "out"), (dz, "dz"), (da, "da"), (dout, "dout"), (dPs, "dPs"), (dPt, "dPt"), (dA2, "dA2")):
         _need(t, nm)
     did = ctypes.c_int32(0)
-    args, keep = _agg_bwd_args(eg, proj, o, bf, w, den, out, dz, da, dPt, dA2, dout, cot_terms, cot_scale, did)
+    args, keep = _agg_bwd_args(eg, proj, o, bf, w, den, out, dz, da, dPt, dA2, dout, cot_terms, cot_scale, did, act, ode)
     at_ptr = ctypes.c_void_p(dA2.data_ptr() + 4)
-    _agg_bwd_call(lib, args, act, stream_ptr(), ode)
+    check(lib.gode_gat_agg_f32_bwd(*args, stream_ptr()), "gode_gat_agg_f32_bwd")
     del keep
     if eg.E > 0 and heads > 1 and raw_scratch is not None and defer_maxpath and not did.value:
         # first half only; gat_dense_vjp_small(..., maxfix=(raw_scratch, eg.src, eg.tgt)) closes the step

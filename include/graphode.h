@@ -439,19 +439,41 @@ int gode_gat_logits_f32(const gode_gat_proj_t* proj, const float* bw, const int3
 #define GODE_GAT_ROUTE_TWO_STAGE 6
 int gode_gat_logits_f32_route(const gode_gat_proj_t* proj, const float* bw, const int32_t* src, const int32_t* tgt,
                               int64_t n_edges, float* a, float* amax, float* scratch, void* stream);
+/* The message activation of the aggregation, and whether the ODE function's relu follows the mean (GAT/layers.py:16, the
+ * layer's `act=`; GAT/models.py:178, relu(layer(.))).  With y_e = act(z_e) and m[v] = sum_k val[k]*w[e_k]*y[e_k] / den[v]:
+ * out = m, or relu(m) with outer_relu; the backward forms dz_e = val w_e dA act'(z_e) and reads y_e in da.  At z == 0 the
+ * derivative is 0 for relu, the slope for leaky_relu, alpha for elu. */
+#define GODE_GAT_ACT_RELU 0
+#define GODE_GAT_ACT_IDENTITY 1
+#define GODE_GAT_ACT_LEAKY_RELU 2
+#define GODE_GAT_ACT_ELU 3
+#define GODE_GAT_ACT_TANH 4
+#define GODE_GAT_ACT_SIGMOID 5
+typedef struct gode_gat_act {
+    int32_t act;         /* GODE_GAT_ACT_*                                   */
+    float   act_param;   /* slope of leaky_relu / alpha of elu, else unread   */
+    int32_t outer_relu;  /* != 0: out = relu(mean) - the ODE function's form */
+} gode_gat_act_t;       /* zeroed == NULL == relu messages, no outer relu    */
 /* mt: CSR by target over the edges (col = edge ids of each target in increasing order, or NULL when the edge list is
  * target-sorted so that edge k is CSR position k), val = Mtgt values (nullable), plus the balanced record list.
  * Above 65 536 targets, with col == NULL and o in {16, 32, 64, 128, 256}, the aggregation runs over the records like
  * the SpMM (streamed per-edge arrays, one coalesced o*4-byte gather per edge); mt->partial must then hold
- * n_slots * (o + 4) floats.  Otherwise a lane group (a whole wave below 65 536 targets) works on one target. */
+ * n_slots * (o + 4) floats.  Otherwise a lane group (a whole wave below 65 536 targets) works on one target.
+ * act (host, nullable, read before any launch) is checked before anything else, in the launching calls and the route
+ * twins alike: a code outside the list above, or a non-finite act_param under leaky_relu / elu, is GODE_E_SHAPE (a parameter
+ * nobody reads may be anything); then, in the backward, a cot with terms under another activation than relu without
+ * outer_relu is GODE_E_UNSUPPORTED (see below), before any pointer but cot is looked at.  Routes do not depend on act, and
+ * relu messages run the same kernels with and without outer_relu, which is the identity on a weighted mean of relu's. */
 int gode_gat_agg_f32_fwd(const gode_graph_t* mt, const int32_t* src, const int32_t* tgt,
                          const gode_gat_proj_t* proj, int64_t o, const float* bf, const float* a, const float* amax,
-                         float eps, float* out, float* w_out, float* den_out, void* stream);
+                         float eps, float* out, float* w_out, float* den_out, const gode_gat_act_t* act, void* stream);
 int gode_gat_agg_f32_fwd_route(const gode_graph_t* mt, const int32_t* src, const int32_t* tgt,
                                const gode_gat_proj_t* proj, int64_t o, const float* bf, const float* a, const float* amax,
-                               float eps, float* out, float* w_out, float* den_out, void* stream);
-/* cotangent: dout (n_rows x o), or - when cot (host, nullable) has terms - cot_scale * (sum_j cot_j) masked by out > 0,
- * i.e. the stage cotangent of the adjoint solve pushed through the relu that follows the layer.
+                               float eps, float* out, float* w_out, float* den_out, const gode_gat_act_t* act, void* stream);
+/* cotangent: dout (n_rows x o, taken as it is: the caller has applied any mask), or - when cot (host, nullable) has terms -
+ * cot_scale * (sum_j cot_j) masked by out > 0, i.e. the stage cotangent of the adjoint solve pushed through the relu that
+ * follows the layer.  That mask is a relu's, so cot is taken under relu messages and, with outer_relu, under every
+ * activation: the stored relu(m) serves exactly - where the mask is open relu(m) = m, where it is closed the cotangent is 0.
  * dz[E x o], da[E] are always written.  dpt / dat / did_target_sums (all nullable): on the record path the kernel also
  * forms dpt[v,:] = sum_{e: tgt_e = v} dz[e,:] and dat[v*ld_dat] = sum da[e] and sets *did_target_sums = 1 (host int);
  * otherwise it leaves them untouched and sets 0 (use gode_gat_scatter_f32). */
@@ -459,66 +481,13 @@ int gode_gat_agg_f32_bwd(const gode_graph_t* mt, const int32_t* src, const int32
                          const gode_gat_proj_t* proj, int64_t o, const float* bf, const float* w, const float* den,
                          const float* out, const float* dout, const gode_lincomb_t* cot, float cot_scale,
                          float* dz, float* da, float* dpt, int64_t ld_dpt, float* dat, int64_t ld_dat,
-                         int32_t* did_target_sums, void* stream);
+                         int32_t* did_target_sums, const gode_gat_act_t* act, void* stream);
 /* (does not write *did_target_sums: the launching call sets it to 1 exactly on GODE_GAT_ROUTE_REC) */
 int gode_gat_agg_f32_bwd_route(const gode_graph_t* mt, const int32_t* src, const int32_t* tgt,
                                const gode_gat_proj_t* proj, int64_t o, const float* bf, const float* w, const float* den,
                                const float* out, const float* dout, const gode_lincomb_t* cot, float cot_scale,
                                float* dz, float* da, float* dpt, int64_t ld_dpt, float* dat, int64_t ld_dat,
-                               int32_t* did_target_sums, void* stream);
-/* The same aggregation with the message activation as an argument: y_e = act(z_e) in the forward, dz_e = val w_e dA act'(z_e)
- * and y_e in da in the backward (the layer's `act=` constructor argument, GAT/layers.py:16).  act_param is the slope of
- * leaky_relu / alpha of elu (ignored otherwise); at z == 0 the derivative is 0 for relu, the slope for leaky_relu, alpha for
- * elu.  Arguments, validation codes (in the same order) and routes are those of the entry points above: the dispatch does not
- * depend on act, and GODE_GAT_ACT_RELU runs the very kernels of the entry points above.  Checked before anything else:
- * act outside the list below, or a non-finite act_param for leaky_relu / elu: GODE_E_SHAPE; another activation than relu
- * with a cot that has terms (the masked cotangent belongs to the ODE function: gode_gat_agg_ode_* below): GODE_E_UNSUPPORTED. */
-#define GODE_GAT_ACT_RELU 0
-#define GODE_GAT_ACT_IDENTITY 1
-#define GODE_GAT_ACT_LEAKY_RELU 2
-#define GODE_GAT_ACT_ELU 3
-#define GODE_GAT_ACT_TANH 4
-#define GODE_GAT_ACT_SIGMOID 5
-int gode_gat_agg_act_f32_fwd(const gode_graph_t* mt, const int32_t* src, const int32_t* tgt,
-                             const gode_gat_proj_t* proj, int64_t o, const float* bf, const float* a, const float* amax,
-                             float eps, float* out, float* w_out, float* den_out, int32_t act, float act_param, void* stream);
-int gode_gat_agg_act_f32_fwd_route(const gode_graph_t* mt, const int32_t* src, const int32_t* tgt,
-                                   const gode_gat_proj_t* proj, int64_t o, const float* bf, const float* a, const float* amax,
-                                   float eps, float* out, float* w_out, float* den_out, int32_t act, float act_param,
-                                   void* stream);
-int gode_gat_agg_act_f32_bwd(const gode_graph_t* mt, const int32_t* src, const int32_t* tgt,
-                             const gode_gat_proj_t* proj, int64_t o, const float* bf, const float* w, const float* den,
-                             const float* out, const float* dout, const gode_lincomb_t* cot, float cot_scale,
-                             float* dz, float* da, float* dpt, int64_t ld_dpt, float* dat, int64_t ld_dat,
-                             int32_t* did_target_sums, int32_t act, float act_param, void* stream);
-int gode_gat_agg_act_f32_bwd_route(const gode_graph_t* mt, const int32_t* src, const int32_t* tgt,
-                                   const gode_gat_proj_t* proj, int64_t o, const float* bf, const float* w, const float* den,
-                                   const float* out, const float* dout, const gode_lincomb_t* cot, float cot_scale,
-                                   float* dz, float* da, float* dpt, int64_t ld_dpt, float* dat, int64_t ld_dat,
-                                   int32_t* did_target_sums, int32_t act, float act_param, void* stream);
-/* The ODE function's aggregation (GAT/models.py:178: relu(layer(.))): message activation inside, relu outside -
- * out = relu(m), m[v] = sum_e val w_e act(z_e) / den_v.  Arguments, validation order (act and act_param first) and routes are
- * those of gode_gat_agg_act_f32_*; GODE_GAT_ACT_RELU runs the very kernels of gode_gat_agg_f32_* (the outer relu is the
- * identity there).  The backward takes a cot with terms under EVERY activation: cot_scale * (sum_j cot_j) masked by out > 0.
- * The stored relu(m) serves it exactly - where the mask is open relu(m) = m, where it is closed the cotangent is 0.  With dout
- * instead of cot no mask is applied (the caller has applied it). */
-int gode_gat_agg_ode_f32_fwd(const gode_graph_t* mt, const int32_t* src, const int32_t* tgt,
-                             const gode_gat_proj_t* proj, int64_t o, const float* bf, const float* a, const float* amax,
-                             float eps, float* out, float* w_out, float* den_out, int32_t act, float act_param, void* stream);
-int gode_gat_agg_ode_f32_fwd_route(const gode_graph_t* mt, const int32_t* src, const int32_t* tgt,
-                                   const gode_gat_proj_t* proj, int64_t o, const float* bf, const float* a, const float* amax,
-                                   float eps, float* out, float* w_out, float* den_out, int32_t act, float act_param,
-                                   void* stream);
-int gode_gat_agg_ode_f32_bwd(const gode_graph_t* mt, const int32_t* src, const int32_t* tgt,
-                             const gode_gat_proj_t* proj, int64_t o, const float* bf, const float* w, const float* den,
-                             const float* out, const float* dout, const gode_lincomb_t* cot, float cot_scale,
-                             float* dz, float* da, float* dpt, int64_t ld_dpt, float* dat, int64_t ld_dat,
-                             int32_t* did_target_sums, int32_t act, float act_param, void* stream);
-int gode_gat_agg_ode_f32_bwd_route(const gode_graph_t* mt, const int32_t* src, const int32_t* tgt,
-                                   const gode_gat_proj_t* proj, int64_t o, const float* bf, const float* w, const float* den,
-                                   const float* out, const float* dout, const gode_lincomb_t* cot, float cot_scale,
-                                   float* dz, float* da, float* dpt, int64_t ld_dpt, float* dat, int64_t ld_dat,
-                                   int32_t* did_target_sums, int32_t act, float act_param, void* stream);
+                               int32_t* did_target_sums, const gode_gat_act_t* act, void* stream);
 /* gradient path through the global maximum of the logits (GAT/layers.py:47): da[e*] -= S, S = sum(da), e* = first
  * argmax; when dat (nullable, with tgt) holds target-side sums formed before the correction, dat[tgt[e*]*ld_dat] -= S.
  * scratch: >= gode_gat_maxpath_scratch_bytes(n_edges) bytes (may be NULL for n_edges <= 32 768 without dat). */
@@ -543,21 +512,17 @@ int gode_gat_maxpath_heads_f32(const float* a, float* da, int64_t n_edges, int64
                                float* dat, int64_t ld_dat, void* scratch, void* stream);
 /* The same three steps WITHOUT the launch that shifts the logits (launch-bound graphs): logits_heads_raw leaves raw logits in
  * a and per-block partial maxima in `scratch` (which must then stay untouched until the stage's max-path step);
- * agg_heads_fwd is gode_gat_agg_f32_fwd on the H-fold graph with every virtual row shifted by its head's maximum, reduced
- * from those partials inside the kernel (same arithmetic: exp(a - max)); maxpath_heads_raw is the max-path step on raw
- * logits (e* = the first edge whose logit EQUALS its head's maximum).  Up to 65 536 virtual rows. */
+ * agg_heads_fwd is the aggregation's forward on the H-fold graph with every virtual row shifted by its head's maximum,
+ * reduced from those partials inside the kernel (same arithmetic: exp(a - max); act as there: checked first, then its own
+ * checks); maxpath_heads_raw is the max-path step on raw logits (e* = the first edge whose logit EQUALS its head's
+ * maximum).  Up to 65 536 virtual rows. */
 int64_t gode_gat_heads_parts(int64_t n_edges);
 int gode_gat_logits_heads_raw_f32(const gode_gat_proj_t* proj, const float* bw, const int32_t* src, const int32_t* tgt,
                                   int64_t n_edges, int64_t heads, float* a, void* scratch, void* stream);
 int gode_gat_agg_heads_f32_fwd(const gode_graph_t* mt, const int32_t* src, const int32_t* tgt, const gode_gat_proj_t* proj,
                                int64_t o, const float* bf, const float* a, const void* scratch, int64_t n_edges,
-                               int64_t heads, float eps, float* out, float* w_out, float* den_out, void* stream);
-/* agg_heads_fwd as the ODE function's aggregation (gode_gat_agg_ode_f32_fwd: act inside, relu outside; act and act_param are
- * checked first, then the checks above; GODE_GAT_ACT_RELU is the entry point above) */
-int gode_gat_agg_heads_ode_f32_fwd(const gode_graph_t* mt, const int32_t* src, const int32_t* tgt, const gode_gat_proj_t* proj,
-                                   int64_t o, const float* bf, const float* a, const void* scratch, int64_t n_edges,
-                                   int64_t heads, float eps, float* out, float* w_out, float* den_out, int32_t act,
-                                   float act_param, void* stream);
+                               int64_t heads, float eps, float* out, float* w_out, float* den_out, const gode_gat_act_t* act,
+                               void* stream);
 int gode_gat_maxpath_heads_raw_f32(const float* a, float* da, int64_t n_edges, int64_t heads, const int32_t* tgt,
                                    float* dat, int64_t ld_dat, void* scratch, void* stream);
 /* the first half of maxpath_heads_raw only (per-block sums and arg-max candidates left in `scratch`): the step is closed by
@@ -870,8 +835,8 @@ typedef struct gode_gat_odefunc {
     /* nullable: gode_gat_small_pack_f32 of (Wsrc, Wtgt, Wlog), refreshed with them - launch-bound graphs only */
     const float* Wpacked;
     /* the layer's message activation (GODE_GAT_ACT_*; act_param: slope of leaky_relu / alpha of elu).  A zeroed struct is
-     * relu: the launches of the relu entry points.  Any other runs the aggregation through gode_gat_agg_ode_* (message
-     * activation inside, the function's relu outside).  Outside the list, or a non-finite act_param for leaky_relu / elu:
+     * relu.  The drivers hand the aggregation gode_gat_act_t{act, act_param, 1}: message activation inside, the
+     * function's relu outside.  Outside the list, or a non-finite act_param for leaky_relu / elu:
      * GODE_E_SHAPE from every gode_gat_ode_* entry point - the first check of the struct, before any launch. */
     int32_t act; float act_param;
 } gode_gat_odefunc_t;

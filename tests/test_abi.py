@@ -86,7 +86,7 @@ def test_struct_layout_matches_the_c_compiler(tmp_path):
     if cc is None:
         import pytest
         pytest.skip("no C compiler in this environment")
-    assert len(_lib.STRUCTS) == 10
+    assert len(_lib.STRUCTS) == 11
     lines, expect = [], []
     for tag, cls in _lib.STRUCTS.items():
         lines.append('printf("%s %%zu\\n", sizeof(%s));' % (tag, tag))
@@ -108,7 +108,7 @@ def test_public_struct_names_are_the_derived_classes():
     for py, tag in (("LinComb", "gode_lincomb_t"), ("SpmmEpilogue", "gode_spmm_epilogue_t"), ("Graph", "gode_graph_t"),
                     ("GcnOdeFunc", "gode_gcn_odefunc_t"), ("GatProj", "gode_gat_proj_t"), ("Rk4Workspace", "gode_rk4_workspace_t"),
                     ("ReduceSeg", "gode_reduce_seg_t"), ("GatOdeFunc", "gode_gat_odefunc_t"),
-                    ("GatWorkspace", "gode_gat_workspace_t"), ("AdamArgs", "gode_adam_args_t")):
+                    ("GatWorkspace", "gode_gat_workspace_t"), ("AdamArgs", "gode_adam_args_t"), ("GatAct", "gode_gat_act_t")):
         assert getattr(_lib, py) is _lib.STRUCTS[tag]
     txt = open(HEADER).read()
     for name in ("GODE_MAX_TERMS", "GODE_ADAM_MAX_TENSORS"):

@@ -1,5 +1,6 @@
-"""The activation argument of the edge-attention entry points (graphode.h: gode_gat_agg_act_f32_fwd / _bwd and their route
-twins), on the CPU: the symbols and constants, the checks that come before everything else, the dispatch (it does not
+"""The activation argument of the edge-attention entry points (graphode.h: gode_gat_act_t on gode_gat_agg_f32_fwd / _bwd,
+their route twins and gode_gat_agg_heads_f32_fwd), on the CPU: the symbols, signatures and constants, the checks that come
+before everything else, the dispatch (it does not
 depend on the activation), gat_layers.message_activation, and the teeth of test_gpu_gat_act.py's comparisons.  The route
 queries launch nothing and read only the values of the pointers they are given, so the pointers here are made up
 (test_gat_routes.py's).
@@ -22,53 +23,56 @@ import test_gpu_gat_act as A                                            # noqa: 
 from graph_odenet_amd import _lib                                       # noqa: E402
 
 E_SHAPE, E_UNSUPPORTED = -2, -5
-NAMES = ("gode_gat_agg_act_f32_fwd", "gode_gat_agg_act_f32_fwd_route", "gode_gat_agg_act_f32_bwd", "gode_gat_agg_act_f32_bwd_route")
+# the entry points that took the activation as `int32_t act, float act_param` before gode_gat_act_t did
+GONE = ("gode_gat_agg_act_f32_fwd", "gode_gat_agg_act_f32_fwd_route", "gode_gat_agg_act_f32_bwd", "gode_gat_agg_act_f32_bwd_route",
+        "gode_gat_agg_ode_f32_fwd", "gode_gat_agg_ode_f32_fwd_route", "gode_gat_agg_ode_f32_bwd", "gode_gat_agg_ode_f32_bwd_route",
+        "gode_gat_agg_heads_ode_f32_fwd")
 CODES = {"RELU": 0, "IDENTITY": 1, "LEAKY_RELU": 2, "ELU": 3, "TANH": 4, "SIGMOID": 5}
 P, vp = T.P, T.vp
 
 
+def want_signatures():
+    """The five aggregation signatures written out: the plain ones from before the activation argument, with
+    POINTER(gode_gat_act_t) before `stream`."""
+    c, i64, f32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_float
+    graph, proj, lincomb, act = (ctypes.POINTER(s) for s in (_lib.Graph, _lib.GatProj, _lib.LinComb, _lib.GatAct))
+    fwd = [graph, c, c, proj, i64, c, c, c, f32, c, c, c, act, c]
+    bwd = [graph, c, c, proj, i64, c, c, c, c, c, lincomb, f32, c, c, c, i64, c, i64, c, act, c]
+    heads = [graph, c, c, proj, i64, c, c, c, i64, i64, f32, c, c, c, act, c]
+    return {"gode_gat_agg_f32_fwd": fwd, "gode_gat_agg_f32_fwd_route": fwd, "gode_gat_agg_f32_bwd": bwd,
+            "gode_gat_agg_f32_bwd_route": bwd, "gode_gat_agg_heads_f32_fwd": heads}
+
+
 def test_symbols_constants_and_struct_count():
     lib = _lib.load()
-    for name in NAMES:
-        assert name in _lib.SIGNATURES and hasattr(lib, name), name
+    sig = _lib.SIGNATURES
+    for name, argtypes in want_signatures().items():
+        assert hasattr(lib, name) and sig[name][0] is ctypes.c_int and sig[name][1] == argtypes, name
+    for kind in ("fwd", "bwd"):                                          # a route twin takes what its launcher takes
+        assert sig["gode_gat_agg_f32_%s_route" % kind] == sig["gode_gat_agg_f32_%s" % kind]
+    assert sorted(n for n in sig if n.startswith("gode_gat_agg_")) == sorted(want_signatures())
+    for name in GONE:
+        assert name not in sig and not hasattr(lib, name), name
+    assert _lib.GatAct._fields_ == [("act", ctypes.c_int32), ("act_param", ctypes.c_float), ("outer_relu", ctypes.c_int32)]
+    assert ctypes.sizeof(_lib.GatAct) == 12
+    fresh = _lib.GatAct()
+    assert (fresh.act, fresh.act_param, fresh.outer_relu) == (0, 0.0, 0)  # zeroed: relu messages, no outer relu
     for k, want in CODES.items():
         assert _lib.CONSTANTS["GODE_GAT_ACT_" + k] == want
-    assert len(_lib.STRUCTS) == 10
-    old_f, new_f = _lib.SIGNATURES["gode_gat_agg_f32_fwd"], _lib.SIGNATURES["gode_gat_agg_act_f32_fwd"]
-    old_b, new_b = _lib.SIGNATURES["gode_gat_agg_f32_bwd"], _lib.SIGNATURES["gode_gat_agg_act_f32_bwd"]
-    for old, new in ((old_f, new_f), (old_b, new_b)):                    # the old arguments, then act, act_param, stream
-        assert new[0] is old[0] and new[1] == old[1][:-1] + [ctypes.c_int32, ctypes.c_float] + old[1][-1:]
-    assert _lib.SIGNATURES["gode_gat_agg_act_f32_fwd_route"] == new_f and _lib.SIGNATURES["gode_gat_agg_act_f32_bwd_route"] == new_b
+    assert len(_lib.STRUCTS) == 11
     from graph_odenet_amd import ops
     assert (ops.GAT_ACT_RELU, ops.GAT_ACT_IDENTITY, ops.GAT_ACT_LEAKY_RELU, ops.GAT_ACT_ELU, ops.GAT_ACT_TANH,
             ops.GAT_ACT_SIGMOID) == (0, 1, 2, 3, 4, 5)
 
 
-# ---- the new twins on test_gat_routes.py's made-up arguments --------------------------------------------------------------
+# ---- the activation without the outer relu, on test_gat_routes.py's made-up arguments -------------------------------------
 def fwd_act(act, param, n_rows, o, out=0, g=None, launch=False):
-    lib = _lib.load()
-    g = g if g is not None else T.graph(n_rows)
-    p = T.proj(o)
-    fn = lib.gode_gat_agg_act_f32_fwd if launch else lib.gode_gat_agg_act_f32_fwd_route
-    return fn(ctypes.byref(g), vp(P["src"]), vp(P["tgt"]), ctypes.byref(p), o, vp(P["bf"]), vp(P["a"]), vp(P["amax"]), 1e-9,
-              vp(P["out"] + out), vp(P["w"]), vp(P["den"]), act, param, None)
+    return T.fwd(n_rows, o, out=out, g=g, act=_lib.GatAct(act, param, 0), launch=launch)
 
 
 def bwd_act(act, param, n_rows, o, terms=0, out=0, g=None, launch=False):
-    lib = _lib.load()
-    g = g if g is not None else T.graph(n_rows)
-    p = T.proj(o)
-    lc = _lib.LinComb()
-    lc.n = terms
-    for j in range(min(terms, _lib.GODE_MAX_TERMS)):
-        lc.coef[j], lc.ptr[j] = 1.0, P["c%d" % min(j, 2)] + 0x100 * j
-    flag = ctypes.c_int32(-7)
-    fn = lib.gode_gat_agg_act_f32_bwd if launch else lib.gode_gat_agg_act_f32_bwd_route
-    rt = fn(ctypes.byref(g), vp(P["src"]), vp(P["tgt"]), ctypes.byref(p), o, vp(P["bf"]), vp(P["w"]), vp(P["den"]),
-            vp(P["out"] + out), vp(P["dout"]), ctypes.byref(lc) if terms else None, -0.5, vp(P["dz"]), vp(P["da"]), vp(P["dpt"]), o,
-            vp(P["dat"]), 2, ctypes.byref(flag), act, param, None)
-    assert flag.value == -7                                              # neither a query nor a refused call writes it
-    return rt
+    # T.bwd asserts that the flag is untouched: neither a query nor a refused call writes it
+    return T.bwd(n_rows, o, terms, out=out, g=g, act=_lib.GatAct(act, param, 0), launch=launch)
 
 
 def test_the_new_checks_come_first():
@@ -85,10 +89,11 @@ def test_the_new_checks_come_first():
     lib = _lib.load()
     nulls_f = (None, None, None, None, 16, None, None, None, 0.0, None, None, None)
     nulls_b = (None, None, None, None, 16, None, None, None, None, None, None, 1.0, None, None, None, 16, None, 2, None)
-    for fn, nulls in ((lib.gode_gat_agg_act_f32_fwd, nulls_f), (lib.gode_gat_agg_act_f32_fwd_route, nulls_f),
-                      (lib.gode_gat_agg_act_f32_bwd, nulls_b), (lib.gode_gat_agg_act_f32_bwd_route, nulls_b)):
-        assert fn(*nulls, 6, 0.0, None) == E_SHAPE and fn(*nulls, CODES["ELU"], nan, None) == E_SHAPE
-        assert fn(*nulls, CODES["ELU"], 1.0, None) == T.E_NULLPTR        # then the old entry's checks, with its codes
+    act = lambda code, param: ctypes.byref(_lib.GatAct(code, param, 0))  # noqa: E731
+    for fn, nulls in ((lib.gode_gat_agg_f32_fwd, nulls_f), (lib.gode_gat_agg_f32_fwd_route, nulls_f),
+                      (lib.gode_gat_agg_f32_bwd, nulls_b), (lib.gode_gat_agg_f32_bwd_route, nulls_b)):
+        assert fn(*nulls, act(6, 0.0), None) == E_SHAPE and fn(*nulls, act(CODES["ELU"], nan), None) == E_SHAPE
+        assert fn(*nulls, act(CODES["ELU"], 1.0), None) == T.E_NULLPTR   # then the old entry's checks, with its codes
     # a parameter nobody reads may be anything; relu with cot terms is the old entry's route
     assert fwd_act(CODES["TANH"], nan, 700, 16) == T.code(T.PF, 4) and fwd_act(CODES["RELU"], nan, 700, 16) == T.code(T.PF, 4)
     for n_rows in (T.BELOW, T.ABOVE):

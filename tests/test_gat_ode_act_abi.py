@@ -1,7 +1,7 @@
-"""The message activation of the fused GAT ODE function on the CPU (graphode.h: gode_gat_agg_ode_f32_fwd / _bwd with their
-route twins, gode_gat_agg_heads_ode_f32_fwd, and `act, act_param` at the end of gode_gat_odefunc_t): the symbols and their
+"""The message activation of the fused GAT ODE function on the CPU (graphode.h: gode_gat_act_t with outer_relu set on the
+five gode_gat_agg_* entry points, and `act, act_param` at the end of gode_gat_odefunc_t): the symbols and their
 signatures, the checks that come first, the dispatch (it does not depend on the activation, with or without cotangent
-terms), the refusal the old gode_gat_agg_act_f32_bwd keeps, and the plan token of the two ODE functions.  Nothing is
+terms), the refusal the backward keeps without the outer relu, and the plan token of the two ODE functions.  Nothing is
 launched: every call either is a route query or returns a validation code, so the pointers are made up
 (test_gat_routes.py's, test_gat_backprop_abi.py's).
 """
@@ -14,7 +14,7 @@ import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import test_gat_routes as T                                             # noqa: E402  (made-up pointers, graph(), proj())
-import test_gat_act_abi as A                                            # noqa: E402  (the _act_ twins on the same arguments)
+import test_gat_act_abi as A                                            # noqa: E402  (the same arguments without the outer relu)
 import test_gat_backprop_abi as B                                       # noqa: E402  (a made-up odefunc / workspace pair)
 
 from graph_odenet_amd import _lib                                       # noqa: E402
@@ -30,13 +30,11 @@ def test_symbols_signatures_and_struct():
     sig = _lib.SIGNATURES
     for name in ("gode_gat_agg_ode_f32_fwd", "gode_gat_agg_ode_f32_fwd_route", "gode_gat_agg_ode_f32_bwd",
                  "gode_gat_agg_ode_f32_bwd_route", "gode_gat_agg_heads_ode_f32_fwd"):
-        assert name in sig and hasattr(lib, name), name
-    for kind in ("fwd", "bwd"):                                          # the _act_ signatures, launching call and twin
-        want = sig["gode_gat_agg_act_f32_%s" % kind]
-        assert sig["gode_gat_agg_ode_f32_%s" % kind] == want and sig["gode_gat_agg_ode_f32_%s_route" % kind] == want
-    old, new = sig["gode_gat_agg_heads_f32_fwd"], sig["gode_gat_agg_heads_ode_f32_fwd"]
-    assert new[0] is old[0] and new[1] == old[1][:-1] + [ctypes.c_int32, ctypes.c_float] + old[1][-1:]
-    assert len(_lib.STRUCTS) == 10
+        assert name in A.GONE and name not in sig and not hasattr(lib, name), name
+    for name, argtypes in A.want_signatures().items():                   # outer_relu rides the one activation argument
+        assert hasattr(lib, name) and sig[name] == (ctypes.c_int, argtypes), name
+    assert _lib.GatAct._fields_[2] == ("outer_relu", ctypes.c_int32) and ctypes.sizeof(_lib.GatAct) == 12
+    assert len(_lib.STRUCTS) == 11
     fields = _lib.GatOdeFunc._fields_
     assert [f[0] for f in fields[-3:]] == ["Wpacked", "act", "act_param"]
     assert fields[-2][1] is ctypes.c_int32 and fields[-1][1] is ctypes.c_float
@@ -46,29 +44,13 @@ def test_symbols_signatures_and_struct():
 
 # ---- the aggregation entry points on test_gat_routes.py's made-up arguments -----------------------------------------------
 def fwd_ode(act, param, n_rows, o, out=0, g=None, launch=False):
-    lib = _lib.load()
-    g = g if g is not None else T.graph(n_rows)
-    p = T.proj(o)
-    fn = lib.gode_gat_agg_ode_f32_fwd if launch else lib.gode_gat_agg_ode_f32_fwd_route
-    return fn(ctypes.byref(g), vp(P["src"]), vp(P["tgt"]), ctypes.byref(p), o, vp(P["bf"]), vp(P["a"]), vp(P["amax"]), 1e-9,
-              vp(P["out"] + out), vp(P["w"]), vp(P["den"]), act, param, None)
+    return T.fwd(n_rows, o, out=out, g=g, act=_lib.GatAct(act, param, 1), launch=launch)
 
 
 def bwd_ode(act, param, n_rows, o, terms=0, out=0, term=0, g=None, launch=False, old=False):
-    lib = _lib.load()
-    g = g if g is not None else T.graph(n_rows)
-    p = T.proj(o)
-    lc = _lib.LinComb()
-    lc.n = terms
-    for j in range(min(terms, _lib.GODE_MAX_TERMS)):
-        lc.coef[j], lc.ptr[j] = 1.0, P["c%d" % min(j, 2)] + 0x100 * j + (term if j == terms - 1 else 0)
-    flag = ctypes.c_int32(-7)
-    name = "gode_gat_agg_%s_f32_bwd%s" % ("act" if old else "ode", "" if launch else "_route")
-    rt = getattr(lib, name)(ctypes.byref(g), vp(P["src"]), vp(P["tgt"]), ctypes.byref(p), o, vp(P["bf"]), vp(P["w"]), vp(P["den"]),
-                            vp(P["out"] + out), vp(P["dout"]), ctypes.byref(lc) if terms else None, -0.5, vp(P["dz"]),
-                            vp(P["da"]), vp(P["dpt"]), o, vp(P["dat"]), 2, ctypes.byref(flag), act, param, None)
-    assert flag.value == -7                                              # neither a query nor a refused call writes it
-    return rt
+    """old: without the outer relu (what gode_gat_agg_act_f32_bwd was).  T.bwd asserts that the flag is untouched: neither
+    a query nor a refused call writes it."""
+    return T.bwd(n_rows, o, terms, out=out, term=term, g=g, act=_lib.GatAct(act, param, 0 if old else 1), launch=launch)
 
 
 def test_the_activation_checks_come_first_then_the_old_checks_in_their_order():
@@ -83,20 +65,22 @@ def test_the_activation_checks_come_first_then_the_old_checks_in_their_order():
     nulls_f = (None, None, None, None, 16, None, None, None, 0.0, None, None, None)
     nulls_b = (None, None, None, None, 16, None, None, None, None, None, None, 1.0, None, None, None, 16, None, 2, None)
     nulls_h = (None, None, None, None, 16, None, None, None, 9000, 8, 0.0, None, None, None)
-    for fn, nulls in ((lib.gode_gat_agg_ode_f32_fwd, nulls_f), (lib.gode_gat_agg_ode_f32_fwd_route, nulls_f),
-                      (lib.gode_gat_agg_ode_f32_bwd, nulls_b), (lib.gode_gat_agg_ode_f32_bwd_route, nulls_b),
-                      (lib.gode_gat_agg_heads_ode_f32_fwd, nulls_h)):
+    mode = lambda act, param: ctypes.byref(_lib.GatAct(act, param, 1))   # noqa: E731
+    for fn, nulls in ((lib.gode_gat_agg_f32_fwd, nulls_f), (lib.gode_gat_agg_f32_fwd_route, nulls_f),
+                      (lib.gode_gat_agg_f32_bwd, nulls_b), (lib.gode_gat_agg_f32_bwd_route, nulls_b),
+                      (lib.gode_gat_agg_heads_f32_fwd, nulls_h)):
         for act in (-1, 6):
-            assert fn(*nulls, act, 0.0, None) == E_SHAPE                 # before any pointer is looked at
-        assert fn(*nulls, CODES["ELU"], NAN, None) == E_SHAPE and fn(*nulls, CODES["LEAKY_RELU"], INF, None) == E_SHAPE
-        assert fn(*nulls, CODES["ELU"], 1.0, None) == E_NULLPTR          # then the old entry's checks, with its codes
-        assert fn(*nulls, CODES["TANH"], NAN, None) == E_NULLPTR         # a parameter nobody reads may be anything
+            assert fn(*nulls, mode(act, 0.0), None) == E_SHAPE           # before any pointer is looked at
+        assert fn(*nulls, mode(CODES["ELU"], NAN), None) == E_SHAPE and fn(*nulls, mode(CODES["LEAKY_RELU"], INF), None) == E_SHAPE
+        assert fn(*nulls, mode(CODES["ELU"], 1.0), None) == E_NULLPTR    # then the old entry's checks, with its codes
+        assert fn(*nulls, mode(CODES["TANH"], NAN), None) == E_NULLPTR   # a parameter nobody reads may be anything
+        assert fn(*nulls, None, None) == E_NULLPTR                       # and no struct at all is relu
     # the heads form: the old checks in the old order behind the new one
     g, p = T.graph(700), T.proj(8)
     def heads(act, o=8, heads=8, n_edges=9000, scratch=True):            # noqa: E306
-        return lib.gode_gat_agg_heads_ode_f32_fwd(ctypes.byref(g), vp(P["src"]), vp(P["tgt"]), ctypes.byref(p), o, vp(P["bf"]),
-                                                  vp(P["a"]), vp(P["scratch"]) if scratch else None, n_edges, heads, 1e-9,
-                                                  vp(P["out"]), vp(P["w"]), vp(P["den"]), act, 1.0, None)
+        return lib.gode_gat_agg_heads_f32_fwd(ctypes.byref(g), vp(P["src"]), vp(P["tgt"]), ctypes.byref(p), o, vp(P["bf"]),
+                                              vp(P["a"]), vp(P["scratch"]) if scratch else None, n_edges, heads, 1e-9,
+                                              vp(P["out"]), vp(P["w"]), vp(P["den"]), mode(act, 1.0), None)
     for act in CODES.values():
         assert heads(act, scratch=False) == E_NULLPTR and heads(act, heads=0) == E_SHAPE and heads(act, n_edges=-1) == E_SHAPE
         assert heads(act, heads=65) == E_UNSUPPORTED and heads(act, o=513) == E_UNSUPPORTED
@@ -116,7 +100,7 @@ def test_routes_are_the_act_routes_with_and_without_cotangent_terms():
             for n_rows in (T.BELOW, T.ABOVE):
                 assert fwd_ode(act, 0.2, n_rows, o) == A.fwd_act(act, 0.2, n_rows, o) == T.fwd(n_rows, o) > 0, (act, o, n_rows)
                 assert bwd_ode(act, 0.2, n_rows, o) == A.bwd_act(act, 0.2, n_rows, o) == T.bwd(n_rows, o) > 0, (act, o, n_rows)
-                for terms in (1, 3):                                     # the relu entry's route: the _act_ twin refuses these
+                for terms in (1, 3):                                     # relu's route; refused without the outer relu
                     want = T.bwd(n_rows, o, terms)
                     assert bwd_ode(act, 0.2, n_rows, o, terms=terms) == want > 0, (act, o, n_rows, terms)
                     assert bwd_ode(act, 0.2, n_rows, o, terms=terms, term=4) == T.bwd(n_rows, o, terms, term=4) > 0

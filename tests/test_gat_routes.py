@@ -79,16 +79,18 @@ def proj(o, ps=0, pt=0, lds=0, ldt=0):
     return p
 
 
-def fwd(n_rows, o, out=0, bf=0, no_bf=False, g=None, **pk):
+def fwd(n_rows, o, out=0, bf=0, no_bf=False, g=None, act=None, launch=False, **pk):
+    """act: None (NULL) or a _lib.GatAct; launch: the launching call, on arguments that stop it before any launch."""
     lib = _lib.load()
     g = g if g is not None else graph(n_rows)
     p = proj(o, **pk)
-    return lib.gode_gat_agg_f32_fwd_route(ctypes.byref(g), vp(P["src"]), vp(P["tgt"]), ctypes.byref(p), o,
-                                          None if no_bf else vp(P["bf"] + bf), vp(P["a"]), vp(P["amax"]), 1e-9,
-                                          vp(P["out"] + out), vp(P["w"]), vp(P["den"]), None)
+    fn = lib.gode_gat_agg_f32_fwd if launch else lib.gode_gat_agg_f32_fwd_route
+    return fn(ctypes.byref(g), vp(P["src"]), vp(P["tgt"]), ctypes.byref(p), o, None if no_bf else vp(P["bf"] + bf), vp(P["a"]),
+              vp(P["amax"]), 1e-9, vp(P["out"] + out), vp(P["w"]), vp(P["den"]), ctypes.byref(act) if act is not None else None, None)
 
 
-def bwd(n_rows, o, terms=0, out=0, bf=0, dz=0, dout=0, term=0, dpt=True, dat=True, did=True, ld_dpt=0, no_dout=False, g=None, **pk):
+def bwd(n_rows, o, terms=0, out=0, bf=0, dz=0, dout=0, term=0, dpt=True, dat=True, did=True, ld_dpt=0, no_dout=False, g=None,
+        act=None, launch=False, zeroes_flag=False, **pk):
     lib = _lib.load()
     g = g if g is not None else graph(n_rows)
     p = proj(o, **pk)
@@ -97,12 +99,13 @@ def bwd(n_rows, o, terms=0, out=0, bf=0, dz=0, dout=0, term=0, dpt=True, dat=Tru
     for j in range(min(terms, _lib.GODE_MAX_TERMS)):
         lc.coef[j], lc.ptr[j] = 1.0, P["c%d" % min(j, 2)] + 0x100 * j + (term if j == terms - 1 else 0)
     flag = ctypes.c_int32(-7)
-    rt = lib.gode_gat_agg_f32_bwd_route(ctypes.byref(g), vp(P["src"]), vp(P["tgt"]), ctypes.byref(p), o, vp(P["bf"] + bf), vp(P["w"]),
-                                        vp(P["den"]), vp(P["out"] + out), None if no_dout else vp(P["dout"] + dout),
-                                        ctypes.byref(lc) if terms else None, -0.5, vp(P["dz"] + dz), vp(P["da"]),
-                                        vp(P["dpt"]) if dpt else None, o + ld_dpt, vp(P["dat"]) if dat else None, 2,
-                                        ctypes.byref(flag) if did else None, None)
-    assert flag.value == -7                                              # the query writes nothing
+    fn = lib.gode_gat_agg_f32_bwd if launch else lib.gode_gat_agg_f32_bwd_route
+    rt = fn(ctypes.byref(g), vp(P["src"]), vp(P["tgt"]), ctypes.byref(p), o, vp(P["bf"] + bf), vp(P["w"]), vp(P["den"]),
+            vp(P["out"] + out), None if no_dout else vp(P["dout"] + dout), ctypes.byref(lc) if terms else None, -0.5,
+            vp(P["dz"] + dz), vp(P["da"]), vp(P["dpt"]) if dpt else None, o + ld_dpt, vp(P["dat"]) if dat else None, 2,
+            ctypes.byref(flag) if did else None, ctypes.byref(act) if act is not None else None, None)
+    # the query writes nothing, nor does a launching call that the activation checks refuse; any other launching call zeroes it
+    assert flag.value == (0 if zeroes_flag else -7)
     return rt
 
 
@@ -206,13 +209,44 @@ def test_validation_codes_come_back_unchanged():
     assert fwd(2 ** 31, 16) == E_RANGE and bwd(2 ** 31, 16) == E_RANGE and scatter(2 ** 31, 16) == E_RANGE
     assert bwd(700, 16, 0, no_dout=True) == E_NULLPTR
     assert bwd(700, 16, 9) == E_RANGE                                            # more than GODE_MAX_TERMS terms
-    assert lib.gode_gat_agg_f32_fwd_route(None, None, None, None, 16, None, None, None, 0.0, None, None, None, None) == E_NULLPTR
+    assert lib.gode_gat_agg_f32_fwd_route(None, None, None, None, 16, None, None, None, 0.0, None, None, None, None, None) == E_NULLPTR
     # and the launching calls answer the same before any launch
-    assert lib.gode_gat_agg_f32_fwd(None, None, None, None, 16, None, None, None, 0.0, None, None, None, None) == E_NULLPTR
+    assert lib.gode_gat_agg_f32_fwd(None, None, None, None, 16, None, None, None, 0.0, None, None, None, None, None) == E_NULLPTR
     g, p = graph(700), proj(513)
     assert lib.gode_gat_agg_f32_fwd(ctypes.byref(g), vp(P["src"]), vp(P["tgt"]), ctypes.byref(p), 513, None, vp(P["a"]),
-                                    vp(P["amax"]), 0.0, vp(P["out"]), vp(P["w"]), vp(P["den"]), None) == E_UNSUPPORTED
+                                    vp(P["amax"]), 0.0, vp(P["out"]), vp(P["w"]), vp(P["den"]), None, None) == E_UNSUPPORTED
     assert lib.gode_gat_scatter_f32(None, None, None, None, None, None, 16, 0, None, 16, None, 16, None, None, 2, None) == 0
+
+
+def test_null_a_zeroed_struct_and_relu_with_the_outer_relu_are_one_spelling():
+    """The `act` argument of the cases above was NULL.  A zeroed gode_gat_act_t and {RELU, nan, 1} (a parameter relu does not
+    read, an outer relu that is the identity there) answer the same on every one of them: the route twin everywhere, the
+    launching call wherever it returns before a launch (the pointers are made up, so nothing here may reach one)."""
+    def spellings():
+        return (None, _lib.GatAct(), _lib.GatAct(0, float("nan"), 1))
+    f_cases = [((n, o), dict(no_bf=nb)) for o in range(1, 513) for n in (BELOW, ABOVE) for nb in (False, True)]
+    b_cases = [((n, o, terms), {}) for o in range(1, 513) for n in (BELOW, ABOVE) for terms in (0, 1, 3, 8)]
+    for o in PF_WIDTHS:
+        f_cases += [((BELOW, o), brk) for brk in BREAK_FWD]
+        b_cases += [((BELOW, o, 0), brk) for brk in BREAK_BWD + [dict(bf=4)]]
+        b_cases += [((BELOW, o, 3), brk) for brk in (dict(term=4), dict(out=4), dict(dz=8), dict(no_dout=True), dict(dout=4))]
+    for o in REC_WIDTHS:
+        f_cases += [((ABOVE, o), brk) for brk in BREAK_FWD]
+        f_cases += [((ABOVE, o), dict(g=g)) for g in (graph(ABOVE, col=True), graph(ABOVE, items=False), graph(ABOVE, n_long=3))]
+        b_cases += [((ABOVE, o, 0), brk) for brk in BREAK_BWD + [dict(ld_dpt=2), dict(dpt=False), dict(dat=False), dict(did=False)]]
+        b_cases += [((ABOVE, o, 3), brk) for brk in (dict(term=4), dict(ldt=1), dict(dpt=False), dict(g=graph(ABOVE, n_long=3)))]
+    refused_f = [((BELOW, 513), {}), ((0, 16), {}), ((-1, 16), {}), ((700, 0), {}), ((700, 16), dict(lds=-1)), ((2 ** 31, 16), {})]
+    refused_b = [((ABOVE, 513, 3), {}), ((0, 16), {}), ((700, -3), {}), ((2 ** 31, 16), {}), ((700, 16, 0), dict(no_dout=True)),
+                 ((700, 16, 9), {})]
+    for call, cases, refused in ((fwd, f_cases, refused_f), (bwd, b_cases, refused_b)):
+        for args, kw in cases:
+            codes = {call(*args, act=s, **kw) for s in spellings()}
+            assert len(codes) == 1 and codes.pop() > 0, (args, kw)
+        for args, kw in refused:
+            twin = {call(*args, act=s, **kw) for s in spellings()}
+            assert len(twin) == 1 and max(twin) <= 0, (args, kw)          # asserted BEFORE the launching call is made
+            zero = dict(zeroes_flag=True) if call is bwd else {}           # the activation passed: a launching call zeroes the flag
+            assert {call(*args, act=s, launch=True, **zero, **kw) for s in spellings()} == twin, (args, kw)
 
 
 def test_logits_and_maxpath_thresholds():

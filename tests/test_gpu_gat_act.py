@@ -1,5 +1,6 @@
 """The message activation of the edge-attention kernels (csrc/edge.hip: the ActAny instantiations behind
-gode_gat_agg_act_f32_fwd / _bwd) against a float64 restatement, route by route, and the layers that reach them.
+the gode_gat_act_t argument of gode_gat_agg_f32_fwd / _bwd)
+against a float64 restatement, route by route, and the layers that reach them.
 
 Restatement.  `reference` below is tests/gat_routes_design.py's arithmetic (float64, index_add only, independent of the
 library and of oracle/) with act / act' in place of the clamp and the mask, dout form only; it fills the same fields, so

@@ -1,5 +1,6 @@
-"""The fused GAT ODE function under message activations other than relu (gode_gat_agg_ode_f32_fwd / _bwd,
-gode_gat_agg_heads_ode_f32_fwd; `act, act_param` of gode_gat_odefunc_t; gat_ode.GatOdeField / GatOdeAdjointField) on the GPU.
+"""The fused GAT ODE function under message activations other than relu (outer_relu of gode_gat_act_t on
+gode_gat_agg_f32_fwd / _bwd and gode_gat_agg_heads_f32_fwd;
+`act, act_param` of gode_gat_odefunc_t; gat_ode.GatOdeField / GatOdeAdjointField) on the GPU.
 
 Kernels: against a float64 restatement with torch's own activations and autograd on tests/gat_routes_design.py's designed
 inputs, under that family's metric (errors relative to the ROW's own scale, all-zero rows exactly zero) and bound D.TOL = 2e-5
@@ -206,7 +207,7 @@ def heads_case(H=2, o=8, n=300, E=4500):
 
 @pytest.mark.parametrize("name", ["elu", "tanh"])
 def test_forward_heads_raw_logit_route(name):
-    """gode_gat_agg_heads_ode_f32_fwd: every virtual row shifted by its head's maximum, reduced in the kernel from the partial
+    """gode_gat_agg_heads_f32_fwd with outer_relu: every virtual row shifted by its head's maximum, reduced in the kernel from the partial
     maxima of the raw-logit launch (HeadMax), relu outside."""
     from graph_odenet_amd import _lib, ops
     c = heads_case()

@@ -3,8 +3,8 @@
 8 heads x 8) by the message activation of the ODE function's attention layer, in one process with the variants taking turns
 round by round:
 
-  relu fused     the reference's activation on the fused fields (gat_ode.py; the relu entry points)
-  elu fused      F.elu on the fused fields (gode_gat_agg_ode_*: message activation inside, the function's relu outside)
+  relu fused     the reference's activation on the fused fields (gat_ode.py; the ActRelu kernels)
+  elu fused      F.elu on the fused fields (gode_gat_act_t with outer_relu: message activation inside, the function's relu outside)
   tanh fused     torch.tanh likewise
   elu unfused    F.elu with the function's gode_fields hook giving None: every evaluation as autograd through the layer
                  (odeint.AutogradField) - what any activation but relu cost before the fused fields took one
