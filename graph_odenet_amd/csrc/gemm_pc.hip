@@ -707,6 +707,119 @@ __global__ __launch_bounds__(768) void gn_gemm_bwd_wgrad_pc_kernel(LinComb xin, 
     __syncthreads();                                                       // pairs with the producers' barrier before the time row
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// The forward rk4 solve of ISOLATED rows in one launch.  A row whose only entry in A and in A^T is its own diagonal obeys
+// x_i' = relu(a_ii [t | GN(x_i)] W + b): nothing of another row enters, over any number of steps.  With four channels per
+// GroupNorm group (or no GroupNorm) the lane of a consumer wave that owns output columns c0 .. c0 + 3 of a row owns a whole
+// group of the stage input as well, so it can keep y, k_0 .. k_2 of its two rows in registers (32) for the whole solve.
+//
+// 512 threads = the eight consumer waves of gn_gemm_fwd_pc_kernel and nobody else; TWO blocks per CU, each on its own
+// tile, so that one block's staging (vector ALU, LDS stores) runs beside the other's matrix phase.  Per 32-row tile: load y
+// and a_ii once; per step and stage the statements of the launches this one replaces, on the same numbers in the same
+// order - the stage combination (fmaf chain from 0, terms in stage_terms order), gn_forward_v, split3_trunc / stage_row4
+// into the piece image, tile_product on acc = t W[0, :], then the DIAG epilogue k = max(fmaf(a_ii, acc, 0) + b, 0) and at
+// the last stage P by the AUX chain and y_new = fmaf(alpha, k, fmaf(1, P, 0)) - hence the same bits.  Two piece images
+// alternate, one LDS barrier per stage: stage s writes image s & 1, whose last readers (the product of stage s - 2) are
+// all past the barrier of stage s - 1.  The only global traffic is y in, y out: 1 KB per row and solve.
+// ---------------------------------------------------------------------------------------------------------------
+template <int CG>   // 0 or 4
+__global__ __launch_bounds__(512, 4) void gcn_local_tail_rk4_kernel(const float* y_in, float* y_out /* may be y_in */,
+                                                                    int n_rows, const float* __restrict__ a_ii, float eps,
+                                                                    const float* __restrict__ gamma,
+                                                                    const float* __restrict__ beta,
+                                                                    const float* __restrict__ W,
+                                                                    const float* __restrict__ bias, LocalTailSteps st)
+{
+    constexpr int R = 32, PIECE_B = Img<R>::PIECE_B, BUF_B = Img<R>::BUF_B;
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    char* lds = reinterpret_cast<char*>(smem);
+    const int wave = threadIdx.x >> 6, l = threadIdx.x & 63, r = l & 15, g = l >> 4;
+    const int n0 = 16 * wave, c0 = n0 + 4 * g;
+    bf16x8 A[4][3];
+    load_weight_pieces(A, [&](int m, int k) { return W[(int64_t)(k + 1) * D + n0 + m]; });          // W1^T slab
+    // the lane's columns of W[0, :], bias, gamma, beta: in LDS behind the images and read where used - none of the 16
+    // values is live across the matrix phase (128 registers: two blocks per CU)
+    float* cst = reinterpret_cast<float*>(lds + 2 * BUF_B);
+    if (threadIdx.x < D) {
+        cst[threadIdx.x] = W[threadIdx.x];
+        cst[D + threadIdx.x] = bias[threadIdx.x];
+        cst[2 * D + threadIdx.x] = gamma ? gamma[threadIdx.x] : 1.f;
+        cst[3 * D + threadIdx.x] = beta ? beta[threadIdx.x] : 0.f;
+    }
+    __syncthreads();
+    const int rd_off = r * LDK * 2 + g * 16;
+    const int wr_off = r * LDK * 2 + c0 * 2;
+    const int n_tiles = (n_rows + R - 1) / R;
+    for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        float4 y[2], k[3][2];
+        float dsc[2];
+        bool valid[2];
+#pragma unroll
+        for (int rt = 0; rt < 2; ++rt) {
+            const int row = tile * R + r + 16 * rt;
+            valid[rt] = row < n_rows;
+            const int rc = valid[rt] ? row : n_rows - 1;
+            y[rt] = ld4(y_in + (int64_t)rc * D + c0);
+            dsc[rt] = a_ii[rc];
+#pragma unroll
+            for (int j = 0; j < 3; ++j) k[j][rt] = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+        for (int i = 0; i < st.n_steps; ++i) {
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                char* img = lds + (s & 1) * BUF_B;
+                const float4 gmv = ld4(cst + 2 * D + c0), btv = ld4(cst + 3 * D + c0);
+#pragma unroll
+                for (int rt = 0; rt < 2; ++rt) {
+                    float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+                    for (int j = 0; j <= s; ++j) {           // the term order and arithmetic of lc_load4_n
+                        const float c = st.coef[s][j];
+                        const float4 v = j == 0 ? y[rt] : k[j - 1][rt];
+                        x.x = fmaf(c, v.x, x.x); x.y = fmaf(c, v.y, x.y); x.z = fmaf(c, v.z, x.z); x.w = fmaf(c, v.w, x.w);
+                    }
+                    float4 xn = gn_forward_v<CG>(x, eps, gmv, btv);
+                    if (!valid[rt]) xn = make_float4(0.f, 0.f, 0.f, 0.f);
+                    stage_row4<PIECE_B>(img + wr_off + rt * 16 * LDK * 2, xn);
+                }
+                lds_barrier();
+                const float t = st.ts[i][s];
+                const float4 w0 = ld4(cst + c0);
+                const f32x4 t0 = {t * w0.x, t * w0.y, t * w0.z, t * w0.w};
+                f32x4 acc[2] = {t0, t0};
+                tile_product<R>(img + rd_off, A, acc);
+                const float4 bv = ld4(cst + D + c0);
+#pragma unroll
+                for (int rt = 0; rt < 2; ++rt) {
+                    float m[4];
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) {
+                        m[c] = fmaf(dsc[rt], acc[rt][c], 0.f);
+                        asm volatile("" : "+v"(m[c]));        // the record's sum is rounded before the bias is added
+                    }
+                    float4 kv = make_float4(fmaxf(m[0] + bv.x, 0.f), fmaxf(m[1] + bv.y, 0.f), fmaxf(m[2] + bv.z, 0.f), fmaxf(m[3] + bv.w, 0.f));
+                    if (s < 3) {
+                        k[s][rt] = kv;
+                    } else {                                  // the closing combination P (the AUX chain), then
+                        float4 a = make_float4(0.f, 0.f, 0.f, 0.f);   // epilogue_store4 with pre = {1.0, P}
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) {
+                            const float c = st.acoef[j];
+                            const float4 v = j == 0 ? y[rt] : k[j - 1][rt];
+                            a.x = fmaf(c, v.x, a.x); a.y = fmaf(c, v.y, a.y); a.z = fmaf(c, v.z, a.z); a.w = fmaf(c, v.w, a.w);
+                        }
+                        y[rt] = make_float4(fmaf(st.alpha, kv.x, fmaf(1.f, a.x, 0.f)), fmaf(st.alpha, kv.y, fmaf(1.f, a.y, 0.f)),
+                                            fmaf(st.alpha, kv.z, fmaf(1.f, a.z, 0.f)), fmaf(st.alpha, kv.w, fmaf(1.f, a.w, 0.f)));
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int rt = 0; rt < 2; ++rt)
+            if (valid[rt]) *reinterpret_cast<float4*>(y_out + (int64_t)(tile * R + r + 16 * rt) * D + c0) = y[rt];
+    }
+}
+
 int64_t pc_blocks(int64_t n_rows, int R) {
     int64_t b = (n_rows + R - 1) / R;
     if (b < 1) b = 1;
@@ -849,5 +962,30 @@ int gode_pc_bwd_wgrad_launch(const LinComb& lc, int64_t n_rows, float eps, const
     if (cg == 0) GODE_BWN(0) else if (cg == 4) GODE_BWN(4)
 #undef GODE_BWN
 #undef GODE_BW
+    return GODE_E_UNSUPPORTED;
+}
+
+// the forward rk4 solve of n_rows isolated rows (gcn_local_tail_rk4_kernel): st.n_steps <= GODE_LOCAL_TAIL_MAX_STEPS steps
+// from y_in into y_out (the same array is fine).  blocks <= 0: kBlocks / 2 = 128 (the driver chooses: ode_driver.hip).
+int gode_pc_local_tail_launch(const float* y_in, float* y_out, int64_t n_rows, const float* a_ii, float eps,
+                              const float* gamma, const float* beta, const float* W, const float* bias,
+                              const LocalTailSteps& st, int cg, int blocks, hipStream_t s)
+{
+    if (n_rows <= 0 || n_rows > INT32_MAX || st.n_steps <= 0 || st.n_steps > GODE_LOCAL_TAIL_MAX_STEPS) return GODE_E_UNSUPPORTED;
+    if (!y_in || !y_out || !a_ii || !W || !bias) return GODE_E_UNSUPPORTED;
+    const int64_t tiles = (n_rows + 31) / 32;
+    int64_t nb = blocks > 0 ? blocks : kBlocks / 2;
+    if (nb > tiles) nb = tiles;
+    const size_t lds = 2 * (size_t)Img<32>::BUF_B + 4 * D * sizeof(float);      // two images | W[0, :], bias, gamma, beta
+    int rc = 0;
+#define GODE_LT(CGV)                                                                                               \
+    { rc = set_lds_pc(gcn_local_tail_rk4_kernel<CGV>, lds); if (rc) return rc;                                      \
+      const int slot = gode_prof_begin(s, D, n_rows, 0, GODE_PROF_LOCAL_TAIL | GODE_PROF_FORM_PC);                  \
+      hipLaunchKernelGGL((gcn_local_tail_rk4_kernel<CGV>), dim3((unsigned)nb), dim3(512), lds, s,                   \
+                         y_in, y_out, (int)n_rows, a_ii, eps, gamma, beta, W, bias, st);                           \
+      gode_prof_end(s, slot);                                                                                      \
+      GODE_LAUNCH_CHECK(); return 0; }
+    if (cg == 0) GODE_LT(0) else if (cg == 4) GODE_LT(4)
+#undef GODE_LT
     return GODE_E_UNSUPPORTED;
 }

@@ -23,6 +23,7 @@
 #include <mutex>
 #include <utility>
 #include "rk_driver.h"
+#include "dense_pc.h"
 #include "options.h"
 
 namespace {
@@ -198,6 +199,77 @@ int rk4_forward_step(const gode_gcn_odefunc_t* f, const gode_rk4_workspace_t* ws
     return 0;
 }
 
+// Side stream + events for the two-chain schedule of the adjoint solve (and the tail launch of the forward solve:
+// tail_in / tail_out): one set per (device, caller stream), created
+// on first use and kept for the life of the process, so that two caller streams (or two threads, each on its own
+// stream) never share a side stream or an event.  The map is the only mutable state here and is mutex-guarded.
+struct Overlap {
+    hipStream_t side = nullptr;
+    hipEvent_t sp = nullptr, gf = nullptr, spt = nullptr, wg = nullptr, tail_in = nullptr, tail_out = nullptr;
+    bool ok = false;
+};
+Overlap* overlap_ctx(hipStream_t caller) {
+    static std::mutex mu;
+    static std::map<std::pair<int, hipStream_t>, Overlap*> ctxs;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return nullptr;
+    std::lock_guard<std::mutex> lk(mu);
+    auto key = std::make_pair(dev, caller);
+    auto it = ctxs.find(key);
+    if (it != ctxs.end()) return it->second;
+    Overlap* c = new Overlap();
+    if (hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking) == hipSuccess) {
+        bool ok = true;
+        for (hipEvent_t* ev : {&c->sp, &c->gf, &c->spt, &c->wg, &c->tail_in, &c->tail_out})
+            ok = ok && hipEventCreateWithFlags(ev, hipEventDisableTiming) == hipSuccess;
+        c->ok = ok;
+    }
+    ctxs[key] = c;
+    return c;
+}
+
+// Isolated rows at the end of the state (option local_tail; gode_gcn_odefunc_t: n_tail).  Such a row's ODE is local to
+// the row, so one launch integrates rows [n - n_tail, n) over the whole solve (gemm_pc.hip: gcn_local_tail_rk4_kernel,
+// the statements of the DIAG launches on the same numbers: same bits) and every dense launch of the solve runs on the
+// rows before them.  The SpMM launches never held those rows (A's core list).  Only where EVERY dense launch of the
+// solve takes its DIAG form - otherwise another kernel's arithmetic would have made those rows.
+// -> channels per GroupNorm group of the tail kernel (0 / 4), or -1: no tail launch.
+int local_tail_cg(const gode_gcn_odefunc_t* f, const gode_rk4_workspace_t* ws, const float* y, bool diag_ok, bool close_once) {
+    if (!gode_opt_local_tail() || !diag_ok || !close_once || !gode_opt_diag_last() || gode_opt_fwd_pc() != 3) return -1;
+    if (f->n_tail <= 0 || f->n_tail >= f->n || f->n - f->n_tail <= kMergedFinishMaxRows) return -1;
+    const int cg = f->groups == 0 ? 0 : (f->groups > 0 && f->d % f->groups == 0 && f->d / f->groups == 4) ? 4 : -1;
+    uintptr_t bits = (uintptr_t)y | (uintptr_t)ws->S | (uintptr_t)f->W | (uintptr_t)f->b | (uintptr_t)f->gamma | (uintptr_t)f->beta;
+    for (int j = 0; j < 4; ++j) bits |= (uintptr_t)ws->ky[j];
+    return (bits & 15) || !f->W || !f->b ? -1 : cg;
+}
+
+// The launches of the tail solve on stream s: n_steps steps from y's tail rows into those of `res` (y itself is fine: a
+// block reads its tile before it writes it).  A launch covers GODE_LOCAL_TAIL_MAX_STEPS steps; further ones go on in `res`.
+int local_tail_solve(const gode_gcn_odefunc_t* f, const float* y, float* res, float t0, double h, int32_t n_steps, int cg,
+                     int blocks, hipStream_t s) {
+    const int64_t off = (f->n - f->n_tail) * f->d;
+    float* const kdummy[4] = {nullptr, nullptr, nullptr, nullptr};
+    LocalTailSteps st = {};
+    for (int q = 0; q < 4; ++q) {
+        const gode_lincomb_t lc = stage_terms(nullptr, kdummy, q, h);
+        if (lc.n != q + 1) return GODE_E_UNSUPPORTED;
+        for (int j = 0; j <= q; ++j) st.coef[q][j] = lc.coef[j];
+    }
+    const gode_lincomb_t pre = combine_terms(nullptr, kdummy, h);
+    for (int j = 0; j < 4; ++j) st.acoef[j] = pre.coef[j];
+    st.alpha = (float)(h * B38[3]);
+    const float* src = y + off;
+    for (int i0 = 0; i0 < n_steps; i0 += GODE_LOCAL_TAIL_MAX_STEPS) {
+        st.n_steps = n_steps - i0 < GODE_LOCAL_TAIL_MAX_STEPS ? n_steps - i0 : GODE_LOCAL_TAIL_MAX_STEPS;
+        for (int i = 0; i < st.n_steps; ++i)
+            for (int q = 0; q < 4; ++q) st.ts[i][q] = (float)(((double)t0 + (i0 + i) * h) + C38[q] * h);   // rk4_forward_step's
+        GODE_TRY(gode_pc_local_tail_launch(src, res + off, f->n_tail, f->a_diag + (f->n - f->n_tail), f->eps, f->gamma, f->beta,
+                                           f->W, f->b, st, cg, blocks, s));
+        src = res + off;
+    }
+    return 0;
+}
+
 }  // namespace
 
 extern "C" int64_t gode_gcn_ode_theta_len(int64_t d) { return (d + 1) * d + 3 * d + 1; }
@@ -219,43 +291,51 @@ extern "C" int gode_gcn_ode_rk4_forward(const gode_gcn_odefunc_t* f, float* y, f
     // to the consumer waves through LDS, and the consumer is the only writer of a diagonal-only row of y_new.
     const bool diag_ok = gode_opt_diag_rows() && !fused && f->n > kMergedFinishMaxRows && f->d == 128 && f->a_core_items &&
                          f->a_diag && f->at_diag && f->A.items && f->a_n_core > 0 && f->a_n_core <= f->A.n_items;
-    for (int i = 0; i < n_steps; ++i) {
-        GODE_TRY(rk4_forward_step(f, ws, cur, k, k[3], false, (double)t0 + i * h, h, fused, close_once, stream, diag_ok));
+    // isolated tail rows (option local_tail): one launch of their own writes them into the buffer *result will name (the
+    // buffers swap once per step); the steps below then run their dense launches on the rows before the tail.  Outside a
+    // capture and with option overlap the launch goes to the side stream, beside the solve's HBM-bound SpMM launches: it
+    // waits for what the caller's stream held at entry, and the caller's stream joins it before the return.
+    const int tail_cg = local_tail_cg(f, ws, y, diag_ok, close_once);
+    gode_gcn_odefunc_t fcore;
+    Overlap* ov = nullptr;
+    if (tail_cg >= 0) {
+        hipStream_t hs = (hipStream_t)stream;
+        float* res = (n_steps & 1) ? ws->ky[3] : y;
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (gode_opt_overlap() && hipStreamIsCapturing(hs, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone) {
+            ov = overlap_ctx(hs);
+            if (ov && !ov->ok) ov = nullptr;
+        }
+        if (ov) {
+            GODE_HIP(hipEventRecord(ov->tail_in, hs));
+            GODE_HIP(hipStreamWaitEvent(ov->side, ov->tail_in, 0));
+        }
+        // grid (measured at 2^20 x 128, 45 % of the rows in the tail): beside the solve 128 blocks - the
+        // dense launches want whole CUs, and a chip-filling tail launch makes them queue behind it; alone on the caller's
+        // stream the full chip, two blocks per CU (128 blocks there take twice as long as the launches they replace save)
+        const int blocks = gode_opt_local_tail_blocks() > 0 ? gode_opt_local_tail_blocks() : ov ? 128 : 512;
+        const int rc = local_tail_solve(f, y, res, t0, h, n_steps, tail_cg, blocks, ov ? ov->side : hs);
+        if (ov) {                                      // joined on every path: the side stream never outlives the call
+            (void)hipEventRecord(ov->tail_out, ov->side);
+            if (rc) (void)hipStreamWaitEvent(hs, ov->tail_out, 0);
+        }
+        if (rc) return rc;
+        fcore = *f;
+        fcore.n = f->n - f->n_tail;                     // Gf of every stage; the SpMM launches take their rows from f->A
+        f = &fcore;
+    }
+    int rc = 0;
+    for (int i = 0; i < n_steps && !rc; ++i) {
+        rc = rk4_forward_step(f, ws, cur, k, k[3], false, (double)t0 + i * h, h, fused, close_once, stream, diag_ok);
         float* tmp = cur; cur = k[3]; k[3] = tmp;      // k[3] holds the new solution
     }
+    if (ov) GODE_HIP(hipStreamWaitEvent((hipStream_t)stream, ov->tail_out, 0));
+    if (rc) return rc;
     *result = cur;
     return 0;
 }
 
 namespace {
-
-// Side stream + events for the two-chain schedule of the adjoint solve: one set per (device, caller stream), created
-// on first use and kept for the life of the process, so that two caller streams (or two threads, each on its own
-// stream) never share a side stream or an event.  The map is the only mutable state here and is mutex-guarded.
-struct Overlap {
-    hipStream_t side = nullptr;
-    hipEvent_t sp = nullptr, gf = nullptr, spt = nullptr, wg = nullptr;
-    bool ok = false;
-};
-Overlap* overlap_ctx(hipStream_t caller) {
-    static std::mutex mu;
-    static std::map<std::pair<int, hipStream_t>, Overlap*> ctxs;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return nullptr;
-    std::lock_guard<std::mutex> lk(mu);
-    auto key = std::make_pair(dev, caller);
-    auto it = ctxs.find(key);
-    if (it != ctxs.end()) return it->second;
-    Overlap* c = new Overlap();
-    if (hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking) == hipSuccess) {
-        bool ok = true;
-        for (hipEvent_t* ev : {&c->sp, &c->gf, &c->spt, &c->wg})
-            ok = ok && hipEventCreateWithFlags(ev, hipEventDisableTiming) == hipSuccess;
-        c->ok = ok;
-    }
-    ctxs[key] = c;
-    return c;
-}
 
 // Launch-bound graphs, fused launches: two per stage - f-eval (+ masked cotangent dZ), VJP (+ block partials) - and one
 // more per step; a single stream.

@@ -144,6 +144,7 @@ def _func_struct(spec):
         fs.at_core_items, fs.at_n_core, fs.at_diag = core.items.data_ptr(), core.n_items, core.diag.data_ptr()
         a = spec.graph.__dict__["_a_core"]
         fs.a_core_items, fs.a_n_core, fs.a_diag = a.items.data_ptr(), a.n_items, a.diag.data_ptr()
+        fs.n_tail = spec.graph.__dict__.get("_n_tail", 0)       # rows [n - n_tail, n): all isolated (local_tail_rows)
     return fs
 
 
@@ -217,6 +218,15 @@ CORE_LIST_MIN_ROWS = 65536
 CORE_LIST_MIN_SHARE_INV = 8
 
 
+def local_tail_rows(g):
+    """n_tail of the ODE block (include/graphode.h: gode_gcn_odefunc_t): the length of the longest suffix of rows of `g` that
+    are all isolated - after the hubs-first renumbering of a graph with self loops everywhere that is every isolated row,
+    degree sum 2 being the minimum - where it is at least the share of the rows the core lists ask for; else 0.  The forward
+    rk4 solve integrates such rows in one row-local launch (csrc/ode_driver.hip, option local_tail)."""
+    n_tail = g.isolated_tail()
+    return n_tail if CORE_LIST_MIN_SHARE_INV * n_tail >= g.n_rows else 0
+
+
 def _hand_core_list(g, info):
     """Decide (from counts alone) whether the ODE block gets the core lists of A and A^T; if so build them on `g`."""
     if getattr(g, "items", None) is None or g.n_rows <= CORE_LIST_MIN_ROWS or g.transpose().items is None:
@@ -230,7 +240,9 @@ def _hand_core_list(g, info):
         g.__dict__["_at_core"] = iso if take else None
         g.__dict__["_a_core"] = g.diag_rows() if take else None      # A's list for the forward solve: every diagonal-only row of A
         g.__dict__["_isolated_count"] = iso.n_flagged
-    info.update(isolated_rows=g.__dict__["_isolated_count"], core_lists=g.__dict__["_at_core"] is not None)
+        g.__dict__["_n_tail"] = local_tail_rows(g) if take else 0
+    info.update(isolated_rows=g.__dict__["_isolated_count"], core_lists=g.__dict__["_at_core"] is not None,
+                n_tail=g.__dict__["_n_tail"])
 
 
 def tuned_graph(graph, d, node_order="auto"):

@@ -117,6 +117,13 @@ class CSRGraph:
             self._isolated_rows = DiagRows(self, among=self.transpose().diag_rows().diag)
         return self._isolated_rows
 
+    def isolated_tail(self):
+        """Length of the longest suffix of rows that isolated_rows() flags, all of them (0: the last row is not isolated).
+        Exact integer arithmetic; one host synchronisation."""
+        flagged = self.isolated_rows().diag != 0
+        other = torch.nonzero(~flagged).flatten()
+        return self.n_rows - (int(other[-1]) + 1 if other.numel() else 0)
+
     # -- transpose (CSR by source) for the backward pass -----------------------
     def transpose(self):
         if self._T is None:

@@ -78,9 +78,14 @@ int         gode_abi_version(void);
  * "diag_rows" (1 default / 0: the rk4 forward and adjoint drivers use the core record lists of A and A^T where the ODE
  * function carries them, see gode_gcn_odefunc_t; 0: the full lists; same bits either way), "diag_last" (1 default / 0:
  * under "diag_rows" and "rk_close_once" the last stage of a forward rk4 step uses A's core list as well,
- * gode_gn_time_gemm_diag_aux_f32; 0: stages 0-2 only; same bits either way).
+ * gode_gn_time_gemm_diag_aux_f32; 0: stages 0-2 only; same bits either way), "local_tail" (1 default / 0: under
+ * "diag_rows", "diag_last" and "rk_close_once" with "fwd_pc" 3, gode_gcn_ode_rk4_forward integrates the n_tail isolated
+ * rows at the end of the state, see gode_gcn_odefunc_t, in one launch of their own - on a side stream beside the solve
+ * when "overlap" is on and the stream is not capturing - and runs its dense launches on the rows before them; same bits
+ * either way), "local_tail_blocks" (0 default: 128 blocks of 512 threads beside the solve, 512 on
+ * the caller's stream; 1..4096: that many blocks; two fit a CU).
  * Initial values come from GODE_GEMM_SPLIT / GODE_OVERLAP / GODE_WGRAD_SPLIT / GODE_BWD_PC / GODE_FWD_PC / GODE_SPMM_PIPE /
- * GODE_DIAG_ROWS / GODE_DIAG_LAST.
+ * GODE_DIAG_ROWS / GODE_DIAG_LAST / GODE_LOCAL_TAIL / GODE_LOCAL_TAIL_BLOCKS.
  * Returns 0 or GODE_E_UNSUPPORTED. */
 int         gode_set_option(const char* name, int value);
 int         gode_get_option(const char* name);
@@ -645,6 +650,11 @@ typedef struct gode_gcn_odefunc {
      * the stage's SpMM on the core list - per launch, where the dense launch reports that form taken.  The last stage
      * does the same on the closed step (gode_gn_time_gemm_diag_aux_f32; options "rk_close_once" and "diag_last"). */
     const int32_t* a_core_items; int64_t a_n_core; const float* a_diag;
+    /* 0 when absent.  The rows [n - n_tail, n) are ALL isolated in A and A^T (their a_ii in a_diag, which must be set):
+     * such a row's ODE is local to the row, so gode_gcn_ode_rk4_forward (option "local_tail", where the lists above are
+     * in use, d = 128, 4 channels per GroupNorm group or no GroupNorm) integrates them over the whole solve in one launch
+     * of their own and runs every dense launch of the solve on the first n - n_tail rows; same bits. */
+    int64_t n_tail;
 } gode_gcn_odefunc_t;
 
 typedef struct gode_rk4_workspace {
@@ -1078,6 +1088,8 @@ int gode_edge_ode_step_close_f32(int32_t n_stages, const float* const* wpart /* 
 #define GODE_PROF_EDGE_STEP_CLOSE 10   /* gode_edge_ode_step_close_f32: one pass per RK step */
 /* csrc/gat_small.hip (rows = nodes; extra = stages closed) */
 #define GODE_PROF_GAT_STEP_CLOSE 11    /* gode_gat_small_close_stages_f32: one pass per swept step of a backprop sweep */
+#define GODE_PROF_LOCAL_TAIL 12        /* gode_gcn_ode_rk4_forward, option "local_tail": the whole forward solve of the isolated
+                                          tail rows (rows = n_tail), up to 16 steps x 4 products of n_tail x d x d per launch */
 /* which kernel of the family ran, OR-ed into the kind of a dense launch (kind & 0xff = family, kind >> 8 = form):
  * exact-fp32 MFMA kernel; bf16-piece kernel, every wave loading + cutting + multiplying; bf16-piece kernel in
  * producer / consumer form (wgrad_split_kernel, gemm_pc.hip) */

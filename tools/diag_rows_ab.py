@@ -8,7 +8,8 @@ the option existed (the forward solve's products with A and the adjoint's produc
 no row stored by the dense launch or by the launch that forms dZ in their place), so the 0 readings are the yardstick; a gain counts when every 1 reading beats every 0 reading and the mean gap is at
 least three times the spread among readings of the same setting (--min-ratio; diag_last was held to five times).
 diag_last 0 likewise issues the launches of the code before that option: the last stage of every forward rk4 step on A's
-full list.
+full list.  local_tail 0 (under diag_rows 1 and diag_last 1): every row through every dense launch of the forward solve, no
+tail launch; --set holds further options fixed over all readings (local_tail_blocks, overlap).
 
     python tools/diag_rows_ab.py [--option diag_rows] [--scale 20] [--edges 10000000] [--ode-steps 16] [--steps 3] [--warmup 1]
 """
@@ -34,7 +35,9 @@ def main():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--order", default="1,0,1,0,1", help="settings of the option, one reading each")
-    ap.add_argument("--option", default="diag_rows", choices=["diag_rows", "diag_last"])
+    ap.add_argument("--option", default="diag_rows", choices=["diag_rows", "diag_last", "local_tail"])
+    ap.add_argument("--set", action="append", default=[], metavar="NAME=VALUE",
+                    help="another option held fixed over all readings (e.g. local_tail_blocks=128, overlap=0)")
     ap.add_argument("--min-ratio", type=float, default=3.0, help="mean gap over same-setting spread that counts as a gain")
     args = ap.parse_args()
     from graph_odenet_amd import _lib, models, parallel
@@ -66,8 +69,12 @@ def main():
 
     name = args.option.encode()
     old = lib.gode_get_option(name)
+    fixed = {kv.split("=")[0].encode(): int(kv.split("=")[1]) for kv in args.set}
+    old_fixed = {k: lib.gode_get_option(k) for k in fixed}
     readings = []
     try:
+        for k, v in fixed.items():
+            assert lib.gode_set_option(k, v) == 0 and lib.gode_get_option(k) == v, k
         for _ in range(2):                       # both settings' kernels loaded before the first reading
             for v in (1, 0):
                 assert lib.gode_set_option(name, v) == 0
@@ -81,9 +88,13 @@ def main():
             print("%s %d: %8.2f ms/step   (loss %.5f)" % (args.option, v, ms, float(loss)), flush=True)
     finally:
         lib.gode_set_option(name, old)
+        for k, v in old_fixed.items():
+            lib.gode_set_option(k, v)
     on = [ms for v, ms in readings if v == 1]
     off = [ms for v, ms in readings if v == 0]
     res = {"readings": [{args.option: v, "ms_per_step": round(ms, 2)} for v, ms in readings]}
+    if fixed:
+        res["fixed"] = {k.decode(): v for k, v in fixed.items()}
     if on and off:
         gap = sum(off) / len(off) - sum(on) / len(on)
         spread = max(max(on) - min(on), max(off) - min(off))
