@@ -1878,7 +1878,7 @@ extern "C" int gode_edge_matvec_f32_fwd(const int32_t* rowptr, const int32_t* ei
                                         int64_t h, int64_t n_rows, float* out, int64_t ldo, void* stream) {
     if (n_rows < 0 || h <= 0 || ldx < h || ldo < h) return GODE_E_SHAPE;
     if (n_rows == 0) return 0;
-    if (!rowptr || !eid || !src || !A || !X || !out) return GODE_E_NULLPTR;
+    if (!rowptr || !src || !A || !X || !out) return GODE_E_NULLPTR;    // eid NULL: edge k is slot k; val NULL: ones
     if (n_rows > INT32_MAX || h > 4096) return GODE_E_RANGE;
     const int64_t rpt = kMsgTile / h > 0 ? kMsgTile / h : 1;
     const size_t lds = (size_t)(2 * ((h + 3) & ~(int64_t)3) + (rpt < h ? rpt : h) * h) * sizeof(float);

@@ -554,6 +554,7 @@ int gode_time_row_fixup3_f32(float* g0, const float* w0, int64_t l0, float* g1, 
 
 /* ---- QC edge-conditioned messages (QC/mpnn.py:27-29, QC/layers.py:143-145) ----------------
  * out[v,:] = sum_k val[k] * A[e_k] (h x h, row-major) * X[src[e_k], :]   over row v of Etgt (CSR).
+ *   eid nullable: e_k = k (edges sorted by target);  val nullable: ones.
  * Backward (one block per edge): dm = edge_val[e] * dM[edge_row[e], :] (edge_row < 0: edge unused),
  *   dA[e] = dm (x) X[src[e]]   (nullable),   dxe[e,:] = A[e]^T dm   (nullable; the caller sums dxe
  *   per source node with gode_spmm_csr_f32 over the src incidence matrix). */
