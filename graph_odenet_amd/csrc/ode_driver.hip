@@ -918,6 +918,177 @@ extern "C" int gode_gcn_ode_dopri5_step_backprop(const gode_gcn_odefunc_t* f, co
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// The adaptive step drivers by method (GODE_RKA_*): the three dopri5 step functions above driven by a tableau and its error
+// weights (rk_driver.h: AdaptiveMethod), on the same routes.  The forward and the adjoint step close with the fused
+// launch of rk.hip (gode_rk_close_err_multi_f32): the solution and the error sums from one pass over the stages.
+// ---------------------------------------------------------------------------------------------------------------
+extern "C" int gode_rka_stages(int32_t method)
+{
+    const AdaptiveMethod* am = adaptive_method(method);
+    return am ? am->tab.stages : GODE_E_SHAPE;
+}
+
+extern "C" int gode_rka_order(int32_t method)
+{
+    const AdaptiveMethod* am = adaptive_method(method);
+    return am ? am->order : GODE_E_SHAPE;
+}
+
+extern "C" int gode_rka_tableau(int32_t method, double* c, double* a, double* b, double* e)
+{
+    const AdaptiveMethod* am = adaptive_method(method);
+    if (!am) return GODE_E_SHAPE;
+    const Tableau& tab = am->tab;
+    const int S = tab.stages;
+    for (int s = 0; s < S; ++s) {
+        if (c) c[s] = tab.c[s];
+        if (b) b[s] = tab.b[s];
+        if (e) e[s] = am->e[s];
+        if (a) for (int j = 0; j < S; ++j) a[s * S + j] = j < s ? tab.a[s * tab.lda + j] : 0.0;
+    }
+    return 0;
+}
+
+extern "C" int gode_gcn_ode_adaptive_step_forward(int32_t method, const gode_gcn_odefunc_t* f, const float* y,
+                                                  float* const* k, float* y1, const gode_rk4_workspace_t* ws, double t,
+                                                  double h, float rtol, float atol, double* sums, void* err_scratch,
+                                                  void* stream)
+{
+    if (!f || !y || !k || !y1 || !ws || !sums || !err_scratch) return GODE_E_NULLPTR;
+    const AdaptiveMethod* am = adaptive_method(method);
+    if (!am) return GODE_E_SHAPE;
+    const Tableau& tab = am->tab;
+    const int S = tab.stages;
+    if (f->n <= 0 || f->d <= 0) return GODE_E_SHAPE;
+    for (int s = 0; s < S; ++s) if (!k[s]) return GODE_E_NULLPTR;
+    if (!ws->S) return GODE_E_NULLPTR;
+    const int64_t nd = f->n * f->d;
+    const bool chain = fused_small(f) && ws->X[0] && ws->X[1];                         // as in the dopri5 step
+    for (int s = 1; s < S; ++s) {
+        gode_lincomb_t yin = tab_stage_terms(tab, y, k, s, h);
+        if (chain && s >= 2) yin = one_term(ws->X[s & 1]);
+        gode_lincomb_t nxt; nxt.n = 0;
+        if (chain && s < S - 1) nxt = tab_stage_terms(tab, y, k, s + 1, h);
+        GODE_TRY(dp_eval_forward(f, ws, &yin, (float)(t + tab.c[s] * h), k[s], nxt.n > 0 ? &nxt : nullptr,
+                                 nxt.n > 0 ? ws->X[(s + 1) & 1] : nullptr, stream));
+    }
+    float ec[GODE_MAX_TERMS];
+    const gode_lincomb_t sol = close_terms(*am, y, k, h, ec);
+    const float* ecp = ec;
+    return gode_rk_close_err_multi_f32(&y1, &sol, &ecp, &nd, 1, rtol, atol, sums, err_scratch, stream);
+}
+
+extern "C" int gode_gcn_ode_adaptive_step_adjoint(int32_t method, const gode_gcn_odefunc_t* f, const float* y,
+                                                  const float* a, const float* theta, float* const* ky, float* const* ka,
+                                                  float* const* kth, float* y1, float* a1, float* theta1,
+                                                  const gode_rk4_workspace_t* ws, double t, double h, float rtol,
+                                                  float atol, double* sums /* 4 */, void* err_scratch, void* stream)
+{
+    if (!f || !y || !a || !theta || !ky || !ka || !kth || !y1 || !a1 || !theta1 || !ws || !sums || !err_scratch)
+        return GODE_E_NULLPTR;
+    const AdaptiveMethod* am = adaptive_method(method);
+    if (!am) return GODE_E_SHAPE;
+    const Tableau& tab = am->tab;
+    const int S = tab.stages;
+    if (f->n <= 0 || f->d <= 0) return GODE_E_SHAPE;
+    for (int s = 0; s < S; ++s) if (!ky[s] || !ka[s] || !kth[s]) return GODE_E_NULLPTR;
+    if (!ws->S || !ws->dZ || !ws->dS || !ws->wpart || !ws->colsum_scratch) return GODE_E_NULLPTR;
+    if (f->groups > 0 && (!ws->gpart || !ws->bpart)) return GODE_E_NULLPTR;
+    const int64_t nd = f->n * f->d, P = gode_gcn_ode_theta_len(f->d);
+    const bool fused = fused_small(f) && ws->small_part;
+    const bool chain = fused && ws->X[0] && ws->X[1];
+    for (int s = 1; s < S; ++s) {
+        gode_lincomb_t yin = tab_stage_terms(tab, y, ky, s, h);
+        if (chain && s >= 2) yin = one_term(ws->X[s & 1]);
+        const gode_lincomb_t ain = tab_stage_terms(tab, a, ka, s, h);
+        gode_lincomb_t nxt; nxt.n = 0;
+        if (chain && s < S - 1) nxt = tab_stage_terms(tab, y, ky, s + 1, h);
+        GODE_TRY(dp_eval_adjoint(f, ws, yin, ain, (float)(t + tab.c[s] * h), ky[s], ka[s], kth[s], nxt.n > 0 ? &nxt : nullptr,
+                                 nxt.n > 0 ? ws->X[(s + 1) & 1] : nullptr, fused ? s - 1 : -1, stream));
+    }
+    if (fused) {      // the S - 1 stages' small components in one launch: nothing inside the step reads them
+        float* kout[6]; float tsv[6];
+        for (int s = 1; s < S; ++s) { kout[s - 1] = kth[s]; tsv[s - 1] = (float)(t + tab.c[s] * h); }
+        GODE_TRY(gode_gcn_small_finish_multi_f32(f, ws->small_part, S - 1, kout, tsv, stream));
+    }
+    // one close for the three outputs and the four error groups: y, a, a_t (the last entry of the packed vector) and the
+    // flattened parameters (the P - 1 before it), each group the decomposition the separate error norm gives it
+    float ec[4][GODE_MAX_TERMS];
+    const gode_lincomb_t sols[4] = {close_terms(*am, y, ky, h, ec[0]), close_terms(*am, a, ka, h, ec[1]),
+                                    close_terms(*am, theta, kth, h, ec[2], P - 1), close_terms(*am, theta, kth, h, ec[3])};
+    float* outs[4] = {y1, a1, theta1 + (P - 1), theta1};
+    const float* ecs[4] = {ec[0], ec[1], ec[2], ec[3]};
+    const int64_t lens[4] = {nd, nd, 1, P - 1};
+    return gode_rk_close_err_multi_f32(outs, sols, ecs, lens, 4, rtol, atol, sums, err_scratch, stream);
+}
+
+extern "C" int gode_gcn_ode_adaptive_step_backprop(int32_t method, const gode_gcn_odefunc_t* f, const float* y,
+                                                   float* const* k, const float* g, const float* kbar_last, double wy,
+                                                   const double* wk, double t, double h, int32_t first,
+                                                   float* const* ybar, float* ybar_n, float* kbar1, float* theta,
+                                                   float* const* ktheta, const gode_rk4_workspace_t* ws,
+                                                   float* cot_colpart, void* stream)
+{
+    if (!f || !y || !k || !g || !wk || !ybar || !ybar_n || !theta || !ktheta || !ws) return GODE_E_NULLPTR;
+    const AdaptiveMethod* am = adaptive_method(method);
+    if (!am) return GODE_E_SHAPE;
+    const Tableau& tab = am->tab;
+    const int S = tab.stages;
+    if (f->n <= 0 || f->d <= 0) return GODE_E_SHAPE;
+    if (!first && !kbar1) return GODE_E_NULLPTR;
+    for (int s = 0; s < S; ++s) if (!k[s] || !ktheta[s]) return GODE_E_NULLPTR;
+    for (int s = 1; s < S; ++s) if (!ybar[s]) return GODE_E_NULLPTR;
+    if (first && !ybar[0]) return GODE_E_NULLPTR;
+    if (ybar_n == g || ybar_n == kbar_last || (kbar1 && (kbar1 == g || kbar1 == kbar_last || kbar1 == ybar_n))) return GODE_E_SHAPE;
+    for (int s = 0; s < S; ++s)
+        if (ybar[s] && (ybar[s] == g || ybar[s] == kbar_last || ybar[s] == ybar_n || ybar[s] == kbar1)) return GODE_E_SHAPE;
+    if (!ws->dZ || !ws->dS || !ws->wpart || !ws->colsum_scratch) return GODE_E_NULLPTR;
+    if (f->groups > 0 && (!ws->gpart || !ws->bpart)) return GODE_E_NULLPTR;
+    const int64_t n = f->n, d = f->d, nd = n * d, P = gode_gcn_ode_theta_len(d);
+    const bool fused = fused_small(f) && ws->small_part != nullptr;
+    const SweepRoute route = sweep_route(f, ws, cot_colpart);
+    const int64_t slot = fused ? gode_gcn_small_parts(n) * gode_gcn_small_part_len(d) : 0;
+    const int last = first ? 0 : 1;                // the last stage the sweep pushes through f
+    bool dead[7] = {};
+    float* kt[7]; float kt_time[7];
+    int live = 0;
+    auto cotangent = [&](int s) {
+        gode_lincomb_t c = stage_cotangent(tab, g, (float)wk[s], ybar, s, h, dead);
+        if (s == S - 1 && kbar_last) { c.coef[c.n] = 1.f; c.ptr[c.n] = kbar_last; ++c.n; }
+        return c;
+    };
+    for (int s = S - 1; s >= last; --s) {
+        const gode_lincomb_t cot = cotangent(s);
+        if (cot.n == 0) { dead[s] = true; continue; }
+        const float ts = (float)(t + tab.c[s] * h);
+        const gode_lincomb_t yin = tab_stage_terms(tab, y, k, s, h);
+        const bool closes = first && s == 0;
+        const gode_lincomb_t pre = sweep_pre(tab, g, (float)wy, ybar, 1, dead);
+        float* out = closes ? ybar_n : ybar[s];
+        if (fused) {
+            GODE_TRY(gode_masked_cot_f32(&cot, k[s], ws->dZ, n, d, nullptr, stream));
+            GODE_TRY(gode_gcn_vjp_small_f32(f, &yin, ws->dZ, 1.f, closes ? &pre : nullptr, out, ws->small_part + live * slot, stream));
+        } else {
+            GODE_TRY(sweep_stage(f, ws, route, cot, k[s], yin, closes ? &pre : nullptr, out, ktheta[live], ts, stream));
+        }
+        kt[live] = ktheta[live]; kt_time[live] = ts;
+        ++live;
+    }
+    if (!first || dead[0]) {
+        // ybar_n = wy g + sum Ybar_s, and (not first) kbar_1 for the step before: one launch
+        float* outs[2] = {ybar_n, kbar1};
+        gode_lincomb_t lcs[2] = {sweep_pre(tab, g, (float)wy, ybar, 1, dead), cotangent(0)};
+        int64_t lens[2] = {nd, nd};
+        int count = first ? 1 : 2;
+        if (count == 2 && lcs[1].n == 0) { GODE_TRY(gode_zero_f32(kbar1, nd, stream)); count = 1; }
+        GODE_TRY(gode_lincomb_multi_f32(outs, lcs, lens, count, stream));
+    }
+    if (live == 0) return 0;
+    if (fused) GODE_TRY(gode_gcn_small_finish_multi_f32(f, ws->small_part, live, kt, kt_time, stream));
+    return add_stage_parts(theta, kt, live, P, stream);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // The fixed-grid drivers by method (GODE_RK_*): the rk4 launch sequences above driven by a tableau (rk_driver.h).  The last
 // stage of a step is the closing one; GODE_RK_RK4_38 calls the rk4 entry point itself.
 // ---------------------------------------------------------------------------------------------------------------

@@ -138,6 +138,91 @@ __global__ __launch_bounds__(256) void final_sum_multi_kernel(double* out, const
     if (threadIdx.x == 0) out[c] = sm[0];
 }
 
+// The close of an adaptive step in ONE launch per up to four components: y1 = sum coef * term (stored unless y1 is null),
+// err = sum ecoef * term over the SAME loads, and the block's fp64 sum of (err / (atol + rtol * max(|y0|, |y1|)))^2 with
+// y0 = term 0 and y1 taken from the registers.  Component c = blockIdx.y keeps the decomposition ratio_sumsq_multi_kernel
+// gives it (nb[c] blocks, the same striding), and both combinations are lc_load4_n's multiply-add chain, so y1 is bit for
+// bit gode_lincomb_f32's and the sum gode_rk_errnorm_f32's on that y1 (finite inputs: a zero coefficient changes no bit).
+// mode 2: every operand 16-byte aligned, 16-byte loads and stores; 0: scalar; 1: the reduction keeps the 16-byte form's
+// order (the separate error norm would take that form: its operands are aligned) while an operand it would not read is
+// not aligned, so the loads and stores are scalar.
+struct MultiClose { LinComb lc[4]; AuxCoef ec[4]; float* y1[4]; int64_t n[4]; int nb[4]; int mode[4]; };
+// the scalar twin of lc_load4_pair_n: all NT loads issued before the first use, the same two multiply-add chains
+template <int NT>
+__device__ __forceinline__ void close_load1_n(const LinComb& lc, const float* ec, int64_t idx, float& r, float& e) {
+    float v[NT];
+#pragma unroll
+    for (int j = 0; j < NT; ++j) v[j] = lc.ptr[j][idx];
+    r = 0.f; e = 0.f;
+#pragma unroll
+    for (int j = 0; j < NT; ++j) { r = fmaf(lc.coef[j], v[j], r); e = fmaf(ec[j], v[j], e); }
+}
+__device__ __forceinline__ void close_load1(const LinComb& lc, const float* ec, int64_t idx, float& r, float& e) {
+    switch (lc.n) {          // wave-uniform
+        case 1: close_load1_n<1>(lc, ec, idx, r, e); break;
+        case 2: close_load1_n<2>(lc, ec, idx, r, e); break;
+        case 3: close_load1_n<3>(lc, ec, idx, r, e); break;
+        case 4: close_load1_n<4>(lc, ec, idx, r, e); break;
+        case 5: close_load1_n<5>(lc, ec, idx, r, e); break;
+        case 6: close_load1_n<6>(lc, ec, idx, r, e); break;
+        case 7: close_load1_n<7>(lc, ec, idx, r, e); break;
+        case 8: close_load1_n<8>(lc, ec, idx, r, e); break;
+        default: r = 0.f; e = 0.f; break;
+    }
+}
+__global__ __launch_bounds__(256) void close_err_multi_kernel(double* part, MultiClose m, float rtol, float atol) {
+    const int c = blockIdx.y;
+    if ((int)blockIdx.x >= m.nb[c]) return;
+    const int64_t stride = (int64_t)m.nb[c] * blockDim.x;
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const float* y0 = m.lc[c].ptr[0];
+    float* y1 = m.y1[c];
+    double s = 0.0;
+    if (m.mode[c] == 2) {
+        for (const int64_t n4 = m.n[c] / 4; i < n4; i += stride) {
+            const float4 a = *reinterpret_cast<const float4*>(y0 + i * 4);
+            float4 b, e;
+            lc_load4_pair(m.lc[c], m.ec[c].c, i * 4, b, e);
+            if (y1) *reinterpret_cast<float4*>(y1 + i * 4) = b;
+            const float4 mm = make_float4(fmaxf(fabsf(a.x), fabsf(b.x)), fmaxf(fabsf(a.y), fabsf(b.y)), fmaxf(fabsf(a.z), fabsf(b.z)),
+                                          fmaxf(fabsf(a.w), fabsf(b.w)));
+            const float r0 = e.x / (atol + rtol * mm.x), r1 = e.y / (atol + rtol * mm.y);
+            const float r2 = e.z / (atol + rtol * mm.z), r3 = e.w / (atol + rtol * mm.w);
+            s += ((double)r0 * (double)r0 + (double)r1 * (double)r1) + ((double)r2 * (double)r2 + (double)r3 * (double)r3);
+        }
+    } else if (m.mode[c] == 1) {
+        for (const int64_t n4 = m.n[c] / 4; i < n4; i += stride) {
+            float b[4], r[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                float e;
+                close_load1(m.lc[c], m.ec[c].c, i * 4 + q, b[q], e);
+                const float mx = fmaxf(fabsf(y0[i * 4 + q]), fabsf(b[q]));
+                r[q] = e / (atol + rtol * mx);
+            }
+            if (y1) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) y1[i * 4 + q] = b[q];
+            }
+            s += ((double)r[0] * (double)r[0] + (double)r[1] * (double)r[1]) + ((double)r[2] * (double)r[2] + (double)r[3] * (double)r[3]);
+        }
+    } else {
+        for (; i < m.n[c]; i += stride) {
+            float b, e;
+            close_load1(m.lc[c], m.ec[c].c, i, b, e);
+            if (y1) y1[i] = b;
+            const float mx = fmaxf(fabsf(y0[i]), fabsf(b));
+            const float r = e / (atol + rtol * mx);
+            s += (double)r * (double)r;
+        }
+    }
+    __shared__ double sm[4];
+    s = wave_sum(s);
+    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) part[(int64_t)c * RED_BLOCKS + blockIdx.x] = sm[0] + sm[1] + sm[2] + sm[3];
+}
+
 __global__ __launch_bounds__(256) void final_sum_kernel(double* out, const double* part, int nparts) {
     __shared__ double sm[256];
     double s = 0.0;
@@ -489,6 +574,48 @@ extern "C" int gode_rk_errnorm_multi_f32(double* out, const float* const* y0, co
     hipLaunchKernelGGL(ratio_sumsq_multi_kernel, dim3((unsigned)nbmax, (unsigned)count), dim3(256), 0, s, (double*)scratch, m, rtol, atol);
     GODE_LAUNCH_CHECK();
     hipLaunchKernelGGL(final_sum_multi_kernel, dim3((unsigned)count), dim3(256), 0, s, out, (const double*)scratch, m);
+    GODE_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int64_t gode_rk_close_err_scratch_bytes(void) { return (int64_t)4 * RED_BLOCKS * sizeof(double); }
+
+extern "C" int gode_rk_close_err_multi_f32(float* const* y1, const gode_lincomb_t* sol, const float* const* err_coef,
+                                           const int64_t* n, int32_t count, float rtol, float atol, double* sums,
+                                           void* scratch, void* stream) {
+    if (!y1 || !sol || !err_coef || !n || !sums || !scratch) return GODE_E_NULLPTR;
+    if (count < 1 || count > 4) return GODE_E_SHAPE;
+    MultiClose m;
+    MultiErr fin;                                              // final_sum_multi_kernel reads nb alone
+    int nbmax = 0;
+    for (int c = 0; c < 4; ++c) {
+        m.lc[c] = make_lincomb(nullptr); m.y1[c] = nullptr; m.n[c] = 0; m.nb[c] = 0; m.mode[c] = 0;
+        for (int j = 0; j < GODE_MAX_TERMS; ++j) m.ec[c].c[j] = 0.f;
+        fin.lc[c] = make_lincomb(nullptr); fin.y0[c] = fin.y1[c] = nullptr; fin.n[c] = 0; fin.nb[c] = 0; fin.vec[c] = 0;
+    }
+    for (int c = 0; c < count; ++c) {
+        if (!err_coef[c]) return GODE_E_NULLPTR;
+        if (sol[c].n < 1 || sol[c].n > GODE_MAX_TERMS || n[c] <= 0) return GODE_E_SHAPE;
+        for (int j = 0; j < sol[c].n; ++j) {
+            if (!sol[c].ptr[j]) return GODE_E_NULLPTR;
+            if (y1[c] && sol[c].ptr[j] == y1[c]) return GODE_E_SHAPE;        // every block reads what another one stores
+        }
+        m.lc[c] = make_lincomb(&sol[c]); m.y1[c] = y1[c]; m.n[c] = n[c];
+        bool all16 = !(((uintptr_t)y1[c]) & 15), err16 = all16 && !(((uintptr_t)sol[c].ptr[0]) & 15);
+        for (int j = 0; j < sol[c].n; ++j) {
+            m.ec[c].c[j] = err_coef[c][j];
+            const bool al = !(((uintptr_t)sol[c].ptr[j]) & 15);
+            all16 = all16 && al;
+            if (err_coef[c][j] != 0.f) err16 = err16 && al;
+        }
+        m.nb[c] = fin.nb[c] = red_blocks(n[c]);                 // as gode_rk_errnorm_f32 decomposes this component
+        m.mode[c] = n[c] % 4 != 0 ? 0 : all16 ? 2 : err16 ? 1 : 0;
+        if (m.nb[c] > nbmax) nbmax = m.nb[c];
+    }
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(close_err_multi_kernel, dim3((unsigned)nbmax, (unsigned)count), dim3(256), 0, s, (double*)scratch, m, rtol, atol);
+    GODE_LAUNCH_CHECK();
+    hipLaunchKernelGGL(final_sum_multi_kernel, dim3((unsigned)count), dim3(256), 0, s, sums, (const double*)scratch, fin);
     GODE_LAUNCH_CHECK();
     return 0;
 }

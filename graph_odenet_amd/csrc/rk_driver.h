@@ -69,6 +69,37 @@ const Tableau TABMID = {&AMID[0][0], 1, 2, BMID, CMID};
 inline const Tableau* fixed_tableau(int method) {
     return method == GODE_RK_RK4_38 ? &TAB38 : method == GODE_RK_EULER ? &TABEU : method == GODE_RK_MIDPOINT ? &TABMID : nullptr;
 }
+// Bogacki-Shampine 3(2) and Heun-Euler 2(1), both in FSAL form as Dormand-Prince is (the last row of a is b); Heun-Euler's
+// third stage f(t + h, y1) is what makes it so.  e = b - b*
+const double BSC[4] = {0.0, 1.0 / 2, 3.0 / 4, 1.0};
+const double BSA[4][3] = {{0, 0, 0}, {1.0 / 2, 0, 0}, {0, 3.0 / 4, 0}, {2.0 / 9, 1.0 / 3, 4.0 / 9}};
+const double BSB[4] = {2.0 / 9, 1.0 / 3, 4.0 / 9, 0};
+const double BSE[4] = {2.0 / 9 - 7.0 / 24, 1.0 / 3 - 1.0 / 4, 4.0 / 9 - 1.0 / 3, -1.0 / 8};
+const double HEC[3] = {0.0, 1.0, 1.0};
+const double HEA[3][2] = {{0, 0}, {1.0, 0}, {1.0 / 2, 1.0 / 2}};
+const double HEB[3] = {1.0 / 2, 1.0 / 2, 0};
+const double HEE[3] = {-1.0 / 2, 1.0 / 2, 0};
+const Tableau TABBS = {&BSA[0][0], 3, 4, BSB, BSC};
+const Tableau TABHE = {&HEA[0][0], 2, 3, HEB, HEC};
+// the adaptive methods by their GODE_RKA_* code: tableau, error weights e, order p; nullptr outside the list
+struct AdaptiveMethod { Tableau tab; const double* e; int order; };
+const AdaptiveMethod ADAPTIVE[3] = {{TABDP, DPE, 5}, {TABBS, BSE, 3}, {TABHE, HEE, 2}};
+inline const AdaptiveMethod* adaptive_method(int method) {
+    return method >= GODE_RKA_DOPRI5 && method <= GODE_RKA_ADAPTIVE_HEUN ? &ADAPTIVE[method] : nullptr;
+}
+// The close of an adaptive step as gode_rk_close_err_multi_f32 takes it: sol = y + h sum_j b_j k_j over the stages whose b
+// or e is non-zero (a stage with b = 0 enters with the coefficient 0, which changes no bit of the sum), ecoef = h e_j over
+// the same terms (0 for y); every array `off` elements in
+inline gode_lincomb_t close_terms(const AdaptiveMethod& am, const float* y, float* const* k, double h, float* ecoef,
+                                  int64_t off = 0) {
+    gode_lincomb_t lc = one_term(y + off);
+    for (int j = 0; j < GODE_MAX_TERMS; ++j) ecoef[j] = 0.f;
+    for (int j = 0; j < am.tab.stages; ++j)
+        if (am.tab.b[j] != 0.0 || am.e[j] != 0.0) {
+            lc.coef[lc.n] = (float)(h * am.tab.b[j]); ecoef[lc.n] = (float)(h * am.e[j]); lc.ptr[lc.n] = k[j] + off; ++lc.n;
+        }
+    return lc;
+}
 // terms of  y + h * sum_{j<s} A[s][j] * k[j]  of any tableau (zero coefficients dropped; stage_terms is the 3/8 rule's)
 inline gode_lincomb_t tab_stage_terms(const Tableau& tab, const float* y, float* const* k, int s, double h) {
     gode_lincomb_t lc = one_term(y);

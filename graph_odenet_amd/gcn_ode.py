@@ -16,7 +16,7 @@ import torch
 
 from . import _lib, ops
 from .graph import as_graph
-from .solver import Field, method_code, n_stages
+from .solver import Field, adaptive_code, adaptive_stages, method_code, n_stages
 
 
 def _graph_struct(g, d):
@@ -532,6 +532,22 @@ class GcnOdeField(_PackedParams, Field):
                    "gode_gcn_ode_dopri5_step_forward")
         return sums
 
+    def adaptive_step_native(self, method, y, kk, y1, t, h, rtol, atol):
+        """dopri5_step_native for any adaptive method (kk: S stage buffers): gode_gcn_ode_adaptive_step_forward, which closes
+        the step with the fused launch (solution and error sum from one pass over the stages)."""
+        lib = _lib.load()
+        s, w = self.s, self.w
+        S = adaptive_stages(method)
+        fs, ws = _func_struct(s), w.workspace_struct(False, s.groups)
+        kptr = (ctypes.c_void_p * S)(*[kk[i][0].data_ptr() for i in range(S)])
+        sums = torch.empty(1, dtype=torch.float64, device=y[0].device)
+        sc = ops._scratch(y[0].device, lib.gode_rk_close_err_scratch_bytes())
+        _lib.check(lib.gode_gcn_ode_adaptive_step_forward(adaptive_code(method), ctypes.byref(fs), _lib.ptr(y[0]), kptr,
+                                                          _lib.ptr(y1[0]), ctypes.byref(ws), float(t), float(h), float(rtol),
+                                                          float(atol), _lib.ptr(sums), _lib.ptr(sc), _lib.stream_ptr()),
+                   "gode_gcn_ode_adaptive_step_forward")
+        return sums
+
     # ---- backprop through an adaptive solve (odeint._OdeintBackprop under dopri5; csrc/ode_driver.hip) -------
     def dopri5_backprop_work(self, like):
         """Work arrays of dopri5_step_backprop for a state like `like`: 7 Ybar, two (ybar_n, kbar_1) pairs that take
@@ -560,11 +576,39 @@ class GcnOdeField(_PackedParams, Field):
         return ybar_n, (None if first else kbar1)
 
 
+    def adaptive_backprop_work(self, method, like):
+        """dopri5_backprop_work for any adaptive method: S Ybar, two (ybar_n, kbar_1) pairs, S packed parameter parts."""
+        lib = _lib.load()
+        S = adaptive_stages(method)
+        P = lib.gode_gcn_ode_theta_len(self.s.d)
+        return {"ybar": [torch.empty_like(like) for _ in range(S)],
+                "pairs": [(torch.empty_like(like), torch.empty_like(like)) for _ in range(2)],
+                "ktheta": [torch.empty(P, dtype=torch.float32, device=like.device) for _ in range(S)]}
+
+    def adaptive_step_backprop(self, method, y, k, g, kbar_last, wy, wk, t, h, first, work, turn, theta):
+        """dopri5_step_backprop for any adaptive method (k, wk of S entries; kbar_last arrives on k_S):
+        gode_gcn_ode_adaptive_step_backprop."""
+        lib = _lib.load()
+        s, w = self.s, self.w
+        S = adaptive_stages(method)
+        w.stage_buffers(True)
+        fs, ws = _func_struct(s), w.workspace_struct(True, s.groups)
+        arr = lambda ts: (ctypes.c_void_p * S)(*[x.data_ptr() for x in ts])      # noqa: E731
+        ybar_n, kbar1 = work["pairs"][turn]
+        _lib.check(lib.gode_gcn_ode_adaptive_step_backprop(
+            adaptive_code(method), ctypes.byref(fs), _lib.ptr(y), arr(k), _lib.ptr(g), _lib.ptr(kbar_last), float(wy),
+            (ctypes.c_double * S)(*[float(v) for v in wk]), float(t), float(h), int(bool(first)), arr(work["ybar"]),
+            _lib.ptr(ybar_n), _lib.ptr(kbar1), _lib.ptr(theta), arr(work["ktheta"]), ctypes.byref(ws),
+            _lib.ptr(w.cot_colpart()), _lib.stream_ptr()), "gode_gcn_ode_adaptive_step_backprop")
+        return ybar_n, (None if first else kbar1)
+
+
 class _PartMixin:
     """Row-partitioned state (partition.py): hooks the adaptive solver uses to see global error norms."""
     rk4_native = None
     fixed_native = None
     dopri5_step_native = None
+    adaptive_step_native = None
     adaptive = False                # set by odeint when the method is adaptive
 
     def _part(self):
@@ -603,6 +647,7 @@ class GcnOdePartField(_PartMixin, GcnOdeField):
     fixed_forward_save = None
     fixed_backprop = None
     dopri5_step_backprop = None
+    adaptive_step_backprop = None
 
     def __init__(self, spec, shared, params_order):
         GcnOdeField.__init__(self, spec, shared, params_order)
@@ -697,6 +742,23 @@ class GcnOdeAdjointField(_PackedParams, Field):
             ctypes.byref(fs), _lib.ptr(y[0]), _lib.ptr(y[1]), _lib.ptr(self._theta_of(y)), arr(0), arr(1), kth,
             _lib.ptr(y1[0]), _lib.ptr(y1[1]), _lib.ptr(self._theta_of(y1)), ctypes.byref(ws), float(t), float(h),
             float(rtol), float(atol), _lib.ptr(sums), _lib.ptr(sc), _lib.stream_ptr()), "gode_gcn_ode_dopri5_step_adjoint")
+        return sums
+
+    def adaptive_step_native(self, method, y, kk, y1, t, h, rtol, atol):
+        """dopri5_step_native for any adaptive method: gode_gcn_ode_adaptive_step_adjoint, whose one fused close writes the
+        three outputs and forms the four error sums."""
+        lib = _lib.load()
+        s, w = self.s, self.w
+        S = adaptive_stages(method)
+        fs, ws = _func_struct(s), w.workspace_struct(True, s.groups)
+        arr = lambda idx: (ctypes.c_void_p * S)(*[kk[i][idx].data_ptr() for i in range(S)])      # noqa: E731
+        kth = (ctypes.c_void_p * S)(*[self._theta_of(kk[i]).data_ptr() for i in range(S)])
+        sums = torch.empty(4, dtype=torch.float64, device=y[0].device)
+        sc = ops._scratch(y[0].device, lib.gode_rk_close_err_scratch_bytes())
+        _lib.check(lib.gode_gcn_ode_adaptive_step_adjoint(
+            adaptive_code(method), ctypes.byref(fs), _lib.ptr(y[0]), _lib.ptr(y[1]), _lib.ptr(self._theta_of(y)), arr(0), arr(1),
+            kth, _lib.ptr(y1[0]), _lib.ptr(y1[1]), _lib.ptr(self._theta_of(y1)), ctypes.byref(ws), float(t), float(h),
+            float(rtol), float(atol), _lib.ptr(sums), _lib.ptr(sc), _lib.stream_ptr()), "gode_gcn_ode_adaptive_step_adjoint")
         return sums
 
     def eval(self, t, terms, out):

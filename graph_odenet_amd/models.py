@@ -186,7 +186,8 @@ class ODEfunc2(nn.Module):
 class ODEBlock(nn.Module):
     """y(1) of y' = odefunc(t, y), y(0) = x (reference: GCN/models.py:181-201).
 
-    method: None / 'dopri5' (adaptive, rtol = atol = tol), or a fixed-grid method on steps of step_size (one step over
+    method: None / 'dopri5', 'bosh3' (Bogacki-Shampine 3(2)) or 'adaptive_heun' (Heun-Euler 2(1)) - adaptive, rtol = atol =
+    tol - or a fixed-grid method on steps of step_size (one step over
     [0, 1] without it): 'rk4' (3/8 rule, 4 evaluations per step), 'midpoint' (2) or 'euler' (1).  Euler at step_size 1/K is
     the weight-tied K-layer residual stack x <- x + odefunc(k/K, x) / K."""
 

@@ -12,8 +12,8 @@ RK arithmetic still in the HIP kernels.
 `odeint` is differentiable as torchdiffeq's is (backprop through the solver's operations, not the adjoint): with grad
 mode on and y0 or a parameter of func requiring grad it returns a tensor with a grad_fn whose gradient is the exact
 derivative of the computed discrete solution w.r.t. y0 and func's parameters (t gets None).  Methods: adaptive `dopri5`
-(the default) and the fixed-grid `rk4` (3/8 rule), `midpoint` and `euler` on the grid options['step_size'] gives (one step
-per interval of t without it); euler at step_size 1/K is the weight-tied K-layer residual stack.  Under adaptive dopri5 the
+(the default), `bosh3` and `adaptive_heun`, and the fixed-grid `rk4` (3/8 rule), `midpoint` and `euler` on the grid options['step_size'] gives (one step
+per interval of t without it); euler at step_size 1/K is the weight-tied K-layer residual stack.  Under the adaptive methods the
 accepted step sizes are constants of that derivative: rejected attempts, the initial-step heuristic and the controller
 contribute nothing (what autograd through a solver whose step sizes are Python floats gives).  Row-partitioned fields
 stay forward-only.
@@ -24,8 +24,9 @@ import torch
 
 from . import ops
 from . import solver
-from .solver import (DP_A, DP_B, DP_C, FIXED_METHODS, FIXED_TABLEAUS, Dopri5Record, Dopri5Stats, Field, integrate_dopri5,
-                     integrate_dopri5_inplace, integrate_fixed, integrate_rk4, interp_weights, n_stages, uniform_grid)
+from .solver import (ADAPTIVE_METHODS, ADAPTIVE_TABLEAUS, FIXED_METHODS, FIXED_TABLEAUS, Dopri5Record, Dopri5Stats, Field,
+                     adaptive_interp_weights, adaptive_stages, integrate_adaptive, integrate_dopri5_inplace, integrate_fixed,
+                     integrate_rk4, n_stages, uniform_grid)
 
 
 NATIVE_RK4 = True      # fused fields: issue a whole fixed-grid solve from one C-ABI call (False: per-stage Python driver)
@@ -139,7 +140,8 @@ def _times(t):
     return tl
 
 
-METHODS = ("dopri5",) + FIXED_METHODS       # adaptive dopri5; fixed-grid rk4 (3/8 rule), euler, midpoint
+# adaptive dopri5; fixed-grid rk4 (3/8 rule), euler, midpoint; adaptive bosh3 (Bogacki-Shampine 3(2)), adaptive_heun (2(1))
+METHODS = ("dopri5",) + FIXED_METHODS + tuple(m for m in ADAPTIVE_METHODS if m != "dopri5")
 
 
 def _method(method):
@@ -160,7 +162,7 @@ def _integrate(field, comps, t0, t1, rtol, atol, method, options, stats):
         if field.big_components is not None:
             field.adaptive = True                  # row-partitioned fields: keep the small components global
         _prepare(field)
-        integrate_dopri5_inplace(field, comps, t0, t1, rtol, atol, stats)
+        integrate_dopri5_inplace(field, comps, t0, t1, rtol, atol, stats, method)
 
 
 _FIXED_ONLY = "odeint: this field supports the fixed-grid methods only (method=%s)" % " / ".join(
@@ -360,17 +362,19 @@ def _fixed_torch(func, y, t0, t1, n, method):
     return y
 
 
-def _dopri5_step_torch(func, y, t, h, x):
-    """One Dormand-Prince step from y at t as differentiable torch ops through func; x: the interpolation abscissa of a
-    last step that overshot the end time (None: the step's own end state is returned)."""
+def _dopri5_step_torch(func, y, t, h, x, method="dopri5"):
+    """One step of an adaptive method (FSAL form) from y at t as differentiable torch ops through func; x: the interpolation
+    abscissa of a last step that overshot the end time (None: the step's own end state is returned)."""
+    C, A, B = ADAPTIVE_TABLEAUS[method][:3]
+    S = len(C)
     tt = lambda v: torch.tensor(v, dtype=y.dtype, device=y.device)      # noqa: E731
     ks = [func(tt(t), y)]
-    for s in range(1, 7 if x is not None else 6):       # k_7 enters the result through the interpolation only
-        ks.append(func(tt(t + DP_C[s] * h), y + sum((h * a) * k for a, k in zip(DP_A[s], ks) if a != 0.0)))
-    y1 = y + sum((h * b) * k for b, k in zip(DP_B, ks) if b != 0.0)
+    for s in range(1, S if x is not None else S - 1):   # k_S enters the result through the interpolation only
+        ks.append(func(tt(t + C[s] * h), y + sum((h * a) * k for a, k in zip(A[s], ks) if a != 0.0)))
+    y1 = y + sum((h * b) * k for b, k in zip(B, ks) if b != 0.0)
     if x is None:
         return y1
-    cy0, cy1, kc = interp_weights(x)
+    cy0, cy1, kc = adaptive_interp_weights(method, x)
     return cy0 * y + cy1 * y1 + sum((h * c) * k for c, k in zip(kc, ks) if c != 0.0)
 
 
@@ -450,64 +454,79 @@ class _Rk4Backprop:
         yield rec, lambda y: _fixed_torch(self.func, y, self.tl[i - 1], self.tl[i], self.steps[i - 1], self.method)
 
 
+def _adaptive_sweep(fwd, method):
+    """(step_native, step_backprop, backprop_work) of a field under an adaptive method, each taking the dopri5 member's
+    arguments - None where the field does not offer it.  dopri5 keeps the members it has always used; a field's seven-stage
+    dopri5 members never serve another method."""
+    if method == "dopri5":
+        return fwd.dopri5_step_native, fwd.dopri5_step_backprop, fwd.dopri5_backprop_work
+    bind = lambda f: None if f is None else (lambda *args: f(method, *args))      # noqa: E731
+    return bind(fwd.adaptive_step_native), bind(fwd.adaptive_step_backprop), bind(fwd.adaptive_backprop_work)
+
+
 class _Dopri5Backprop:
-    """What _OdeintBackprop does per interval under adaptive dopri5; the accepted step sizes are constants of the
+    """What _OdeintBackprop does per interval under an adaptive method (dopri5, bosh3, adaptive_heun; S stages); the accepted step sizes are constants of the
     derivative.  The forward runs the solve's own launches on buffers a solver.Dopri5Record keeps.  Fused (a field offering
-    dopri5_step_backprop: GcnOdeField, qc_ode.EdgeOdeField): y_n and k_1..k_7 of every accepted step - or y_n and k_1 past
-    BACKPROP_SAVE_MAX_BYTES, each step then re-run by one native step call before its sweep (never for a field without
-    dopri5_step_native: it keeps all seven) - swept in reverse, one call per step (csrc/ode_driver.hip; qc_ode.py).
+    the method's sweep - _adaptive_sweep: dopri5_step_backprop under dopri5 (GcnOdeField, GatOdeField, qc_ode.EdgeOdeField),
+    adaptive_step_backprop under bosh3 / adaptive_heun (GcnOdeField)): y_n and k_1..k_S of every accepted step - or y_n and k_1
+    past BACKPROP_SAVE_MAX_BYTES, each step then re-run by one native step call before its sweep (never for a field without
+    the method's native step: it keeps all S) - swept in reverse, one call per step (csrc/ode_driver.hip; qc_ode.py).
     Generic: y_n alone, each accepted step re-run as torch ops through func, k_1 = func(t_n, y_n) recomputed: the same
-    function of y_n as the derivative FSAL hands over, since Y_7 and y_{n+1} are the same combination."""
+    function of y_n as the derivative FSAL hands over, since Y_S and y_{n+1} are the same combination."""
     own_cotangent = False             # fused_reverse hands back one of its work arrays
 
-    def __init__(self, func, fwd, tl, rtol, atol, options, y0c):
+    def __init__(self, func, fwd, tl, rtol, atol, options, y0c, method="dopri5"):
         if fwd.fixed_grid_only:
             raise NotImplementedError(_FIXED_ONLY)
         self.func, self.fwd, self.tl, self.tols = func, fwd, tl, (rtol, atol)
-        self.fused = fwd.dopri5_step_backprop is not None and solver.DOPRI5_NATIVE
+        # the other adaptive methods (S stages) go through the adaptive_* members, which take the method first
+        self.method, self.S = method, adaptive_stages(method)
+        self.step_native, self.step_backprop, self.backprop_work = _adaptive_sweep(fwd, method)
+        self.fused = self.step_backprop is not None and solver.DOPRI5_NATIVE
         self.stats = Dopri5Stats()
         self.left = BACKPROP_SAVE_MAX_BYTES
         _prepare(fwd)
 
     def forward(self, i, cur, start):
-        fused, left = self.fused, self.left
-        if fused and self.fwd.dopri5_step_native is None:
-            rec = Dopri5Record(7)                 # no native step to re-run a step with: all seven, whatever the bound
+        fused, left, S = self.fused, self.left, self.S
+        if fused and self.step_native is None:
+            rec = Dopri5Record(S, full=S)         # no native step to re-run a step with: all S, whatever the bound
         else:
-            rec = Dopri5Record(7, left) if fused and left is not None else Dopri5Record(1 if fused else 0)
-        (cur,), _ = integrate_dopri5(self.fwd, [cur], self.tl[i - 1], self.tl[i], *self.tols, self.stats, record=rec)
+            rec = Dopri5Record(S, left, full=S) if fused and left is not None else Dopri5Record(1 if fused else 0, full=S)
+        (cur,), _ = integrate_adaptive(self.fwd, [cur], self.tl[i - 1], self.tl[i], *self.tols, self.method, self.stats,
+                                       record=rec)
         if fused and left is not None:
-            self.left = left - rec.bytes if rec.keep == 7 else None      # past the bound: the later intervals keep k_1 only
+            self.left = left - rec.bytes if rec.keep == S else None      # past the bound: the later intervals keep k_1 only
         return rec, cur
 
     def fused_reverse(self, i, rec, a, theta, work):
-        fwd = self.fwd
+        S, B = self.S, ADAPTIVE_TABLEAUS[self.method][2]
         if not work:
             # turn: which (ybar_n, kbar_1) pair the next call writes: never the one it reads
-            work.update(arrays=fwd.dopri5_backprop_work(a), rerun=None, turn=0)
+            work.update(arrays=self.backprop_work(a), rerun=None, turn=0)
         kbar7 = None
         for j in range(len(rec.steps) - 1, -1, -1):
             t, h, x, y, ks = rec.steps[j]
             ks = [k[0] for k in ks]
-            if len(ks) < 7:                 # re-run the step into a one-step record (the forward's launches)
+            if len(ks) < S:                 # re-run the step into a one-step record (the forward's launches)
                 if work["rerun"] is None:
-                    work["rerun"] = [torch.empty_like(a) for _ in range(7)]
+                    work["rerun"] = [torch.empty_like(a) for _ in range(S)]
                 rerun = work["rerun"]
-                fwd.dopri5_step_native(y, [[ks[0]]] + [[b] for b in rerun[:6]], [rerun[6]], t, h, *self.tols)
-                ks = [ks[0]] + rerun[:6]
+                self.step_native(y, [[ks[0]]] + [[b] for b in rerun[:S - 1]], [rerun[S - 1]], t, h, *self.tols)
+                ks = [ks[0]] + rerun[:S - 1]
             if x is None:
-                wy, wk = 1.0, [h * b for b in DP_B]
+                wy, wk = 1.0, [h * b for b in B]
             else:
-                cy0, cy1, kc = interp_weights(x)
-                wy, wk = cy0 + cy1, [h * (cy1 * b + c) for b, c in zip(DP_B, kc)]
-            a, kbar7 = fwd.dopri5_step_backprop(y[0], ks, a, kbar7, wy, wk, t, h, j == 0, work["arrays"], work["turn"], theta)
+                cy0, cy1, kc = adaptive_interp_weights(self.method, x)
+                wy, wk = cy0 + cy1, [h * (cy1 * b + c) for b, c in zip(B, kc)]
+            a, kbar7 = self.step_backprop(y[0], ks, a, kbar7, wy, wk, t, h, j == 0, work["arrays"], work["turn"], theta)
             work["turn"] ^= 1
         return a
 
     def generic_reverse(self, i, rec):
         for (t, h, x, y, _) in reversed(rec.steps):
             yield (_gather(y[0], self.fwd.row_inverse, copy=False),
-                   lambda yn, t=t, h=h, x=x: _dopri5_step_torch(self.func, yn, t, h, x))
+                   lambda yn, t=t, h=h, x=x: _dopri5_step_torch(self.func, yn, t, h, x, self.method))
 
 
 class _OdeintBackprop(torch.autograd.Function):
@@ -527,7 +546,7 @@ class _OdeintBackprop(torch.autograd.Function):
             if method in FIXED_METHODS:
                 sweep = _Rk4Backprop(func, fwd, tl, rtol, atol, options, y0c, method)
             else:
-                sweep = _Dopri5Backprop(func, fwd, tl, rtol, atol, options, y0c)
+                sweep = _Dopri5Backprop(func, fwd, tl, rtol, atol, options, y0c, method)
             cur = _gather(y0c, fwd.row_order)
             for i in range(1, len(tl)):
                 rec, cur = sweep.forward(i, cur, outs[-1])
@@ -588,7 +607,7 @@ def odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None):
         if y0.requires_grad or params:
             covered = tuple(fields[2]) + _extra_inputs(func)       # a field with a sweep returns the extra inputs' gradients too
             same = len(covered) == len(params) and all(p is q for p, q in zip(covered, params))
-            sweep = _fixed_sweep(fwd, method) if method in FIXED_METHODS else fwd.dopri5_step_backprop
+            sweep = _fixed_sweep(fwd, method) if method in FIXED_METHODS else _adaptive_sweep(fwd, method)[1]
             if sweep is not None and not same:
                 fwd = AutogradField(func, y0)         # the fused field does not cover these parameters
             return _OdeintBackprop.apply(func, fwd, tl, float(rtol), float(atol), method, options, y0, *params)
@@ -721,7 +740,7 @@ class _OdeintAdjoint(torch.autograd.Function):
 
 
 def odeint_adjoint(func, y0, t, rtol=1e-6, atol=1e-12, method=None, options=None, _last_only=False):
-    """torchdiffeq's odeint_adjoint for dopri5 and the fixed-grid methods (rk4, midpoint, euler).  `_last_only=True` (not part of the reference
+    """torchdiffeq's odeint_adjoint for the adaptive methods (dopri5, bosh3, adaptive_heun) and the fixed-grid ones (rk4, midpoint, euler).  `_last_only=True` (not part of the reference
     API; used by models.ODEBlock, which keeps `out[1]` only) returns y(t[-1]) instead of the stack over t."""
     _check_state(y0)
     tl = _times(t)

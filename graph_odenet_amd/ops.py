@@ -176,6 +176,43 @@ def rk_error_sumsq(y0, y1, err_terms, rtol, atol, out=None):
     return out
 
 
+def rk_close_err_multi(y1s, sols, err_coefs, rtol, atol, out=None):
+    """The close of an adaptive step for up to four components in two launches: y1s[c] = sum sols[c] (None: not stored),
+    and the fp64 device tensor of sum_i (err_i / (atol + rtol*max(|y0_i|,|y1_i|)))^2 per component, err = sum_j
+    err_coefs[c][j] * tensor j of sols[c], y0 = the first tensor of sols[c] - bit for bit lincomb_ followed by
+    rk_error_sumsq over the terms with a non-zero err coefficient."""
+    lib = _lib.load()
+    k = len(sols)
+    if not (k == len(y1s) == len(err_coefs)) or not 1 <= k <= 4:
+        raise ValueError("rk_close_err_multi: one output and one coefficient list per term list, at most four")
+    lcs = (_lib.LinComb * k)()
+    ptrs = (ctypes.c_void_p * k)()
+    ecs = (ctypes.c_void_p * k)()
+    ns = (ctypes.c_int64 * k)()
+    keep = []
+    for c, (y1, terms, ec) in enumerate(zip(y1s, sols, err_coefs)):
+        n = _need_terms(terms, "sol")
+        if y1 is not None:
+            _need(y1, "y1")
+            if y1.numel() != n:
+                raise ValueError("rk_close_err_multi: size mismatch in component %d" % c)
+        if len(ec) != len(terms):
+            raise ValueError("rk_close_err_multi: one err coefficient per term in component %d" % c)
+        lcs[c] = lincomb(terms)
+        ptrs[c] = y1.data_ptr() if y1 is not None else None
+        arr = (ctypes.c_float * _lib.GODE_MAX_TERMS)(*[float(v) for v in ec])
+        keep.append(arr)
+        ecs[c] = ctypes.addressof(arr)
+        ns[c] = n
+    dev = sols[0][0][1].device
+    if out is None:
+        out = torch.empty(k, dtype=torch.float64, device=dev)
+    sc = _scratch(dev, lib.gode_rk_close_err_scratch_bytes())
+    check(lib.gode_rk_close_err_multi_f32(ptrs, lcs, ecs, ns, k, float(rtol), float(atol), ptr(out), ptr(sc), stream_ptr()),
+          "gode_rk_close_err_multi_f32")
+    return out
+
+
 def rk_scaled_sumsq(terms, y, rtol, atol, out=None):
     """sum_i ((sum terms)_i / (atol + rtol*|y_i|))^2 as a 1-element fp64 device tensor."""
     lib = _lib.load()

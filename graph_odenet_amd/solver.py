@@ -11,6 +11,9 @@ module re-creates the two methods the hot path needs from the published algorith
                         state tensor, safety 0.9 / ifactor 10 / dfactor 0.2, 4th-order
                         interpolation to the end time (the reference's default: no
                         `method=` is passed, rtol = atol = 1e-5);
+  * adaptive `bosh3`, `adaptive_heun` : Bogacki-Shampine 3(2) and Heun-Euler 2(1) in FSAL form, run by the same driver as
+                        dopri5 from their tableaus (ADAPTIVE_TABLEAUS, integrate_adaptive): the controller with exponent
+                        1/p, the cubic Hermite fit at the end time;
   * `odeint_adjoint`  : O(1)-memory adjoint; the augmented state (y, a, [a_t], a_theta) is
                         integrated backwards with the same method.
 
@@ -82,6 +85,47 @@ def interp_weights(x):
     return cy0, cy1, kc
 
 
+# Bogacki-Shampine 3(2) and Heun-Euler 2(1), both written in FSAL form as Dormand-Prince is: the last row of a equals b, so
+# k_S of an accepted step is k_1 of the next.  Heun-Euler's natural two-stage form is not FSAL; its third stage f(t + h, y1)
+# makes it so, at the price of one wasted evaluation per rejected attempt.  e = b - b*.
+BS_C = [0.0, 1 / 2, 3 / 4, 1.0]
+BS_A = [[], [1 / 2], [0, 3 / 4], [2 / 9, 1 / 3, 4 / 9]]
+BS_B = [2 / 9, 1 / 3, 4 / 9, 0]
+BS_E = [2 / 9 - 7 / 24, 1 / 3 - 1 / 4, 4 / 9 - 1 / 3, -1 / 8]
+HE_C = [0.0, 1.0, 1.0]
+HE_A = [[], [1.0], [1 / 2, 1 / 2]]
+HE_B = [1 / 2, 1 / 2, 0]
+HE_E = [-1 / 2, 1 / 2, 0]
+# the adaptive methods by name: (c, a, b, e, order p); the order is that of the GODE_RKA_* codes of include/graphode.h
+ADAPTIVE_TABLEAUS = {"dopri5": (DP_C, DP_A, DP_B, DP_E, 5), "bosh3": (BS_C, BS_A, BS_B, BS_E, 3),
+                     "adaptive_heun": (HE_C, HE_A, HE_B, HE_E, 2)}
+ADAPTIVE_METHODS = tuple(ADAPTIVE_TABLEAUS)
+
+
+def adaptive_code(method):
+    """The GODE_RKA_* code of an adaptive method name."""
+    return ADAPTIVE_METHODS.index(method)
+
+
+def adaptive_stages(method):
+    return len(ADAPTIVE_TABLEAUS[method][0])
+
+
+def hermite_weights(x, S):
+    """(cy0, cy1, kc[S]): the cubic Hermite fit through (y_n, f_n, y_{n+1}, f_{n+1}) of an FSAL-form step at abscissa x, in
+    interp_weights' form (f_n = k_1, f_{n+1} = k_S)."""
+    x2, x3 = x * x, x * x * x
+    kc = [0.0] * S
+    kc[0] = x3 - 2 * x2 + x
+    kc[S - 1] = x3 - x2
+    return 2 * x3 - 3 * x2 + 1, -2 * x3 + 3 * x2, kc
+
+
+def adaptive_interp_weights(method, x):
+    """The end-of-interval fit of an adaptive method: dopri5's quartic (interp_weights), the cubic Hermite fit otherwise."""
+    return interp_weights(x) if method == "dopri5" else hermite_weights(x, adaptive_stages(method))
+
+
 class Field:
     """A vector field over a list of state components.
 
@@ -120,6 +164,11 @@ class Field:
     dopri5_step_native = None     # dopri5_step_native(y, kk, y1, t, h, rtol, atol) -> error sums per ratio group (fp64,
     #                               on the device): integrate_dopri5, one attempted step as one C call
     ratio_groups = None           # components whose error norms pool (a state tensor of torchdiffeq): both error norms
+    # ---- the other adaptive methods (a name of ADAPTIVE_TABLEAUS; S stages) ---------------------------------------------------
+    #                               the dopri5_* members keep their meaning and serve dopri5 alone; a field without the
+    #                               members below runs these methods on the per-stage driver through `eval`
+    adaptive_step_native = None   # adaptive_step_native(method, y, kk, y1, t, h, rtol, atol) -> error sums per ratio group:
+    #                               integrate_adaptive, one attempted step (kk: S stage buffers) as one C call
     # ---- row-partitioned fields (big_components is not None) ------------------------------------------------------------
     big_components = None         # the components that are row slices; odeint keeps such fields forward-only
     adaptive = False              # set by odeint before an adaptive solve: the small components are then kept global
@@ -139,6 +188,9 @@ class Field:
     #                               offering it without dopri5_step_native gets all seven k_s of every step, whatever the
     #                               byte bound (there is nothing to re-run a step with)
     dopri5_backprop_work = None   # dopri5_backprop_work(like) -> the work arrays dopri5_step_backprop takes
+    adaptive_step_backprop = None  # adaptive_step_backprop(method, y, k, g, kbar_last, wy, wk, t, h, first, work, turn, theta):
+    #                               dopri5_step_backprop for the other adaptive methods (k, wk of S entries)
+    adaptive_backprop_work = None  # adaptive_backprop_work(method, like) -> the work arrays adaptive_step_backprop takes
     packed_grads = None           # packed_grads(device) -> zeroed buffer `theta` the sweeps add parameter gradients to
     packed_param_grads = None     # packed_param_grads(theta) -> the gradients in func.parameters() order
 
@@ -324,7 +376,7 @@ def _rms_groups(terms_per_comp, y, rtol, atol, field, pooled):
     return [math.sqrt(sum(sums[c] for c in grp) / sum(_numel(field, y, c) for c in grp)) for grp in groups]
 
 
-def _initial_step(field, t0, y, f0, rtol, atol, sgn, scratch_y, scratch_f, stats):
+def _initial_step(field, t0, y, f0, rtol, atol, sgn, scratch_y, scratch_f, stats, order=5):
     if INITIAL_STEP_NORM not in ("per_tensor", "pooled"):
         raise ValueError("solver.INITIAL_STEP_NORM must be 'per_tensor' or 'pooled'")
     pooled = INITIAL_STEP_NORM == "pooled"
@@ -342,7 +394,7 @@ def _initial_step(field, t0, y, f0, rtol, atol, sgn, scratch_y, scratch_f, stats
     if max(d1) <= 1e-15 and max(d2) <= 1e-15:
         h1 = max(1e-6, h0 * 1e-3)
     else:
-        h1 = (0.01 / max(d1 + d2)) ** (1.0 / 5.0)
+        h1 = (0.01 / max(d1 + d2)) ** (1.0 / order)
     return min(100 * h0, h1)
 
 
@@ -359,11 +411,11 @@ def _optimal_step(last, ratio, safety=0.9, ifactor=10.0, dfactor=0.2, order=5):
 class Dopri5Record:
     """What backprop through an adaptive solve keeps of it (odeint._OdeintBackprop under dopri5): one entry per accepted step,
     (t_n, h_n, x, y_n, [k_1..k_keep]) with x the interpolation abscissa of a last step that overshot the end time, else
-    None.  keep = 7: all stage derivatives; 1: k_1 only; 0: the state alone.  The entries hold the solve's own buffers,
-    which the solve then leaves alone; with max_bytes given, a record of 7 that outgrows it drops to 1."""
+    None.  keep = S (7 under dopri5): all stage derivatives; 1: k_1 only; 0: the state alone.  The entries hold the solve's
+    own buffers, which the solve then leaves alone; with max_bytes given, a record of `full` = S that outgrows it drops to 1."""
 
-    def __init__(self, keep, max_bytes=None):
-        self.keep, self.max_bytes = keep, max_bytes
+    def __init__(self, keep, max_bytes=None, full=7):
+        self.keep, self.max_bytes, self.full = keep, max_bytes, full
         self.steps = []
         self.bytes = 0
 
@@ -371,17 +423,21 @@ class Dopri5Record:
         """-> how many of the leading stage buffers kk[0..] the record has kept."""
         self.steps.append((t, h, x, y, list(kk[:self.keep])))
         self.bytes += sum(c.numel() * c.element_size() for c in y) * (1 + self.keep)
-        if self.keep == 7 and self.max_bytes is not None and self.bytes > self.max_bytes:
+        if self.keep == self.full and self.keep > 1 and self.max_bytes is not None and self.bytes > self.max_bytes:
             self.keep = 1
             self.steps = [(t_, h_, x_, y_, k_[:1]) for (t_, h_, x_, y_, k_) in self.steps]
         return self.keep
 
 
-def integrate_dopri5(field, y, t0, t1, rtol, atol, stats=None, max_steps=100000, record=None):
-    """In-place adaptive integration of the component list y from t0 to t1 (either direction).  record (a
-    Dopri5Record): every accepted step is entered there with the buffers that hold its y_n and stage derivatives, and the
-    solve continues in fresh ones (a rejected attempt's are reused) - the same launches on other addresses, so the
-    values are bit for bit those of the plain solve; the result is then returned in a buffer of its own."""
+def integrate_adaptive(field, y, t0, t1, rtol, atol, method="dopri5", stats=None, max_steps=100000, record=None):
+    """In-place adaptive integration of the component list y from t0 to t1 (either direction) by a method of
+    ADAPTIVE_TABLEAUS.  record (a Dopri5Record): every accepted step is entered there with the buffers that hold its y_n and
+    stage derivatives, and the solve continues in fresh ones (a rejected attempt's are reused) - the same launches on other
+    addresses, so the values are bit for bit those of the plain solve; the result is then returned in a buffer of its own.
+    dopri5 takes the launches it has always taken; the other methods close an attempt with ops.rk_close_err_multi."""
+    C, A, B, E, p = ADAPTIVE_TABLEAUS[method]
+    S = len(C)
+    dp = method == "dopri5"
     stats = stats if stats is not None else Dopri5Stats()
     nc = len(y)
     sgn = 1.0 if t1 >= t0 else -1.0
@@ -389,12 +445,16 @@ def integrate_dopri5(field, y, t0, t1, rtol, atol, stats=None, max_steps=100000,
     # a field may lay out the work copies of the state itself (e.g. small components packed in one buffer) and may
     # offer the whole step as one native call (csrc/ode_driver.hip) when `dopri5_native` is set
     alloc = field.alloc_like or _alloc_like
-    native = field.dopri5_step_native if DOPRI5_NATIVE else None
-    ks = alloc(y, 7)
+    native = None
+    if DOPRI5_NATIVE:
+        native = field.dopri5_step_native if dp else field.adaptive_step_native
+        if native is not None and not dp:
+            native = (lambda f: lambda *args: f(method, *args))(native)
+    ks = alloc(y, S)
     y1, tmp = alloc(y, 2)
     field.eval(t0, [[(1.0, y[c])] for c in range(nc)], ks[0])
     stats.nfe += 1
-    dt = _initial_step(field, t0, y, ks[0], rtol, atol, sgn, tmp, y1, stats)
+    dt = _initial_step(field, t0, y, ks[0], rtol, atol, sgn, tmp, y1, stats, p)
     seq = []                       # (|dt|, accepted, ratio) of every attempt of THIS solve
     forced = REPLAY.pop(0) if REPLAY else None
     if forced is not None:
@@ -406,25 +466,34 @@ def integrate_dopri5(field, y, t0, t1, rtol, atol, stats=None, max_steps=100000,
     while tau < span:
         steps += 1
         if steps > max_steps:
-            raise RuntimeError("dopri5: max_num_steps exceeded")
+            raise RuntimeError("%s: max_num_steps exceeded" % method)
         h = sgn * dt
         # stage buffers: slot 0 is whichever buffer holds the FSAL value
-        order = [fsal] + [i for i in range(7) if i != fsal]
+        order = [fsal] + [i for i in range(S) if i != fsal]
         kk = [ks[i] for i in order]
         t = t0 + sgn * tau
         groups = field.ratio_groups or [[c] for c in range(nc)]
         if native is not None:
             gsums = native(y, kk, y1, t, h, rtol, atol).tolist()     # one call, one device->host sync
-            stats.nfe += 6
+            stats.nfe += S - 1
             ratios = [gs / sum(y[c].numel() for c in grp) for gs, grp in zip(gsums, groups)]
         else:
-            for s in range(1, 7):
-                field.eval(t + DP_C[s] * h, _stage_terms(y, kk, DP_A[s], h), kk[s])
+            for s in range(1, S):
+                field.eval(t + C[s] * h, _stage_terms(y, kk, A[s], h), kk[s])
                 stats.nfe += 1
-            for c in range(nc):
-                ops.lincomb_(y1[c], [(1.0, y[c])] + [(h * DP_B[s], kk[s][c]) for s in range(7) if DP_B[s] != 0.0])
-            sums = [ops.rk_error_sumsq(y[c], y1[c], [(h * DP_E[s], kk[s][c]) for s in range(7) if DP_E[s] != 0.0],
-                                       rtol, atol) for c in range(nc)]
+            if dp:
+                for c in range(nc):
+                    ops.lincomb_(y1[c], [(1.0, y[c])] + [(h * B[s], kk[s][c]) for s in range(S) if B[s] != 0.0])
+                sums = [ops.rk_error_sumsq(y[c], y1[c], [(h * E[s], kk[s][c]) for s in range(S) if E[s] != 0.0],
+                                           rtol, atol) for c in range(nc)]
+            else:
+                # solution and error sums from one pass over the stages, four components per pair of launches
+                live = [s for s in range(S) if B[s] != 0.0 or E[s] != 0.0]
+                ec = [0.0] + [h * E[s] for s in live]
+                sums = [ops.rk_close_err_multi(y1[c0:c0 + 4],
+                                               [[(1.0, y[c])] + [(h * B[s], kk[s][c]) for s in live]
+                                                for c in range(c0, min(c0 + 4, nc))],
+                                               [ec] * (min(c0 + 4, nc) - c0), rtol, atol) for c0 in range(0, nc, 4)]
             sums = torch.cat(sums).tolist()          # the one device->host sync of this step
             if field.reduce_error_sums is not None:
                 sums = field.reduce_error_sums(sums)     # row-partitioned state: every rank sees the global sums
@@ -435,7 +504,8 @@ def integrate_dopri5(field, y, t0, t1, rtol, atol, stats=None, max_steps=100000,
         if accept:
             stats.accepted += 1
             if tau + dt >= span:
-                # interpolate back to the end time with the 4th-order fit through (y0, y_mid, y1, f0, f1)
+                # interpolate back to the end time: dopri5's 4th-order fit through (y0, y_mid, y1, f0, f1), the cubic
+                # Hermite fit through (y0, f0, y1, f1) for the other methods
                 x = (span - tau) / dt
                 res = y                                   # the result overwrites y_n, unless a record keeps that
                 if record is not None:
@@ -446,34 +516,39 @@ def integrate_dopri5(field, y, t0, t1, rtol, atol, stats=None, max_steps=100000,
                         if res[c] is not y1[c]:
                             res[c].copy_(y1[c])
                 else:
-                    cy0, cy1, kc = interp_weights(x)
+                    cy0, cy1, kc = adaptive_interp_weights(method, x)
                     for c in range(nc):
                         ops.lincomb_(res[c], [(cy0, y[c]), (cy1, y1[c])] +
-                                     [(h * kc[s], kk[s][c]) for s in range(7) if kc[s] != 0.0])
+                                     [(h * kc[s], kk[s][c]) for s in range(S) if kc[s] != 0.0])
                 y = res
                 tau = span
                 break
             if record is not None:
                 kept = record.accepted(t, h, None, y, kk)
-                for j in range(min(kept, 6)):             # kk[6] goes on as the next step's k_1 and is read only
+                for j in range(min(kept, S - 1)):         # kk[S - 1] goes on as the next step's k_1 and is read only
                     ks[order[j]] = alloc(y, 1)[0]
                 y = alloc(y, 1)[0]                        # takes y1's place below
             y, y1 = y1, y
             last = y1
             tau += dt
-            fsal = order[6]
+            fsal = order[S - 1]
         else:
             stats.rejected += 1
-        dt = _optimal_step(dt, ratio) if forced is None else float(forced[min(len(seq), len(forced) - 1)][0])
+        dt = _optimal_step(dt, ratio, order=p) if forced is None else float(forced[min(len(seq), len(forced) - 1)][0])
     stats.attempts.extend(seq)
     if TRACE is not None:
         TRACE.append(seq)
     return y, stats
 
 
-def integrate_dopri5_inplace(field, y, t0, t1, rtol, atol, stats=None):
+def integrate_dopri5(field, y, t0, t1, rtol, atol, stats=None, max_steps=100000, record=None):
+    """integrate_adaptive under Dormand-Prince 5(4)."""
+    return integrate_adaptive(field, y, t0, t1, rtol, atol, "dopri5", stats, max_steps, record)
+
+
+def integrate_dopri5_inplace(field, y, t0, t1, rtol, atol, stats=None, method="dopri5"):
     """Wrapper keeping the caller's tensors as the result holders."""
-    res, stats = integrate_dopri5(field, list(y), t0, t1, rtol, atol, stats)
+    res, stats = integrate_adaptive(field, list(y), t0, t1, rtol, atol, method, stats)
     for dst, src in zip(y, res):
         if dst.data_ptr() != src.data_ptr():
             dst.copy_(src)

@@ -827,6 +827,59 @@ int gode_gcn_ode_dopri5_step_backprop(const gode_gcn_odefunc_t* f, const float* 
                                       float* const* ktheta /* 7 */, const gode_rk4_workspace_t* ws,
                                       float* cot_colpart /* nullable */, void* stream);
 
+/* The close of an adaptive step in two launches instead of three.  Per component c (count of them, 1..4; blockIdx.y):
+ *   y1[c]   = sum_j sol[c].coef[j] * sol[c].ptr[j]      (stored unless y1[c] is NULL: a component that is an error group
+ *                                                        of its own but lies inside another one's output),
+ *   sums[c] = sum_i (err_i / (atol + rtol * max(|y0_i|, |y1_i|)))^2,  err = sum_j err_coef[c][j] * sol[c].ptr[j],
+ * with y0 = sol[c].ptr[0] (the step's start state, coefficient 1) and every term loaded once.  16-byte loads and stores
+ * where n[c] % 4 == 0 and every pointer of the component is 16-byte aligned, scalar ones otherwise.  For finite inputs
+ * y1[c] is bit for bit what gode_lincomb_f32 stores for sol[c] and sums[c] what gode_rk_errnorm_f32 forms from that y1
+ * and the terms with a non-zero err_coef (a zero coefficient changes no bit).  No atomics; one stream.
+ * GODE_E_NULLPTR: a NULL argument, err_coef[c] or term; GODE_E_SHAPE: count outside 1..4, a term count outside
+ * 1..GODE_MAX_TERMS, n[c] <= 0, or a y1[c] that is one of its own terms.  scratch: gode_rk_close_err_scratch_bytes(). */
+int64_t gode_rk_close_err_scratch_bytes(void);
+int gode_rk_close_err_multi_f32(float* const* y1 /* host[count], entries nullable */,
+                                const gode_lincomb_t* sol /* host[count]: ptr[0] = y0 with coef 1, then the k's */,
+                                const float* const* err_coef /* host[count] -> GODE_MAX_TERMS floats over sol's terms */,
+                                const int64_t* n /* host[count] */, int32_t count /* 1..4 */, float rtol, float atol,
+                                double* sums /* device[count] */, void* scratch, void* stream);
+
+/* The adaptive methods of the step drivers below by code, in FSAL form (the last row of a equals b: k_S of an accepted step
+ * is k_1 of the next), and their tableaus (host queries: no device is touched).  gode_rka_stages: S; gode_rka_order: p, the
+ * order of the solution the step advances with; gode_rka_tableau: c (S), a (S x S, row-major, strictly lower
+ * triangular), b (S) and e = b - b* (S: the error weights); any output may be NULL.  GODE_E_SHAPE for a code outside the list.
+ *   GODE_RKA_DOPRI5         Dormand-Prince 5(4), S = 7 (what the gode_*_dopri5_step_* entry points run)
+ *   GODE_RKA_BOSH3          Bogacki-Shampine 3(2), S = 4
+ *   GODE_RKA_ADAPTIVE_HEUN  Heun-Euler 2(1) as its three-stage FSAL extension, S = 3: c = [0, 1, 1], the third stage is
+ *                           f(t + h, y1) */
+#define GODE_RKA_DOPRI5        0
+#define GODE_RKA_BOSH3         1
+#define GODE_RKA_ADAPTIVE_HEUN 2
+int gode_rka_stages(int32_t method);
+int gode_rka_order(int32_t method);
+int gode_rka_tableau(int32_t method, double* c, double* a, double* b, double* e);
+
+/* The three dopri5 step drivers above for any adaptive method (GODE_RKA_*): the same arguments after the code, with k /
+ * ky / ka / ktheta / ybar of S entries and wk of S; small_part, when given, must hold S slots.  The same routes; the
+ * forward and the adjoint step close with gode_rk_close_err_multi_f32 (the adjoint: one call for its three outputs and
+ * four error groups), so GODE_RKA_DOPRI5 returns the dopri5 entry points' arrays and sums bit for bit.
+ * Validation: null pointers, then a method outside the list (GODE_E_SHAPE), then the dopri5 counterpart's checks;
+ * err_scratch >= gode_rk_close_err_scratch_bytes(). */
+int gode_gcn_ode_adaptive_step_forward(int32_t method, const gode_gcn_odefunc_t* f, const float* y, float* const* k /* S */,
+                                       float* y1, const gode_rk4_workspace_t* ws, double t, double h, float rtol,
+                                       float atol, double* sums, void* err_scratch, void* stream);
+int gode_gcn_ode_adaptive_step_adjoint(int32_t method, const gode_gcn_odefunc_t* f, const float* y, const float* a,
+                                       const float* theta, float* const* ky /* S */, float* const* ka /* S */,
+                                       float* const* ktheta /* S */, float* y1, float* a1, float* theta1,
+                                       const gode_rk4_workspace_t* ws, double t, double h, float rtol, float atol,
+                                       double* sums /* 4 */, void* err_scratch, void* stream);
+int gode_gcn_ode_adaptive_step_backprop(int32_t method, const gode_gcn_odefunc_t* f, const float* y, float* const* k /* S */,
+                                        const float* g, const float* kbar_last /* nullable */, double wy,
+                                        const double* wk /* host, S */, double t, double h, int32_t first,
+                                        float* const* ybar /* S */, float* ybar_n, float* kbar1, float* theta,
+                                        float* const* ktheta /* S */, const gode_rk4_workspace_t* ws,
+                                        float* cot_colpart /* nullable */, void* stream);
+
 /* The same for the GAT ODE function  f(t, x) = relu(EdgeAttention([t | GroupNorm(x)]))  (GAT/models.py:172-179 ->
  * GAT/layers.py:95-122; the layer's message activation is any GODE_GAT_ACT_*: `act` below), with the two Linear layers packed by role: Wsrc, Wtgt ((d+1) x d: message parts by source /
  * target, time row first) and Wlog ((d+1) x 2: the two logit columns).  Adjoint state: (y, a, a_t, theta) with
