@@ -9,7 +9,8 @@
 // The launch sequence of one evaluation is graph_odenet_amd/gat_ode.py (GatOdeField / GatOdeAdjointField), which
 // branches on the head count where this file does.
 // At the end of the file: backprop through rk4 and dopri5 solves on launch-bound graphs (gode_gat_ode_rk4_forward_save,
-// gode_gat_ode_rk4_backprop, gode_gat_ode_dopri5_step_backprop), whose stage reverse is the adjoint stage's (stage_vjp).
+// gode_gat_ode_rk4_backprop, gode_gat_ode_dopri5_step_backprop), whose stage reverse is the adjoint stage's (stage_vjp), and
+// the three step functions for any adaptive method (gode_gat_ode_adaptive_step_*: bosh3, adaptive_heun, dopri5 from its tableau).
 #include "rk_driver.h"
 #include "options.h"
 #include <cmath>
@@ -139,13 +140,16 @@ int stage_vjp(const gode_gat_odefunc_t* f, const gode_gat_workspace_t* w, gode_l
 }
 
 // theta-k layout: [Wsrc ((d+1)*d) | Wtgt ((d+1)*d) | Wlog ((d+1)*2H) | bf (d) | bw (H) | gamma (d) | beta (d)]   (H = 1: one head)
-// An adjoint stage: the stage VJP with cotangent -a, then the parameter derivative closed from what it left.
+// An adjoint stage: the stage VJP with cotangent -a, then the parameter derivative closed from what it left.  `slot`
+// (one-launch route only): the stage's partials go there instead of w->small_part and the caller closes them, with those
+// of the step's other stages, in one gode_gat_small_finish_multi_f32.
 int eval_adjoint(const gode_gat_odefunc_t* f, const gode_gat_workspace_t* w, gode_lincomb_t yin, const gode_lincomb_t& ain,
-                 float t, float* ky, float* ka, float* kat, float* kth, void* stream) {
+                 float t, float* ky, float* ka, float* kat, float* kth, void* stream, float* slot = nullptr) {
     const int64_t H = n_heads(f);
     const int64_t n = f->n, d = f->d, nW = (d + 1) * d, nL = (d + 1) * 2 * H;
-    float* part = (w->small_part && small_dense(f)) ? w->small_part : nullptr;
+    float* part = (w->small_part && small_dense(f)) ? (slot ? slot : w->small_part) : nullptr;
     GODE_TRY(stage_vjp(f, w, &yin, ain, -1.f, t, ky, ka, nullptr, part, stream));
+    if (part && slot) return 0;
     if (part) return gode_gat_small_finish_f32(part, n, d, H, t, kth, kat, stream);      // one more launch to close
     float* g_src = kth; float* g_tgt = kth + nW; float* g_log = kth + 2 * nW;
     float* g_bf = g_log + nL; float* g_bw = g_bf + d; float* g_gamma = g_bw + H; float* g_beta = g_gamma + d;
@@ -485,4 +489,124 @@ extern "C" int gode_gat_ode_fixed_backprop(int32_t method, const gode_gat_odefun
         GODE_TRY(gode_lincomb_f32(a, &sum, nd, stream));
     }
     return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// The adaptive step drivers by method (GODE_RKA_*): the three dopri5 step functions above driven by a tableau and its error
+// weights (rk_driver.h: AdaptiveMethod), on the same routes and under every message activation.  The forward and the
+// adjoint step close with the fused launch of rk.hip (gode_rk_close_err_multi_f32): the solution and the error sums from
+// one pass over the stages.  On the one-launch route the adjoint step, given `parts`, leaves each stage's partials in a
+// slot of their own and closes the S - 1 stages with ONE gode_gat_small_finish_multi_f32: nothing inside the step reads
+// kth[s] / kat[s] before the close.
+// ---------------------------------------------------------------------------------------------------------------
+extern "C" int gode_gat_ode_adaptive_step_forward(int32_t method, const gode_gat_odefunc_t* f, const float* y,
+                                                  float* const* k, float* y1, const gode_gat_workspace_t* w, double t,
+                                                  double h, float rtol, float atol, double* sums, void* err_scratch,
+                                                  void* stream)
+{
+    if (!f || !w || !y || !k || !y1 || !sums || !err_scratch) return GODE_E_NULLPTR;
+    const AdaptiveMethod* am = adaptive_method(method);
+    if (!am) return GODE_E_SHAPE;
+    int rc = check_common(f, w, false); if (rc) return rc;
+    const Tableau& tab = am->tab;
+    const int S = tab.stages;
+    for (int s = 0; s < S; ++s) if (!k[s]) return GODE_E_NULLPTR;
+    const int64_t nd = f->n * f->d;
+    for (int s = 1; s < S; ++s) {
+        gode_lincomb_t yin = tab_stage_terms(tab, y, k, s, h);
+        GODE_TRY(eval_forward(f, w, &yin, (float)(t + tab.c[s] * h), k[s], stream));
+    }
+    float ec[GODE_MAX_TERMS];
+    const gode_lincomb_t sol = close_terms(*am, y, k, h, ec);
+    const float* ecp = ec;
+    return gode_rk_close_err_multi_f32(&y1, &sol, &ecp, &nd, 1, rtol, atol, sums, err_scratch, stream);
+}
+
+extern "C" int gode_gat_ode_adaptive_step_adjoint(int32_t method, const gode_gat_odefunc_t* f, const float* y, const float* a,
+                                                  const float* a_t, const float* theta, float* const* ky, float* const* ka,
+                                                  float* const* kat, float* const* kth, float* y1, float* a1, float* a_t1,
+                                                  float* theta1, const gode_gat_workspace_t* w, float* parts, double t,
+                                                  double h, float rtol, float atol, double* sums /* 4 */, void* err_scratch,
+                                                  void* stream)
+{
+    if (!f || !w || !y || !a || !a_t || !theta || !ky || !ka || !kat || !kth || !y1 || !a1 || !a_t1 || !theta1 || !sums ||
+        !err_scratch) return GODE_E_NULLPTR;
+    const AdaptiveMethod* am = adaptive_method(method);
+    if (!am) return GODE_E_SHAPE;
+    int rc = check_common(f, w, true); if (rc) return rc;
+    const Tableau& tab = am->tab;
+    const int S = tab.stages;
+    for (int s = 0; s < S; ++s) if (!ky[s] || !ka[s] || !kat[s] || !kth[s]) return GODE_E_NULLPTR;
+    const int64_t nd = f->n * f->d, H = n_heads(f), P = gode_gat_ode_theta_len_heads(f->d, H);
+    const bool multi = parts && w->small_part && small_dense(f);      // the stages' closing launches as one
+    const int64_t slot = multi ? part_slot(f) : 0;
+    float tsv[7];
+    for (int s = 1; s < S; ++s) {
+        gode_lincomb_t yin = tab_stage_terms(tab, y, ky, s, h);
+        gode_lincomb_t ain = tab_stage_terms(tab, a, ka, s, h);
+        tsv[s - 1] = (float)(t + tab.c[s] * h);
+        GODE_TRY(eval_adjoint(f, w, yin, ain, tsv[s - 1], ky[s], ka[s], kat[s], kth[s], stream,
+                              multi ? parts + (s - 1) * slot : nullptr));
+    }
+    if (multi) GODE_TRY(gode_gat_small_finish_multi_f32(parts, f->n, f->d, H, S - 1, kth + 1, kat + 1, tsv, stream));
+    // one close for the four outputs and the four error groups y, a, a_t, theta, each group the decomposition the separate
+    // error norm gives it
+    float ec[4][GODE_MAX_TERMS];
+    const gode_lincomb_t sols[4] = {close_terms(*am, y, ky, h, ec[0]), close_terms(*am, a, ka, h, ec[1]),
+                                    close_terms(*am, a_t, kat, h, ec[2]), close_terms(*am, theta, kth, h, ec[3])};
+    float* outs[4] = {y1, a1, a_t1, theta1};
+    const float* ecs[4] = {ec[0], ec[1], ec[2], ec[3]};
+    const int64_t lens[4] = {nd, nd, 1, P};
+    return gode_rk_close_err_multi_f32(outs, sols, ecs, lens, 4, rtol, atol, sums, err_scratch, stream);
+}
+
+extern "C" int gode_gat_ode_adaptive_step_backprop(int32_t method, const gode_gat_odefunc_t* f, const float* y,
+                                                   float* const* k, const float* g, const float* kbar_last, double wy,
+                                                   const double* wk, double t, double h, int32_t first, float* const* ybar,
+                                                   float* ybar_n, float* kbar1, float* theta, float* k_scratch, float* parts,
+                                                   const gode_gat_workspace_t* ws, void* stream)
+{
+    if (!f || !ws || !y || !k || !g || !wk || !ybar || !ybar_n || !theta || !k_scratch || !parts) return GODE_E_NULLPTR;
+    if (!first && !kbar1) return GODE_E_NULLPTR;
+    const AdaptiveMethod* am = adaptive_method(method);
+    if (!am) return GODE_E_SHAPE;                  // the entries of k / ybar are looked at below: their count is the method's
+    const Tableau& tab = am->tab;
+    const int S = tab.stages;
+    for (int s = 0; s < S; ++s) if (!k[s]) return GODE_E_NULLPTR;
+    for (int s = first ? 0 : 1; s < S; ++s) if (!ybar[s]) return GODE_E_NULLPTR;
+    if (ybar_n == g || ybar_n == kbar_last || ybar_n == k_scratch || k_scratch == g || k_scratch == kbar_last) return GODE_E_SHAPE;
+    if (!first && (kbar1 == g || kbar1 == kbar_last || kbar1 == ybar_n || kbar1 == k_scratch)) return GODE_E_SHAPE;
+    for (int s = first ? 0 : 1; s < S; ++s) {
+        if (ybar[s] == g || ybar[s] == kbar_last || ybar[s] == ybar_n || (!first && ybar[s] == kbar1) || ybar[s] == k_scratch)
+            return GODE_E_SHAPE;
+        for (int r = s + 1; r < S; ++r) if (ybar[s] == ybar[r]) return GODE_E_SHAPE;
+    }
+    int rc = check_sweep(f, ws); if (rc) return rc;
+    const int64_t n = f->n, d = f->d, nd = n * d, H = n_heads(f), slot = part_slot(f);
+    const int last = first ? 0 : 1;                // the last stage the sweep pushes through f
+    bool dead[7] = {};
+    float ts[7];
+    int live = 0;
+    auto cotangent = [&](int s) {
+        gode_lincomb_t c = stage_cotangent(tab, g, (float)wk[s], ybar, s, h, dead);
+        if (s == S - 1 && kbar_last) { c.coef[c.n] = 1.f; c.ptr[c.n] = kbar_last; ++c.n; }
+        return c;
+    };
+    for (int s = S - 1; s >= last; --s) {
+        const gode_lincomb_t cot = cotangent(s);
+        if (cot.n == 0) { dead[s] = true; continue; }
+        ts[live] = (float)(t + tab.c[s] * h);
+        gode_lincomb_t yin = tab_stage_terms(tab, y, k, s, h);
+        GODE_TRY(stage_vjp(f, ws, &yin, cot, 1.f, ts[live], k_scratch, ybar[s], nullptr, parts + live * slot, stream));
+        ++live;
+    }
+    // ybar_n = wy g + sum Ybar_s, and (not first) kbar_1 for the step before: one launch
+    float* outs[2] = {ybar_n, kbar1};
+    gode_lincomb_t lcs[2] = {sweep_pre(tab, g, (float)wy, ybar, last, dead), first ? gode_lincomb_t() : cotangent(0)};
+    int64_t lens[2] = {nd, nd};
+    int count = first ? 1 : 2;
+    if (count == 2 && lcs[1].n == 0) { GODE_TRY(gode_zero_f32(kbar1, nd, stream)); count = 1; }
+    GODE_TRY(gode_lincomb_multi_f32(outs, lcs, lens, count, stream));
+    if (live == 0) return 0;
+    return gode_gat_small_close_stages_f32(parts, n, d, H, live, ts, theta, stream);
 }

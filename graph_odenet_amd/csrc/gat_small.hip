@@ -16,6 +16,8 @@
 //                                  bw = odd columns of colsum(dA2)), dgamma, dbeta, and the block's share of
 //                                  a_t = colsums . W[0, :]: replaces 3 + 3 + 2 launches
 //   gode_gat_small_finish_f32      k_theta and k_a_t from the partials: one launch, every load in flight at once
+//   gode_gat_small_finish_multi_f32  the same for the up to seven stages of an adaptive adjoint step: one launch, a stage per
+//                                  blockIdx.y, each stage's outputs bit for bit the single form's
 //   gode_gat_small_close_stages_f32  theta += sum_s k_theta(stage s) over the up to seven stages a backprop sweep pushed
 //                                  through f in one step (gat_driver.hip): one launch, one barrier for all slots
 //
@@ -643,6 +645,8 @@ __global__ __launch_bounds__(256) void gat_dense_vjp_d64_kernel(LinComb xin, int
     if (threadIdx.x == 0) out[rA] = (at_w[0] + at_w[1]) + (at_w[2] + at_w[3]);
 }
 
+// (The load, column-sum and scale body below stands three times in this file - here, in gat_small_finish_multi_kernel and in
+// gat_small_close_stages_kernel - and the tests hold the three to the same bits: a change to one goes into all three.)
 // k_theta = [Wsrc | Wtgt | Wlog | bf | bw | gamma | beta] (time rows scaled by t) and k_a_t from the block partials:
 // 1 024 threads = 32 part-groups x 32 outputs, 16 loads per thread in flight together (512 partial rows: one round).
 struct GatFinish {
@@ -719,12 +723,60 @@ __global__ __launch_bounds__(1024) void gat_small_finish_kernel(GatFinish g)
     }
 }
 
+// The kernel above on its overwrite path (n_slots == 0) for up to seven stages in one launch, blockIdx.y = stage: an adaptive
+// adjoint step closes all its stages at once - nothing inside the step reads the small components' stage derivatives
+// (csrc/gat_driver.hip), and the stages' loads are in flight side by side instead of one launch after the other.  Stage s:
+// partials at part + s * n_part * plen, time t = ts[s], outputs ktheta[s] / kat[s]; per stage the arithmetic is the kernel
+// above's - the 16 loads per round summed in the same order, the same sm[32][33] column sum, the same scale * tsum: the same
+// bits.  (The loops are spelled out again, as in gat_small_close_stages_kernel, and the kernel above is left as it was: with
+// the two sums moved into functions both kernels call, its instructions came out in another order.  The third copy is
+// gat_small_close_stages_kernel: a change to the loads, the column sum or the scaling goes into all three.)
+constexpr int kGatFinishStages = 7;
+struct GatFinishMulti {
+    const float* part; int n_part, plen, d, nl, nlp, heads, out_len;
+    float ts[kGatFinishStages]; float* ktheta[kGatFinishStages]; float* kat[kGatFinishStages];
+};
+__global__ __launch_bounds__(1024) void gat_small_finish_multi_kernel(GatFinishMulti g)
+{
+    __shared__ float sm[32][33];
+    const int st = blockIdx.y;
+    const int jj = threadIdx.x & 31, qq = threadIdx.x >> 5;
+    const int j = (int)blockIdx.x * 32 + jj;
+    bool is_time_row;
+    const int src = gat_finish_source(j, g.d, g.nl, g.nlp, g.heads, g.out_len, g.plen, is_time_row);
+    const float scale = is_time_row ? g.ts[st] : 1.f;
+    const float* part = g.part + (int64_t)st * g.n_part * g.plen;
+    float v = 0.f;
+    if (src >= 0) {
+        for (int p0 = qq; p0 < g.n_part; p0 += 32 * 16) {           // 16 independent loads in flight per thread
+            float x[16];
+#pragma unroll
+            for (int u = 0; u < 16; ++u) {
+                const int p = p0 + 32 * u;
+                x[u] = p < g.n_part ? part[(int64_t)p * g.plen + src] : 0.f;
+            }
+#pragma unroll
+            for (int u = 0; u < 16; ++u) v += x[u];
+        }
+    }
+    sm[qq][jj] = v;
+    __syncthreads();
+    if (qq == 0 && src >= 0) {
+        float tsum = sm[0][jj];
+#pragma unroll
+        for (int k = 1; k < 32; ++k) tsum += sm[k][jj];
+        const float total = (j < g.out_len ? scale : 1.f) * tsum;
+        if (j < g.out_len) g.ktheta[st][j] = total; else *g.kat[st] = total;
+    }
+}
+
 // theta += sum_s k_theta(stage s) over the n_slots <= 7 stages a backprop sweep pushed through f in one step (the RK weights
 // are already inside the stages' cotangents; a backprop sweep has no a_t).  Same thread layout and the same sums per slot
 // as the kernel above - the 16 partial-row loads of a slot in flight at once - but every slot is summed into a register
 // of its own before ONE barrier, where the kernel above takes a barrier pair per slot.  (As compiled, a slot's loads are
 // waited for before the next slot's are issued: the slots are still up to seven load round trips, one after the other.)
-// The slots are added slot 0 first.  `unit` is 1.0 passed at RUN time: fmaf(unit, sc * tsum, total) is the multiply-add
+// (The per-slot loads and column sum are those of gat_small_finish_kernel and gat_small_finish_multi_kernel: keep the three in
+// step.)  The slots are added slot 0 first.  `unit` is 1.0 passed at RUN time: fmaf(unit, sc * tsum, total) is the multiply-add
 // of the four-slot closing launch with unit weights (the same bits), and with a literal 1 the compiler may contract
 // sc * tsum + total into fma(sc, tsum, total), which rounds the product away and breaks that equality.
 constexpr int kGatCloseSlots = 7;
@@ -925,6 +977,32 @@ extern "C" int gode_gat_small_finish_f32(const float* part, int64_t n_rows, int6
     for (int q = 0; q < 4; ++q) { g.ts[q] = 0.f; g.w[q] = 0.f; }
     const int blocks = (g.out_len + 1 + 31) / 32;
     hipLaunchKernelGGL(gat_small_finish_kernel, dim3((unsigned)blocks), dim3(1024), 0, (hipStream_t)stream, g);
+    GODE_LAUNCH_CHECK();
+    return 0;
+}
+
+// gode_gat_small_finish_f32 for the n_stages <= 7 stages of one adaptive adjoint step in ONE launch: stage s's partials at
+// part + s * parts * part_len, closed at t = ts[s] into ktheta[s] / kat[s] - each bit for bit what the single form gives.
+extern "C" int gode_gat_small_finish_multi_f32(const float* part, int64_t n_rows, int64_t d, int64_t heads, int32_t n_stages,
+                                               float* const* ktheta /* host */, float* const* kat /* host */,
+                                               const float* ts /* host */, void* stream)
+{
+    if (heads < 1) heads = 1;
+    if (!part || !ktheta || !kat || !ts) return GODE_E_NULLPTR;
+    if (n_rows <= 0 || d <= 0 || n_stages < 1 || n_stages > kGatFinishStages) return GODE_E_SHAPE;
+    for (int s = 0; s < n_stages; ++s) if (!ktheta[s] || !kat[s]) return GODE_E_NULLPTR;
+    if (!gode_gat_small_supported(n_rows, d, (int32_t)d, heads)) return GODE_E_UNSUPPORTED;     // the kernels' shapes, whatever the grouping
+    GatFinishMulti g;
+    g.part = part; g.n_part = (int)gode_gat_small_parts(n_rows, d); g.plen = (int)gode_gat_small_part_len(d, heads);
+    g.d = (int)d; g.nl = (int)(2 * heads); g.nlp = g.nl <= 4 ? 4 : 16; g.heads = (int)heads;
+    g.out_len = (int)(2 * (d + 1) * d + (d + 1) * 2 * heads + d + heads + 2 * d);
+    for (int s = 0; s < kGatFinishStages; ++s) {
+        g.ts[s] = s < n_stages ? ts[s] : 0.f;
+        g.ktheta[s] = s < n_stages ? ktheta[s] : nullptr;
+        g.kat[s] = s < n_stages ? kat[s] : nullptr;
+    }
+    const int blocks = (g.out_len + 1 + 31) / 32;
+    hipLaunchKernelGGL(gat_small_finish_multi_kernel, dim3((unsigned)blocks, (unsigned)n_stages), dim3(1024), 0, (hipStream_t)stream, g);
     GODE_LAUNCH_CHECK();
     return 0;
 }

@@ -26,18 +26,20 @@ at the end of the solve.
 
 Backprop through the solve (odeint, adjoint=False) on launch-bound graphs - GatOdeField.small(), no padded logit columns:
 the forward field offers the backprop half of solver.Field's protocol, issued from C (csrc/gat_driver.hip:
-gode_gat_ode_rk4_forward_save / _rk4_backprop / _dopri5_step_backprop).  The reverse of a stage is the adjoint stage's
+gode_gat_ode_rk4_forward_save / _rk4_backprop / _dopri5_step_backprop, and - with GatOdeField.ADAPTIVE_NATIVE on -
+gode_gat_ode_adaptive_step_backprop for bosh3 and adaptive_heun).  The reverse of a stage is the adjoint stage's
 launch sequence with the stage's cotangent kbar_s in place of -a; each swept stage leaves its parameter partials in a slot of
 its own and one gode_gat_small_close_stages_f32 launch per step adds them to the packed theta.  Elsewhere the members stay
 None and odeint re-runs each interval as torch ops under autograd.
 """
 import ctypes
+import os
 
 import torch
 
 from . import _lib, ops
 from .gat_layers import message_activation
-from .solver import Field, method_code
+from .solver import Field, adaptive_code, adaptive_stages, method_code
 
 
 # launch-bound graphs: the reduction launches that close an adjoint stage run as one (ops.reduce_segments_); larger graphs
@@ -147,12 +149,14 @@ class _Work:
         self.pair = torch.empty(2 * H, **f)
         self.colsum_scratch = torch.empty(max(lib.gode_colsum_scratch_bytes(n, d), 16), **u8)
         self.colsum_scratch2 = torch.empty(max(lib.gode_colsum_scratch_bytes(n, 2 * H), 16), **u8)
-        self.err_scratch = torch.empty(lib.gode_rk_errnorm_scratch_bytes(), **u8)
+        # the dopri5 drivers' error norm and the tableau-driven drivers' fused close share it: the larger of the two
+        self.err_scratch = torch.empty(max(lib.gode_rk_errnorm_scratch_bytes(), lib.gode_rk_close_err_scratch_bytes()), **u8)
         # launch-bound graphs: block partials of the one-launch dense VJP (csrc/gat_small.hip)
         small = not spec.pad_logits and lib.gode_gat_small_supported(n, d, spec.groups, H)
         self.small_part = ops.gat_small_part(n, d, H, device) if small else None
         self.step_parts = None                 # four such buffers, one per stage of a fixed-grid step (allocated on first use)
         self.sweep = None                      # work arrays of the backprop sweeps (_SweepWork, allocated on first use)
+        self.adj_parts = None                  # partial slots of a one-call adaptive adjoint step (allocated on first use)
 
 
 class _SweepWork:
@@ -196,17 +200,26 @@ class GatOdeField(Field):
     n_components = 1
     fused = True
     BACKPROP_FUSED = True            # False: no backprop members (odeint re-runs each interval as torch ops under autograd)
+    # bosh3 / adaptive_heun on the one-call step and the fused sweep (csrc/gat_driver.hip: gode_gat_ode_adaptive_step_*).  An
+    # opt-in (the environment's GODE_GAT_ADAPTIVE_NATIVE=1, or this attribute set before the fields are built): off, the fields
+    # offer no adaptive_* member and the two methods run on the per-stage driver as before (generic backprop under
+    # adjoint=False) - what tests/test_gpu_adaptive_methods.py: test_gat_bosh3 states of a GAT field
+    ADAPTIVE_NATIVE = os.environ.get("GODE_GAT_ADAPTIVE_NATIVE", "0") == "1"
 
     def __init__(self, spec, work, order=None):
         self.s, self.w = spec, work
         self.token = ("gat-heads" if spec.heads > 1 else "gat", id(spec.eg))
         if spec.pad_logits:
             self.dopri5_step_native = None
+        elif self.ADAPTIVE_NATIVE:
+            self.adaptive_step_native = self._adaptive_step_native      # a member of the instance, as the sweeps below
         if order is not None and self.BACKPROP_FUSED and not spec.pad_logits and self.small():
             self.order = order
             self.rk4_forward_save, self.rk4_backprop = self._rk4_forward_save, self._rk4_backprop
             self.fixed_forward_save, self.fixed_backprop = self._fixed_forward_save, self._fixed_backprop
             self.dopri5_step_backprop, self.dopri5_backprop_work = self._dopri5_step_backprop, self._dopri5_backprop_work
+            if self.ADAPTIVE_NATIVE:
+                self.adaptive_step_backprop, self.adaptive_backprop_work = self._adaptive_step_backprop, self._adaptive_backprop_work
             self.packed_grads, self.packed_param_grads = self._packed_grads, self._packed_param_grads
 
     def prepare(self):
@@ -271,6 +284,21 @@ class GatOdeField(Field):
                                                         float(t), float(h), float(rtol), float(atol), _lib.ptr(sums),
                                                         _lib.ptr(self.w.err_scratch), _lib.stream_ptr()),
                    "gode_gat_ode_dopri5_step_forward")
+        return sums
+
+    def _adaptive_step_native(self, method, y, kk, y1, t, h, rtol, atol):
+        """dopri5_step_native for any adaptive method (kk: S stage buffers): gode_gat_ode_adaptive_step_forward, which closes
+        the step with the fused launch (solution and error sum from one pass over the stages)."""
+        lib = _lib.load()
+        S = adaptive_stages(method)
+        fs, ws = self._structs(False)
+        kptr = (ctypes.c_void_p * S)(*[kk[i][0].data_ptr() for i in range(S)])
+        sums = torch.empty(1, dtype=torch.float64, device=y[0].device)
+        _lib.check(lib.gode_gat_ode_adaptive_step_forward(adaptive_code(method), ctypes.byref(fs), _lib.ptr(y[0]), kptr,
+                                                          _lib.ptr(y1[0]), ctypes.byref(ws), float(t), float(h), float(rtol),
+                                                          float(atol), _lib.ptr(sums), _lib.ptr(self.w.err_scratch),
+                                                          _lib.stream_ptr()),
+                   "gode_gat_ode_adaptive_step_forward")
         return sums
 
     # ---- backprop through the solve (odeint._OdeintBackprop): launch-bound graphs, csrc/gat_driver.hip ------------------
@@ -342,6 +370,27 @@ class GatOdeField(Field):
             ctypes.byref(fs), _lib.ptr(y), kptr, _lib.ptr(g), _lib.ptr(kbar7), float(wy), wka, float(t), float(h),
             1 if first else 0, ybar, _lib.ptr(ybar_n), _lib.ptr(kbar1), _lib.ptr(theta), _lib.ptr(sw.k_scratch),
             _lib.ptr(sw.parts), ctypes.byref(ws), _lib.stream_ptr()), "gode_gat_ode_dopri5_step_backprop")
+        return ybar_n, (None if first else kbar1)
+
+    def _adaptive_backprop_work(self, method, like):
+        """_dopri5_backprop_work for any adaptive method: _SweepWork's 7 Ybar and 7 slots serve every S."""
+        return self._dopri5_backprop_work(like)
+
+    def _adaptive_step_backprop(self, method, y, k, g, kbar_last, wy, wk, t, h, first, work, turn, theta):
+        """_dopri5_step_backprop for any adaptive method (k, wk of S entries; kbar_last arrives on k_S):
+        gode_gat_ode_adaptive_step_backprop."""
+        fs, ws = self._structs(True)
+        sw = self._sweep_work()
+        S = adaptive_stages(method)
+        ybar_n, kbar1 = work["pairs"][turn]
+        kptr = (ctypes.c_void_p * S)(*[x.data_ptr() for x in k])
+        ybar = (ctypes.c_void_p * S)(*[b.data_ptr() for b in work["ybar"][:S]])
+        wka = (ctypes.c_double * S)(*[float(v) for v in wk])
+        _lib.check(_lib.load().gode_gat_ode_adaptive_step_backprop(
+            adaptive_code(method), ctypes.byref(fs), _lib.ptr(y), kptr, _lib.ptr(g), _lib.ptr(kbar_last), float(wy), wka,
+            float(t), float(h), 1 if first else 0, ybar, _lib.ptr(ybar_n), _lib.ptr(kbar1), _lib.ptr(theta),
+            _lib.ptr(sw.k_scratch), _lib.ptr(sw.parts), ctypes.byref(ws), _lib.stream_ptr()),
+            "gode_gat_ode_adaptive_step_backprop")
         return ybar_n, (None if first else kbar1)
 
     def _project(self, t, y_terms):
@@ -421,6 +470,33 @@ class GatOdeAdjointField(GatOdeField):
             _lib.ptr(y1[0]), _lib.ptr(y1[1]), _lib.ptr(y1[2]), _lib.ptr(y1[3]), ctypes.byref(ws), float(t), float(h),
             float(rtol), float(atol), _lib.ptr(sums), _lib.ptr(self.w.err_scratch), _lib.stream_ptr()),
             "gode_gat_ode_dopri5_step_adjoint")
+        return sums
+
+    def _adjoint_parts(self, S):
+        """S - 1 partial slots for a one-call adaptive step on the one-launch route (the sweeps' slots when they exist), else
+        None: each stage then closes its own partials."""
+        w = self.w
+        if not self.small():
+            return None
+        if w.sweep is not None:
+            return w.sweep.parts
+        if w.adj_parts is None or w.adj_parts.numel() < (S - 1) * w.small_part.numel():
+            w.adj_parts = torch.empty((S - 1) * w.small_part.numel(), dtype=torch.float32, device=w.small_part.device)
+        return w.adj_parts
+
+    def _adaptive_step_native(self, method, y, kk, y1, t, h, rtol, atol):
+        """dopri5_step_native for any adaptive method: gode_gat_ode_adaptive_step_adjoint - on launch-bound graphs the S - 1
+        stages' closing launches as one (gode_gat_small_finish_multi_f32), and one fused close for the four components."""
+        lib = _lib.load()
+        S = adaptive_stages(method)
+        fs, ws = self._structs(True)
+        arr = lambda c: (ctypes.c_void_p * S)(*[kk[i][c].data_ptr() for i in range(S)])      # noqa: E731
+        sums = torch.empty(4, dtype=torch.float64, device=y[0].device)
+        _lib.check(lib.gode_gat_ode_adaptive_step_adjoint(
+            adaptive_code(method), ctypes.byref(fs), _lib.ptr(y[0]), _lib.ptr(y[1]), _lib.ptr(y[2]), _lib.ptr(y[3]), arr(0),
+            arr(1), arr(2), arr(3), _lib.ptr(y1[0]), _lib.ptr(y1[1]), _lib.ptr(y1[2]), _lib.ptr(y1[3]), ctypes.byref(ws),
+            _lib.ptr(self._adjoint_parts(S)), float(t), float(h), float(rtol), float(atol), _lib.ptr(sums),
+            _lib.ptr(self.w.err_scratch), _lib.stream_ptr()), "gode_gat_ode_adaptive_step_adjoint")
         return sums
 
     # ---- fixed-grid steps on launch-bound graphs: the small components (a_t, theta) are advanced once per RK step ----

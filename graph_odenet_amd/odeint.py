@@ -468,7 +468,8 @@ class _Dopri5Backprop:
     """What _OdeintBackprop does per interval under an adaptive method (dopri5, bosh3, adaptive_heun; S stages); the accepted step sizes are constants of the
     derivative.  The forward runs the solve's own launches on buffers a solver.Dopri5Record keeps.  Fused (a field offering
     the method's sweep - _adaptive_sweep: dopri5_step_backprop under dopri5 (GcnOdeField, GatOdeField, qc_ode.EdgeOdeField),
-    adaptive_step_backprop under bosh3 / adaptive_heun (GcnOdeField)): y_n and k_1..k_S of every accepted step - or y_n and k_1
+    adaptive_step_backprop under bosh3 / adaptive_heun (GcnOdeField, qc_ode.EdgeOdeField, and GatOdeField with its opt-in
+    gat_ode.GatOdeField.ADAPTIVE_NATIVE on - off by default)): y_n and k_1..k_S of every accepted step - or y_n and k_1
     past BACKPROP_SAVE_MAX_BYTES, each step then re-run by one native step call before its sweep (never for a field without
     the method's native step: it keeps all S) - swept in reverse, one call per step (csrc/ode_driver.hip; qc_ode.py).
     Generic: y_n alone, each accepted step re-run as torch ops through func, k_1 = func(t_n, y_n) recomputed: the same

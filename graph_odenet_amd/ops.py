@@ -365,6 +365,26 @@ def gat_small_finish(part, n_rows, d, heads, t, ktheta, kat):
           "gode_gat_small_finish_f32")
 
 
+def gat_small_finish_multi(parts, n_rows, d, heads, ts, kthetas, kats):
+    """gat_small_finish for the len(ts) <= 7 stages of one adaptive adjoint step in one launch: stage s's partials in slot s of
+    `parts`, closed at ts[s] into kthetas[s] / kats[s] (csrc/gat_small.hip; the single form's bits)."""
+    lib = _lib.load()
+    _need(parts, "parts")
+    k = len(ts)
+    if not 1 <= k <= 7 or len(kthetas) != k or len(kats) != k:
+        raise ValueError("gat_small_finish_multi: one to seven stages, an output pair each")
+    for kt, ka in zip(kthetas, kats):
+        _need(kt, "ktheta"); _need(ka, "kat")
+        if kt.numel() != lib.gode_gat_ode_theta_len_heads(d, heads) or ka.numel() != 1:
+            raise ValueError("gat_small_finish_multi: buffers have wrong size")
+    if parts.numel() < k * lib.gode_gat_small_parts(n_rows, d) * lib.gode_gat_small_part_len(d, heads):
+        raise ValueError("gat_small_finish_multi: buffers have wrong size")
+    tsa = (ctypes.c_float * k)(*[float(v) for v in ts])
+    kta, kaa = (ctypes.c_void_p * k)(*[x.data_ptr() for x in kthetas]), (ctypes.c_void_p * k)(*[x.data_ptr() for x in kats])
+    check(lib.gode_gat_small_finish_multi_f32(ptr(parts), n_rows, d, heads, k, kta, kaa, tsa, stream_ptr()),
+          "gode_gat_small_finish_multi_f32")
+
+
 def gat_small_finish_step(parts, n_rows, d, heads, ts, ws, theta, at):
     """theta += sum_s ws[s] * k_theta(stage s), at likewise, from the partial buffers of the len(ts) <= 4 stages of one
     fixed-grid RK step laid out one after the other in `parts` (csrc/gat_small.hip: one closing launch per STEP)."""

@@ -49,7 +49,7 @@ import torch.nn.functional as F
 from . import _lib, ops
 from .functional import GroupNorm
 from .qc_layers import EdgeGraphConvolution, _edges, _EdgeSet
-from .solver import DP_A, DP_C, FIXED_METHODS, FIXED_TABLEAUS, Field, _stage_terms
+from .solver import ADAPTIVE_TABLEAUS, FIXED_METHODS, FIXED_TABLEAUS, Field, _stage_terms
 
 
 def _edge_index(Esrc, Etgt):
@@ -189,7 +189,8 @@ class _BackpropWork:
 class EdgeOdeField(Field):
     """The forward field.  eval_combine folds the solution combine y + h sum b_s k_s of a fixed-grid step into the launch
     that ends its last stage.  Built with the parameter order (gode_fields) on a launch-bound batch it also offers the
-    backprop half of the protocol (solver.Field); it has no dopri5_step_native, so a dopri5 record keeps all seven k_s.
+    backprop half of the protocol (solver.Field); it has no dopri5_step_native / adaptive_step_native, so an adaptive record keeps all S k_s
+    (seven under dopri5).
     Memory of that half: packed_param_grads hands out views of the one packed buffer, so as long as a parameter's .grad is
     such a view the whole buffer stays alive, its E h^2 edge-matrix tail included; and the field is rebuilt with every
     batch, so every odeint call that is backpropagated allocates a _BackpropWork (7 x 3 or 4 n x d arrays and 7 sets of
@@ -208,6 +209,7 @@ class EdgeOdeField(Field):
             self.rk4_forward_save, self.rk4_backprop = self._rk4_forward_save, self._rk4_backprop
             self.fixed_forward_save, self.fixed_backprop = self._fixed_forward_save, self._fixed_backprop
             self.dopri5_step_backprop, self.dopri5_backprop_work = self._dopri5_step_backprop, self._dopri5_backprop_work
+            self.adaptive_step_backprop, self.adaptive_backprop_work = self._adaptive_step_backprop, self._adaptive_backprop_work
             self.packed_grads, self.packed_param_grads = self._packed_grads, self._packed_param_grads
 
     # ---- backprop through the solve (odeint._OdeintBackprop): launch-bound batches -----------------------------------------
@@ -291,31 +293,42 @@ class EdgeOdeField(Field):
 
     def _dopri5_backprop_work(self, like):
         """Work arrays of dopri5_step_backprop: 7 Ybar and two (ybar_n, kbar_1) pairs that take turns from step to step."""
-        return {"ybar": [torch.empty_like(like) for _ in range(7)],
-                "pairs": [(torch.empty_like(like), torch.empty_like(like)) for _ in range(2)]}
+        return self._adaptive_backprop_work("dopri5", like)
 
     def _dopri5_step_backprop(self, y, k, g, kbar7, wy, wk, t, h, first, work, turn, theta):
-        """Reverse sweep over one accepted step, the algebra of gode_gcn_ode_dopri5_step_backprop (csrc/ode_driver.hip):
-        kbar_s = wk[s] g + h sum_{r > s} a_rs Ybar_r (+ kbar7 on the last stage), Ybar_s through the stage for s = 7..2 (and 1
-        when `first`), ybar_n = wy g + sum Ybar_s; a stage whose cotangent has no term is skipped.  Returns (ybar_n, kbar_1)
-        in work["pairs"][turn]; kbar_1 is None when `first`."""
+        """_adaptive_step_backprop under the dopri5 tableau: the launches this member has always issued, in their order."""
+        return self._adaptive_step_backprop("dopri5", y, k, g, kbar7, wy, wk, t, h, first, work, turn, theta)
+
+    def _adaptive_backprop_work(self, method, like):
+        """Work arrays of adaptive_step_backprop: S Ybar and two (ybar_n, kbar_1) pairs that take turns from step to step."""
+        S = len(ADAPTIVE_TABLEAUS[method][0])
+        return {"ybar": [torch.empty_like(like) for _ in range(S)],
+                "pairs": [(torch.empty_like(like), torch.empty_like(like)) for _ in range(2)]}
+
+    def _adaptive_step_backprop(self, method, y, k, g, kbar_last, wy, wk, t, h, first, work, turn, theta):
+        """Reverse sweep over one accepted step of an adaptive method (S stages, tableau c, a), the algebra of
+        gode_gcn_ode_adaptive_step_backprop (csrc/ode_driver.hip): kbar_s = wk[s] g + h sum_{r > s} a_rs Ybar_r (+ kbar_last on
+        the last stage), Ybar_s through the stage for s = S..2 (and 1 when `first`), ybar_n = wy g + sum Ybar_s; a stage whose
+        cotangent has no term is skipped.  Returns (ybar_n, kbar_1) in work["pairs"][turn]; kbar_1 is None when `first`."""
+        C, A = ADAPTIVE_TABLEAUS[method][:2]
+        S = len(C)
         ybar = work["ybar"]
         ybar_n, kbar1 = work["pairs"][turn]
-        swept = [False] * 7
+        swept = [False] * S
 
         def cotangent(q):
             c = [(wk[q], g)] if wk[q] != 0.0 else []
-            c += [(h * DP_A[r][q], ybar[r]) for r in range(q + 1, 7) if DP_A[r][q] != 0.0 and swept[r]]
-            return c + [(1.0, kbar7)] if (q == 6 and kbar7 is not None) else c
+            c += [(h * A[r][q], ybar[r]) for r in range(q + 1, S) if A[r][q] != 0.0 and swept[r]]
+            return c + [(1.0, kbar_last)] if (q == S - 1 and kbar_last is not None) else c
         stages = []
-        for q in range(6, -1 if first else 0, -1):
+        for q in range(S - 1, -1 if first else 0, -1):
             cot = cotangent(q)
             if not cot:
                 continue
-            yin = _stage_terms([y], [[x] for x in k], DP_A[q], h)[0]
-            stages.append(self._stage_bwd(len(stages), cot, k[q], yin, t + DP_C[q] * h, ybar[q]))
+            yin = _stage_terms([y], [[x] for x in k], A[q], h)[0]
+            stages.append(self._stage_bwd(len(stages), cot, k[q], yin, t + C[q] * h, ybar[q]))
             swept[q] = True
-        pre = [(wy, g)] + [(1.0, ybar[q]) for q in range(7) if swept[q]]
+        pre = [(wy, g)] + [(1.0, ybar[q]) for q in range(S) if swept[q]]
         c0 = None if first else cotangent(0)
         if c0:
             ops.lincomb_multi_([ybar_n, kbar1], [pre, c0])

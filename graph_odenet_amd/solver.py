@@ -166,7 +166,9 @@ class Field:
     ratio_groups = None           # components whose error norms pool (a state tensor of torchdiffeq): both error norms
     # ---- the other adaptive methods (a name of ADAPTIVE_TABLEAUS; S stages) ---------------------------------------------------
     #                               the dopri5_* members keep their meaning and serve dopri5 alone; a field without the
-    #                               members below runs these methods on the per-stage driver through `eval`
+    #                               members below runs these methods on the per-stage driver through `eval` (the GCN fields
+    #                               offer the step, the GAT fields with gat_ode.GatOdeField.ADAPTIVE_NATIVE on - off by
+    #                               default; they and qc_ode.EdgeOdeField the sweep further down)
     adaptive_step_native = None   # adaptive_step_native(method, y, kk, y1, t, h, rtol, atol) -> error sums per ratio group:
     #                               integrate_adaptive, one attempted step (kk: S stage buffers) as one C call
     # ---- row-partitioned fields (big_components is not None) ------------------------------------------------------------

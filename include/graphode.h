@@ -955,6 +955,15 @@ int gode_gat_dense_vjp_small_f32(const gode_lincomb_t* xin, int64_t n_rows, int6
                                  const float* packed /* nullable: gode_gat_small_pack_f32 */, void* stream);
 int gode_gat_small_finish_f32(const float* part, int64_t n_rows, int64_t d, int64_t heads, float t, float* ktheta,
                               float* kat, void* stream);
+/* finish for the n_stages (1..7) stages of ONE adaptive adjoint step in one launch (gode_gat_ode_adaptive_step_adjoint:
+ * nothing inside the step reads the small components' stage derivatives): stage s's partials at part + s * parts * part_len,
+ * closed at t = ts[s] into ktheta[s] (gode_gat_ode_theta_len_heads floats, overwritten) and *kat[s].  Every output is bit
+ * for bit what gode_gat_small_finish_f32 gives on that slot with t = ts[s].
+ * Validation: null pointers, then n_stages outside 1..7 (GODE_E_SHAPE), then a shape gode_gat_small_supported refuses
+ * (GODE_E_UNSUPPORTED). */
+int gode_gat_small_finish_multi_f32(const float* part, int64_t n_rows, int64_t d, int64_t heads, int32_t n_stages,
+                                    float* const* ktheta /* host */, float* const* kat /* host */,
+                                    const float* ts /* host */, void* stream);
 /* The closing launches of the n_slots <= 4 stages of ONE fixed-grid Runge-Kutta step as one: theta += sum_s w[s] k_theta(s),
  * a_t += sum_s w[s] k_at(s), stage s evaluated at ts[s], its partials at part + s * parts * part_len (round 4: the small
  * components of the adjoint state are linear in the ODE and never read inside a fixed-grid step). */
@@ -1027,6 +1036,33 @@ int gode_gat_ode_dopri5_step_backprop(const gode_gat_odefunc_t* f, const float* 
                                       double t, double h, int32_t first, float* const* ybar /* 7 */, float* ybar_n,
                                       float* kbar1, float* theta, float* k_scratch, float* parts,
                                       const gode_gat_workspace_t* ws, void* stream);
+
+/* The three GAT dopri5 step drivers above for any adaptive method (GODE_RKA_*): the same arguments after the code, with k /
+ * ky / ka / ka_t / ktheta / ybar of S entries and wk of S.  The same routes (one head or H, shifted or raw logits, the
+ * one-launch dense kernels or the separate launches) and every message activation; the forward and the adjoint step close
+ * with gode_rk_close_err_multi_f32 (the adjoint: one call for its four outputs and four error groups y, a, a_t, theta), so
+ * GODE_RKA_DOPRI5 returns the dopri5 entry points' arrays and sums bit for bit.
+ * adjoint, `parts` (nullable; S - 1 slots of gode_gat_small_parts(n, d) * gode_gat_small_part_len(d, heads) floats): on the
+ *   one-launch route (gode_gat_small_supported, option small_fused, ws->small_part set) the evaluation that fills ky[s]
+ *   (s = 1..S-1) writes its partials into slot s - 1 and ONE gode_gat_small_finish_multi_f32 after the last stage produces
+ *   every ktheta[s] / ka_t[s] - the same bits as with parts == NULL, where (as off that route) each stage closes its own.
+ * backprop: `parts` holds S slots; GODE_E_UNSUPPORTED off the one-launch route, as for the dopri5 form.
+ * Validation: null pointers, then a method outside the list (GODE_E_SHAPE), then the dopri5 counterpart's checks;
+ * err_scratch >= gode_rk_close_err_scratch_bytes().  One stream. */
+int gode_gat_ode_adaptive_step_forward(int32_t method, const gode_gat_odefunc_t* f, const float* y, float* const* k /* S */,
+                                       float* y1, const gode_gat_workspace_t* ws, double t, double h, float rtol,
+                                       float atol, double* sums, void* err_scratch, void* stream);
+int gode_gat_ode_adaptive_step_adjoint(int32_t method, const gode_gat_odefunc_t* f, const float* y, const float* a,
+                                       const float* a_t, const float* theta, float* const* ky /* S */,
+                                       float* const* ka /* S */, float* const* ka_t /* S */, float* const* ktheta /* S */,
+                                       float* y1, float* a1, float* a_t1, float* theta1, const gode_gat_workspace_t* ws,
+                                       float* parts /* nullable */, double t, double h, float rtol, float atol,
+                                       double* sums /* 4 */, void* err_scratch, void* stream);
+int gode_gat_ode_adaptive_step_backprop(int32_t method, const gode_gat_odefunc_t* f, const float* y, float* const* k /* S */,
+                                        const float* g, const float* kbar_last /* nullable */, double wy,
+                                        const double* wk /* host, S */, double t, double h, int32_t first,
+                                        float* const* ybar /* S */, float* ybar_n, float* kbar1, float* theta,
+                                        float* k_scratch, float* parts, const gode_gat_workspace_t* ws, void* stream);
 
 /* ---- Set2Set readout: LSTM cell, one launch per direction (csrc/lstm.hip; replaces the single-layer `self.lstm` step of
  * QC/set2set.py:44-47,61 = torch.lstm_cell: two library GEMMs + a cell kernel forward, four GEMMs + reductions backward).
