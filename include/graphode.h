@@ -256,6 +256,9 @@ int gode_gn_time_gemm_pair_f32(const gode_lincomb_t* xin /* host */, int64_t n_r
  * Also accumulates (when non-NULL) the per-row reductions needed for the
  * parameter gradients into fp32 buffers of block partials:
  *   dgamma_part/dbeta_part : [n_part][d_in]   (n_part = gode_gemm_bwd_parts(n_rows))
+ * Every one of the n_part rows is written (the rows no block owns with zeros), so the caller sums all of them.
+ * Without GroupNorm there is nothing to reduce: dgamma_part and dbeta_part are left untouched where groups == 0,
+ * on every kernel the call can select.
  */
 int64_t gode_gemm_bwd_parts(int64_t n_rows);
 int gode_gn_time_gemm_bwd_f32(const gode_lincomb_t* xin /* host */, int64_t n_rows, int64_t d_in,
