@@ -1340,3 +1340,317 @@ extern "C" int gode_gcn_ode_fixed_backprop(int32_t method, const gode_gcn_odefun
     *a_result = acur;
     return 0;
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// explicit_adams (4th-order Adams-Bashforth on the fixed grid): kAdamsStart 3/8-rule steps - rk4_forward_step /
+// rk4_adjoint_small's launches, whose k_1 = f_i is kept - then ONE evaluation per step.  A multistep step is explicit
+// Euler's closing stage with more pre terms: the launch that evaluates f_i on y_i stores f_i (the save form) and
+// y_{i+1} = (y_i + h sum_{j>=1} beta_j f_{i-j}) + h beta_0 f_i.  At most kAdamsStart steps: the rk4 entry point itself.
+// Arrays: y, the four ws->ky (ka) and two more per chain from `extra` take turns as the solution, the history and the stage
+// buffers; nothing is allocated.
+// ---------------------------------------------------------------------------------------------------------------
+namespace {
+
+// The arrays of one chain (y or a) of a multistep solve: the solution, the rk4 stage buffers and the history take turns
+struct AdamsChain {
+    float* cur; float* k[4]; float* spare[2];
+    const float* fh[4];                                  // f_{i-1}, f_{i-2}, f_{i-3} (and the one that falls out)
+    float* free_[4]; int n_free = 0;
+    AdamsChain(float* y, float* const* ky, float* e0, float* e1) : cur(y), k{ky[0], ky[1], ky[2], ky[3]}, spare{e0, e1}, fh{} {}
+    // after start-up step i (k[3] holds the new solution, k[0] = f_i): f_i joins the history, the chain moves on
+    void close_start(int i) {
+        fh[2] = fh[1]; fh[1] = fh[0]; fh[0] = k[0];
+        float* tmp = cur; cur = k[3]; k[3] = tmp;
+        if (i < 2) k[0] = spare[i];
+        else { free_[0] = k[1]; free_[1] = k[2]; free_[2] = k[3]; n_free = 3; }
+    }
+    float* take() { return free_[--n_free]; }
+    // after a multistep step that wrote y_{i+1} into ynext and f_i into fnew
+    void close_multi(float* ynext, float* fnew) {
+        if (fh[2]) free_[n_free++] = (float*)fh[2];      // f_{i-3}: no later step reads it
+        free_[n_free++] = cur;
+        fh[2] = fh[1]; fh[1] = fh[0]; fh[0] = fnew;
+        cur = ynext;
+    }
+};
+
+}  // namespace
+
+extern "C" int gode_gcn_ode_adams_forward(const gode_gcn_odefunc_t* f, float* y, float** result,
+                                          const gode_rk4_workspace_t* ws, float* const* extra, float t0, float t1,
+                                          int32_t n_steps, void* stream)
+{
+    if (!f || !y || !ws || !result || !extra) return GODE_E_NULLPTR;
+    if (n_steps <= 0 || f->n <= 0 || f->d <= 0) return GODE_E_SHAPE;
+    if (n_steps <= kAdamsStart) return gode_gcn_ode_rk4_forward(f, y, result, ws, t0, t1, n_steps, stream);
+    if (!ws->S || !ws->ky[0] || !ws->ky[1] || !ws->ky[2] || !ws->ky[3] || !extra[0] || !extra[1]) return GODE_E_NULLPTR;
+    const double h = ((double)t1 - (double)t0) / n_steps;
+    const bool fused = fused_small(f);
+    const bool close_once = close_once_route(f);
+    const bool diag_ok = gode_opt_diag_rows() && !fused && f->n > kMergedFinishMaxRows && f->d == 128 && f->a_core_items &&
+                         f->a_diag && f->at_diag && f->A.items && f->a_n_core > 0 && f->a_n_core <= f->A.n_items;
+    // (option local_tail is rk4's alone: the tail rows take the launches of the other rows here)
+    AdamsChain c(y, ws->ky, extra[0], extra[1]);
+    for (int i = 0; i < kAdamsStart; ++i) {
+        GODE_TRY(rk4_forward_step(f, ws, c.cur, c.k, c.k[3], false, (double)t0 + i * h, h, fused, close_once, stream, diag_ok));
+        c.close_start(i);
+    }
+    const float hb0 = (float)(h * ADAMS_B[0]);
+    for (int i = kAdamsStart; i < n_steps; ++i) {
+        const float ts = (float)((double)t0 + i * h);
+        float* ynext = c.take(); float* fnew = c.take();
+        const gode_lincomb_t xin = one_term(c.cur);
+        const StepClose close = {adams_pre(c.cur, c.fh, h), hb0, false};
+        if (fused) GODE_TRY(gode_gcn_feval_small_save_f32(f, &xin, ts, hb0, &close.pre, ynext, fnew, stream));
+        else GODE_TRY(feval_large(f, xin, ts, ws->S, ynext, &close, fnew, stream));
+        c.close_multi(ynext, fnew);
+    }
+    *result = c.cur;
+    return 0;
+}
+
+// The adjoint solve on the launch-bound route: rk4_adjoint_small's stages for the start-up (k_1 of y and of a kept), then
+// two launches and the closing reduction per step - the forward recompute leaves f_i, the masked cotangent and y_{i+1}, the
+// VJP leaves a's derivative for the history and a_{i+1}.  The parameter and a_t components are pure quadratures (no stage
+// input reads them): every evaluation's partials are added ONCE, with the weight the evaluation ends up with (adams_weight;
+// a start-up step's k_1 gets it on top of h b_1), so theta holds its value at t1 only when the call returns.
+extern "C" int gode_gcn_ode_adams_adjoint(const gode_gcn_odefunc_t* f, float* y, float* a, float* theta,
+                                          float** y_result, float** a_result, const gode_rk4_workspace_t* ws,
+                                          float* const* extra, float t0, float t1, int32_t n_steps, void* stream)
+{
+    if (!f || !y || !a || !theta || !ws || !y_result || !a_result || !extra) return GODE_E_NULLPTR;
+    if (n_steps <= 0 || f->n <= 0 || f->d <= 0) return GODE_E_SHAPE;
+    if (!(fused_small(f) && ws->small_part != nullptr)) return GODE_E_UNSUPPORTED;      // the launch-bound route only
+    if (n_steps <= kAdamsStart) return gode_gcn_ode_rk4_adjoint(f, y, a, theta, y_result, a_result, ws, t0, t1, n_steps, stream);
+    for (int s = 0; s < 4; ++s) if (!ws->ky[s] || !ws->ka[s] || !extra[s]) return GODE_E_NULLPTR;
+    if (!ws->dZ) return GODE_E_NULLPTR;
+    const double h = ((double)t1 - (double)t0) / n_steps;   // negative: the adjoint runs from t0 (later) to t1 (earlier)
+    const int64_t slot = gode_gcn_small_parts(f->n) * gode_gcn_small_part_len(f->d);
+    AdamsChain cy(y, ws->ky, extra[0], extra[1]), ca(a, ws->ka, extra[2], extra[3]);
+    const float hb3 = (float)(h * B38[3]);
+    for (int i = 0; i < kAdamsStart; ++i) {
+        float stage_t[4];
+        const gode_lincomb_t ypre = combine_terms(cy.cur, cy.k, h), apre = combine_terms(ca.cur, ca.k, h);
+        for (int s = 0; s < 4; ++s) {
+            stage_t[s] = (float)((double)t0 + i * h + C38[s] * h);
+            const gode_lincomb_t yin = stage_terms(cy.cur, cy.k, s, h);
+            const gode_lincomb_t cot = negated(stage_terms(ca.cur, ca.k, s, h));          // cotangent of the VJP is -a
+            GODE_TRY(gode_gcn_feval_small_f32(f, &yin, stage_t[s], s == 3 ? hb3 : 1.f, s == 3 ? &ypre : nullptr,
+                                              &cot, ws->dZ, cy.k[s], stream));
+            GODE_TRY(gode_gcn_vjp_small_f32(f, &yin, ws->dZ, s == 3 ? hb3 : 1.f, s == 3 ? &apre : nullptr,
+                                            ca.k[s], ws->small_part + s * slot, stream));
+        }
+        const float wb[4] = {(float)(h * B38[0] + adams_weight(i, n_steps, h)), (float)(h * B38[1]), (float)(h * B38[2]), hb3};
+        GODE_TRY(gode_gcn_small_finish_step_f32(f, ws->small_part, 4, theta, wb, stage_t, stream));
+        cy.close_start(i);
+        ca.close_start(i);
+    }
+    const float hb0 = (float)(h * ADAMS_B[0]);
+    for (int i = kAdamsStart; i < n_steps; ++i) {
+        const float ts = (float)((double)t0 + i * h);
+        float* ynext = cy.take(); float* fnew = cy.take();
+        float* anext = ca.take(); float* ganew = ca.take();
+        const gode_lincomb_t yin = one_term(cy.cur);
+        const gode_lincomb_t ypre = adams_pre(cy.cur, cy.fh, h), apre = adams_pre(ca.cur, ca.fh, h);
+        const gode_lincomb_t cot = negated(one_term(ca.cur));
+        GODE_TRY(gode_gcn_feval_small_save_cot_f32(f, &yin, ts, hb0, &ypre, &cot, ws->dZ, ynext, fnew, stream));
+        GODE_TRY(gode_gcn_vjp_small_raw_f32(f, &yin, ws->dZ, hb0, &apre, anext, ws->small_part, ganew, stream));
+        const float w = (float)adams_weight(i, n_steps, h);
+        GODE_TRY(gode_gcn_small_finish_step_f32(f, ws->small_part, 1, theta, &w, &ts, stream));
+        cy.close_multi(ynext, fnew);
+        ca.close_multi(anext, ganew);
+    }
+    *y_result = cy.cur;
+    *a_result = ca.cur;
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Backprop through an explicit_adams solve.  Records are compact: a start-up step keeps [ y_i | k_1..k_4 ] (5 n d floats,
+// the rk4 record), a multistep step [ y_i | f_i ] (2 n d); in both f_i sits right behind y_i.  With ybar_{m+1} the
+// cotangent of y_{m+1}, f_i receives  fbar_i = sum_j h beta_j ybar_{i+j+1}  over the multistep steps m = i + j >= 3 that read
+// it (j <= 3, m <= n - 1): at most the four latest cotangents are pending.  A multistep step is then ONE stage,
+//   ybar_i = ybar_{i+1} + J_i^T fbar_i,   theta += (df/dtheta)_i^T fbar_i,   the mask [f_i > 0] from the record;
+// a start-up step is the rk4 sweep's step with fbar_i added to kbar_1 (4 + at most 3 terms).
+// ---------------------------------------------------------------------------------------------------------------
+extern "C" int64_t gode_adams_record_offset(int32_t step, int64_t nd)
+{
+    if (step < 0 || nd < 0) return GODE_E_SHAPE;
+    const int64_t start = step < kAdamsStart ? step : kAdamsStart;
+    return (5 * start + 2 * (int64_t)(step - start)) * nd;
+}
+
+extern "C" int gode_gcn_ode_adams_forward_save(const gode_gcn_odefunc_t* f, const float* y0, float* y_end, float* save,
+                                               const float* const* hist, const gode_rk4_workspace_t* ws, float t0, float t1,
+                                               int32_t n_steps, int32_t step_begin, int32_t step_end, void* stream)
+{
+    if (!f || !y0 || !y_end || !save || !ws) return GODE_E_NULLPTR;
+    if (n_steps <= 0 || f->n <= 0 || f->d <= 0) return GODE_E_SHAPE;
+    if (step_begin < 0 || step_end > n_steps || step_begin >= step_end) return GODE_E_SHAPE;
+    if (n_steps <= kAdamsStart)
+        return gode_gcn_ode_rk4_forward_save(f, y0, y_end, save, ws, t0, t1, n_steps, step_begin, step_end, stream);
+    if (!ws->S) return GODE_E_NULLPTR;
+    if (step_begin > 0 && step_end > kAdamsStart) {               // f of up to three steps before step_begin
+        if (!hist) return GODE_E_NULLPTR;
+        for (int j = 0; j < kAdamsStart && j < step_begin; ++j) if (!hist[j]) return GODE_E_NULLPTR;
+    }
+    const int64_t nd = f->n * f->d;
+    const double h = ((double)t1 - (double)t0) / n_steps;
+    const bool fused = fused_small(f);
+    const bool close_once = close_once_route(f);
+    auto record = [&](int i) { return save + (gode_adams_record_offset(i, nd) - gode_adams_record_offset(step_begin, nd)); };
+    auto f_of = [&](int j) -> const float* { return j >= step_begin ? record(j) + nd : hist[step_begin - 1 - j]; };
+    if (y0 != save) {                                            // record 0 starts with a copy of y0
+        const gode_lincomb_t c = one_term(y0);
+        GODE_TRY(gode_lincomb_f32(save, &c, nd, stream));
+    }
+    const float hb0 = (float)(h * ADAMS_B[0]);
+    for (int i = step_begin; i < step_end; ++i) {
+        float* rec = record(i);
+        float* ynext = (i + 1 < step_end) ? record(i + 1) : y_end;       // the next record's y_i, or the result
+        if (i < kAdamsStart) {
+            float* k[4] = {rec + nd, rec + 2 * nd, rec + 3 * nd, rec + 4 * nd};
+            GODE_TRY(rk4_forward_step(f, ws, rec, k, ynext, true, (double)t0 + i * h, h, fused, close_once, stream));
+            continue;
+        }
+        const float* fh[3] = {f_of(i - 1), f_of(i - 2), f_of(i - 3)};
+        const float ts = (float)((double)t0 + i * h);
+        const gode_lincomb_t xin = one_term(rec);
+        const StepClose close = {adams_pre(rec, fh, h), hb0, false};
+        if (fused) GODE_TRY(gode_gcn_feval_small_save_f32(f, &xin, ts, hb0, &close.pre, ynext, rec + nd, stream));
+        else GODE_TRY(feval_large(f, xin, ts, ws->S, ynext, &close, rec + nd, stream));
+    }
+    return 0;
+}
+
+namespace {
+
+// The pending cotangents of the sweep: P[j] = ybar_{i+1+j}, j < count <= 4, in a ring of five arrays
+struct AdamsPending {
+    float* P[4]; int count;
+    float* free_[5]; int n_free;
+    float* take() { return free_[--n_free]; }
+    void push(float* ybar_i) {
+        if (count == 4) free_[n_free++] = P[3]; else ++count;
+        P[3] = P[2]; P[2] = P[1]; P[1] = P[0]; P[0] = ybar_i;
+    }
+};
+// lc + fbar_i: the terms h beta_j ybar_{i+j+1} of the multistep steps i + j (>= 3, <= n - 1) that read f_i
+gode_lincomb_t adams_fbar(gode_lincomb_t lc, const AdamsPending& p, int i, int n, double h) {
+    for (int j = i < kAdamsStart ? kAdamsStart - i : 0; j <= 3 && i + j <= n - 1; ++j) {
+        lc.coef[lc.n] = (float)(h * ADAMS_B[j]); lc.ptr[lc.n] = p.P[j]; ++lc.n;
+    }
+    return lc;
+}
+
+}  // namespace
+
+// save: the records of steps 0 .. n_steps - 1 (gode_adams_record_offset) - or, with `rerun` given (5 n d floats), the
+// start-up steps' y_0, y_1, y_2 alone (3 n d floats) followed by the multistep records: each start-up step is then re-run
+// into `rerun` (rk4_forward_step, the forward's launches) just before its sweep.  work: four n x d arrays; with `a` they
+// hold the pending cotangents, and *a_result names the one that holds dL/dy_0.
+extern "C" int gode_gcn_ode_adams_backprop(const gode_gcn_odefunc_t* f, const float* save, float* rerun, float* a, float* theta,
+                                           float** a_result, const gode_rk4_workspace_t* ws, float* cot_colpart,
+                                           float* const* work, float t0, float t1, int32_t n_steps, void* stream)
+{
+    if (!f || !save || !a || !theta || !a_result || !ws || !work) return GODE_E_NULLPTR;
+    if (n_steps <= 0 || f->n <= 0 || f->d <= 0) return GODE_E_SHAPE;
+    if (n_steps <= kAdamsStart) {
+        if (rerun) return GODE_E_SHAPE;                           // the rk4 sweep's own re-run mode is its caller's
+        return gode_gcn_ode_rk4_backprop(f, save, a, theta, a_result, ws, cot_colpart, t0, t1, n_steps, 0, n_steps, stream);
+    }
+    for (int s = 0; s < 4; ++s) if (!ws->ka[s] || !ws->ktheta[s] || !work[s]) return GODE_E_NULLPTR;
+    if (!ws->dZ || !ws->dS || !ws->wpart || !ws->colsum_scratch) return GODE_E_NULLPTR;
+    if (f->groups > 0 && (!ws->gpart || !ws->bpart)) return GODE_E_NULLPTR;
+    if (rerun && !ws->S) return GODE_E_NULLPTR;
+    const int64_t n = f->n, d = f->d, nd = n * d, P = gode_gcn_ode_theta_len(d);
+    const double h = ((double)t1 - (double)t0) / n_steps;
+    const bool fused = fused_small(f) && ws->small_part != nullptr;
+    const bool close_once = close_once_route(f);
+    const int64_t slot = fused ? gode_gcn_small_parts(n) * gode_gcn_small_part_len(d) : 0;
+    const SweepRoute route = sweep_route(f, ws, cot_colpart);
+    const int64_t multi0 = rerun ? (int64_t)kAdamsStart * nd : gode_adams_record_offset(kAdamsStart, nd);
+    auto multi = [&](int i) { return save + multi0 + (int64_t)(i - kAdamsStart) * 2 * nd; };
+    AdamsPending pend = {{a, nullptr, nullptr, nullptr}, 1, {work[0], work[1], work[2], work[3], nullptr}, 4};
+    float* dz[2] = {ws->dZ, ws->dS};
+    int cur = 0;
+    const float one = 1.f;
+    gode_lincomb_t none; none.n = 0;
+    if (fused) {                                                 // the masked cotangent of the last step opens the chain
+        const gode_lincomb_t c = adams_fbar(none, pend, n_steps - 1, n_steps, h);
+        GODE_TRY(gode_masked_cot_f32(&c, multi(n_steps - 1) + nd, dz[0], n, d, nullptr, stream));
+    }
+    for (int i = n_steps - 1; i >= kAdamsStart; --i) {
+        const float* rec = multi(i);
+        const float ts = (float)((double)t0 + i * h);
+        const gode_lincomb_t yin = one_term(rec), pre = one_term(pend.P[0]);
+        float* out = pend.take();
+        if (!fused) {
+            const gode_lincomb_t cot = adams_fbar(none, pend, i, n_steps, h);
+            GODE_TRY(sweep_stage(f, ws, route, cot, rec + nd, yin, &pre, out, ws->ktheta[0], ts, stream));
+            GODE_TRY(add_stage_parts(theta, ws->ktheta, 1, P, stream));
+            pend.push(out);
+            continue;
+        }
+        if (i > kAdamsStart) {                                   // ... and every VJP launch forms the next step's
+            AdamsPending nxt = pend;
+            nxt.push(out);                                       // names `out`: this launch's rows
+            const gode_lincomb_t cn = adams_fbar(none, nxt, i - 1, n_steps, h);
+            GODE_TRY(gode_gcn_vjp_small_next_f32(f, &yin, dz[cur], 1.f, &pre, out, ws->small_part, &cn, multi(i - 1) + nd,
+                                                 dz[cur ^ 1], stream));
+            cur ^= 1;
+        } else {
+            GODE_TRY(gode_gcn_vjp_small_f32(f, &yin, dz[cur], 1.f, &pre, out, ws->small_part, stream));
+        }
+        GODE_TRY(gode_gcn_small_finish_step_f32(f, ws->small_part, 1, theta, &one, &ts, stream));
+        pend.push(out);
+    }
+    float* yb[4] = {nullptr, ws->ka[1], ws->ka[2], ws->ka[3]};   // yb[1..3]: Ybar_2..4 of a start-up step; yb[0]: ybar_i
+    for (int i = kAdamsStart - 1; i >= 0; --i) {
+        const double t = (double)t0 + i * h;
+        const float* y = rerun ? save + (int64_t)i * nd : save + gode_adams_record_offset(i, nd);
+        float* k[4];
+        if (rerun) {
+            for (int s = 0; s < 4; ++s) k[s] = rerun + (int64_t)(s + 1) * nd;
+            GODE_TRY(rk4_forward_step(f, ws, y, k, rerun, true, t, h, fused_small(f), close_once, stream));
+        } else {
+            for (int s = 0; s < 4; ++s) k[s] = (float*)y + (int64_t)(s + 1) * nd;
+        }
+        const float* abar = pend.P[0];
+        yb[0] = pend.take();
+        const gode_lincomb_t pre = sweep_pre(TAB38, abar, 1.f, yb, 1);
+        // kbar_s of the rk4 sweep; kbar_1 also carries fbar_i
+        auto kbar = [&](int s) {
+            const gode_lincomb_t c = stage_cotangent(TAB38, abar, (float)(h * B38[s]), yb, s, h);
+            return s == 0 ? adams_fbar(c, pend, i, n_steps, h) : c;
+        };
+        if (fused) {
+            const gode_lincomb_t c4 = kbar(3);
+            GODE_TRY(gode_masked_cot_f32(&c4, k[3], dz[cur], n, d, nullptr, stream));
+            float stage_t[4];
+            for (int s = 3; s >= 0; --s) {
+                stage_t[s] = (float)(t + C38[s] * h);
+                const gode_lincomb_t yin = stage_terms(y, k, s, h);
+                float* part = ws->small_part + s * slot;
+                if (s > 0) {
+                    const gode_lincomb_t nxt = kbar(s - 1);                      // names yb[s]: this launch's rows
+                    GODE_TRY(gode_gcn_vjp_small_next_f32(f, &yin, dz[cur], 1.f, nullptr, yb[s], part, &nxt, k[s - 1],
+                                                         dz[cur ^ 1], stream));
+                    cur ^= 1;
+                } else {
+                    GODE_TRY(gode_gcn_vjp_small_f32(f, &yin, dz[cur], 1.f, &pre, yb[0], part, stream));
+                }
+            }
+            const float w1[4] = {1.f, 1.f, 1.f, 1.f};               // h is already inside kbar
+            GODE_TRY(gode_gcn_small_finish4_f32(f, ws->small_part, theta, w1, stage_t, stream));
+        } else {
+            for (int s = 3; s >= 0; --s)
+                GODE_TRY(sweep_stage(f, ws, route, kbar(s), k[s], stage_terms(y, k, s, h), s == 0 ? &pre : nullptr, yb[s],
+                                     ws->ktheta[s], (float)(t + C38[s] * h), stream));
+            GODE_TRY(add_stage_parts(theta, ws->ktheta, 4, P, stream));
+        }
+        pend.push(yb[0]);
+    }
+    *a_result = pend.P[0];
+    return 0;
+}

@@ -69,6 +69,24 @@ const Tableau TABMID = {&AMID[0][0], 1, 2, BMID, CMID};
 inline const Tableau* fixed_tableau(int method) {
     return method == GODE_RK_RK4_38 ? &TAB38 : method == GODE_RK_EULER ? &TABEU : method == GODE_RK_MIDPOINT ? &TABMID : nullptr;
 }
+// explicit_adams: 4th-order Adams-Bashforth, y_{i+1} = y_i + h sum_j ADAMS_B[j] f_{i-j}, after kAdamsStart 3/8-rule steps
+constexpr int kAdamsStart = 3;
+const double ADAMS_B[4] = {55.0 / 24.0, -59.0 / 24.0, 37.0 / 24.0, -9.0 / 24.0};
+// terms of  y + h * sum_{j=1..3} ADAMS_B[j] * fh[j - 1]  (fh: f_{i-1}, f_{i-2}, f_{i-3}): what the launch that evaluates f_i
+// adds h ADAMS_B[0] f_i to
+inline gode_lincomb_t adams_pre(const float* y, const float* const* fh, double h) {
+    gode_lincomb_t lc = one_term(y);
+    for (int j = 1; j < 4; ++j) { lc.coef[lc.n] = (float)(h * ADAMS_B[j]); lc.ptr[lc.n] = fh[j - 1]; ++lc.n; }
+    return lc;
+}
+// the weight f_i (the evaluation that opens step i of n) ends up with over the multistep steps that read it:
+// h * sum of ADAMS_B[m - i] over m = max(i, 3) .. min(i + 3, n - 1)  (solver.multistep_weight, the same sum in double)
+inline double adams_weight(int i, int n, double h) {
+    double s = 0.0;
+    const int lo = i > kAdamsStart ? i : kAdamsStart, hi = i + 3 < n - 1 ? i + 3 : n - 1;
+    for (int m = lo; m <= hi; ++m) s += ADAMS_B[m - i];
+    return h * s;
+}
 // Bogacki-Shampine 3(2) and Heun-Euler 2(1), both in FSAL form as Dormand-Prince is (the last row of a is b); Heun-Euler's
 // third stage f(t + h, y1) is what makes it so.  e = b - b*
 const double BSC[4] = {0.0, 1.0 / 2, 3.0 / 4, 1.0};

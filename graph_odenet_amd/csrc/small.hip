@@ -213,10 +213,13 @@ __device__ __forceinline__ float4 gn_backward4(const float4 x, const float4 dy, 
 // ---------------------------------------------------------------------------------------------------------------
 // NXT (gode_gcn_vjp_small_next_f32, the reverse sweep of a backprop solve): the launch also forms the NEXT stage's masked
 // cotangent dZn = (sum cot) * [k > 0] row by row; a term of cot that names `ka` takes this row's value from the register
-template <bool NXT> struct VjpNext { LinComb cot; const float* k; float* dZn; };
-template <> struct VjpNext<false> {};
+// NXT = 2 (gode_gcn_vjp_small_raw_f32, a multistep step of the adjoint solve): the launch also stores the derivative dx
+// itself in `raw` - ka = (sum pre) + out_scale * dx advances a, raw goes into the history the next three steps read
+template <int NXT> struct VjpNext { LinComb cot; const float* k; float* dZn; };
+template <> struct VjpNext<0> {};
+template <> struct VjpNext<2> { float* raw; };
 
-template <int D, int CG, int GW, bool NXT>
+template <int D, int CG, int GW, int NXT>
 __global__ __launch_bounds__(256) void gcn_vjp_small_kernel(const int* __restrict__ rowptrT, const int* __restrict__ colT,
                                                            const float* __restrict__ valT, LinComb xin, int n_rows,
                                                            float eps, const float* __restrict__ gamma,
@@ -292,7 +295,8 @@ __global__ __launch_bounds__(256) void gcn_vjp_small_kernel(const int* __restric
             float4 out = make_float4(out_scale * dx.x, out_scale * dx.y, out_scale * dx.z, out_scale * dx.w);
             if (pre.n > 0) { const float4 p = lc_load4(pre, o); out.x += p.x; out.y += p.y; out.z += p.z; out.w += p.w; }
             *reinterpret_cast<float4*>(ka + o) = out;
-            if constexpr (NXT) {
+            if constexpr (NXT == 2) *reinterpret_cast<float4*>(vn.raw + o) = dx;
+            if constexpr (NXT == 1) {
                 float4 g = lc_load4_self(vn.cot, o, ka, out);
                 const float4 kk = ld4(vn.k + o);
                 g.x = kk.x > 0.f ? g.x : 0.f; g.y = kk.y > 0.f ? g.y : 0.f; g.z = kk.z > 0.f ? g.z : 0.f; g.w = kk.w > 0.f ? g.w : 0.f;
@@ -570,9 +574,14 @@ namespace {
 
 int vjp_small(const gode_gcn_odefunc_t* f, const gode_lincomb_t* xin, const float* dZ, float out_scale,
               const gode_lincomb_t* pre, float* ka, float* part, const gode_lincomb_t* cot_next, const float* k_next,
-              float* dZ_next, void* stream)
+              float* dZ_next, void* stream, float* raw = nullptr)
 {
     if (!f || !xin || !dZ || !ka || !part) return GODE_E_NULLPTR;
+    if (raw) {
+        if (dZ_next) return GODE_E_SHAPE;                                   // one extra output per launch
+        if (raw == ka || raw == dZ) return GODE_E_SHAPE;                    // dZ is gathered by other blocks
+        if (((uintptr_t)raw) & 15) return GODE_E_ALIGN;
+    }
     if (dZ_next) {
         if (!cot_next || !k_next) return GODE_E_NULLPTR;
         int rcn = check_lincomb(cot_next, true); if (rcn) return rcn;
@@ -590,10 +599,12 @@ int vjp_small(const gode_gcn_odefunc_t* f, const gode_lincomb_t* xin, const floa
     const int cg = small_cg(d, f->groups);
     const dim3 grid((unsigned)gode_gcn_small_parts(f->n));
     const bool r4 = rows4(f->n);
-    VjpNext<true> vna; vna.cot = make_lincomb(cot_next); vna.k = k_next; vna.dZn = dZ_next;
-    const VjpNext<false> vn0;
+    VjpNext<1> vna; vna.cot = make_lincomb(cot_next); vna.k = k_next; vna.dZn = dZ_next;
+    const VjpNext<0> vn0;
+    VjpNext<2> vnr; vnr.raw = raw;
 #define GODE_VJS(DV, CGV) if (r4) GODE_VJS_(DV, CGV, 16) else GODE_VJS_(DV, CGV, 64)
-#define GODE_VJS_(DV, CGV, GWV) if (dZ_next) GODE_VJS__(DV, CGV, GWV, true, vna) else GODE_VJS__(DV, CGV, GWV, false, vn0)
+#define GODE_VJS_(DV, CGV, GWV) if (dZ_next) GODE_VJS__(DV, CGV, GWV, 1, vna) else if (raw) GODE_VJS__(DV, CGV, GWV, 2, vnr) \
+                                else GODE_VJS__(DV, CGV, GWV, 0, vn0)
 #define GODE_VJS__(DV, CGV, GWV, NV, VNA) hipLaunchKernelGGL((gcn_vjp_small_kernel<DV, CGV, GWV, NV>), grid, dim3(256), 0, (hipStream_t)stream, \
                                              f->AT.rowptr, f->AT.col, f->AT.val, lx, (int)f->n, f->eps, f->gamma, f->beta, f->W, \
                                              dZ, out_scale, lp, ka, part, VNA);
@@ -622,19 +633,37 @@ extern "C" int gode_gcn_vjp_small_next_f32(const gode_gcn_odefunc_t* f, const go
     return vjp_small(f, xin, dZ, out_scale, pre, ka, part, cot_next, k_next, dZ_next, stream);
 }
 
-// forward evaluation that also stores relu(z) into k (before the combine with pre / alpha)
-extern "C" int gode_gcn_feval_small_save_f32(const gode_gcn_odefunc_t* f, const gode_lincomb_t* xin, float t, float alpha,
-                                             const gode_lincomb_t* pre, float* out, float* k, void* stream)
+// the same VJP launch, which also stores the derivative dx itself in raw (ka = (sum pre) + out_scale * dx)
+extern "C" int gode_gcn_vjp_small_raw_f32(const gode_gcn_odefunc_t* f, const gode_lincomb_t* xin, const float* dZ,
+                                          float out_scale, const gode_lincomb_t* pre, float* ka, float* part, float* raw,
+                                          void* stream)
+{
+    if (!raw) return GODE_E_NULLPTR;
+    return vjp_small(f, xin, dZ, out_scale, pre, ka, part, nullptr, nullptr, nullptr, stream, raw);
+}
+
+namespace {
+
+// forward evaluation that also stores relu(z) into k (before the combine with pre / alpha) - and, Y2 given, the masked
+// cotangent (sum cot) * [z > 0] as gode_gcn_feval_small_f32 does
+int feval_small_save(const gode_gcn_odefunc_t* f, const gode_lincomb_t* xin, float t, float alpha, const gode_lincomb_t* pre,
+                     const gode_lincomb_t* cot, float* Y2, float* out, float* k, void* stream)
 {
     if (!f || !xin || !out || !k) return GODE_E_NULLPTR;
     if (k == out) return GODE_E_SHAPE;
+    if (Y2 && (Y2 == out || Y2 == k)) return GODE_E_SHAPE;
     if (!gode_gcn_small_supported(f->n, f->d, f->groups)) return GODE_E_UNSUPPORTED;
     if (!f->A.rowptr || !f->A.col || !f->W) return GODE_E_NULLPTR;
     int rc = check_lincomb(xin, true); if (rc) return rc;
+    if (Y2)                                                                // rows of xin are gathered by other blocks
+        for (int j = 0; j < xin->n; ++j)
+            if (xin->ptr[j] == out || xin->ptr[j] == k || xin->ptr[j] == Y2) return GODE_E_SHAPE;
     if (pre && pre->n > 0) { rc = check_lincomb(pre, true); if (rc) return rc; } else pre = nullptr;
-    if (!lincomb_aligned16(xin) || !lincomb_aligned16(pre) ||
-        ((((uintptr_t)out) | ((uintptr_t)k) | ((uintptr_t)f->gamma) | ((uintptr_t)f->beta) | ((uintptr_t)f->b)) & 15)) return GODE_E_ALIGN;
-    const LinComb lx = make_lincomb(xin), lp = make_lincomb(pre), lcot = make_lincomb(nullptr);
+    if (Y2) { rc = check_lincomb(cot, true); if (rc) return rc; } else cot = nullptr;
+    if (!lincomb_aligned16(xin) || !lincomb_aligned16(pre) || !lincomb_aligned16(cot) ||
+        ((((uintptr_t)out) | ((uintptr_t)k) | ((uintptr_t)Y2) | ((uintptr_t)f->gamma) | ((uintptr_t)f->beta) | ((uintptr_t)f->b)) & 15))
+        return GODE_E_ALIGN;
+    const LinComb lx = make_lincomb(xin), lp = make_lincomb(pre), lcot = make_lincomb(cot);
     const int64_t d = f->d;
     const int cg = small_cg(d, f->groups);
     const dim3 grid((unsigned)feval_blocks(f->n));
@@ -643,12 +672,29 @@ extern "C" int gode_gcn_feval_small_save_f32(const gode_gcn_odefunc_t* f, const 
 #define GODE_FSV(DV, CGV) if (r4) GODE_FSV_(DV, CGV, 16) else GODE_FSV_(DV, CGV, 64)
 #define GODE_FSV_(DV, CGV, GWV) hipLaunchKernelGGL((gcn_feval_small_kernel<DV, CGV, GWV, 2>), grid, dim3(256), 0, (hipStream_t)stream, \
                                              f->A.rowptr, f->A.col, f->A.val, lx, (int)f->n, f->eps, f->gamma, f->beta, f->W,    \
-                                             f->b, t, alpha, lp, lcot, nullptr, out, ks);
+                                             f->b, t, alpha, lp, lcot, Y2, out, ks);
     GODE_SMALL_DISPATCH(GODE_FSV)
 #undef GODE_FSV
 #undef GODE_FSV_
     GODE_LAUNCH_CHECK();
     return 0;
+}
+
+}  // namespace
+
+extern "C" int gode_gcn_feval_small_save_f32(const gode_gcn_odefunc_t* f, const gode_lincomb_t* xin, float t, float alpha,
+                                             const gode_lincomb_t* pre, float* out, float* k, void* stream)
+{
+    return feval_small_save(f, xin, t, alpha, pre, nullptr, nullptr, out, k, stream);
+}
+
+// the save form with the masked cotangent Y2 = (sum cot) * [z > 0] as a third output (a multistep step of the adjoint solve)
+extern "C" int gode_gcn_feval_small_save_cot_f32(const gode_gcn_odefunc_t* f, const gode_lincomb_t* xin, float t, float alpha,
+                                                 const gode_lincomb_t* pre, const gode_lincomb_t* cot, float* Y2, float* out,
+                                                 float* k, void* stream)
+{
+    if (!cot || !Y2) return GODE_E_NULLPTR;
+    return feval_small_save(f, xin, t, alpha, pre, cot, Y2, out, k, stream);
 }
 
 // theta-k = [ W ((d+1) d, row 0 = t * colsum(dS)) | b | gamma | beta | a_t ] from the block partials of

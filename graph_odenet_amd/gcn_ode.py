@@ -16,7 +16,7 @@ import torch
 
 from . import _lib, ops
 from .graph import as_graph
-from .solver import Field, adaptive_code, adaptive_stages, method_code, n_stages
+from .solver import Field, adaptive_code, adaptive_stages, method_code, multistep_nfe, n_stages
 
 
 def _graph_struct(g, d):
@@ -109,6 +109,14 @@ class _Shared:
                     self._y2_colsum = torch.empty(self.y2_rows, self.d, dtype=torch.float32, device=self.device)
                 ws.y2_colsum = self._y2_colsum.data_ptr()
         return ws
+
+    def adams_extra(self, adjoint):
+        """The further n x d arrays the multistep C drivers rotate through (gode_gcn_ode_adams_*): 2 forward, 4 adjoint."""
+        n = 4 if adjoint else 2
+        have = getattr(self, "_adams_extra", [])
+        if len(have) < n:
+            self._adams_extra = have = have + [torch.empty_like(self.S) for _ in range(n - len(have))]
+        return have[:n]
 
     def cot_colpart(self):
         """Per-block column sums of the masked cotangent of a backprop sweep (csrc/backprop.hip); None when the width has
@@ -460,6 +468,54 @@ class GcnOdeField(_PackedParams, Field):
             comps[0].copy_(out)
         return n_stages(method) * n_steps
 
+    def multistep_native(self, comps, t0, t1, n_steps, method):
+        """The whole solve of a multistep method in one C call (gode_gcn_ode_adams_forward), every route."""
+        lib = _lib.load()
+        s, w = self.s, self.w
+        ky, extra = w.stage_buffers(False)[0], w.adams_extra(False)
+        fs, ws = _func_struct(s), w.workspace_struct(False, s.groups)
+        res = ctypes.c_void_p()
+        _lib.check(lib.gode_gcn_ode_adams_forward(ctypes.byref(fs), _lib.ptr(comps[0]), ctypes.byref(res), ctypes.byref(ws),
+                                                  (ctypes.c_void_p * 2)(*[x.data_ptr() for x in extra]), float(t0), float(t1),
+                                                  int(n_steps), _lib.stream_ptr()), "gode_gcn_ode_adams_forward")
+        out = _by_ptr(res.value, [comps[0]] + ky + extra)
+        if out is not comps[0]:
+            comps[0].copy_(out)
+        return multistep_nfe(method, n_steps)
+
+    @staticmethod
+    def multistep_record_floats(method, n_steps, step, nd):
+        """Floats in front of step's record in the compact record of a multistep solve (step = n_steps: the total): a start-up
+        step keeps [y | k_1..k_4], a later step [y | f]."""
+        return int(_lib.load().gode_adams_record_offset(int(step), int(nd)))
+
+    def multistep_forward_save(self, method, y0, y_end, save, t0, t1, n_steps, i0, i1, hist=None):
+        """Steps i0 .. i1-1 of the solve into the flat record `save` (which starts at step i0's record), multistep_native's
+        launches on other addresses; hist: f of the steps i0-1, i0-2, i0-3 where a multistep step needs them."""
+        lib = _lib.load()
+        s, w = self.s, self.w
+        fs, ws = _func_struct(s), w.workspace_struct(False, s.groups)
+        hp = None if hist is None else (ctypes.c_void_p * 3)(*[None if x is None else x.data_ptr() for x in (list(hist) + [None] * 3)[:3]])
+        _lib.check(lib.gode_gcn_ode_adams_forward_save(ctypes.byref(fs), _lib.ptr(y0), _lib.ptr(y_end), _lib.ptr(save), hp,
+                                                       ctypes.byref(ws), float(t0), float(t1), int(n_steps), int(i0), int(i1),
+                                                       _lib.stream_ptr()), "gode_gcn_ode_adams_forward_save")
+
+    def multistep_backprop(self, method, save, a, theta, t0, t1, n_steps, rerun=None):
+        """The reverse sweep over a whole interval's records (gode_gcn_ode_adams_backprop); rerun: a one-step rk4 record to
+        re-run the start-up steps into, `save` then holding their y_i alone.  Returns the tensor holding dL/dy_0 (`a` or one
+        of the work arrays)."""
+        lib = _lib.load()
+        s, w = self.s, self.w
+        ka = w.stage_buffers(True)[1]
+        work = w.adams_extra(True)
+        fs, ws = _func_struct(s), w.workspace_struct(True, s.groups)
+        res = ctypes.c_void_p()
+        _lib.check(lib.gode_gcn_ode_adams_backprop(ctypes.byref(fs), _lib.ptr(save), _lib.ptr(rerun), _lib.ptr(a), _lib.ptr(theta),
+                                                   ctypes.byref(res), ctypes.byref(ws), _lib.ptr(w.cot_colpart()),
+                                                   (ctypes.c_void_p * 4)(*[x.data_ptr() for x in work]), float(t0), float(t1),
+                                                   int(n_steps), _lib.stream_ptr()), "gode_gcn_ode_adams_backprop")
+        return _by_ptr(res.value, [a] + work + ka)
+
     def fixed_forward_save(self, method, y0, y_end, save, t0, t1, n_steps, i0, i1):
         """rk4_forward_save for any fixed-grid method: save[r] = [y_n, k_1..k_S] of step i0 + r."""
         lib = _lib.load()
@@ -607,6 +663,7 @@ class _PartMixin:
     """Row-partitioned state (partition.py): hooks the adaptive solver uses to see global error norms."""
     rk4_native = None
     fixed_native = None
+    multistep_native = None
     dopri5_step_native = None
     adaptive_step_native = None
     adaptive = False                # set by odeint when the method is adaptive
@@ -646,6 +703,8 @@ class GcnOdePartField(_PartMixin, GcnOdeField):
     rk4_backprop = None
     fixed_forward_save = None
     fixed_backprop = None
+    multistep_forward_save = None
+    multistep_backprop = None
     dopri5_step_backprop = None
     adaptive_step_backprop = None
 
@@ -711,6 +770,30 @@ class GcnOdeAdjointField(_PackedParams, Field):
         if ao is not comps[1]:
             comps[1].copy_(ao)
         return n_stages(method) * n_steps
+
+    def multistep_native(self, comps, t0, t1, n_steps, method):
+        """The whole adjoint solve of a multistep method on the launch-bound route (gode_gcn_ode_adams_adjoint); None off
+        that route: solver.integrate_multistep then runs the steps."""
+        lib = _lib.load()
+        s, w = self.s, self.w
+        ky, ka, _, _ = w.stage_buffers(True)
+        extra = w.adams_extra(True)
+        fs, ws = _func_struct(s), w.workspace_struct(True, s.groups)
+        yr, ar = ctypes.c_void_p(), ctypes.c_void_p()
+        rc = lib.gode_gcn_ode_adams_adjoint(ctypes.byref(fs), _lib.ptr(comps[0]), _lib.ptr(comps[1]), _lib.ptr(self.theta),
+                                            ctypes.byref(yr), ctypes.byref(ar), ctypes.byref(ws),
+                                            (ctypes.c_void_p * 4)(*[x.data_ptr() for x in extra]), float(t0), float(t1),
+                                            int(n_steps), _lib.stream_ptr())
+        if rc == E_UNSUPPORTED:
+            return None
+        _lib.check(rc, "gode_gcn_ode_adams_adjoint")
+        yo = _by_ptr(yr.value, [comps[0]] + ky + extra[:2])
+        ao = _by_ptr(ar.value, [comps[1]] + ka + extra[2:])
+        if yo is not comps[0]:
+            comps[0].copy_(yo)
+        if ao is not comps[1]:
+            comps[1].copy_(ao)
+        return multistep_nfe(method, n_steps)
 
     def param_grads(self, comps):
         return self._in_params_order(comps)

@@ -189,7 +189,8 @@ class ODEBlock(nn.Module):
     method: None / 'dopri5', 'bosh3' (Bogacki-Shampine 3(2)) or 'adaptive_heun' (Heun-Euler 2(1)) - adaptive, rtol = atol =
     tol - or a fixed-grid method on steps of step_size (one step over
     [0, 1] without it): 'rk4' (3/8 rule, 4 evaluations per step), 'midpoint' (2) or 'euler' (1).  Euler at step_size 1/K is
-    the weight-tied K-layer residual stack x <- x + odefunc(k/K, x) / K."""
+    the weight-tied K-layer residual stack x <- x + odefunc(k/K, x) / K.  'explicit_adams' (4th-order Adams-Bashforth) runs on
+    the same steps: three rk4 steps, then one evaluation per step."""
 
     def __init__(self, odefunc, tol=1e-5, method=None, step_size=None, node_order=None, adjoint=True):
         super(ODEBlock, self).__init__()

@@ -13,7 +13,9 @@ RK arithmetic still in the HIP kernels.
 mode on and y0 or a parameter of func requiring grad it returns a tensor with a grad_fn whose gradient is the exact
 derivative of the computed discrete solution w.r.t. y0 and func's parameters (t gets None).  Methods: adaptive `dopri5`
 (the default), `bosh3` and `adaptive_heun`, and the fixed-grid `rk4` (3/8 rule), `midpoint` and `euler` on the grid options['step_size'] gives (one step
-per interval of t without it); euler at step_size 1/K is the weight-tied K-layer residual stack.  Under the adaptive methods the
+per interval of t without it); euler at step_size 1/K is the weight-tied K-layer residual stack.  `explicit_adams` (4th-order
+Adams-Bashforth) runs on the same grid: three rk4 start-up steps per interval of t, then one evaluation per step; a grid of at
+most three steps per interval is the rk4 solve.  Under the adaptive methods the
 accepted step sizes are constants of that derivative: rejected attempts, the initial-step heuristic and the controller
 contribute nothing (what autograd through a solver whose step sizes are Python floats gives).  Row-partitioned fields
 stay forward-only.
@@ -24,9 +26,10 @@ import torch
 
 from . import ops
 from . import solver
-from .solver import (ADAPTIVE_METHODS, ADAPTIVE_TABLEAUS, FIXED_METHODS, FIXED_TABLEAUS, Dopri5Record, Dopri5Stats, Field,
-                     adaptive_interp_weights, adaptive_stages, integrate_adaptive, integrate_dopri5_inplace, integrate_fixed,
-                     integrate_rk4, n_stages, uniform_grid)
+from .solver import (ADAPTIVE_METHODS, ADAPTIVE_TABLEAUS, FIXED_METHODS, FIXED_TABLEAUS, MULTISTEP_BETAS, MULTISTEP_METHODS,
+                     Dopri5Record, Dopri5Stats, Field, adaptive_interp_weights, adaptive_stages, integrate_adaptive,
+                     integrate_dopri5_inplace, integrate_fixed, integrate_multistep, integrate_rk4, multistep_nfe, n_stages,
+                     uniform_grid)
 
 
 NATIVE_RK4 = True      # fused fields: issue a whole fixed-grid solve from one C-ABI call (False: per-stage Python driver)
@@ -144,17 +147,37 @@ def _times(t):
 METHODS = ("dopri5",) + FIXED_METHODS + tuple(m for m in ADAPTIVE_METHODS if m != "dopri5")
 
 
+# ... and the multistep ones (explicit_adams: 4th-order Adams-Bashforth, rk4 start-up).  GRID_METHODS: every method that runs
+# on the uniform grid of options['step_size'] and never looks at dL/dt or the tolerances
+GRID_METHODS = FIXED_METHODS + MULTISTEP_METHODS
+
+
 def _method(method):
     m = "dopri5" if method is None else method
-    if m not in METHODS:
-        raise ValueError("odeint: unsupported method %r (supported: %s)" % (method, ", ".join(METHODS)))
+    if m not in METHODS and m not in MULTISTEP_METHODS:
+        raise ValueError("odeint: unsupported method %r (supported: %s)" % (method, ", ".join(METHODS + MULTISTEP_METHODS)))
     return m
+
+
+def _grid_method(method, tl, options):
+    """A multistep method on intervals of at most K - 1 steps each never leaves its rk4 start-up: the solve IS the rk4 solve
+    of that grid, and runs as one (every native path, sweep and captured plan of rk4; bit for bit its results)."""
+    if method in MULTISTEP_METHODS:
+        step_size = (options or {}).get("step_size")
+        if all(uniform_grid(tl[i - 1], tl[i], step_size) < len(MULTISTEP_BETAS[method]) for i in range(1, len(tl))):
+            return "rk4"
+    return method
+
+
+def _grid_nfe(method, n):
+    """Evaluations of an n-step solve of one interval under a method of GRID_METHODS."""
+    return multistep_nfe(method, n) if method in MULTISTEP_METHODS else n_stages(method) * n
 
 
 def _integrate(field, comps, t0, t1, rtol, atol, method, options, stats):
     if method == "rk4":
         stats.nfe += _run_rk4(field, comps, t0, t1, uniform_grid(t0, t1, (options or {}).get("step_size")))
-    elif method in FIXED_METHODS:
+    elif method in GRID_METHODS:
         stats.nfe += _run_fixed(field, comps, t0, t1, uniform_grid(t0, t1, (options or {}).get("step_size")), method)
     else:
         if field.fixed_grid_only:
@@ -166,7 +189,7 @@ def _integrate(field, comps, t0, t1, rtol, atol, method, options, stats):
 
 
 _FIXED_ONLY = "odeint: this field supports the fixed-grid methods only (method=%s)" % " / ".join(
-    repr(m) for m in FIXED_METHODS)
+    repr(m) for m in GRID_METHODS)
 
 
 class _GraphedSolve:
@@ -177,7 +200,7 @@ class _GraphedSolve:
         lib = _lib.load()
         self.field = field
         self.inputs = list(comps)
-        self.nfe = n_stages(method) * n_steps
+        self.nfe = _grid_nfe(method, n_steps)
         work = list(comps)
         overlap = lib.gode_get_option(b"overlap")
         lib.gode_set_option(b"overlap", 0)           # launch-bound sizes gain nothing from the second stream
@@ -242,7 +265,7 @@ def _plan_for(func, y0, tl, method, options, params):
     shape and the parameter storage (i.e. the graph)."""
     tok = getattr(func, "gode_plan_token", None)
     token = None
-    if (tok is not None and GRAPH_CAPTURE_MAX_ELEMS > 0 and method in FIXED_METHODS and len(tl) == 2
+    if (tok is not None and GRAPH_CAPTURE_MAX_ELEMS > 0 and method in GRID_METHODS and len(tl) == 2
             and y0.numel() <= GRAPH_CAPTURE_MAX_ELEMS and not torch.cuda.is_current_stream_capturing()):
         token = tok(y0)
     if token is None:
@@ -273,10 +296,24 @@ def _run_rk4(field, comps, t0, t1, n):
     return integrate_rk4(field, comps, t0, t1, n)
 
 
+def _run_multistep(field, comps, t0, t1, n, method):
+    """A solve of one interval by a method of solver.MULTISTEP_BETAS; at most K - 1 steps: _run_rk4's launches exactly."""
+    if n < len(MULTISTEP_BETAS[method]):
+        return _run_rk4(field, comps, t0, t1, n)
+    _prepare(field)
+    if field.multistep_native is not None and NATIVE_RK4:
+        nfe = field.multistep_native(comps, t0, t1, n, method)     # whole solve issued from C; None: not on that route
+        if nfe is not None:
+            return nfe
+    return integrate_multistep(field, comps, t0, t1, n, method)
+
+
 def _run_fixed(field, comps, t0, t1, n, method):
-    """A fixed-grid solve by any method of solver.FIXED_TABLEAUS; rk4 takes _run_rk4's launches exactly."""
+    """A uniform-grid solve by any method of GRID_METHODS; rk4 takes _run_rk4's launches exactly."""
     if method == "rk4":
         return _run_rk4(field, comps, t0, t1, n)
+    if method in MULTISTEP_METHODS:
+        return _run_multistep(field, comps, t0, t1, n, method)
     _prepare(field)
     if field.fixed_native is not None and NATIVE_RK4:
         nfe = field.fixed_native(comps, t0, t1, n, method)     # whole solve issued from C; None: not on that route
@@ -359,6 +396,32 @@ def _fixed_torch(func, y, t0, t1, n, method):
         for s in range(len(C)):
             ks.append(func(tt(t + C[s] * h), y + sum((h * a) * k for a, k in zip(A[s], ks) if a != 0.0)))
         y = y + sum((h * b) * k for b, k in zip(B, ks) if b != 0.0)
+    return y
+
+
+def _multistep_torch(func, y, t0, t1, n, method):
+    """n steps of a multistep method from t0 to t1 as differentiable torch ops through func: _rk4_torch's step for the
+    start-up, k_1 kept; then one evaluation per step.  Autograd through it gives f_i the cotangent of every later step that
+    reads it, on top of what k_1 gets inside its own rk4 step."""
+    beta = MULTISTEP_BETAS[method]
+    K = len(beta)
+    if n < K:
+        return _rk4_torch(func, y, t0, t1, n)
+    h = (t1 - t0) / n
+    tt = lambda v: torch.tensor(v, dtype=y.dtype, device=y.device)      # noqa: E731
+    fs = []                                                              # f_{i-1}, f_{i-2}, ... (newest first)
+    for i in range(n):
+        t = t0 + i * h
+        k1 = func(tt(t), y)
+        fs.insert(0, k1)
+        if i < K - 1:
+            k2 = func(tt(t + h / 3.0), y + h * k1 / 3.0)
+            k3 = func(tt(t + 2.0 * h / 3.0), y + h * (k2 - k1 / 3.0))
+            k4 = func(tt(t + h), y + h * (k1 - k2 + k3))
+            y = y + (k1 + 3.0 * (k2 + k3) + k4) * (h * 0.125)
+        else:
+            y = y + sum((h * b) * f for b, f in zip(beta, fs))
+            fs.pop()
     return y
 
 
@@ -454,6 +517,83 @@ class _Rk4Backprop:
         yield rec, lambda y: _fixed_torch(self.func, y, self.tl[i - 1], self.tl[i], self.steps[i - 1], self.method)
 
 
+def _multistep_sweep(fwd, method):
+    """(forward_save, backprop, record_floats) of a field under a multistep method - or None."""
+    if fwd.multistep_forward_save is None or fwd.multistep_backprop is None:
+        return None
+    bind = lambda f: (lambda *args, **kw: f(method, *args, **kw))      # noqa: E731
+    return bind(fwd.multistep_forward_save), bind(fwd.multistep_backprop), bind(fwd.multistep_record_floats)
+
+
+class _MultistepBackprop(_Rk4Backprop):
+    """What _OdeintBackprop does per interval under a multistep method (K - 1 rk4 start-up steps, then one evaluation per
+    step).  Fused (a field offering multistep_forward_save / multistep_backprop: GcnOdeField): a flat record, [y_i, k_1..k_4]
+    of a start-up step and [y_i, f_i] of a later one, swept in reverse by one C call per interval - or, when the whole solve
+    outgrows BACKPROP_SAVE_MAX_BYTES, y_i alone of the start-up steps, each re-run into a one-step record just before its
+    sweep (the later steps' records are kept whole).  An interval of at most K - 1 steps is an rk4 solve and takes
+    _Rk4Backprop's path.  Generic: the record is the interval's start state, from which the interval is re-run as torch ops
+    through func (_multistep_torch)."""
+
+    def __init__(self, func, fwd, tl, rtol, atol, options, y0c, method):
+        self.func, self.fwd, self.tl, self.tols, self.options = func, fwd, tl, (rtol, atol), options
+        self.method, self.K, self.S = method, len(MULTISTEP_BETAS[method]), 4
+        step_size = (options or {}).get("step_size")
+        self.steps = [uniform_grid(tl[i - 1], tl[i], step_size) for i in range(1, len(tl))]
+        sweep = _multistep_sweep(fwd, method) if NATIVE_RK4 else None
+        rk4 = _fixed_sweep(fwd, "rk4") if NATIVE_RK4 else None
+        self.fused = sweep is not None and rk4 is not None
+        self.stats = Dopri5Stats()
+        self.ms_one = None
+        if self.fused:
+            self.ms_forward_save, self.ms_backprop, self.floats = sweep
+            self.forward_save, self.backprop = rk4                        # _Rk4Backprop's members: the short intervals
+            _prepare(fwd)
+            nd = y0c.numel()
+            total = sum(self.floats(n, n, nd) if n >= self.K else 5 * n * nd for n in self.steps)
+            self.save_all = total * 4 <= BACKPROP_SAVE_MAX_BYTES
+
+    def forward(self, i, cur, start):
+        n = self.steps[i - 1]
+        if not self.fused or n < self.K:
+            return _Rk4Backprop.forward(self, i, cur, start)      # generic: _integrate counts; fused: an rk4 interval
+        fwd, t0, t1, nd, K = self.fwd, self.tl[i - 1], self.tl[i], cur.numel(), self.K
+        like = dict(dtype=cur.dtype, device=cur.device)
+        y_end = torch.empty_like(cur)
+        if self.save_all:
+            rec = torch.empty(self.floats(n, n, nd), **like)
+            rec[:nd].copy_(cur.reshape(-1))
+            self.ms_forward_save(rec, y_end, rec, t0, t1, n, 0, n)
+        else:
+            start_n = (K - 1) * nd                                          # y_0 .. y_{K-2}, then the multistep records
+            rec = torch.empty(start_n + self.floats(n, n, nd) - self.floats(n, K - 1, nd), **like)
+            tmp = torch.empty(self.floats(n, K - 1, nd), **like)           # the start-up records, until the forward is over
+            tmp[:nd].copy_(cur.reshape(-1))
+            self.ms_forward_save(tmp, rec[start_n:start_n + nd], tmp, t0, t1, n, 0, K - 1)
+            for j in range(K - 1):
+                rec[j * nd:(j + 1) * nd].copy_(tmp[5 * j * nd:(5 * j + 1) * nd])
+            hist = [tmp[(5 * j + 1) * nd:(5 * j + 2) * nd] for j in range(K - 2, -1, -1)]      # k_1 = f of steps K-2 .. 0
+            self.ms_forward_save(rec[start_n:start_n + nd], y_end, rec[start_n:], t0, t1, n, K - 1, n, hist=hist)
+        self.stats.nfe += _grid_nfe(self.method, n)
+        return rec, y_end
+
+    def fused_reverse(self, i, rec, a, theta, work):
+        n = self.steps[i - 1]
+        if n < self.K:
+            return _Rk4Backprop.fused_reverse(self, i, rec, a, theta, work)
+        rerun = None
+        if not self.save_all:                  # (kept beside `work`, which _Rk4Backprop fills for the short intervals)
+            if self.ms_one is None:
+                self.ms_one = torch.empty(5 * a.numel(), dtype=a.dtype, device=a.device)
+            rerun = self.ms_one
+        res = self.ms_backprop(rec, a, theta, self.tl[i - 1], self.tl[i], n, rerun=rerun)
+        if res is not a:
+            a.copy_(res)
+        return a
+
+    def generic_reverse(self, i, rec):
+        yield rec, lambda y: _multistep_torch(self.func, y, self.tl[i - 1], self.tl[i], self.steps[i - 1], self.method)
+
+
 def _adaptive_sweep(fwd, method):
     """(step_native, step_backprop, backprop_work) of a field under an adaptive method, each taking the dopri5 member's
     arguments - None where the field does not offer it.  dopri5 keeps the members it has always used; a field's seven-stage
@@ -544,7 +684,9 @@ class _OdeintBackprop(torch.autograd.Function):
         outs = [y0c.clone()]
         records = []
         with torch.no_grad():
-            if method in FIXED_METHODS:
+            if method in MULTISTEP_METHODS:
+                sweep = _MultistepBackprop(func, fwd, tl, rtol, atol, options, y0c, method)
+            elif method in FIXED_METHODS:
                 sweep = _Rk4Backprop(func, fwd, tl, rtol, atol, options, y0c, method)
             else:
                 sweep = _Dopri5Backprop(func, fwd, tl, rtol, atol, options, y0c, method)
@@ -600,7 +742,7 @@ def odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None):
     a forward solve without gradient support."""
     _check_state(y0)
     tl = _times(t)
-    method = _method(method)
+    method = _grid_method(_method(method), tl, options)
     fields = _fields(func, y0)
     fwd = fields[0]
     if torch.is_grad_enabled() and fwd.big_components is None:
@@ -608,7 +750,10 @@ def odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None):
         if y0.requires_grad or params:
             covered = tuple(fields[2]) + _extra_inputs(func)       # a field with a sweep returns the extra inputs' gradients too
             same = len(covered) == len(params) and all(p is q for p, q in zip(covered, params))
-            sweep = _fixed_sweep(fwd, method) if method in FIXED_METHODS else _adaptive_sweep(fwd, method)[1]
+            if method in MULTISTEP_METHODS:
+                sweep = _multistep_sweep(fwd, method)
+            else:
+                sweep = _fixed_sweep(fwd, method) if method in FIXED_METHODS else _adaptive_sweep(fwd, method)[1]
             if sweep is not None and not same:
                 fwd = AutogradField(func, y0)         # the fused field does not cover these parameters
             return _OdeintBackprop.apply(func, fwd, tl, float(rtol), float(atol), method, options, y0, *params)
@@ -718,7 +863,7 @@ class _OdeintAdjoint(torch.autograd.Function):
             _gather(g_raw(-1), order, out=comps[1])
             for i in range(len(tl) - 1, 0, -1):
                 comps[0].copy_(ans[i])
-                if ctx.method not in FIXED_METHODS:
+                if ctx.method not in GRID_METHODS:
                     # dL/dt at the output time enters the adaptive error control (torchdiffeq evaluates
                     # func once more here); a fixed grid never looks at it, so the fixed-grid methods skip the eval.
                     fwd.eval(tl[i], [[(1.0, ans[i])]], [ctx_tmp])
@@ -735,17 +880,18 @@ class _OdeintAdjoint(torch.autograd.Function):
             # the cotangent of the start state is added after the rows are back in the caller's order: one pass, and
             # no gather of a slice that is all zeros whenever the loss only looks at the end state
             gy0 = add_start(back(comps[1]))
-        skipped = (n_t - 1) if (ctx.method in FIXED_METHODS and NFE_COUNTS_SKIPPED_DLDT_EVAL) else 0
+        skipped = (n_t - 1) if (ctx.method in GRID_METHODS and NFE_COUNTS_SKIPPED_DLDT_EVAL) else 0
         _bump_nfe(func, adj, stats.nfe, skipped)
         return (None, None, None, None, None, None, None, gy0, *adj.param_grads(comps))
 
 
 def odeint_adjoint(func, y0, t, rtol=1e-6, atol=1e-12, method=None, options=None, _last_only=False):
-    """torchdiffeq's odeint_adjoint for the adaptive methods (dopri5, bosh3, adaptive_heun) and the fixed-grid ones (rk4, midpoint, euler).  `_last_only=True` (not part of the reference
+    """torchdiffeq's odeint_adjoint for the adaptive methods (dopri5, bosh3, adaptive_heun), the fixed-grid ones (rk4, midpoint, euler)
+    and the multistep explicit_adams.  `_last_only=True` (not part of the reference
     API; used by models.ODEBlock, which keeps `out[1]` only) returns y(t[-1]) instead of the stack over t."""
     _check_state(y0)
     tl = _times(t)
-    method = _method(method)
+    method = _grid_method(_method(method), tl, options)
     if not isinstance(func, torch.nn.Module):
         raise ValueError("odeint_adjoint: func must be an nn.Module")
     params = _params(func)

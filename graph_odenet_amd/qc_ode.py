@@ -49,7 +49,7 @@ import torch.nn.functional as F
 from . import _lib, ops
 from .functional import GroupNorm
 from .qc_layers import EdgeGraphConvolution, _edges, _EdgeSet
-from .solver import ADAPTIVE_TABLEAUS, FIXED_METHODS, FIXED_TABLEAUS, Field, _stage_terms
+from .solver import ADAPTIVE_TABLEAUS, FIXED_METHODS, FIXED_TABLEAUS, MULTISTEP_METHODS, Field, _stage_terms
 
 
 def _edge_index(Esrc, Etgt):
@@ -455,7 +455,7 @@ class EdgeODEBlock(nn.Module):
         from .odeint import odeint, odeint_adjoint
         self.integration_time = self.integration_time.type_as(x)
         self.odefunc.set_edges(Esrc, Etgt, edge_data)
-        self.odefunc.fixed_grid = self.method in FIXED_METHODS
+        self.odefunc.fixed_grid = self.method in FIXED_METHODS or self.method in MULTISTEP_METHODS
         options = None if self.step_size is None else {"step_size": self.step_size}
         if not self.adjoint:
             return odeint(self.odefunc, x, self.integration_time, rtol=self.tol, atol=self.tol, method=self.method,

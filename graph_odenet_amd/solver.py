@@ -7,6 +7,8 @@ module re-creates the two methods the hot path needs from the published algorith
   * fixed-grid `rk4`  : 3/8-rule steps on a uniform grid (options['step_size']);
   * fixed-grid `euler`, `midpoint` : torchdiffeq's one- and two-stage methods on the same grid, run by the same driver from
                         their tableaus (FIXED_TABLEAUS, integrate_fixed);
+  * multistep `explicit_adams` : 4th-order Adams-Bashforth on the same grid, three rk4 start-up steps per interval, then one
+                        evaluation per step (MULTISTEP_BETAS, integrate_multistep);
   * adaptive `dopri5` : Dormand-Prince 5(4), FSAL, RMS mixed-tolerance error ratio per
                         state tensor, safety 0.9 / ifactor 10 / dfactor 0.2, 4th-order
                         interpolation to the end time (the reference's default: no
@@ -40,6 +42,30 @@ MIDPOINT_C, MIDPOINT_A, MIDPOINT_B = [0.0, 0.5], [[], [0.5]], [0.0, 1.0]
 FIXED_TABLEAUS = {"rk4": (RK38_C, RK38_A, RK38_B), "euler": (EULER_C, EULER_A, EULER_B),
                   "midpoint": (MIDPOINT_C, MIDPOINT_A, MIDPOINT_B)}
 FIXED_METHODS = tuple(FIXED_TABLEAUS)
+
+
+# The multistep methods by name: the weights beta_j of f_{i-j} in  y_{i+1} = y_i + h sum_j beta_j f_{i-j}.  explicit_adams is the
+# 4th-order Adams-Bashforth method on the fixed grid, started with len(beta) - 1 3/8-rule steps whose k_1 = f_i is kept
+# (integrate_multistep); the history restarts at every interval of t.  They have no GODE_RK_* code: include/graphode.h gives
+# them entry points of their own (gode_gcn_ode_adams_*).
+ADAMS_BETA = [55.0 / 24.0, -59.0 / 24.0, 37.0 / 24.0, -9.0 / 24.0]
+MULTISTEP_BETAS = {"explicit_adams": ADAMS_BETA}
+MULTISTEP_METHODS = ("explicit_adams",)
+
+
+def multistep_nfe(method, n):
+    """Evaluations of an n-step solve of one interval: four per start-up step, one per multistep step."""
+    start = min(n, len(MULTISTEP_BETAS[method]) - 1)
+    return 4 * start + (n - start)
+
+
+def multistep_weight(method, i, n, h):
+    """The weight f_i (the evaluation that opens step i of n) ends up with over all multistep steps that read it:
+    h * sum of beta_{m - i} over the steps m = max(i, K - 1) .. min(i + K - 1, n - 1), formed in double.  A component no
+    stage input reads (a pure quadrature) may take each evaluation once with this weight instead of keeping a history."""
+    beta = MULTISTEP_BETAS[method]
+    K = len(beta)
+    return h * sum(beta[m - i] for m in range(max(i, K - 1), min(i + K - 1, n - 1) + 1))
 
 
 def method_code(method):
@@ -160,6 +186,17 @@ class Field:
     #                               integrate_rk4: the last stage closes the step, finish_rk4_step receives S weights
     fixed_native = None           # fixed_native(comps, t0, t1, n, method) -> nfe: odeint, the whole solve as one C call;
     #                               None from the call itself = not on this route, take the per-stage driver
+    # ---- the multistep methods (a name of MULTISTEP_BETAS) on more steps than the start-up takes -------------------------------
+    #                               begin_rk4_step / finish_rk4_step serve integrate_multistep too: a multistep step is one
+    #                               evaluation, and finish_rk4_step receives each evaluation's final weight (multistep_weight)
+    multistep_native = None       # multistep_native(comps, t0, t1, n, method) -> nfe: odeint, the whole solve as one C call;
+    #                               None from the call itself = not on this route, take integrate_multistep
+    multistep_forward_save = None  # multistep_forward_save(method, y0, y_end, save, t0, t1, n, i0, i1, hist=None): steps i0..i1-1
+    #                               into the flat record `save` - [y_i, k_1..k_4] of a start-up step, [y_i, f_i] of a later
+    #                               one; multistep_record_floats(method, n, step, nd) -> the floats in front of step's record
+    multistep_record_floats = None
+    multistep_backprop = None     # multistep_backprop(method, save, a, theta, t0, t1, n, rerun=None) -> tensor holding dL/dy
+    #                               before step 0; rerun: a one-step rk4 record, `save` then keeps y_i alone of the start-up
     # ---- adaptive dopri5 ------------------------------------------------------------------------------------------
     dopri5_step_native = None     # dopri5_step_native(y, kk, y1, t, h, rtol, atol) -> error sums per ratio group (fp64,
     #                               on the device): integrate_dopri5, one attempted step as one C call
@@ -276,51 +313,102 @@ def integrate_rk4(field, y, t0, t1, n_steps, work=None):
     return nfe
 
 
+def _fixed_step(field, y, ks, t, h, tableau, extra=None):
+    """One step of a fixed-grid method from the component list y at time t (integrate_fixed's body).  extra: a weight added
+    to k_1's in finish_rk4_step (the deferred components of a multistep start-up step); no other launch sees it."""
+    C, A, B = tableau
+    S = len(C)
+    L = S - 1
+    nc = len(y)
+    fused = field.eval_combine
+    begin, finish = field.begin_rk4_step, field.finish_rk4_step
+    deferred = begin is not None and begin()
+    for s in range(L):
+        field.eval(t + C[s] * h, _stage_terms(y, ks, A[s], h), ks[s])
+    done = ()
+    if fused is not None:
+        pre = [[(1.0, y[c])] + [(h * B[s], ks[s][c]) for s in range(L) if B[s] != 0.0] for c in range(nc)]
+        done = fused(t + C[L] * h, _stage_terms(y, ks, A[L], h), pre, h * B[L], ks[L])
+    else:
+        field.eval(t + C[L] * h, _stage_terms(y, ks, A[L], h), ks[L])
+    if deferred:
+        weights = [h * b for b in B]
+        if extra is not None:
+            weights[0] += extra
+        done = tuple(done) + tuple(finish(weights, y))
+    todo = []
+    for c in range(nc):
+        if c in done:
+            if deferred and c in field.deferred_components:
+                continue                           # advanced in place by finish_rk4_step
+            y[c], ks[L][c] = ks[L][c], y[c]        # ks[L][c] already holds the new solution
+        else:
+            todo.append(c)
+    for g0 in range(0, len(todo), 4):
+        grp = todo[g0:g0 + 4]
+        terms = [[(1.0, y[c])] + [(h * B[s], ks[s][c]) for s in range(S) if B[s] != 0.0] for c in grp]
+        if len(grp) == 1:
+            ops.lincomb_(y[grp[0]], terms[0])
+        else:
+            ops.lincomb_multi_([y[c] for c in grp], terms)
+    return deferred
+
+
 def integrate_fixed(field, y, t0, t1, n_steps, method, work=None):
     """integrate_rk4 for any method of FIXED_TABLEAUS, the same protocol: `eval` for every stage but the last,
     `eval_combine` for the last - its pre is y + h * sum of the earlier stages with a non-zero b, its coefficient h * b_last -
     begin_rk4_step / finish_rk4_step around the stages (S weights), and the remaining components in lincomb_multi_ launches of
     four.  Terms with a zero coefficient are dropped.  Returns nfe; read the result from `y[c]`."""
-    C, A, B = FIXED_TABLEAUS[method]
-    S = len(C)
-    L = S - 1
+    tableau = FIXED_TABLEAUS[method]
+    S = len(tableau[0])
     alloc = field.alloc_like or _alloc_like
     ks = work if work is not None else alloc(y, S)
     h = (t1 - t0) / n_steps
-    nfe = 0
-    nc = len(y)
-    fused = field.eval_combine
-    begin, finish = field.begin_rk4_step, field.finish_rk4_step
     for i in range(n_steps):
+        _fixed_step(field, y, ks, t0 + i * h, h, tableau)
+    return S * n_steps
+
+
+def integrate_multistep(field, y, t0, t1, n_steps, method, work=None):
+    """A method of MULTISTEP_BETAS (K weights) on n_steps equal steps from t0 to t1, the protocol of integrate_fixed.  Steps
+    0 .. min(n_steps, K - 1) - 1 are integrate_fixed's rk4 step (eval_combine and the deferral honoured); their k_1 = f_i is
+    kept.  A later step is one `eval` of f_i on y_i, then  y += h sum_j beta_j f_{i-j}  over the components in lincomb_multi_
+    launches of four (K + 1 terms; eval_combine is not used there: it would not leave f_i for the steps after it).  Where the
+    field defers components (begin_rk4_step), no history of theirs exists: finish_rk4_step adds each evaluation once with the
+    weight it ends up with (multistep_weight; a start-up step's k_1 gets it on top of h b_1), so such a component holds its
+    value at t1 only when the solve is over.  work: K + 2 work copies of the state.  Returns nfe; read the result from `y[c]`."""
+    beta = MULTISTEP_BETAS[method]
+    K = len(beta)
+    if n_steps < K:                                     # start-up only: the rk4 solve itself
+        return integrate_fixed(field, y, t0, t1, n_steps, "rk4", work[:4] if work is not None else None)
+    alloc = field.alloc_like or _alloc_like
+    bufs = list(work) if work is not None else alloc(y, K + 2)
+    ks, spare = bufs[:4], bufs[4:]
+    h = (t1 - t0) / n_steps
+    nc = len(y)
+    hist = []                                           # f_{i-1}, f_{i-2}, ... (newest first)
+    begin, finish = field.begin_rk4_step, field.finish_rk4_step
+    for i in range(K - 1):
+        _fixed_step(field, y, ks, t0 + i * h, h, FIXED_TABLEAUS["rk4"], extra=multistep_weight(method, i, n_steps, h))
+        hist.insert(0, ks[0])
+        ks[0] = spare.pop() if spare else ks[1]         # after the last start-up step ks is free: its buffers go on as the ring
+    free = [b for b in ks if all(b is not q for q in hist)][:1]
+    for i in range(K - 1, n_steps):
         t = t0 + i * h
+        fnew = free.pop() if free else hist.pop()       # the buffer of f_{i-K}, which no later step reads
         deferred = begin is not None and begin()
-        for s in range(L):
-            field.eval(t + C[s] * h, _stage_terms(y, ks, A[s], h), ks[s])
-        done = ()
-        if fused is not None:
-            pre = [[(1.0, y[c])] + [(h * B[s], ks[s][c]) for s in range(L) if B[s] != 0.0] for c in range(nc)]
-            done = fused(t + C[L] * h, _stage_terms(y, ks, A[L], h), pre, h * B[L], ks[L])
-        else:
-            field.eval(t + C[L] * h, _stage_terms(y, ks, A[L], h), ks[L])
-        nfe += S
-        if deferred:
-            done = tuple(done) + tuple(finish([h * b for b in B], y))
-        todo = []
-        for c in range(nc):
-            if c in done:
-                if deferred and c in field.deferred_components:
-                    continue                           # advanced in place by finish_rk4_step
-                y[c], ks[L][c] = ks[L][c], y[c]        # ks[L][c] already holds the new solution
-            else:
-                todo.append(c)
+        field.eval(t, [[(1.0, y[c])] for c in range(nc)], fnew)
+        hist.insert(0, fnew)
+        done = tuple(finish([multistep_weight(method, i, n_steps, h)], y)) if deferred else ()
+        todo = [c for c in range(nc) if c not in done]
         for g0 in range(0, len(todo), 4):
             grp = todo[g0:g0 + 4]
-            terms = [[(1.0, y[c])] + [(h * B[s], ks[s][c]) for s in range(S) if B[s] != 0.0] for c in grp]
+            terms = [[(1.0, y[c])] + [(h * beta[j], hist[j][c]) for j in range(K)] for c in grp]
             if len(grp) == 1:
                 ops.lincomb_(y[grp[0]], terms[0])
             else:
                 ops.lincomb_multi_([y[c] for c in grp], terms)
-    return nfe
+    return multistep_nfe(method, n_steps)
 
 
 DOPRI5_NATIVE = True      # fused fields: one C-ABI call per adaptive step (False: per-stage Python driver)

@@ -50,7 +50,7 @@ def build_parser():
     p.add_argument('--early_stopping_epochs', type=int, default=10)          # parsed and unused, as in the reference
     p.add_argument('--early_stopping_threshold', type=float, default=1e-10)  # idem
     p.add_argument('--models', default=",".join(FAMILIES))
-    p.add_argument('--method', choices=["dopri5", "rk4", "midpoint", "euler", "bosh3", "adaptive_heun"], default=None)
+    p.add_argument('--method', choices=["dopri5", "rk4", "midpoint", "euler", "bosh3", "adaptive_heun", "explicit_adams"], default=None)
     p.add_argument('--step_size', type=float, default=None)
     p.add_argument('--out_dir', default=".")
     p.add_argument('--data_dir', default=None)

@@ -51,7 +51,7 @@ def build_parser():
     p.add_argument('--dropout', type=float, default=0.5)
     p.add_argument('--dataset', choices=["cora", "citeseer", "pubmed"], default="cora")
     p.add_argument('--model', choices=sorted(MODELS), default="res3")
-    p.add_argument('--method', choices=["dopri5", "rk4", "midpoint", "euler", "bosh3", "adaptive_heun"], default=None)
+    p.add_argument('--method', choices=["dopri5", "rk4", "midpoint", "euler", "bosh3", "adaptive_heun", "explicit_adams"], default=None)
     p.add_argument('--step_size', type=float, default=None)
     p.add_argument('--tol', type=float, default=1e-5)
     p.add_argument('--data_dir', default=None)

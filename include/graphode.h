@@ -790,6 +790,60 @@ int gode_gcn_ode_fixed_backprop(int32_t method, const gode_gcn_odefunc_t* f, con
                                 float** a_result, const gode_rk4_workspace_t* ws, float* cot_colpart /* nullable */,
                                 float t0, float t1, int32_t n_steps, int32_t step_begin, int32_t step_end, void* stream);
 
+/* explicit_adams: the 4th-order Adams-Bashforth method on the n_steps-step grid from t0 to t1,
+ *   y_{i+1} = y_i + h (55 f_i - 59 f_{i-1} + 37 f_{i-2} - 9 f_{i-3}) / 24,   f_i = f(t_i, y_i),
+ * started with three 3/8-rule steps - the launches of the rk4 drivers, every option but "local_tail" included - whose k_1 is
+ * f_i.  After them a step is ONE evaluation: its launch stores f_i and closes the step (pre = y_i and the three older f,
+ * alpha = 55 h / 24).  n_steps <= 3 is the rk4 entry point itself.  h and every h * coefficient product are formed in double
+ * and rounded once.  The method has no GODE_RK_* code: 3 stays GODE_E_SHAPE in the drivers above.
+ * extra: host array of further n x d work arrays, 2 for the forward solve, 4 for the adjoint (2 for y's chain, then 2 for
+ *   a's); with y (a) and ws->ky (ws->ka) they take turns as solution, history and stage buffers, and *result (*y_result,
+ *   *a_result) names the one that holds the result.
+ * adams_adjoint: the launch-bound route only, as gode_gcn_ode_fixed_adjoint (GODE_E_UNSUPPORTED before any launch elsewhere).
+ *   A multistep step is two launches (gode_gcn_feval_small_save_cot_f32, gode_gcn_vjp_small_raw_f32) and the closing reduction.
+ *   theta is a pure quadrature: each evaluation's partials are added once, with the weight the evaluation ends up with over
+ *   the steps that read it, so theta is complete only when the call returns.
+ * Validation: null arguments, then shapes, then (adjoint) the route, then the members of ws and extra. */
+int gode_gcn_ode_adams_forward(const gode_gcn_odefunc_t* f, float* y, float** result, const gode_rk4_workspace_t* ws,
+                               float* const* extra /* host, 2 */, float t0, float t1, int32_t n_steps, void* stream);
+int gode_gcn_ode_adams_adjoint(const gode_gcn_odefunc_t* f, float* y, float* a, float* theta, float** y_result,
+                               float** a_result, const gode_rk4_workspace_t* ws, float* const* extra /* host, 4 */,
+                               float t0, float t1, int32_t n_steps, void* stream);
+/* Backprop through an explicit_adams solve: the counterparts of gode_gcn_ode_fixed_forward_save / _fixed_backprop.
+ * Records are compact: a start-up step (0, 1, 2) keeps [ y_i | k_1 .. k_4 ] (5 n x d floats, the rk4 record), a later step
+ * [ y_i | f_i ] (2 n x d).  gode_adams_record_offset(step, nd): the floats in front of step's record (host query; step =
+ * n_steps gives the solve's total; GODE_E_SHAPE for a negative argument) - 2^20 x 128, 16 steps: 22 GB against rk4's 43 GB.
+ * adams_forward_save: steps step_begin .. step_end - 1 into `save`, which starts at step_begin's record; the launches of
+ *   gode_gcn_ode_adams_forward on other addresses.  hist (host array of 3, read when step_begin > 0 and a multistep step is
+ *   run): f of the steps step_begin - 1, - 2, - 3, where they exist.  n_steps <= 3: gode_gcn_ode_rk4_forward_save itself.
+ * adams_backprop: the reverse sweep over all n_steps records in one call.  a = dL/dy_n on entry; work: host array of 4
+ *   further n x d arrays - with `a` they hold the pending cotangents (a step's f is read by up to four later steps), and
+ *   *a_result names the one that holds dL/dy_0; theta is incremented as by gode_gcn_ode_rk4_backprop, ws as there.  A
+ *   multistep step is one stage (launch-bound route: one gode_gcn_vjp_small_next_f32 launch and the closing reduction); a
+ *   start-up step is the rk4 sweep's step with the later steps' cotangent added to k_1's (4 + at most 3 terms).
+ *   rerun (nullable, 5 n x d floats): `save` then holds y_0, y_1, y_2 alone (3 n x d floats) in front of the multistep
+ *   records, and each start-up step is re-run into `rerun` before its sweep (the forward's launches: the same gradients bit
+ *   for bit).  n_steps <= 3 (rerun must be NULL): gode_gcn_ode_rk4_backprop itself.
+ * Validation: null arguments, then shapes and step ranges, then the members of ws, hist and work. */
+int64_t gode_adams_record_offset(int32_t step, int64_t nd);
+int gode_gcn_ode_adams_forward_save(const gode_gcn_odefunc_t* f, const float* y0, float* y_end, float* save,
+                                    const float* const* hist /* host, 3, nullable */, const gode_rk4_workspace_t* ws,
+                                    float t0, float t1, int32_t n_steps, int32_t step_begin, int32_t step_end, void* stream);
+int gode_gcn_ode_adams_backprop(const gode_gcn_odefunc_t* f, const float* save, float* rerun /* nullable */, float* a,
+                                float* theta, float** a_result, const gode_rk4_workspace_t* ws,
+                                float* cot_colpart /* nullable */, float* const* work /* host, 4 */, float t0, float t1,
+                                int32_t n_steps, void* stream);
+/* The two one-launch forms a multistep adjoint step is made of (csrc/small.hip).  save_cot: gode_gcn_feval_small_save_f32
+ * with the masked cotangent Y2 = (sum cot) * [z > 0] as a third output; out, k and Y2 are distinct and none is a term of xin.
+ * vjp_raw: gode_gcn_vjp_small_f32 which also stores the derivative dx itself in raw (ka = (sum pre) + out_scale * dx); raw
+ * is neither ka nor dZ. */
+int gode_gcn_feval_small_save_cot_f32(const gode_gcn_odefunc_t* f, const gode_lincomb_t* xin /* host */, float t, float alpha,
+                                      const gode_lincomb_t* pre /* host, nullable */, const gode_lincomb_t* cot /* host */,
+                                      float* Y2, float* out, float* k, void* stream);
+int gode_gcn_vjp_small_raw_f32(const gode_gcn_odefunc_t* f, const gode_lincomb_t* xin /* host */, const float* dZ,
+                               float out_scale, const gode_lincomb_t* pre /* host, nullable */, float* ka, float* part,
+                               float* raw, void* stream);
+
 /* One Dormand-Prince 5(4) step of the same ODE function per call (adaptive solves on launch-bound sizes; the controller
  * - step-size selection, accept / reject, interpolation - stays with the caller, as in torchdiffeq).
  * forward: k[0] = f(t, y) on entry (FSAL); on return k[1..6] hold the other stages, y1 the 5th-order solution and
