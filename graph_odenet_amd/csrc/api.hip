@@ -24,7 +24,7 @@ extern "C" const char* gode_error_string(int code) {
 
 namespace {
 int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
-int g_gemm_split = -1, g_overlap = -1, g_wgrad_split = -1, g_wgrad_split_small = 0, g_bwd_pc = -1, g_fwd_pc = -1, g_small_fused = -1, g_bwd_wgrad = -1, g_y2_colsum = -1, g_rk_close_once = -1, g_spmm_pipe = -1, g_diag_rows = -1, g_diag_last = -1, g_local_tail = -1, g_local_tail_blocks = -1;
+int g_gemm_split = -1, g_overlap = -1, g_wgrad_split = -1, g_wgrad_split_small = 0, g_bwd_pc = -1, g_fwd_pc = -1, g_small_fused = -1, g_bwd_wgrad = -1, g_y2_colsum = -1, g_rk_close_once = -1, g_spmm_pipe = -1, g_diag_rows = -1, g_diag_last = -1, g_local_tail = -1, g_local_tail_blocks = -1, g_adjoint_tail = -1;
 }
 
 int gode_opt_gemm_split() { if (g_gemm_split < 0) { const int v = env_int("GODE_GEMM_SPLIT", 2); g_gemm_split = (v == 1 || v == 2) ? v : 0; } return g_gemm_split; }
@@ -43,6 +43,7 @@ int gode_opt_spmm_pipe() { if (g_spmm_pipe < 0) { const int v = env_int("GODE_SP
 int gode_opt_diag_rows() { if (g_diag_rows < 0) g_diag_rows = env_int("GODE_DIAG_ROWS", 1) != 0; return g_diag_rows; }
 int gode_opt_diag_last() { if (g_diag_last < 0) g_diag_last = env_int("GODE_DIAG_LAST", 1) != 0; return g_diag_last; }
 int gode_opt_local_tail() { if (g_local_tail < 0) g_local_tail = env_int("GODE_LOCAL_TAIL", 1) != 0; return g_local_tail; }
+int gode_opt_adjoint_tail() { if (g_adjoint_tail < 0) g_adjoint_tail = env_int("GODE_ADJOINT_TAIL", 1) != 0; return g_adjoint_tail; }
 int gode_opt_local_tail_blocks() { if (g_local_tail_blocks < 0) { const int v = env_int("GODE_LOCAL_TAIL_BLOCKS", 0); g_local_tail_blocks = (v < 0 || v > 4096) ? 0 : v; } return g_local_tail_blocks; }
 int gode_opt_overlap() { if (g_overlap < 0) g_overlap = env_int("GODE_OVERLAP", 1) != 0; return g_overlap; }
 
@@ -60,6 +61,7 @@ extern "C" int gode_set_option(const char* name, int value) {
     if (!strcmp(name, "diag_rows")) { g_diag_rows = value != 0; return 0; }
     if (!strcmp(name, "diag_last")) { g_diag_last = value != 0; return 0; }
     if (!strcmp(name, "local_tail")) { g_local_tail = value != 0; return 0; }
+    if (!strcmp(name, "adjoint_tail")) { g_adjoint_tail = value != 0; return 0; }
     if (!strcmp(name, "local_tail_blocks")) { if (value < 0 || value > 4096) return GODE_E_UNSUPPORTED; g_local_tail_blocks = value; return 0; }
     if (!strcmp(name, "fwd_pc")) { if (value < 0 || value > 3) return GODE_E_UNSUPPORTED; g_fwd_pc = value; return 0; }
     if (!strcmp(name, "wgrad_split")) { if (value != 0 && value != 6 && value != 8) return GODE_E_UNSUPPORTED; g_wgrad_split = value; return 0; }
@@ -80,6 +82,7 @@ extern "C" int gode_get_option(const char* name) {
     if (!strcmp(name, "diag_rows")) return gode_opt_diag_rows();
     if (!strcmp(name, "diag_last")) return gode_opt_diag_last();
     if (!strcmp(name, "local_tail")) return gode_opt_local_tail();
+    if (!strcmp(name, "adjoint_tail")) return gode_opt_adjoint_tail();
     if (!strcmp(name, "local_tail_blocks")) return gode_opt_local_tail_blocks();
     if (!strcmp(name, "fwd_pc")) return gode_opt_fwd_pc();
     return GODE_E_UNSUPPORTED;

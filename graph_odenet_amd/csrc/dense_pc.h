@@ -36,3 +36,20 @@ struct LocalTailSteps { float coef[4][4]; float acoef[4]; float alpha; int n_ste
 int gode_pc_local_tail_launch(const float* y_in, float* y_out, int64_t n_rows, const float* a_ii, float eps,
                               const float* gamma, const float* beta, const float* W, const float* bias,
                               const LocalTailSteps& st, int cg, int blocks, hipStream_t s);
+// One stage of the adjoint solve's forward recompute on n_rows isolated rows (gemm_pc.hip: gcn_adjoint_tail_kernel): Gf and
+// the one-entry records of Sp(g) with the cotangent epilogue in one launch, with the bits that pair gives those rows.
+// Every pointer names the FIRST ROW OF THE TAIL (the terms of yin and cot as well).  yin and cot have the same 1-4 terms
+// count; cot's coefficients are negated already (ep.cot).  k: the stage's derivative - or, last, y_new = fmaf(alpha, k,
+// fmaf(1, P, 0)) with P = sum pcoef[j] yin.ptr[j]; dS = fmaf(at_ii, g, 0) of the relu-masked g; x_out (nullable): the
+// combined input; last: cot_out = sum c3[j] cot.ptr[j], unmasked.  colpart: gode_pc_adjoint_tail_colsum_rows(n_rows)
+// rows of 128 floats, row q = g[8 q] + g[8 q + 1] + .. + g[8 q + 7] of the unscaled g, added in that order (what a block of
+// the d = 128 SpMM leaves for 8 consecutive one-entry records).  The S and dZ rows of the tail are not stored.
+struct AdjTail {
+    const float* a_ii; const float* at_ii; const float* bias;
+    float* k; float* dS; float* x_out; float* cot_out; float* colpart;
+    float pcoef[4], c3[4], alpha;
+};
+int64_t gode_pc_adjoint_tail_blocks(int64_t n_rows, int terms);   // the grid
+int64_t gode_pc_adjoint_tail_colsum_rows(int64_t n_rows);
+int gode_pc_adjoint_tail_launch(const LinComb& yin, const LinComb& cot, int64_t n_rows, float eps, const float* gamma,
+                                const float* beta, const float* W, float t, const AdjTail& at, bool last, int cg, hipStream_t s);

@@ -1509,6 +1509,44 @@ extern "C" int gode_gn_time_gemm_diag_aux_f32(const gode_lincomb_t* xin, int64_t
                                           aux_coef, K, stream);
 }
 
+// One stage of the adjoint's forward recompute on isolated rows (gemm_pc.hip: gcn_adjoint_tail_kernel).  No other kernel
+// has this form: a shape outside it is GODE_E_UNSUPPORTED, never another arithmetic.
+extern "C" int64_t gode_gcn_adjoint_tail_colsum_rows(int64_t n_rows)
+{
+    return gode_pc_adjoint_tail_colsum_rows(n_rows);
+}
+
+extern "C" int gode_gcn_adjoint_tail_stage_f32(const gode_lincomb_t* yin, const gode_lincomb_t* cot, int64_t n_rows, int64_t d,
+                                               int32_t groups, float eps, const float* gamma, const float* beta,
+                                               const float* W, float t, const float* a_ii, const float* at_ii,
+                                               const float* bias, float* k_out, float* dS_out, float* x_out,
+                                               const float* p_coef, float alpha, const float* cot_out_coef, float* cot_out,
+                                               float* colsum, void* stream)
+{
+    int rc = check_common(yin, n_rows, d, groups, d); if (rc) return rc;
+    rc = check_lincomb(cot, true); if (rc) return rc;
+    if (n_rows == 0) return 0;
+    if (!W || !a_ii || !at_ii || !bias || !k_out || !dS_out || !colsum) return GODE_E_NULLPTR;
+    if (p_coef && (!cot_out_coef || !cot_out)) return GODE_E_NULLPTR;
+    const int cg = fast_cg(d, d, groups);
+    if (d != 128 || (cg != 0 && cg != 4) || yin->n > 4 || cot->n != yin->n || (p_coef != nullptr) != (yin->n == 4)) return GODE_E_UNSUPPORTED;
+    uintptr_t bits = (uintptr_t)W | (uintptr_t)bias | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)k_out | (uintptr_t)dS_out |
+                     (uintptr_t)x_out | (uintptr_t)cot_out | (uintptr_t)colsum;
+    if ((bits & 15) || !lincomb_aligned16(yin) || !lincomb_aligned16(cot)) return GODE_E_UNSUPPORTED;
+    float* outs[4] = {k_out, dS_out, x_out, p_coef ? cot_out : nullptr};
+    for (int a = 0; a < 4; ++a) {
+        if (!outs[a]) continue;
+        for (int b = a + 1; b < 4; ++b) if (outs[a] == outs[b]) return GODE_E_RANGE;
+        for (int j = 0; j < yin->n; ++j) if (outs[a] == yin->ptr[j] || outs[a] == cot->ptr[j]) return GODE_E_RANGE;
+    }
+    AdjTail at = {};
+    at.a_ii = a_ii; at.at_ii = at_ii; at.bias = bias; at.k = k_out; at.dS = dS_out; at.x_out = x_out;
+    at.cot_out = p_coef ? cot_out : nullptr; at.colpart = colsum; at.alpha = alpha;
+    for (int j = 0; j < 4; ++j) { at.pcoef[j] = p_coef ? p_coef[j] : 0.f; at.c3[j] = p_coef ? cot_out_coef[j] : 0.f; }
+    return gode_pc_adjoint_tail_launch(make_lincomb(yin), make_lincomb(cot), n_rows, eps, gamma, beta, W, t, at, p_coef != nullptr,
+                                       cg, (hipStream_t)stream);
+}
+
 // aux_out == nullptr: the plain launch.  With aux_out every branch below either launches a kernel that forms it or
 // returns GODE_E_UNSUPPORTED before anything is launched; the kernel taken is the one the plain launch would take.
 extern "C" int gode_gn_time_gemm_xout_aux_f32(const gode_lincomb_t* xin, int64_t n_rows, int64_t d_in, int32_t groups,

@@ -820,6 +820,171 @@ __global__ __launch_bounds__(512, 4) void gcn_local_tail_rk4_kernel(const float*
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// One stage of the ADJOINT solve's forward recompute on ISOLATED rows (option adjoint_tail): what Gf and then Sp(g) with the
+// cotangent epilogue make of a row whose only entry in A and in A^T is its own diagonal, in one launch over the contiguous
+// tail, so that Sp(g) runs without those records and nobody stores their rows of S and dZ.  Every row of the launch is
+// isolated: no flags, no branches on them.
+//
+// The eight consumer waves alone, as in gcn_local_tail_rk4_kernel (the lane that owns output columns c0 .. c0 + 3 of a row
+// owns that GroupNorm group of the input).  Per 32-row tile the statements of the launches this replaces, on the same
+// numbers in the same order: x by the fmaf chain from 0 (x_out stores it), at the last stage P by the AUX chain,
+// gn_forward_v, split3_trunc / stage_row4, tile_product on acc = t W[0, :]; then the one-entry record of Sp(g):
+// m = fmaf(a_ii, acc, 0) rounded before the bias, z = m + b, k = max(z, 0), g by lc_load4's chain over the cotangent terms
+// (at the last stage lc_load4_pair's second chain beside it), masked by z > 0, dS = fmaf(at_ii, g, 0), and at the last
+// stage y_new = fmaf(alpha, k, fmaf(1, P, 0)).  Hence the same bits in k / y_new, dS, x_out and the third output.
+//
+// Loads are unconditional, from clamped rows, and a tile ahead of their use: the cotangent terms and the two diagonals of a
+// tile are requested before its matrix phase and used after it, the y-terms of the block's next tile before the matrix
+// phase of this one.  Two piece images alternate, one LDS barrier per tile (gcn_local_tail_rk4_kernel's protocol).
+// Column sums of the UNSCALED g: one row per 8 consecutive rows of the launch, g_0 + g_1 + .. + g_7 added in that order
+// from g_0 - what a block of spmm_vec4_kernel<32> (8 records) leaves in its row of Y2_colsum when those rows are 8
+// consecutive one-entry records of its list (block_colsum_store).  The driver starts the launch on a block boundary of
+// A's record list, so ws->y2_colsum holds the rows Sp(g) on the whole list would have left, bit for bit, and the bias
+// gradient keeps its bits.  The 8 lanes that hold a group's rows are neighbours in a row of 16 lanes (r = 8 q .. 8 q + 7):
+// the first reads the other seven by DPP row shifts and stores; a fixed order, no atomics.
+// ---------------------------------------------------------------------------------------------------------------
+// acc += the value lane + J of the same row of 16 lanes holds (DPP row_shl: no LDS traffic; past the row: 0)
+template <int J>
+__device__ __forceinline__ void row_shl_add(float4& acc, const float4 v) {
+    auto get = [](float x) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x100 + J, 0xf, 0xf, true)); };
+    acc.x += get(v.x); acc.y += get(v.y); acc.z += get(v.z); acc.w += get(v.w);
+}
+
+template <int CG, int NX, bool LAST>   // CG 0 / 4; NX terms of y and of the cotangent (1..4); LAST: the closed step (NX = 4)
+__global__ __launch_bounds__(512, NX == 1 ? 4 : 2) void gcn_adjoint_tail_kernel(LinComb yin, LinComb cot, int n_rows, float eps,
+                                                                                const float* __restrict__ gamma,
+                                                                                const float* __restrict__ beta,
+                                                                                const float* __restrict__ W, float t, AdjTail at)
+{
+    static_assert(LAST == (NX == 4), "four terms: the closed step, and only it");
+    constexpr int R = 32, PIECE_B = Img<R>::PIECE_B, BUF_B = Img<R>::BUF_B;
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    char* lds = reinterpret_cast<char*>(smem);
+    const int wave = threadIdx.x >> 6, l = threadIdx.x & 63, r = l & 15, g = l >> 4;
+    const int n0 = 16 * wave, c0 = n0 + 4 * g;
+    bf16x8 A[4][3];
+    load_weight_pieces(A, [&](int m, int k) { return W[(int64_t)(k + 1) * D + n0 + m]; });          // W1^T slab
+    // W[0, :], bias, gamma, beta in LDS behind the images, read where used (none is live across the matrix phase)
+    float* cst = reinterpret_cast<float*>(lds + 2 * BUF_B);
+    if (threadIdx.x < D) {
+        cst[threadIdx.x] = W[threadIdx.x];
+        cst[D + threadIdx.x] = at.bias[threadIdx.x];
+        cst[2 * D + threadIdx.x] = gamma ? gamma[threadIdx.x] : 1.f;
+        cst[3 * D + threadIdx.x] = beta ? beta[threadIdx.x] : 0.f;
+    }
+    __syncthreads();
+    const int rd_off = r * LDK * 2 + g * 16;
+    const int wr_off = r * LDK * 2 + c0 * 2;
+    const int n_tiles = (n_rows + R - 1) / R;
+    float4 yv[NX][2];
+    auto load_y = [&](int tile) {
+#pragma unroll
+        for (int rt = 0; rt < 2; ++rt) {
+            const int64_t off = (int64_t)min(tile * R + r + 16 * rt, n_rows - 1) * D + c0;
+#pragma unroll
+            for (int j = 0; j < NX; ++j) yv[j][rt] = ld4(yin.ptr[j] + off);
+        }
+    };
+    load_y(min((int)blockIdx.x, n_tiles - 1));
+    int k = 0;
+    for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x, ++k) {
+        char* img = lds + (k & 1) * BUF_B;
+        float4 P[2];
+        int rc[2];                                        // the lane's rows, clamped: loads are unconditional
+        bool valid[2];
+        auto off = [&](int rt) { return (int64_t)rc[rt] * D + c0; };
+        {
+            const float4 gmv = ld4(cst + 2 * D + c0), btv = ld4(cst + 3 * D + c0);
+#pragma unroll
+            for (int rt = 0; rt < 2; ++rt) {
+                const int row = tile * R + r + 16 * rt;
+                valid[rt] = row < n_rows;
+                rc[rt] = valid[rt] ? row : n_rows - 1;
+                float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+                for (int j = 0; j < NX; ++j) {            // the term order and arithmetic of lc_load4_n
+                    const float c = yin.coef[j];
+                    x.x = fmaf(c, yv[j][rt].x, x.x); x.y = fmaf(c, yv[j][rt].y, x.y);
+                    x.z = fmaf(c, yv[j][rt].z, x.z); x.w = fmaf(c, yv[j][rt].w, x.w);
+                }
+                if (at.x_out && valid[rt]) *reinterpret_cast<float4*>(at.x_out + off(rt)) = x;
+                if constexpr (LAST) {                     // the closing combination P (the AUX chain)
+                    float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+                    for (int j = 0; j < NX; ++j) {
+                        const float c = at.pcoef[j];
+                        a.x = fmaf(c, yv[j][rt].x, a.x); a.y = fmaf(c, yv[j][rt].y, a.y);
+                        a.z = fmaf(c, yv[j][rt].z, a.z); a.w = fmaf(c, yv[j][rt].w, a.w);
+                    }
+                    P[rt] = a;
+                }
+                float4 xn = gn_forward_v<CG>(x, eps, gmv, btv);
+                if (!valid[rt]) xn = make_float4(0.f, 0.f, 0.f, 0.f);
+                stage_row4<PIECE_B>(img + wr_off + rt * 16 * LDK * 2, xn);
+            }
+        }
+        // in flight across the matrix phase: this tile's cotangent terms and diagonals, the next tile's y-terms
+        float4 cv[NX][2];
+        float dsc[2], asc[2];
+#pragma unroll
+        for (int rt = 0; rt < 2; ++rt) {
+#pragma unroll
+            for (int j = 0; j < NX; ++j) cv[j][rt] = ld4(cot.ptr[j] + off(rt));
+            dsc[rt] = at.a_ii[rc[rt]];
+            asc[rt] = at.at_ii[rc[rt]];
+        }
+        load_y(min(tile + (int)gridDim.x, n_tiles - 1));
+        lds_barrier();
+        const float4 w0 = ld4(cst + c0);
+        const f32x4 t0 = {t * w0.x, t * w0.y, t * w0.z, t * w0.w};
+        f32x4 acc[2] = {t0, t0};
+        tile_product<R>(img + rd_off, A, acc);
+        const float4 bv = ld4(cst + D + c0);
+#pragma unroll
+        for (int rt = 0; rt < 2; ++rt) {
+            float m[4];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                m[c] = fmaf(dsc[rt], acc[rt][c], 0.f);
+                asm volatile("" : "+v"(m[c]));            // the record's sum is rounded before the bias is added
+            }
+            const float4 z = make_float4(m[0] + bv.x, m[1] + bv.y, m[2] + bv.z, m[3] + bv.w);
+            float4 kv = make_float4(fmaxf(z.x, 0.f), fmaxf(z.y, 0.f), fmaxf(z.z, 0.f), fmaxf(z.w, 0.f));
+            if constexpr (LAST)                           // epilogue_store4 with pre = {1.0, P}
+                kv = make_float4(fmaf(at.alpha, kv.x, fmaf(1.f, P[rt].x, 0.f)), fmaf(at.alpha, kv.y, fmaf(1.f, P[rt].y, 0.f)),
+                                 fmaf(at.alpha, kv.z, fmaf(1.f, P[rt].z, 0.f)), fmaf(at.alpha, kv.w, fmaf(1.f, P[rt].w, 0.f)));
+            float4 gv = make_float4(0.f, 0.f, 0.f, 0.f), g3 = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+            for (int j = 0; j < NX; ++j) {                // lc_load4_n / lc_load4_pair_n on the values loaded above
+                const float c = cot.coef[j];
+                gv.x = fmaf(c, cv[j][rt].x, gv.x); gv.y = fmaf(c, cv[j][rt].y, gv.y);
+                gv.z = fmaf(c, cv[j][rt].z, gv.z); gv.w = fmaf(c, cv[j][rt].w, gv.w);
+                if constexpr (LAST) {
+                    const float c2 = at.c3[j];
+                    g3.x = fmaf(c2, cv[j][rt].x, g3.x); g3.y = fmaf(c2, cv[j][rt].y, g3.y);
+                    g3.z = fmaf(c2, cv[j][rt].z, g3.z); g3.w = fmaf(c2, cv[j][rt].w, g3.w);
+                }
+            }
+            gv.x = z.x > 0.f ? gv.x : 0.f; gv.y = z.y > 0.f ? gv.y : 0.f;
+            gv.z = z.z > 0.f ? gv.z : 0.f; gv.w = z.w > 0.f ? gv.w : 0.f;
+            if (valid[rt]) {
+                *reinterpret_cast<float4*>(at.k + off(rt)) = kv;
+                *reinterpret_cast<float4*>(at.dS + off(rt)) =
+                    make_float4(fmaf(asc[rt], gv.x, 0.f), fmaf(asc[rt], gv.y, 0.f), fmaf(asc[rt], gv.z, 0.f), fmaf(asc[rt], gv.w, 0.f));
+                if constexpr (LAST) *reinterpret_cast<float4*>(at.cot_out + off(rt)) = g3;
+            }
+            // the column-sum row of this row's group of 8 (rows past the end add 0.0, as the SpMM's idle lane groups do)
+            if (!valid[rt]) gv = make_float4(0.f, 0.f, 0.f, 0.f);
+            float4 gs = gv;                                           // lane r: g[r] + g[r + 1] + .. + g[r + 7], used where r % 8 == 0
+            row_shl_add<1>(gs, gv); row_shl_add<2>(gs, gv); row_shl_add<3>(gs, gv); row_shl_add<4>(gs, gv);
+            row_shl_add<5>(gs, gv); row_shl_add<6>(gs, gv); row_shl_add<7>(gs, gv);
+            const int grow = tile * R + 16 * rt + (r & 8);            // first row of the group
+            if ((r & 7) == 0 && grow < n_rows) *reinterpret_cast<float4*>(at.colpart + (int64_t)(grow >> 3) * D + c0) = gs;
+        }
+    }
+}
+
 int64_t pc_blocks(int64_t n_rows, int R) {
     int64_t b = (n_rows + R - 1) / R;
     if (b < 1) b = 1;
@@ -987,5 +1152,40 @@ int gode_pc_local_tail_launch(const float* y_in, float* y_out, int64_t n_rows, c
       GODE_LAUNCH_CHECK(); return 0; }
     if (cg == 0) GODE_LT(0) else if (cg == 4) GODE_LT(4)
 #undef GODE_LT
+    return GODE_E_UNSUPPORTED;
+}
+
+// one stage of the adjoint's forward recompute on n_rows isolated rows (gcn_adjoint_tail_kernel).  The grid: as many blocks
+// as stay resident (two per CU with one term, one from two on: 128 registers do not hold two terms of y a tile ahead beside
+// two of the cotangent without scratch), never more than tiles.  The column sums take one row per 8 rows of the launch.
+int64_t gode_pc_adjoint_tail_blocks(int64_t n_rows, int terms)
+{
+    if (n_rows <= 0 || terms < 1 || terms > 4) return 0;
+    const int64_t tiles = (n_rows + 31) / 32, nb = terms == 1 ? 2 * kBlocks : kBlocks;
+    return nb < tiles ? nb : tiles;
+}
+int64_t gode_pc_adjoint_tail_colsum_rows(int64_t n_rows) { return n_rows > 0 ? (n_rows + 7) / 8 : 0; }
+
+int gode_pc_adjoint_tail_launch(const LinComb& yin, const LinComb& cot, int64_t n_rows, float eps, const float* gamma,
+                                const float* beta, const float* W, float t, const AdjTail& at, bool last, int cg, hipStream_t s)
+{
+    if (n_rows <= 0 || n_rows > INT32_MAX || yin.n < 1 || yin.n > 4 || cot.n != yin.n || last != (yin.n == 4)) return GODE_E_UNSUPPORTED;
+    if (!W || !at.a_ii || !at.at_ii || !at.bias || !at.k || !at.dS || !at.colpart || (last && !at.cot_out)) return GODE_E_UNSUPPORTED;
+    const int64_t nb = gode_pc_adjoint_tail_blocks(n_rows, yin.n);
+    const size_t lds = 2 * (size_t)Img<32>::BUF_B + 4 * D * sizeof(float);      // two images | W[0, :], bias, gamma, beta
+    int rc = 0;
+#define GODE_AT(CGV, NXV, LV)                                                                                      \
+    { rc = set_lds_pc(gcn_adjoint_tail_kernel<CGV, NXV, LV>, lds); if (rc) return rc;                               \
+      const int slot = gode_prof_begin(s, D, n_rows, 2 * (int64_t)yin.n - 1 + (at.x_out ? 1 : 0) + (LV ? 1 : 0),    \
+                                       GODE_PROF_ADJOINT_TAIL | GODE_PROF_FORM_PC);                                 \
+      hipLaunchKernelGGL((gcn_adjoint_tail_kernel<CGV, NXV, LV>), dim3((unsigned)nb), dim3(512), lds, s,            \
+                         yin, cot, (int)n_rows, eps, gamma, beta, W, t, at);                                       \
+      gode_prof_end(s, slot);                                                                                      \
+      GODE_LAUNCH_CHECK(); return 0; }
+#define GODE_ATN(CGV) { if (last) GODE_AT(CGV, 4, true) else if (yin.n == 1) GODE_AT(CGV, 1, false) else if (yin.n == 2) GODE_AT(CGV, 2, false) \
+                        else if (yin.n == 3) GODE_AT(CGV, 3, false) }
+    if (cg == 0) GODE_ATN(0) else if (cg == 4) GODE_ATN(4)
+#undef GODE_ATN
+#undef GODE_AT
     return GODE_E_UNSUPPORTED;
 }

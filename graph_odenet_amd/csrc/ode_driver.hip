@@ -431,15 +431,81 @@ extern "C" int gode_gcn_ode_rk4_adjoint(const gode_gcn_odefunc_t* f, float* y, f
     // gradient must come from Sp(g)'s per-block column sums: those rows of dZ itself are not written.
     const bool at_core = bw && y2rows > 0 && gode_opt_diag_rows() && f->at_core_items && f->at_diag && f->AT.items &&
                          f->at_n_core > 0 && f->at_n_core <= f->AT.n_items;
+    // Isolated tail rows (option adjoint_tail; with at_core): rows [n - n_tail, n) gather nothing, so what Gf(g) and Sp(g)
+    // make of them - k_y (or the closed step), a_ii dZ[i] into dS, x_out, the closing combination of the cotangent - is
+    // row-local work on a number Gf(g) held in registers.  Gf(g) runs on the rows before the tail, one dense launch of
+    // their own (gemm_pc.hip: gcn_adjoint_tail_kernel, the statements of the pair on the same numbers: same bits)
+    // recomputes the stage on the tail, and Sp(g) runs on A's record list without the tail's records (launched with the
+    // whole list's count: the same kernels).  The S and dZ rows of the tail are never stored.  The tail's records are the
+    // last of A's list, in row order (gode_gcn_odefunc_t: a_head_items), and the launch starts on a block boundary of that
+    // list - the up to 7 tail rows whose records fill the head's last block of 8 stay with Gf and Sp(g) - and leaves, per 8
+    // rows, the column-sum row Sp(g)'s block would have left in ws->y2_colsum: close_bias reduces the same rows holding the
+    // same numbers, so the bias gradient keeps its bits, like everything else.  A last stage goes this way only on the
+    // closing-combination-once route (its P is formed inside the launch); otherwise it keeps the full list.
+    const int tail_cg = f->groups == 0 ? 0 : (f->groups > 0 && d % f->groups == 0 && d / f->groups == 4) ? 4 : -1;
+    const int64_t kRec = 8;                                                   // records per block of the d = 128 SpMM
+    const int64_t head_items = f->a_head_items ? (f->a_n_head + kRec - 1) / kRec * kRec : 0;
+    const int64_t n_tail = f->A.n_items - head_items;                         // rows of the tail launch
+    const int64_t n_head = n - n_tail;
+    const int64_t head_rows = head_items / kRec;
+    bool a_tail = at_core && gode_opt_adjoint_tail() && gode_opt_fwd_pc() == 3 && d == 128 && tail_cg >= 0 && f->n_tail > 0 &&
+                  f->a_head_items && f->a_head_items == f->A.items && f->a_diag && f->W && f->b && f->a_n_head > 0 &&
+                  f->a_n_head == f->A.n_items - f->n_tail && n_tail > 0 && n_head > kMergedFinishMaxRows &&
+                  head_items > 65536 && head_rows + gode_pc_adjoint_tail_colsum_rows(n_tail) <= y2rows;
+    if (a_tail) {
+        uintptr_t bits = (uintptr_t)y | (uintptr_t)a | (uintptr_t)ws->dS | (uintptr_t)ws->y2_colsum | (uintptr_t)f->W |
+                         (uintptr_t)f->b | (uintptr_t)f->gamma | (uintptr_t)f->beta | (uintptr_t)ws->X[0] | (uintptr_t)ws->X[1];
+        for (int j = 0; j < 4; ++j) bits |= (uintptr_t)ws->ky[j] | (uintptr_t)ws->ka[j];
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        a_tail = !(bits & 15) && hipStreamIsCapturing(hs, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone;
+    }
+    int full_g = -1;            // a last stage whose Gf could not form P (below): that stage keeps the full list
+    auto tail_stage = [&](int g) { return a_tail && (g % 4 != 3 || close_once) && g != full_g; };
+    gode_gcn_odefunc_t fhead = *f;
+    fhead.n = n_head;
     // Gf(g) from the y-chain as it stands (stage g's step must be the current one: Sp of a last stage swaps the chain)
     auto gf = [&](int g, void* st) -> int {
         const gode_lincomb_t yin = stage_terms(ycur, ky, g % 4, h);
-        if (g % 4 == 3 && close_once)
-            return gf_last_stage(f, yin, combine_terms(ycur, ky, h), stage_time(g), Sbuf[g & 1], x_out_of(g), ky[3], &py_formed, st);
-        return gode_gn_time_gemm_xout_f32(&yin, n, d, f->groups, f->eps, f->gamma, f->beta, f->W, d, 1, stage_time(g),
+        const bool tl = tail_stage(g);
+        if (g % 4 == 3 && close_once) {
+            GODE_TRY(gf_last_stage(tl ? &fhead : f, yin, combine_terms(ycur, ky, h), stage_time(g), Sbuf[g & 1], x_out_of(g), ky[3],
+                                   &py_formed, st));
+            if (tl && !py_formed) {         // the tail launch forms P itself, so Sp(3) would have to read {1.0, P}: the kernel
+                full_g = g;                 // the options select cannot form it - this stage goes the parent's way, on every row
+                return gode_gn_time_gemm_xout_f32(&yin, n, d, f->groups, f->eps, f->gamma, f->beta, f->W, d, 1, stage_time(g),
+                                                  Sbuf[g & 1], x_out_of(g), st);
+            }
+            return 0;
+        }
+        return gode_gn_time_gemm_xout_f32(&yin, tl ? n_head : n, d, f->groups, f->eps, f->gamma, f->beta, f->W, d, 1, stage_time(g),
                                           Sbuf[g & 1], x_out_of(g), st);
     };
+    // the tail launch of stage g, from both chains as they stand, on the caller's stream: issued once the side chain of
+    // stage g - 1 is joined (it reads ws->y2_colsum), behind the dense launch of stage g - 1 (the last reader of dS and the
+    // writer of ka[(g - 1) % 4]) and ahead of Sp(g)
+    auto gf_tail = [&](int g) -> int {
+        if (!tail_stage(g)) return 0;
+        const int s = g % 4;
+        const int64_t off = n_head * d;
+        gode_lincomb_t yin = stage_terms(ycur, ky, s, h), cot = negated(stage_terms(acur, ka, s, h));
+        if (yin.n != cot.n || yin.n != s + 1) return GODE_E_UNSUPPORTED;
+        for (int j = 0; j < yin.n; ++j) { yin.ptr[j] += off; cot.ptr[j] += off; }
+        AdjTail at = {};
+        at.a_ii = f->a_diag + n_head; at.at_ii = f->at_diag + n_head; at.bias = f->b;
+        at.k = ky[s] + off; at.dS = ws->dS + off; at.x_out = x_out_of(g) ? x_out_of(g) + off : nullptr;
+        at.colpart = ws->y2_colsum + head_rows * d;
+        if (s == 3) {
+            const gode_lincomb_t ypre = combine_terms(ycur, ky, h), apre = combine_terms(acur, ka, h);
+            if (ypre.n != 4 || apre.n != 4) return GODE_E_UNSUPPORTED;
+            for (int j = 0; j < 4; ++j) { at.pcoef[j] = ypre.coef[j]; at.c3[j] = apre.coef[j]; }
+            at.alpha = (float)(h * B38[3]);
+            at.cot_out = ka[3] + off;
+        }
+        return gode_pc_adjoint_tail_launch(make_lincomb(&yin), make_lincomb(&cot), n_tail, f->eps, f->gamma, f->beta, f->W,
+                                           stage_time(g), at, s == 3, tail_cg, hs);
+    };
     GODE_TRY(gf(0, stream));
+    GODE_TRY(gf_tail(0));
     bool wg_pending = false;
     for (int g = 0; g < total; ++g) {
         const int s = g % 4;
@@ -472,6 +538,12 @@ extern "C" int gode_gcn_ode_rk4_adjoint(const gode_gcn_odefunc_t* f, float* y, f
             ep.Y2_scaled = ws->dS;
         }
         if (two && g > 0) GODE_HIP(hipStreamWaitEvent(hs, ov->gf, 0));          // S of this stage was produced on the side stream
+        const bool tl = tail_stage(g);
+        if (tl) {                                                               // Sp(g) without the tail's records
+            ep.n_items_full = f->A.n_items;                                     // same kernels, same name in the profile
+            GODE_TRY(gode_spmm_csr_f32(f->A.rowptr, f->A.col, f->A.val, f->A.items, head_items, f->A.long_rows, f->A.n_long,
+                                       f->A.partial, Sbuf[g & 1], d, ky[s], d, f->A.n_rows, d, &ep, stream));
+        } else
         GODE_TRY(spmm(f->A, Sbuf[g & 1], ky[s], d, &ep, stream));               // Sp(g): k_y (or new y) and dZ
         if (s == 3) { float* tmp = ycur; ycur = ky[3]; ky[3] = tmp; }           // the y-chain as Gf(g+1) will see it
         if (two && wg_pending) GODE_HIP(hipStreamWaitEvent(hs, ov->wg, 0));     // previous Wg still reads dS
@@ -539,6 +611,7 @@ extern "C" int gode_gcn_ode_rk4_adjoint(const gode_gcn_odefunc_t* f, float* y, f
             GODE_TRY(gode_lincomb_f32(theta, &tc, gode_gcn_ode_theta_len(d), stream));
             float* tmp = acur; acur = ka[3]; ka[3] = tmp;
         }
+        if (g + 1 < total) GODE_TRY(gf_tail(g + 1));      // both chains are stage g + 1's now, and the side chain is joined
     }
     if (two) {                      // join: nothing of this call is left running on the side stream
         GODE_HIP(hipEventRecord(ov->gf, ov->side));

@@ -532,7 +532,9 @@ int launch_vec4(const int* rowptr, const int* col, const float* val, const int4*
     if (n_long > 0) {
         const int64_t b2 = ((int64_t)n_long * LPR + 255) / 256;
         Epilogue ep2 = ep;
-        ep2.colpart_row0 = blocks;                             // its partial rows follow the main launch's
+        // its partial rows follow the main launch's - the WHOLE list's, so that a sub-list (whose caller fills the rows
+        // between) leaves them where the whole list does
+        ep2.colpart_row0 = ((int64_t)full_items * LPR + 255) / 256;
         hipLaunchKernelGGL((spmm_finish_vec4_kernel<LPR, OUT3>), dim3((unsigned)b2), dim3(256), 0, s,
                            long_rows, n_long, partial, Y, ldy, ep2);
         GODE_LAUNCH_CHECK();

@@ -153,6 +153,9 @@ def _func_struct(spec):
         a = spec.graph.__dict__["_a_core"]
         fs.a_core_items, fs.a_n_core, fs.a_diag = a.items.data_ptr(), a.n_items, a.diag.data_ptr()
         fs.n_tail = spec.graph.__dict__.get("_n_tail", 0)       # rows [n - n_tail, n): all isolated (local_tail_rows)
+        head = spec.graph.__dict__.get("_a_head")               # A's records without the tail rows (adjoint_tail)
+        if head is not None:
+            fs.a_head_items, fs.a_n_head = head.data_ptr(), head.shape[0]
     return fs
 
 
@@ -235,6 +238,22 @@ def local_tail_rows(g):
     return n_tail if CORE_LIST_MIN_SHARE_INV * n_tail >= g.n_rows else 0
 
 
+def head_items(g, n_tail):
+    """A's record list without the records of the rows [n - n_tail, n) (gode_gcn_odefunc_t: a_head_items): the list Sp(g) of
+    the adjoint solve walks when the tail rows are recomputed in a dense launch of their own (csrc/ode_driver.hip, option
+    adjoint_tail).  None when there is no tail, no more than CORE_LIST_MIN_ROWS rows before it (the driver's large route
+    starts above that), or when the tail's records are not the last n_tail of the list in row order (a graph with empty
+    rows: their records sort behind the one-entry ones) - the driver wants the head to be a prefix of the list, so that the
+    tail launch can leave the per-block column sums the whole list would have.  Exact integer comparisons."""
+    if n_tail <= 0 or g.n_rows - n_tail <= CORE_LIST_MIN_ROWS or g.items is None:
+        return None
+    n_head = g.n_items - n_tail                                       # every tail row is isolated, hence one record
+    want = torch.arange(g.n_rows - n_tail, g.n_rows, dtype=g.items.dtype, device=g.items.device)
+    if n_head <= 0 or not torch.equal(g.items[n_head:, 0], want):
+        return None
+    return g.items[:n_head]
+
+
 def _hand_core_list(g, info):
     """Decide (from counts alone) whether the ODE block gets the core lists of A and A^T; if so build them on `g`."""
     if getattr(g, "items", None) is None or g.n_rows <= CORE_LIST_MIN_ROWS or g.transpose().items is None:
@@ -249,8 +268,10 @@ def _hand_core_list(g, info):
         g.__dict__["_a_core"] = g.diag_rows() if take else None      # A's list for the forward solve: every diagonal-only row of A
         g.__dict__["_isolated_count"] = iso.n_flagged
         g.__dict__["_n_tail"] = local_tail_rows(g) if take else 0
+        g.__dict__["_a_head"] = head_items(g, g.__dict__["_n_tail"])
+    head = g.__dict__["_a_head"]
     info.update(isolated_rows=g.__dict__["_isolated_count"], core_lists=g.__dict__["_at_core"] is not None,
-                n_tail=g.__dict__["_n_tail"])
+                n_tail=g.__dict__["_n_tail"], head_records=0 if head is None else int(head.shape[0]))
 
 
 def tuned_graph(graph, d, node_order="auto"):

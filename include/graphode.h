@@ -83,9 +83,12 @@ int         gode_abi_version(void);
  * rows at the end of the state, see gode_gcn_odefunc_t, in one launch of their own - on a side stream beside the solve
  * when "overlap" is on and the stream is not capturing - and runs its dense launches on the rows before them; same bits
  * either way), "local_tail_blocks" (0 default: 128 blocks of 512 threads beside the solve, 512 on
- * the caller's stream; 1..4096: that many blocks; two fit a CU).
+ * the caller's stream; 1..4096: that many blocks; two fit a CU), "adjoint_tail" (1 default / 0: under "diag_rows" and
+ * "rk_close_once" with "fwd_pc" 3, the one-pass branch of gode_gcn_ode_rk4_adjoint recomputes a stage of the n_tail
+ * isolated rows in one dense launch of their own, gode_gcn_adjoint_tail_stage_f32, and runs Sp(g) on A's record list
+ * without them, see gode_gcn_odefunc_t; same bits either way).
  * Initial values come from GODE_GEMM_SPLIT / GODE_OVERLAP / GODE_WGRAD_SPLIT / GODE_BWD_PC / GODE_FWD_PC / GODE_SPMM_PIPE /
- * GODE_DIAG_ROWS / GODE_DIAG_LAST / GODE_LOCAL_TAIL / GODE_LOCAL_TAIL_BLOCKS.
+ * GODE_DIAG_ROWS / GODE_DIAG_LAST / GODE_LOCAL_TAIL / GODE_LOCAL_TAIL_BLOCKS / GODE_ADJOINT_TAIL.
  * Returns 0 or GODE_E_UNSUPPORTED. */
 int         gode_set_option(const char* name, int value);
 int         gode_get_option(const char* name);
@@ -243,6 +246,30 @@ int gode_gn_time_gemm_diag_aux_f32(const gode_lincomb_t* xin /* host */, int64_t
                                    float* S, const float* aux_coef /* host */, float* K, float alpha,
                                    const float* diag, const float* skip, const float* bias,
                                    int32_t* taken /* host */, void* stream);
+
+/* One stage of the adjoint solve's forward recompute on n_rows ISOLATED rows - rows whose only stored entry in A and in A^T
+ * is their own non-zero diagonal - in one launch (d = 128, time row in W, 0 or 4 channels per GroupNorm group, 16-byte
+ * aligned operands; otherwise GODE_E_UNSUPPORTED and nothing launched).  Per row, bit for bit what
+ * gode_gn_time_gemm_xout_f32 (last stage: gode_gn_time_gemm_xout_aux_f32) followed by gode_spmm_csr_f32 with bias, relu,
+ * the cotangent outputs and Y2_scale makes of a one-entry record:
+ *   x = sum yin;  S = [t | GroupNorm(x)] W;  z = fmaf(a_ii, S, 0) + bias;  k = max(z, 0);  g = (sum cot) * (z > 0)
+ *   k_out = k                                         (p_coef == NULL)
+ *   k_out = fmaf(alpha, k, fmaf(1, P, 0)), P = sum_j p_coef[j]*yin.ptr[j];  cot_out = sum_j cot_out_coef[j]*cot.ptr[j]
+ *                                                     (p_coef != NULL: the closed step; four terms)
+ *   dS_out = fmaf(at_ii, g, 0);  x_out = x (nullable)
+ * yin and cot (host) have the same count of 1-4 terms; a_ii, at_ii: n_rows floats; every array n_rows x 128 contiguous,
+ * outputs distinct from the terms and from each other.  S and the unscaled g are not stored; colsum receives
+ * gode_gcn_adjoint_tail_colsum_rows(n_rows) = ceil(n_rows / 8) rows of 128 floats, row q = g[8q] + g[8q + 1] + .. + g[8q + 7]
+ * added in that order (rows past the end add 0.0): what a block of gode_spmm_csr_f32 leaves in Y2_colsum for 8 consecutive
+ * one-entry records at d = 128. */
+int64_t gode_gcn_adjoint_tail_colsum_rows(int64_t n_rows);
+int gode_gcn_adjoint_tail_stage_f32(const gode_lincomb_t* yin /* host */, const gode_lincomb_t* cot /* host */, int64_t n_rows,
+                                    int64_t d, int32_t groups, float eps, const float* gamma, const float* beta,
+                                    const float* W, float t, const float* a_ii, const float* at_ii, const float* bias,
+                                    float* k_out, float* dS_out, float* x_out /* nullable */,
+                                    const float* p_coef /* host, nullable */, float alpha,
+                                    const float* cot_out_coef /* host, with p_coef */, float* cot_out /* with p_coef */,
+                                    float* colsum, void* stream);
 
 /* Two square products (d_out = d_in = d) over the same input in one launch: Sa = [t | xn] Wa, Sb = [t | xn] Wb
  * (the two message projections of the GAT ODE function); x_out as above. */
@@ -659,6 +686,16 @@ typedef struct gode_gcn_odefunc {
      * in use, d = 128, 4 channels per GroupNorm group or no GroupNorm) integrates them over the whole solve in one launch
      * of their own and runs every dense launch of the solve on the first n - n_tail rows; same bits. */
     int64_t n_tail;
+    /* nullable (with n_tail > 0 and the lists above).  a_head_items = A.items without the records of the rows
+     * [n - n_tail, n) (a_n_head = A.n_items - n_tail records; every tail row is one record).  Only where those records are
+     * the LAST n_tail of A.items, in row order - so that the head is the first a_n_head records of A.items, and a_head_items
+     * must be A.items itself (any other pointer: the launches as they were); the list builder of graph.py (longest first,
+     * stable) gives that order whenever no row is empty.  The one-pass branch of
+     * gode_gcn_ode_rk4_adjoint (option "adjoint_tail") then recomputes a stage of the tail rows in one dense launch
+     * (gode_gcn_adjoint_tail_stage_f32) and runs Sp(g) on that prefix of A.items, rounded up to whole blocks of 8 records (the
+     * up to 7 tail rows whose records fill the last block stay with Gf and Sp(g)); the S and dZ rows of the other tail rows
+     * are not stored, and ws->y2_colsum receives the rows the whole list would have left there, bit for bit. */
+    const int32_t* a_head_items; int64_t a_n_head;
 } gode_gcn_odefunc_t;
 
 typedef struct gode_rk4_workspace {
@@ -1237,6 +1274,8 @@ int gode_edge_ode_step_close_f32(int32_t n_stages, const float* const* wpart /* 
 #define GODE_PROF_GAT_STEP_CLOSE 11    /* gode_gat_small_close_stages_f32: one pass per swept step of a backprop sweep */
 #define GODE_PROF_LOCAL_TAIL 12        /* gode_gcn_ode_rk4_forward, option "local_tail": the whole forward solve of the isolated
                                           tail rows (rows = n_tail), up to 16 steps x 4 products of n_tail x d x d per launch */
+#define GODE_PROF_ADJOINT_TAIL 13      /* gode_gcn_ode_rk4_adjoint, option "adjoint_tail": one stage of the forward recompute on the
+                                          isolated tail rows (rows = the rows of the launch) */
 /* which kernel of the family ran, OR-ed into the kind of a dense launch (kind & 0xff = family, kind >> 8 = form):
  * exact-fp32 MFMA kernel; bf16-piece kernel, every wave loading + cutting + multiplying; bf16-piece kernel in
  * producer / consumer form (wgrad_split_kernel, gemm_pc.hip) */

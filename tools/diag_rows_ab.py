@@ -9,7 +9,8 @@ no row stored by the dense launch or by the launch that forms dZ in their place)
 least three times the spread among readings of the same setting (--min-ratio; diag_last was held to five times).
 diag_last 0 likewise issues the launches of the code before that option: the last stage of every forward rk4 step on A's
 full list.  local_tail 0 (under diag_rows 1 and diag_last 1): every row through every dense launch of the forward solve, no
-tail launch; --set holds further options fixed over all readings (local_tail_blocks, overlap).
+tail launch; adjoint_tail 0 (under diag_rows 1): every row through Gf and Sp(g) of the adjoint solve's forward recompute, no
+tail launch there; --set holds further options fixed over all readings (local_tail_blocks, overlap).
 
     python tools/diag_rows_ab.py [--option diag_rows] [--scale 20] [--edges 10000000] [--ode-steps 16] [--steps 3] [--warmup 1]
 """
@@ -35,7 +36,7 @@ def main():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--order", default="1,0,1,0,1", help="settings of the option, one reading each")
-    ap.add_argument("--option", default="diag_rows", choices=["diag_rows", "diag_last", "local_tail"])
+    ap.add_argument("--option", default="diag_rows", choices=["diag_rows", "diag_last", "local_tail", "adjoint_tail"])
     ap.add_argument("--set", action="append", default=[], metavar="NAME=VALUE",
                     help="another option held fixed over all readings (e.g. local_tail_blocks=128, overlap=0)")
     ap.add_argument("--min-ratio", type=float, default=3.0, help="mean gap over same-setting spread that counts as a gain")
