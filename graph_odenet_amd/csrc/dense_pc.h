@@ -29,7 +29,7 @@ int gode_pc_bwd_wgrad_launch(const LinComb& lc, int64_t n_rows, float eps, const
 // The forward rk4 (3/8 rule) solve of rows that are isolated in A and A^T, in one launch (gemm_pc.hip:
 // gcn_local_tail_rk4_kernel): row i of y_out = st.n_steps steps of x' = relu(a_ii[i] [t | GN(x)] W + bias) from row i of
 // y_in, with the bits the dense DIAG launches of ode_driver.hip give that row.  coef[s]: the s + 1 coefficients of
-// stage_terms(s); acoef: those of combine_terms; alpha = h b_3; ts[i][s]: the stage times, rounded from double by the host.
+// tab_stage_terms(TAB38, .., s, h); acoef: those of tab_combine_terms(TAB38, ..); alpha = h b_3; ts[i][s]: the stage times, rounded from double by the host.
 // W has its time row; cg 0 / 4; y_out may be y_in.
 #define GODE_LOCAL_TAIL_MAX_STEPS 16
 struct LocalTailSteps { float coef[4][4]; float acoef[4]; float alpha; int n_steps; float ts[GODE_LOCAL_TAIL_MAX_STEPS][4]; };

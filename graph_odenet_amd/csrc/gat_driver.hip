@@ -1,4 +1,4 @@
-// gat_driver.hip — one Dormand-Prince 5(4) step of the GAT ODE function per C-ABI call.
+// gat_driver.hip — one adaptive step of the GAT ODE function per C-ABI call, and backprop through its solves.
 //
 // f(t, x) = relu(EdgeAttention([t | GroupNorm(x)]))  (reference: GAT/models.py:172-179 -> GAT/layers.py:95-122).
 // The layer's message activation is f->act (GODE_GAT_ACT_*; zeroed: relu): eval_forward and stage_vjp hand it to the
@@ -8,9 +8,15 @@
 // and the error-ratio sums, so that an adaptive step on a citation-size graph is one call instead of ~200.
 // The launch sequence of one evaluation is graph_odenet_amd/gat_ode.py (GatOdeField / GatOdeAdjointField), which
 // branches on the head count where this file does.
-// At the end of the file: backprop through rk4 and dopri5 solves on launch-bound graphs (gode_gat_ode_rk4_forward_save,
-// gode_gat_ode_rk4_backprop, gode_gat_ode_dopri5_step_backprop), whose stage reverse is the adjoint stage's (stage_vjp), and
-// the three step functions for any adaptive method (gode_gat_ode_adaptive_step_*: bosh3, adaptive_heun, dopri5 from its tableau).
+// After the dopri5 steps: backprop through the solve on launch-bound graphs, whose stage reverse is the adjoint stage's
+// (stage_vjp).  Each of its launch sequences is ONE body over a tableau of rk_driver.h:
+//   forward_save   gode_gat_ode_rk4_forward_save (TAB38), gode_gat_ode_fixed_forward_save (the tableau of the GODE_RK_* code)
+//   backprop       gode_gat_ode_rk4_backprop, gode_gat_ode_fixed_backprop
+//   step_backprop  gode_gat_ode_dopri5_step_backprop (ADAPTIVE[GODE_RKA_DOPRI5]), gode_gat_ode_adaptive_step_backprop
+// An entry point names its tableau and calls the body, which validates (a code outside the list: a null tableau, refused where
+// the method's entry point always refused it).  At the end of the file the forward and the adjoint step for any adaptive
+// method (gode_gat_ode_adaptive_step_*: bosh3, adaptive_heun, dopri5 from its tableau); they close a step with another launch
+// than the dopri5 steps at the top, so those stay apart.
 #include "rk_driver.h"
 #include "options.h"
 #include <cmath>
@@ -221,6 +227,21 @@ int check_common(const gode_gat_odefunc_t* f, const gode_gat_workspace_t* w, boo
     return 0;
 }
 
+// the backprop sweeps run on the one-launch route only
+int check_sweep(const gode_gat_odefunc_t* f, const gode_gat_workspace_t* w) {
+    int rc = check_common(f, w, true); if (rc) return rc;
+    if (!small_dense(f) || !w->small_part) return GODE_E_UNSUPPORTED;
+    return 0;
+}
+int check_steps(int32_t n_steps, int32_t step_begin, int32_t step_end) {
+    if (n_steps <= 0 || step_begin < 0 || step_end > n_steps || step_begin >= step_end) return GODE_E_SHAPE;
+    return 0;
+}
+// floats of one stage's slot of parameter partials
+inline int64_t part_slot(const gode_gat_odefunc_t* f) {
+    return gode_gat_small_parts(f->n, f->d) * gode_gat_small_part_len(f->d, n_heads(f));
+}
+
 }  // namespace
 
 extern "C" int64_t gode_gat_ode_theta_len(int64_t d) { return 2 * (d + 1) * d + (d + 1) * 2 + d + 1 + 2 * d; }
@@ -238,7 +259,7 @@ extern "C" int gode_gat_ode_dopri5_step_forward(const gode_gat_odefunc_t* f, con
     for (int s = 0; s < 7; ++s) if (!k[s]) return GODE_E_NULLPTR;
     const int64_t nd = f->n * f->d;
     for (int s = 1; s < 7; ++s) {
-        gode_lincomb_t yin = dp_terms(y, k, DPA[s], s, h, true);
+        gode_lincomb_t yin = tab_stage_terms(TABDP, y, k, s, h);
         GODE_TRY(eval_forward(f, w, &yin, (float)(t + DPC[s] * h), k[s], stream));
     }
     gode_lincomb_t sol = dp_terms(y, k, DPB, 7, h, true);
@@ -260,8 +281,8 @@ extern "C" int gode_gat_ode_dopri5_step_adjoint(const gode_gat_odefunc_t* f, con
     for (int s = 0; s < 7; ++s) if (!ky[s] || !ka[s] || !kat[s] || !kth[s]) return GODE_E_NULLPTR;
     const int64_t nd = f->n * f->d, P = gode_gat_ode_theta_len_heads(f->d, n_heads(f));
     for (int s = 1; s < 7; ++s) {
-        gode_lincomb_t yin = dp_terms(y, ky, DPA[s], s, h, true);
-        gode_lincomb_t ain = dp_terms(a, ka, DPA[s], s, h, true);
+        gode_lincomb_t yin = tab_stage_terms(TABDP, y, ky, s, h);
+        gode_lincomb_t ain = tab_stage_terms(TABDP, a, ka, s, h);
         GODE_TRY(eval_adjoint(f, w, yin, ain, (float)(t + DPC[s] * h), ky[s], ka[s], kat[s], kth[s], stream));
     }
     struct Part { const float* y0; float* const* k; float* y1; int64_t len; };
@@ -286,141 +307,14 @@ extern "C" int gode_gat_ode_dopri5_step_adjoint(const gode_gat_odefunc_t* f, con
 // ---------------------------------------------------------------------------------------------------------------
 namespace {
 
-int check_sweep(const gode_gat_odefunc_t* f, const gode_gat_workspace_t* w) {
-    int rc = check_common(f, w, true); if (rc) return rc;
-    if (!small_dense(f) || !w->small_part) return GODE_E_UNSUPPORTED;
-    return 0;
-}
-int check_steps(int32_t n_steps, int32_t step_begin, int32_t step_end) {
-    if (n_steps <= 0 || step_begin < 0 || step_end > n_steps || step_begin >= step_end) return GODE_E_SHAPE;
-    return 0;
-}
-inline int64_t part_slot(const gode_gat_odefunc_t* f) {
-    return gode_gat_small_parts(f->n, f->d) * gode_gat_small_part_len(f->d, n_heads(f));
-}
-
-}  // namespace
-
-extern "C" int gode_gat_ode_rk4_forward_save(const gode_gat_odefunc_t* f, const float* y0, float* y_end, float* save,
-                                             const gode_gat_workspace_t* ws, float t0, float t1, int32_t n_steps,
-                                             int32_t step_begin, int32_t step_end, void* stream)
+// Steps step_begin .. step_end - 1 of a fixed-grid solve into records of (S + 1) n x d floats, [ y_n | k_1 .. k_S ]
+// (tabp == NULL, here and below: a code outside GODE_RK_*, refused after the null checks)
+int forward_save(const Tableau* tabp, const gode_gat_odefunc_t* f, const float* y0, float* y_end, float* save,
+                 const gode_gat_workspace_t* ws, float t0, float t1, int32_t n_steps, int32_t step_begin, int32_t step_end,
+                 void* stream)
 {
     if (!f || !ws || !y0 || !y_end || !save) return GODE_E_NULLPTR;
-    int rc = check_steps(n_steps, step_begin, step_end); if (rc) return rc;
-    rc = check_sweep(f, ws); if (rc) return rc;
-    const int64_t nd = f->n * f->d;
-    const double h = ((double)t1 - (double)t0) / n_steps;
-    if (y0 != save) {                                            // record 0 starts with a copy of y0
-        const gode_lincomb_t c = one_term(y0);
-        GODE_TRY(gode_lincomb_f32(save, &c, nd, stream));
-    }
-    for (int i = step_begin; i < step_end; ++i) {
-        float* rec = save + (int64_t)(i - step_begin) * 5 * nd;
-        float* k[4] = {rec + nd, rec + 2 * nd, rec + 3 * nd, rec + 4 * nd};
-        float* ynext = (i + 1 < step_end) ? rec + 5 * nd : y_end;      // the next record's y_n, or the result
-        const double t = (double)t0 + i * h;
-        for (int s = 0; s < 4; ++s) {
-            gode_lincomb_t yin = stage_terms(rec, k, s, h);
-            GODE_TRY(eval_forward(f, ws, &yin, (float)(t + C38[s] * h), k[s], stream));
-        }
-        gode_lincomb_t sol = one_term(rec);
-        for (int s = 0; s < 4; ++s) { sol.coef[sol.n] = (float)(h * B38[s]); sol.ptr[sol.n] = k[s]; ++sol.n; }
-        GODE_TRY(gode_lincomb_f32(ynext, &sol, nd, stream));
-    }
-    return 0;
-}
-
-extern "C" int gode_gat_ode_rk4_backprop(const gode_gat_odefunc_t* f, const float* save, float* a, float* theta,
-                                         float* const* ybar, float* k_scratch, float* parts, const gode_gat_workspace_t* ws,
-                                         float t0, float t1, int32_t n_steps, int32_t step_begin, int32_t step_end,
-                                         void* stream)
-{
-    if (!f || !ws || !save || !a || !theta || !ybar || !k_scratch || !parts) return GODE_E_NULLPTR;
-    for (int s = 0; s < 4; ++s) if (!ybar[s]) return GODE_E_NULLPTR;
-    int rc = check_steps(n_steps, step_begin, step_end); if (rc) return rc;
-    for (int s = 0; s < 4; ++s) {
-        if (ybar[s] == a || ybar[s] == k_scratch) return GODE_E_SHAPE;
-        for (int r = s + 1; r < 4; ++r) if (ybar[s] == ybar[r]) return GODE_E_SHAPE;
-    }
-    if (k_scratch == a) return GODE_E_SHAPE;
-    rc = check_sweep(f, ws); if (rc) return rc;
-    const int64_t n = f->n, d = f->d, nd = n * d, H = n_heads(f), slot = part_slot(f);
-    const double h = ((double)t1 - (double)t0) / n_steps;
-    for (int i = step_end - 1; i >= step_begin; --i) {
-        float* y = (float*)save + (int64_t)(i - step_begin) * 5 * nd;     // read only
-        float* k[4] = {y + nd, y + 2 * nd, y + 3 * nd, y + 4 * nd};
-        const double t = (double)t0 + i * h;
-        float ts[4];
-        for (int s = 3; s >= 0; --s) {
-            ts[s] = (float)(t + C38[s] * h);
-            const gode_lincomb_t cot = stage_cotangent(TAB38, a, (float)(h * B38[s]), ybar, s, h);
-            gode_lincomb_t yin = stage_terms(y, k, s, h);
-            GODE_TRY(stage_vjp(f, ws, &yin, cot, 1.f, ts[s], k_scratch, ybar[s], nullptr, parts + s * slot, stream));
-        }
-        GODE_TRY(gode_gat_small_close_stages_f32(parts, n, d, H, 4, ts, theta, stream));
-        const gode_lincomb_t sum = sweep_pre(TAB38, a, 1.f, ybar, 0);    // a + Ybar_1 + .. + Ybar_4
-        GODE_TRY(gode_lincomb_f32(a, &sum, nd, stream));
-    }
-    return 0;
-}
-
-extern "C" int gode_gat_ode_dopri5_step_backprop(const gode_gat_odefunc_t* f, const float* y, float* const* k, const float* g,
-                                                 const float* kbar7, double wy, const double* wk, double t, double h,
-                                                 int32_t first, float* const* ybar, float* ybar_n, float* kbar1, float* theta,
-                                                 float* k_scratch, float* parts, const gode_gat_workspace_t* ws, void* stream)
-{
-    if (!f || !ws || !y || !k || !g || !wk || !ybar || !ybar_n || !theta || !k_scratch || !parts) return GODE_E_NULLPTR;
-    if (!first && !kbar1) return GODE_E_NULLPTR;
-    for (int s = 0; s < 7; ++s) if (!k[s]) return GODE_E_NULLPTR;
-    for (int s = first ? 0 : 1; s < 7; ++s) if (!ybar[s]) return GODE_E_NULLPTR;
-    if (ybar_n == g || ybar_n == kbar7 || ybar_n == k_scratch || k_scratch == g || k_scratch == kbar7) return GODE_E_SHAPE;
-    if (!first && (kbar1 == g || kbar1 == kbar7 || kbar1 == ybar_n || kbar1 == k_scratch)) return GODE_E_SHAPE;
-    for (int s = first ? 0 : 1; s < 7; ++s) {
-        if (ybar[s] == g || ybar[s] == kbar7 || ybar[s] == ybar_n || (!first && ybar[s] == kbar1) || ybar[s] == k_scratch)
-            return GODE_E_SHAPE;
-        for (int r = s + 1; r < 7; ++r) if (ybar[s] == ybar[r]) return GODE_E_SHAPE;
-    }
-    int rc = check_sweep(f, ws); if (rc) return rc;
-    const int64_t n = f->n, d = f->d, nd = n * d, H = n_heads(f), slot = part_slot(f);
-    const int last = first ? 0 : 1;                // the last stage the sweep pushes through f
-    bool dead[7] = {};
-    float ts[7];
-    int live = 0;
-    auto cotangent = [&](int s) {
-        gode_lincomb_t c = stage_cotangent(TABDP, g, (float)wk[s], ybar, s, h, dead);
-        if (s == 6 && kbar7) { c.coef[c.n] = 1.f; c.ptr[c.n] = kbar7; ++c.n; }
-        return c;
-    };
-    for (int s = 6; s >= last; --s) {
-        const gode_lincomb_t cot = cotangent(s);
-        if (cot.n == 0) { dead[s] = true; continue; }
-        ts[live] = (float)(t + DPC[s] * h);
-        gode_lincomb_t yin = dp_terms(y, k, DPA[s], s, h, true);
-        GODE_TRY(stage_vjp(f, ws, &yin, cot, 1.f, ts[live], k_scratch, ybar[s], nullptr, parts + live * slot, stream));
-        ++live;
-    }
-    // ybar_n = wy g + sum Ybar_s, and (not first) kbar_1 for the step before: one launch
-    float* outs[2] = {ybar_n, kbar1};
-    gode_lincomb_t lcs[2] = {sweep_pre(TABDP, g, (float)wy, ybar, last, dead), first ? gode_lincomb_t() : cotangent(0)};
-    int64_t lens[2] = {nd, nd};
-    int count = first ? 1 : 2;
-    if (count == 2 && lcs[1].n == 0) { GODE_TRY(gode_zero_f32(kbar1, nd, stream)); count = 1; }
-    GODE_TRY(gode_lincomb_multi_f32(outs, lcs, lens, count, stream));
-    if (live == 0) return 0;
-    return gode_gat_small_close_stages_f32(parts, n, d, H, live, ts, theta, stream);
-}
-
-// The rk4 pair above for any fixed-grid method (GODE_RK_*; GODE_RK_RK4_38 calls it): records of (S + 1) n x d floats, S
-// slots of `parts`, one closing launch per swept step.
-extern "C" int gode_gat_ode_fixed_forward_save(int32_t method, const gode_gat_odefunc_t* f, const float* y0, float* y_end,
-                                               float* save, const gode_gat_workspace_t* ws, float t0, float t1,
-                                               int32_t n_steps, int32_t step_begin, int32_t step_end, void* stream)
-{
-    if (!f || !ws || !y0 || !y_end || !save) return GODE_E_NULLPTR;
-    const Tableau* tabp = fixed_tableau(method);
     if (!tabp) return GODE_E_SHAPE;
-    if (method == GODE_RK_RK4_38)
-        return gode_gat_ode_rk4_forward_save(f, y0, y_end, save, ws, t0, t1, n_steps, step_begin, step_end, stream);
     int rc = check_steps(n_steps, step_begin, step_end); if (rc) return rc;
     rc = check_sweep(f, ws); if (rc) return rc;
     const Tableau& tab = *tabp;
@@ -449,16 +343,13 @@ extern "C" int gode_gat_ode_fixed_forward_save(int32_t method, const gode_gat_od
     return 0;
 }
 
-extern "C" int gode_gat_ode_fixed_backprop(int32_t method, const gode_gat_odefunc_t* f, const float* save, float* a,
-                                           float* theta, float* const* ybar, float* k_scratch, float* parts,
-                                           const gode_gat_workspace_t* ws, float t0, float t1, int32_t n_steps,
-                                           int32_t step_begin, int32_t step_end, void* stream)
+// The reverse sweep over those records: S slots of `parts`, one closing launch per swept step
+int backprop(const Tableau* tabp, const gode_gat_odefunc_t* f, const float* save, float* a, float* theta, float* const* ybar,
+             float* k_scratch, float* parts, const gode_gat_workspace_t* ws, float t0, float t1, int32_t n_steps,
+             int32_t step_begin, int32_t step_end, void* stream)
 {
     if (!f || !ws || !save || !a || !theta || !ybar || !k_scratch || !parts) return GODE_E_NULLPTR;
-    const Tableau* tabp = fixed_tableau(method);
     if (!tabp) return GODE_E_SHAPE;
-    if (method == GODE_RK_RK4_38)
-        return gode_gat_ode_rk4_backprop(f, save, a, theta, ybar, k_scratch, parts, ws, t0, t1, n_steps, step_begin, step_end, stream);
     const Tableau& tab = *tabp;
     const int S = tab.stages;
     for (int s = 0; s < S; ++s) if (!ybar[s]) return GODE_E_NULLPTR;
@@ -491,9 +382,104 @@ extern "C" int gode_gat_ode_fixed_backprop(int32_t method, const gode_gat_odefun
     return 0;
 }
 
+// The reverse sweep over one accepted step of an adaptive method (am == NULL: a code outside GODE_RKA_*; the entries of k /
+// ybar are looked at after that: their count is the method's).  kbar_last arrives on k_S.
+int step_backprop(const AdaptiveMethod* am, const gode_gat_odefunc_t* f, const float* y, float* const* k, const float* g,
+                  const float* kbar_last, double wy, const double* wk, double t, double h, int32_t first, float* const* ybar,
+                  float* ybar_n, float* kbar1, float* theta, float* k_scratch, float* parts, const gode_gat_workspace_t* ws,
+                  void* stream)
+{
+    if (!f || !ws || !y || !k || !g || !wk || !ybar || !ybar_n || !theta || !k_scratch || !parts) return GODE_E_NULLPTR;
+    if (!first && !kbar1) return GODE_E_NULLPTR;
+    if (!am) return GODE_E_SHAPE;
+    const Tableau& tab = am->tab;
+    const int S = tab.stages;
+    for (int s = 0; s < S; ++s) if (!k[s]) return GODE_E_NULLPTR;
+    for (int s = first ? 0 : 1; s < S; ++s) if (!ybar[s]) return GODE_E_NULLPTR;
+    if (ybar_n == g || ybar_n == kbar_last || ybar_n == k_scratch || k_scratch == g || k_scratch == kbar_last) return GODE_E_SHAPE;
+    if (!first && (kbar1 == g || kbar1 == kbar_last || kbar1 == ybar_n || kbar1 == k_scratch)) return GODE_E_SHAPE;
+    for (int s = first ? 0 : 1; s < S; ++s) {
+        if (ybar[s] == g || ybar[s] == kbar_last || ybar[s] == ybar_n || (!first && ybar[s] == kbar1) || ybar[s] == k_scratch)
+            return GODE_E_SHAPE;
+        for (int r = s + 1; r < S; ++r) if (ybar[s] == ybar[r]) return GODE_E_SHAPE;
+    }
+    int rc = check_sweep(f, ws); if (rc) return rc;
+    const int64_t n = f->n, d = f->d, nd = n * d, H = n_heads(f), slot = part_slot(f);
+    const int last = first ? 0 : 1;                // the last stage the sweep pushes through f
+    bool dead[7] = {};
+    float ts[7];
+    int live = 0;
+    auto cotangent = [&](int s) {
+        gode_lincomb_t c = stage_cotangent(tab, g, (float)wk[s], ybar, s, h, dead);
+        if (s == S - 1 && kbar_last) { c.coef[c.n] = 1.f; c.ptr[c.n] = kbar_last; ++c.n; }
+        return c;
+    };
+    for (int s = S - 1; s >= last; --s) {
+        const gode_lincomb_t cot = cotangent(s);
+        if (cot.n == 0) { dead[s] = true; continue; }
+        ts[live] = (float)(t + tab.c[s] * h);
+        gode_lincomb_t yin = tab_stage_terms(tab, y, k, s, h);
+        GODE_TRY(stage_vjp(f, ws, &yin, cot, 1.f, ts[live], k_scratch, ybar[s], nullptr, parts + live * slot, stream));
+        ++live;
+    }
+    // ybar_n = wy g + sum Ybar_s, and (not first) kbar_1 for the step before: one launch
+    float* outs[2] = {ybar_n, kbar1};
+    gode_lincomb_t lcs[2] = {sweep_pre(tab, g, (float)wy, ybar, last, dead), first ? gode_lincomb_t() : cotangent(0)};
+    int64_t lens[2] = {nd, nd};
+    int count = first ? 1 : 2;
+    if (count == 2 && lcs[1].n == 0) { GODE_TRY(gode_zero_f32(kbar1, nd, stream)); count = 1; }
+    GODE_TRY(gode_lincomb_multi_f32(outs, lcs, lens, count, stream));
+    if (live == 0) return 0;
+    return gode_gat_small_close_stages_f32(parts, n, d, H, live, ts, theta, stream);
+}
+
+}  // namespace
+
+// The entry points: the rk4 pair under the 3/8 rule's tableau, the fixed pair under that of its GODE_RK_* code, the dopri5
+// sweep under ADAPTIVE[GODE_RKA_DOPRI5] (the adaptive one is below, with the other adaptive steps).
+extern "C" int gode_gat_ode_rk4_forward_save(const gode_gat_odefunc_t* f, const float* y0, float* y_end, float* save,
+                                             const gode_gat_workspace_t* ws, float t0, float t1, int32_t n_steps,
+                                             int32_t step_begin, int32_t step_end, void* stream)
+{
+    return forward_save(&TAB38, f, y0, y_end, save, ws, t0, t1, n_steps, step_begin, step_end, stream);
+}
+
+extern "C" int gode_gat_ode_fixed_forward_save(int32_t method, const gode_gat_odefunc_t* f, const float* y0, float* y_end,
+                                               float* save, const gode_gat_workspace_t* ws, float t0, float t1,
+                                               int32_t n_steps, int32_t step_begin, int32_t step_end, void* stream)
+{
+    return forward_save(fixed_tableau(method), f, y0, y_end, save, ws, t0, t1, n_steps, step_begin, step_end, stream);
+}
+
+extern "C" int gode_gat_ode_rk4_backprop(const gode_gat_odefunc_t* f, const float* save, float* a, float* theta,
+                                         float* const* ybar, float* k_scratch, float* parts, const gode_gat_workspace_t* ws,
+                                         float t0, float t1, int32_t n_steps, int32_t step_begin, int32_t step_end,
+                                         void* stream)
+{
+    return backprop(&TAB38, f, save, a, theta, ybar, k_scratch, parts, ws, t0, t1, n_steps, step_begin, step_end, stream);
+}
+
+extern "C" int gode_gat_ode_fixed_backprop(int32_t method, const gode_gat_odefunc_t* f, const float* save, float* a,
+                                           float* theta, float* const* ybar, float* k_scratch, float* parts,
+                                           const gode_gat_workspace_t* ws, float t0, float t1, int32_t n_steps,
+                                           int32_t step_begin, int32_t step_end, void* stream)
+{
+    return backprop(fixed_tableau(method), f, save, a, theta, ybar, k_scratch, parts, ws, t0, t1, n_steps, step_begin, step_end,
+                    stream);
+}
+
+extern "C" int gode_gat_ode_dopri5_step_backprop(const gode_gat_odefunc_t* f, const float* y, float* const* k, const float* g,
+                                                 const float* kbar7, double wy, const double* wk, double t, double h,
+                                                 int32_t first, float* const* ybar, float* ybar_n, float* kbar1, float* theta,
+                                                 float* k_scratch, float* parts, const gode_gat_workspace_t* ws, void* stream)
+{
+    return step_backprop(&ADAPTIVE[GODE_RKA_DOPRI5], f, y, k, g, kbar7, wy, wk, t, h, first, ybar, ybar_n, kbar1, theta, k_scratch,
+                         parts, ws, stream);
+}
+
 // ---------------------------------------------------------------------------------------------------------------
-// The adaptive step drivers by method (GODE_RKA_*): the three dopri5 step functions above driven by a tableau and its error
-// weights (rk_driver.h: AdaptiveMethod), on the same routes and under every message activation.  The forward and the
+// The adaptive step drivers by method (GODE_RKA_*): the dopri5 steps at the top driven by a tableau and its error weights
+// (rk_driver.h: AdaptiveMethod), on the same routes and under every message activation; the sweep is step_backprop.  The forward and the
 // adjoint step close with the fused launch of rk.hip (gode_rk_close_err_multi_f32): the solution and the error sums from
 // one pass over the stages.  On the one-launch route the adjoint step, given `parts`, leaves each stage's partials in a
 // slot of their own and closes the S - 1 stages with ONE gode_gat_small_finish_multi_f32: nothing inside the step reads
@@ -566,47 +552,6 @@ extern "C" int gode_gat_ode_adaptive_step_backprop(int32_t method, const gode_ga
                                                    float* ybar_n, float* kbar1, float* theta, float* k_scratch, float* parts,
                                                    const gode_gat_workspace_t* ws, void* stream)
 {
-    if (!f || !ws || !y || !k || !g || !wk || !ybar || !ybar_n || !theta || !k_scratch || !parts) return GODE_E_NULLPTR;
-    if (!first && !kbar1) return GODE_E_NULLPTR;
-    const AdaptiveMethod* am = adaptive_method(method);
-    if (!am) return GODE_E_SHAPE;                  // the entries of k / ybar are looked at below: their count is the method's
-    const Tableau& tab = am->tab;
-    const int S = tab.stages;
-    for (int s = 0; s < S; ++s) if (!k[s]) return GODE_E_NULLPTR;
-    for (int s = first ? 0 : 1; s < S; ++s) if (!ybar[s]) return GODE_E_NULLPTR;
-    if (ybar_n == g || ybar_n == kbar_last || ybar_n == k_scratch || k_scratch == g || k_scratch == kbar_last) return GODE_E_SHAPE;
-    if (!first && (kbar1 == g || kbar1 == kbar_last || kbar1 == ybar_n || kbar1 == k_scratch)) return GODE_E_SHAPE;
-    for (int s = first ? 0 : 1; s < S; ++s) {
-        if (ybar[s] == g || ybar[s] == kbar_last || ybar[s] == ybar_n || (!first && ybar[s] == kbar1) || ybar[s] == k_scratch)
-            return GODE_E_SHAPE;
-        for (int r = s + 1; r < S; ++r) if (ybar[s] == ybar[r]) return GODE_E_SHAPE;
-    }
-    int rc = check_sweep(f, ws); if (rc) return rc;
-    const int64_t n = f->n, d = f->d, nd = n * d, H = n_heads(f), slot = part_slot(f);
-    const int last = first ? 0 : 1;                // the last stage the sweep pushes through f
-    bool dead[7] = {};
-    float ts[7];
-    int live = 0;
-    auto cotangent = [&](int s) {
-        gode_lincomb_t c = stage_cotangent(tab, g, (float)wk[s], ybar, s, h, dead);
-        if (s == S - 1 && kbar_last) { c.coef[c.n] = 1.f; c.ptr[c.n] = kbar_last; ++c.n; }
-        return c;
-    };
-    for (int s = S - 1; s >= last; --s) {
-        const gode_lincomb_t cot = cotangent(s);
-        if (cot.n == 0) { dead[s] = true; continue; }
-        ts[live] = (float)(t + tab.c[s] * h);
-        gode_lincomb_t yin = tab_stage_terms(tab, y, k, s, h);
-        GODE_TRY(stage_vjp(f, ws, &yin, cot, 1.f, ts[live], k_scratch, ybar[s], nullptr, parts + live * slot, stream));
-        ++live;
-    }
-    // ybar_n = wy g + sum Ybar_s, and (not first) kbar_1 for the step before: one launch
-    float* outs[2] = {ybar_n, kbar1};
-    gode_lincomb_t lcs[2] = {sweep_pre(tab, g, (float)wy, ybar, last, dead), first ? gode_lincomb_t() : cotangent(0)};
-    int64_t lens[2] = {nd, nd};
-    int count = first ? 1 : 2;
-    if (count == 2 && lcs[1].n == 0) { GODE_TRY(gode_zero_f32(kbar1, nd, stream)); count = 1; }
-    GODE_TRY(gode_lincomb_multi_f32(outs, lcs, lens, count, stream));
-    if (live == 0) return 0;
-    return gode_gat_small_close_stages_f32(parts, n, d, H, live, ts, theta, stream);
+    return step_backprop(adaptive_method(method), f, y, k, g, kbar_last, wy, wk, t, h, first, ybar, ybar_n, kbar1, theta,
+                         k_scratch, parts, ws, stream);
 }

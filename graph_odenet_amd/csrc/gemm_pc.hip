@@ -716,7 +716,7 @@ __global__ __launch_bounds__(768) void gn_gemm_bwd_wgrad_pc_kernel(LinComb xin, 
 // 512 threads = the eight consumer waves of gn_gemm_fwd_pc_kernel and nobody else; TWO blocks per CU, each on its own
 // tile, so that one block's staging (vector ALU, LDS stores) runs beside the other's matrix phase.  Per 32-row tile: load y
 // and a_ii once; per step and stage the statements of the launches this one replaces, on the same numbers in the same
-// order - the stage combination (fmaf chain from 0, terms in stage_terms order), gn_forward_v, split3_trunc / stage_row4
+// order - the stage combination (fmaf chain from 0, terms in the order of tab_stage_terms(TAB38, ..)), gn_forward_v, split3_trunc / stage_row4
 // into the piece image, tile_product on acc = t W[0, :], then the DIAG epilogue k = max(fmaf(a_ii, acc, 0) + b, 0) and at
 // the last stage P by the AUX chain and y_new = fmaf(alpha, k, fmaf(1, P, 0)) - hence the same bits.  Two piece images
 // alternate, one LDS barrier per stage: stage s writes image s & 1, whose last readers (the product of stage s - 2) are

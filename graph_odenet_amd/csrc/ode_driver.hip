@@ -3,22 +3,32 @@
 // The reference drives its ODE function from Python (torchdiffeq, call site GCN/models.py:192).  On
 // citation-graph sizes (Cora: 2708 x 16 state) every kernel runs for a few microseconds, so the
 // integration is bound by the host's per-launch cost; these entry points issue the complete launch
-// sequence of an rk4 (3/8 rule) forward solve or adjoint solve from C with no allocation and no
+// sequence of a forward solve, an adjoint solve or a backprop sweep from C with no allocation and no
 // synchronisation, which also makes the call capturable into a HIP graph by the caller.
 // Launch sequence per stage = graph_odenet_amd/gcn_ode.py (GcnOdeField / GcnOdeAdjointField).
 //
-// Every launch sequence is stated once (tables and term lists: rk_driver.h):
-//   feval_large         Gf then Sp of one evaluation on the large route (optionally closing a step, optionally keeping k_4)
-//   rk4_forward_step    one step of the forward solve, fused or large route
+// Every launch sequence is stated once, over a tableau (tables and term lists: rk_driver.h); no method has a copy of its own:
+//   feval_large         Gf then Sp of one evaluation on the large route (optionally closing a step, optionally keeping k_S)
+//   fixed_forward_step  one step of a fixed-grid forward solve, fused or large route
+//   forward_solve / forward_save   fixed_forward_step per step, swapping buffers / into records
+//   adjoint_small_step / fixed_adjoint_small   a step / the solve of the fused launch-bound schedule of a fixed-grid adjoint solve
 //   close_bias / close_weight / close_affine    the reductions that close a stage's parameter derivative, large route
 //   stage_finish_merged the same as ONE launch, launch-bound sizes
-//   rk4_adjoint_small   the fused launch-bound schedule of the adjoint solve
-//   sweep_pre           the four terms a backprop step's last launch adds up to abar_n
-// and the entry points compose them:
-//   gode_gcn_ode_rk4_forward, gode_gcn_ode_rk4_forward_save   rk4_forward_step per step (swapping buffers / into records)
-//   gode_gcn_ode_rk4_adjoint     rk4_adjoint_small, or the two-chain loop: Gf (one lambda), Sp, SpT, dense VJP, close_*
-//   gode_gcn_ode_dopri5_step_*   dp_eval_forward (feval_large) / dp_eval_adjoint (close_*) per stage
-//   gode_gcn_ode_rk4_backprop    the fused sweep, or per stage masked cotangent, SpT, dense VJP, close_*
+//   sweep_stage         one stage of a reverse sweep on the multi-launch routes
+//   backprop            the reverse sweep over forward_save's records: the fused sweep, or sweep_stage per stage
+//   step_backprop       the reverse sweep over one accepted step of an adaptive method
+//   sweep_pre           the terms a backprop step's last launch adds up to abar_n
+// and the entry points name a tableau and call them.  A body validates, in the order its entry points always did; it takes
+// the tableau by pointer, NULL being a method code outside the list, refused where the by-method entry point refused it:
+//   gode_gcn_ode_rk4_forward, _rk4_forward_save, _rk4_backprop     forward_solve, forward_save, backprop under TAB38
+//   gode_gcn_ode_fixed_forward, _fixed_forward_save, _fixed_backprop   the same under fixed_tableau(method)
+//   gode_gcn_ode_rk4_adjoint     fixed_adjoint_small under TAB38, or the two-chain loop: Gf (one lambda), Sp, SpT, dense VJP,
+//                                close_* (the 3/8 rule's alone); gode_gcn_ode_fixed_adjoint: fixed_adjoint_small, rk4 to the former
+//   gode_gcn_ode_dopri5_step_backprop, gode_gcn_ode_adaptive_step_backprop   step_backprop under ADAPTIVE[..]
+//   gode_gcn_ode_dopri5_step_forward / _adjoint   dp_eval_forward (feval_large) / dp_eval_adjoint (close_*) per stage; the
+//                                adaptive_step_forward / _adjoint run the same stages and close the step with ONE fused launch
+//                                where these use two, so the two pairs stay apart
+//   gode_gcn_ode_adams_*         fixed_forward_step / adjoint_small_step under TAB38 for the start-up steps
 #include <map>
 #include <mutex>
 #include <utility>
@@ -178,25 +188,45 @@ int feval_large(const gode_gcn_odefunc_t* f, const gode_lincomb_t& xin, float t,
                                   S, d, out, d, g.n_rows, d, &ep, k_save, stream);
 }
 
-// One step of the forward solve from y at time t: k_1..k_3 into k[0..2], y_{n+1} into ynext (which may be k[3]: the
-// folded last stage never materialises k_4) - or, keep_k4, k_4 into k[3] as well (ynext is then another array).
-int rk4_forward_step(const gode_gcn_odefunc_t* f, const gode_rk4_workspace_t* ws, const float* y, float* const* k,
-                     float* ynext, bool keep_k4, double t, double h, bool fused, bool close_once, void* stream,
-                     bool diag_ok = false) {
-    for (int s = 0; s < 4; ++s) {
-        const gode_lincomb_t xin = stage_terms(y, k, s, h);
-        const float ts = (float)(t + C38[s] * h);
-        if (s < 3) {
+// the closing-combination-once launch needs the last stage's input and the closing combination to name the same arrays in
+// the same order, and saves something only where they are several (the 3/8 rule).  The midpoint rule's differ and explicit
+// Euler's is y alone: both close from their terms - one array, as the once route reads.
+bool same_arrays(const gode_lincomb_t& x, const gode_lincomb_t& p) {
+    if (x.n != p.n || x.n < 2) return false;
+    for (int j = 0; j < x.n; ++j) if (x.ptr[j] != p.ptr[j]) return false;
+    return true;
+}
+
+// One step of the forward solve from y at time t: k_1..k_{S-1} into k[0..S-2], y_{n+1} into ynext (which may be k[S-1]: the
+// folded last stage never materialises k_S) - or, keep_last, k_S into k[S-1] as well (ynext is then another array).
+int fixed_forward_step(const Tableau& tab, const gode_gcn_odefunc_t* f, const gode_rk4_workspace_t* ws, const float* y,
+                       float* const* k, float* ynext, bool keep_last, double t, double h, bool fused, bool close_once,
+                       void* stream, bool diag_ok = false) {
+    const int S = tab.stages;
+    for (int s = 0; s < S; ++s) {
+        const gode_lincomb_t xin = tab_stage_terms(tab, y, k, s, h);
+        const float ts = (float)(t + tab.c[s] * h);
+        if (s + 1 < S) {
             if (fused) GODE_TRY(gode_gcn_feval_small_f32(f, &xin, ts, 1.f, nullptr, nullptr, nullptr, k[s], stream));
             else GODE_TRY(feval_large(f, xin, ts, ws->S, k[s], nullptr, nullptr, stream, diag_ok));
             continue;
         }
-        const StepClose close = {combine_terms(y, k, h), (float)(h * B38[3]), close_once};
-        if (!fused) GODE_TRY(feval_large(f, xin, ts, ws->S, ynext, &close, keep_k4 ? k[3] : nullptr, stream, diag_ok));
-        else if (keep_k4) GODE_TRY(gode_gcn_feval_small_save_f32(f, &xin, ts, close.alpha, &close.pre, ynext, k[3], stream));
+        StepClose close = {tab_combine_terms(tab, y, k, h), (float)(h * tab.b[s]), close_once};
+        close.once = close_once && same_arrays(xin, close.pre);
+        float* klast = keep_last ? k[s] : nullptr;
+        if (!fused) GODE_TRY(feval_large(f, xin, ts, ws->S, ynext, &close, klast, stream, diag_ok));
+        else if (keep_last) GODE_TRY(gode_gcn_feval_small_save_f32(f, &xin, ts, close.alpha, &close.pre, ynext, klast, stream));
         else GODE_TRY(gode_gcn_feval_small_f32(f, &xin, ts, close.alpha, &close.pre, nullptr, nullptr, ynext, stream));
     }
     return 0;
+}
+
+// diagonal-only rows of A (option diag_rows; large route at d = 128): stages before the last, and on the closing-combination-
+// once route the last stage as well (option diag_last): the producer waves of its dense launch hand the closing combination
+// to the consumer waves through LDS, and the consumer is the only writer of a diagonal-only row of y_new.
+bool diag_rows_route(const gode_gcn_odefunc_t* f, bool fused) {
+    return gode_opt_diag_rows() && !fused && f->n > kMergedFinishMaxRows && f->d == 128 && f->a_core_items && f->a_diag &&
+           f->at_diag && f->A.items && f->a_n_core > 0 && f->a_n_core <= f->A.n_items;
 }
 
 // Side stream + events for the two-chain schedule of the adjoint solve (and the tail launch of the forward solve:
@@ -251,18 +281,18 @@ int local_tail_solve(const gode_gcn_odefunc_t* f, const float* y, float* res, fl
     float* const kdummy[4] = {nullptr, nullptr, nullptr, nullptr};
     LocalTailSteps st = {};
     for (int q = 0; q < 4; ++q) {
-        const gode_lincomb_t lc = stage_terms(nullptr, kdummy, q, h);
+        const gode_lincomb_t lc = tab_stage_terms(TAB38, nullptr, kdummy, q, h);
         if (lc.n != q + 1) return GODE_E_UNSUPPORTED;
         for (int j = 0; j <= q; ++j) st.coef[q][j] = lc.coef[j];
     }
-    const gode_lincomb_t pre = combine_terms(nullptr, kdummy, h);
+    const gode_lincomb_t pre = tab_combine_terms(TAB38, nullptr, kdummy, h);
     for (int j = 0; j < 4; ++j) st.acoef[j] = pre.coef[j];
     st.alpha = (float)(h * B38[3]);
     const float* src = y + off;
     for (int i0 = 0; i0 < n_steps; i0 += GODE_LOCAL_TAIL_MAX_STEPS) {
         st.n_steps = n_steps - i0 < GODE_LOCAL_TAIL_MAX_STEPS ? n_steps - i0 : GODE_LOCAL_TAIL_MAX_STEPS;
         for (int i = 0; i < st.n_steps; ++i)
-            for (int q = 0; q < 4; ++q) st.ts[i][q] = (float)(((double)t0 + (i0 + i) * h) + C38[q] * h);   // rk4_forward_step's
+            for (int q = 0; q < 4; ++q) st.ts[i][q] = (float)(((double)t0 + (i0 + i) * h) + C38[q] * h);   // fixed_forward_step's
         GODE_TRY(gode_pc_local_tail_launch(src, res + off, f->n_tail, f->a_diag + (f->n - f->n_tail), f->eps, f->gamma, f->beta,
                                            f->W, f->b, st, cg, blocks, s));
         src = res + off;
@@ -270,32 +300,31 @@ int local_tail_solve(const gode_gcn_odefunc_t* f, const float* y, float* res, fl
     return 0;
 }
 
-}  // namespace
-
-extern "C" int64_t gode_gcn_ode_theta_len(int64_t d) { return (d + 1) * d + 3 * d + 1; }
-
-extern "C" int gode_gcn_ode_rk4_forward(const gode_gcn_odefunc_t* f, float* y, float** result,
-                                        const gode_rk4_workspace_t* ws, float t0, float t1, int32_t n_steps,
-                                        void* stream)
+// The forward solve of a fixed-grid method (tabp == NULL, here and in the bodies below: a code outside GODE_RK_*, refused
+// after the null checks): fixed_forward_step per step, the solution and k[S-1] swapping.
+int forward_solve(const Tableau* tabp, const gode_gcn_odefunc_t* f, float* y, float** result, const gode_rk4_workspace_t* ws,
+                  float t0, float t1, int32_t n_steps, void* stream)
 {
     if (!f || !y || !ws || !result) return GODE_E_NULLPTR;
+    if (!tabp) return GODE_E_SHAPE;
     if (n_steps <= 0 || f->n <= 0 || f->d <= 0) return GODE_E_SHAPE;
-    if (!ws->S || !ws->ky[0] || !ws->ky[1] || !ws->ky[2] || !ws->ky[3]) return GODE_E_NULLPTR;
+    const Tableau& tab = *tabp;
+    const int S = tab.stages, L = S - 1;
+    if (!ws->S) return GODE_E_NULLPTR;
+    for (int s = 0; s < S; ++s) if (!ws->ky[s]) return GODE_E_NULLPTR;
     const double h = ((double)t1 - (double)t0) / n_steps;
     float* cur = y;
     float* k[4] = {ws->ky[0], ws->ky[1], ws->ky[2], ws->ky[3]};
     const bool fused = fused_small(f);
     const bool close_once = close_once_route(f);
-    // diagonal-only rows of A (option diag_rows; large route at d = 128): stages 0-2, and on the closing-combination-once
-    // route the last stage as well (option diag_last): the producer waves of its dense launch hand the closing combination
-    // to the consumer waves through LDS, and the consumer is the only writer of a diagonal-only row of y_new.
-    const bool diag_ok = gode_opt_diag_rows() && !fused && f->n > kMergedFinishMaxRows && f->d == 128 && f->a_core_items &&
-                         f->a_diag && f->at_diag && f->A.items && f->a_n_core > 0 && f->a_n_core <= f->A.n_items;
-    // isolated tail rows (option local_tail): one launch of their own writes them into the buffer *result will name (the
-    // buffers swap once per step); the steps below then run their dense launches on the rows before the tail.  Outside a
-    // capture and with option overlap the launch goes to the side stream, beside the solve's HBM-bound SpMM launches: it
-    // waits for what the caller's stream held at entry, and the caller's stream joins it before the return.
-    const int tail_cg = local_tail_cg(f, ws, y, diag_ok, close_once);
+    const bool diag_ok = diag_rows_route(f, fused);
+    // isolated tail rows (option local_tail; the 3/8 rule only: the tail kernel integrates its step): one launch of their own
+    // writes them into the buffer *result will name (the buffers swap once per step); the steps below then run their dense
+    // launches on the rows before the tail.  Outside a capture and with option overlap the launch goes to the side stream,
+    // beside the solve's HBM-bound SpMM launches: it waits for what the caller's stream held at entry, and the caller's
+    // stream joins it before the return.
+    // (the pointer test is sound inside this file: TAB38 has one copy per translation unit, and fixed_tableau() of this one returns it)
+    const int tail_cg = tabp == &TAB38 ? local_tail_cg(f, ws, y, diag_ok, close_once) : -1;
     gode_gcn_odefunc_t fcore;
     Overlap* ov = nullptr;
     if (tail_cg >= 0) {
@@ -326,8 +355,8 @@ extern "C" int gode_gcn_ode_rk4_forward(const gode_gcn_odefunc_t* f, float* y, f
     }
     int rc = 0;
     for (int i = 0; i < n_steps && !rc; ++i) {
-        rc = rk4_forward_step(f, ws, cur, k, k[3], false, (double)t0 + i * h, h, fused, close_once, stream, diag_ok);
-        float* tmp = cur; cur = k[3]; k[3] = tmp;      // k[3] holds the new solution
+        rc = fixed_forward_step(tab, f, ws, cur, k, k[L], false, (double)t0 + i * h, h, fused, close_once, stream, diag_ok);
+        float* tmp = cur; cur = k[L]; k[L] = tmp;      // k[L] holds the new solution
     }
     if (ov) GODE_HIP(hipStreamWaitEvent((hipStream_t)stream, ov->tail_out, 0));
     if (rc) return rc;
@@ -335,34 +364,46 @@ extern "C" int gode_gcn_ode_rk4_forward(const gode_gcn_odefunc_t* f, float* y, f
     return 0;
 }
 
-namespace {
+// One step of the adjoint solve on launch-bound graphs, fused launches, from (y, a) at time t: two launches per stage - f-eval
+// (+ masked cotangent dZ), VJP (+ block partials) - and one more, which adds h * sum_s b_s ktheta_s to theta straight from
+// the stages' block partials (w0_extra: added to the first stage's weight h b_1 - explicit_adams' start-up steps); a single
+// stream.  The new y and a are left in ky[S-1] and ka[S-1].  Any tableau of up to 4 stages.
+int adjoint_small_step(const Tableau& tab, const gode_gcn_odefunc_t* f, const gode_rk4_workspace_t* ws, const float* y,
+                       float* const* ky, const float* a, float* const* ka, float* theta, double t, double h, double w0_extra,
+                       void* stream) {
+    const int S = tab.stages, L = S - 1;
+    const int64_t slot = gode_gcn_small_parts(f->n) * gode_gcn_small_part_len(f->d);
+    const float hbl = (float)(h * tab.b[L]);
+    float stage_t[4], wb[4];
+    const gode_lincomb_t ypre = tab_combine_terms(tab, y, ky, h), apre = tab_combine_terms(tab, a, ka, h);
+    for (int s = 0; s < S; ++s) {
+        stage_t[s] = (float)(t + tab.c[s] * h);
+        wb[s] = (float)(h * tab.b[s] + (s == 0 ? w0_extra : 0.0));
+        const gode_lincomb_t yin = tab_stage_terms(tab, y, ky, s, h);
+        const gode_lincomb_t cot = negated(tab_stage_terms(tab, a, ka, s, h));          // cotangent of the VJP is -a
+        GODE_TRY(gode_gcn_feval_small_f32(f, &yin, stage_t[s], s == L ? hbl : 1.f, s == L ? &ypre : nullptr,
+                                          &cot, ws->dZ, ky[s], stream));
+        GODE_TRY(gode_gcn_vjp_small_f32(f, &yin, ws->dZ, s == L ? hbl : 1.f, s == L ? &apre : nullptr,
+                                        ka[s], ws->small_part + s * slot, stream));
+    }
+    // every weight rounded to zero (an empty or denormal-sized interval): the launch below refuses such a step, and theta stays
+    bool any = false;
+    for (int s = 0; s < S; ++s) any = any || wb[s] != 0.f;
+    if (!any) return 0;
+    return gode_gcn_small_finish_step_f32(f, ws->small_part, S, theta, wb, stage_t, stream);
+}
 
-// Launch-bound graphs, fused launches: two per stage - f-eval (+ masked cotangent dZ), VJP (+ block partials) - and one
-// more per step; a single stream.
-int rk4_adjoint_small(const gode_gcn_odefunc_t* f, const gode_rk4_workspace_t* ws, float* y, float* a, float* theta,
-                      float** y_result, float** a_result, float t0, double h, int32_t n_steps, void* stream) {
+// The whole solve: adjoint_small_step per step, the solutions and ky[S-1] / ka[S-1] swapping
+int fixed_adjoint_small(const Tableau& tab, const gode_gcn_odefunc_t* f, const gode_rk4_workspace_t* ws, float* y, float* a,
+                        float* theta, float** y_result, float** a_result, float t0, double h, int32_t n_steps, void* stream) {
+    const int L = tab.stages - 1;
     float* ycur = y; float* acur = a;
     float* ky[4] = {ws->ky[0], ws->ky[1], ws->ky[2], ws->ky[3]};
     float* ka[4] = {ws->ka[0], ws->ka[1], ws->ka[2], ws->ka[3]};
-    const int64_t slot = gode_gcn_small_parts(f->n) * gode_gcn_small_part_len(f->d);
-    const float hb3 = (float)(h * B38[3]);
     for (int i = 0; i < n_steps; ++i) {
-        float stage_t[4];
-        const gode_lincomb_t ypre = combine_terms(ycur, ky, h), apre = combine_terms(acur, ka, h);
-        for (int s = 0; s < 4; ++s) {
-            stage_t[s] = (float)((double)t0 + i * h + C38[s] * h);
-            const gode_lincomb_t yin = stage_terms(ycur, ky, s, h);
-            const gode_lincomb_t cot = negated(stage_terms(acur, ka, s, h));          // cotangent of the VJP is -a
-            GODE_TRY(gode_gcn_feval_small_f32(f, &yin, stage_t[s], s == 3 ? hb3 : 1.f, s == 3 ? &ypre : nullptr,
-                                              &cot, ws->dZ, ky[s], stream));
-            GODE_TRY(gode_gcn_vjp_small_f32(f, &yin, ws->dZ, s == 3 ? hb3 : 1.f, s == 3 ? &apre : nullptr,
-                                            ka[s], ws->small_part + s * slot, stream));
-        }
-        // theta <- theta + h * sum_s b_s ktheta_s straight from the four stages' block partials: one launch per step
-        const float wb[4] = {(float)(h * B38[0]), (float)(h * B38[1]), (float)(h * B38[2]), hb3};
-        GODE_TRY(gode_gcn_small_finish4_f32(f, ws->small_part, theta, wb, stage_t, stream));
-        float* tmp = ycur; ycur = ky[3]; ky[3] = tmp;
-        tmp = acur; acur = ka[3]; ka[3] = tmp;
+        GODE_TRY(adjoint_small_step(tab, f, ws, ycur, ky, acur, ka, theta, (double)t0 + i * h, h, 0.0, stream));
+        float* tmp = ycur; ycur = ky[L]; ky[L] = tmp;
+        tmp = acur; acur = ka[L]; ka[L] = tmp;
     }
     *y_result = ycur;
     *a_result = acur;
@@ -370,6 +411,15 @@ int rk4_adjoint_small(const gode_gcn_odefunc_t* f, const gode_rk4_workspace_t* w
 }
 
 }  // namespace
+
+extern "C" int64_t gode_gcn_ode_theta_len(int64_t d) { return (d + 1) * d + 3 * d + 1; }
+
+extern "C" int gode_gcn_ode_rk4_forward(const gode_gcn_odefunc_t* f, float* y, float** result,
+                                        const gode_rk4_workspace_t* ws, float t0, float t1, int32_t n_steps,
+                                        void* stream)
+{
+    return forward_solve(&TAB38, f, y, result, ws, t0, t1, n_steps, stream);
+}
 
 // Adjoint solve.  Per stage the launches form two chains:
 //   F (forward recompute):  Gf(s) = [t|GN(y_s)]W  ->  Sp(s) = relu(A . + b) (+ masked cotangent dZ)
@@ -390,7 +440,7 @@ extern "C" int gode_gcn_ode_rk4_adjoint(const gode_gcn_odefunc_t* f, float* y, f
     const int64_t n = f->n, d = f->d;
     const double h = ((double)t1 - (double)t0) / n_steps;   // negative: the adjoint runs from t0 (later) to t1 (earlier)
     if (fused_small(f) && ws->small_part != nullptr)
-        return rk4_adjoint_small(f, ws, y, a, theta, y_result, a_result, t0, h, n_steps, stream);
+        return fixed_adjoint_small(TAB38, f, ws, y, a, theta, y_result, a_result, t0, h, n_steps, stream);
     hipStream_t hs = (hipStream_t)stream;
     // the side stream exists only for callers that ask for the two-chain schedule (never created inside a capture:
     // odeint turns the option off around its HIP-graph captures)
@@ -465,10 +515,10 @@ extern "C" int gode_gcn_ode_rk4_adjoint(const gode_gcn_odefunc_t* f, float* y, f
     fhead.n = n_head;
     // Gf(g) from the y-chain as it stands (stage g's step must be the current one: Sp of a last stage swaps the chain)
     auto gf = [&](int g, void* st) -> int {
-        const gode_lincomb_t yin = stage_terms(ycur, ky, g % 4, h);
+        const gode_lincomb_t yin = tab_stage_terms(TAB38, ycur, ky, g % 4, h);
         const bool tl = tail_stage(g);
         if (g % 4 == 3 && close_once) {
-            GODE_TRY(gf_last_stage(tl ? &fhead : f, yin, combine_terms(ycur, ky, h), stage_time(g), Sbuf[g & 1], x_out_of(g), ky[3],
+            GODE_TRY(gf_last_stage(tl ? &fhead : f, yin, tab_combine_terms(TAB38, ycur, ky, h), stage_time(g), Sbuf[g & 1], x_out_of(g), ky[3],
                                    &py_formed, st));
             if (tl && !py_formed) {         // the tail launch forms P itself, so Sp(3) would have to read {1.0, P}: the kernel
                 full_g = g;                 // the options select cannot form it - this stage goes the parent's way, on every row
@@ -487,7 +537,7 @@ extern "C" int gode_gcn_ode_rk4_adjoint(const gode_gcn_odefunc_t* f, float* y, f
         if (!tail_stage(g)) return 0;
         const int s = g % 4;
         const int64_t off = n_head * d;
-        gode_lincomb_t yin = stage_terms(ycur, ky, s, h), cot = negated(stage_terms(acur, ka, s, h));
+        gode_lincomb_t yin = tab_stage_terms(TAB38, ycur, ky, s, h), cot = negated(tab_stage_terms(TAB38, acur, ka, s, h));
         if (yin.n != cot.n || yin.n != s + 1) return GODE_E_UNSUPPORTED;
         for (int j = 0; j < yin.n; ++j) { yin.ptr[j] += off; cot.ptr[j] += off; }
         AdjTail at = {};
@@ -495,7 +545,7 @@ extern "C" int gode_gcn_ode_rk4_adjoint(const gode_gcn_odefunc_t* f, float* y, f
         at.k = ky[s] + off; at.dS = ws->dS + off; at.x_out = x_out_of(g) ? x_out_of(g) + off : nullptr;
         at.colpart = ws->y2_colsum + head_rows * d;
         if (s == 3) {
-            const gode_lincomb_t ypre = combine_terms(ycur, ky, h), apre = combine_terms(acur, ka, h);
+            const gode_lincomb_t ypre = tab_combine_terms(TAB38, ycur, ky, h), apre = tab_combine_terms(TAB38, acur, ka, h);
             if (ypre.n != 4 || apre.n != 4) return GODE_E_UNSUPPORTED;
             for (int j = 0; j < 4; ++j) { at.pcoef[j] = ypre.coef[j]; at.c3[j] = apre.coef[j]; }
             at.alpha = (float)(h * B38[3]);
@@ -511,17 +561,17 @@ extern "C" int gode_gcn_ode_rk4_adjoint(const gode_gcn_odefunc_t* f, float* y, f
         const int s = g % 4;
         const float ts = stage_time(g);
         // terms of THIS stage (used by Gb / Wg below)
-        const gode_lincomb_t yin = x_out_of(g) ? one_term(x_out_of(g)) : stage_terms(ycur, ky, s, h);
-        const gode_lincomb_t ain = stage_terms(acur, ka, s, h);
+        const gode_lincomb_t yin = x_out_of(g) ? one_term(x_out_of(g)) : tab_stage_terms(TAB38, ycur, ky, s, h);
+        const gode_lincomb_t ain = tab_stage_terms(TAB38, acur, ka, s, h);
         gode_spmm_epilogue_t ep = relu_bias_epilogue(f);
         ep.cot = negated(ain);                                // cotangent of the VJP is -a
         ep.Y2 = ws->dZ;
         if (y2rows > 0) ep.Y2_colsum = ws->y2_colsum;
         gode_lincomb_t apre; apre.n = 0;
         if (s == 3) {
-            ep.pre = py_formed ? one_term(ky[3]) : combine_terms(ycur, ky, h);
+            ep.pre = py_formed ? one_term(ky[3]) : tab_combine_terms(TAB38, ycur, ky, h);
             ep.alpha = (float)(h * B38[3]);
-            apre = combine_terms(acur, ka, h);
+            apre = tab_combine_terms(TAB38, acur, ka, h);
             if (close_once && ain.n == apre.n) {              // the cotangent terms are a, ka0, ka1, ka2 in this order
                 ep.cot_out = ka[3];
                 for (int j = 0; j < apre.n; ++j) ep.cot_out_coef[j] = apre.coef[j];
@@ -685,10 +735,10 @@ extern "C" int gode_gcn_ode_dopri5_step_forward(const gode_gcn_odefunc_t* f, con
     // the stage before it (same multiply-adds in the same order as combining the terms on the fly: bit-identical)
     const bool chain = fused_small(f) && ws->X[0] && ws->X[1];
     for (int s = 1; s < 7; ++s) {
-        gode_lincomb_t yin = dp_terms(y, k, DPA[s], s, h, true);
+        gode_lincomb_t yin = tab_stage_terms(TABDP, y, k, s, h);
         if (chain && s >= 2) yin = one_term(ws->X[s & 1]);
         gode_lincomb_t nxt; nxt.n = 0;
-        if (chain && s < 6) nxt = dp_terms(y, k, DPA[s + 1], s + 1, h, true);
+        if (chain && s < 6) nxt = tab_stage_terms(TABDP, y, k, s + 1, h);
         GODE_TRY(dp_eval_forward(f, ws, &yin, (float)(t + DPC[s] * h), k[s], nxt.n > 0 ? &nxt : nullptr,
                                  nxt.n > 0 ? ws->X[(s + 1) & 1] : nullptr, stream));
     }
@@ -714,11 +764,11 @@ extern "C" int gode_gcn_ode_dopri5_step_adjoint(const gode_gcn_odefunc_t* f, con
     const bool fused = fused_small(f) && ws->small_part;
     const bool chain = fused && ws->X[0] && ws->X[1];                                   // as in the forward step
     for (int s = 1; s < 7; ++s) {
-        gode_lincomb_t yin = dp_terms(y, ky, DPA[s], s, h, true);
+        gode_lincomb_t yin = tab_stage_terms(TABDP, y, ky, s, h);
         if (chain && s >= 2) yin = one_term(ws->X[s & 1]);
-        gode_lincomb_t ain = dp_terms(a, ka, DPA[s], s, h, true);
+        gode_lincomb_t ain = tab_stage_terms(TABDP, a, ka, s, h);
         gode_lincomb_t nxt; nxt.n = 0;
-        if (chain && s < 6) nxt = dp_terms(y, ky, DPA[s + 1], s + 1, h, true);
+        if (chain && s < 6) nxt = tab_stage_terms(TABDP, y, ky, s + 1, h);
         GODE_TRY(dp_eval_adjoint(f, ws, yin, ain, (float)(t + DPC[s] * h), ky[s], ka[s], kth[s], nxt.n > 0 ? &nxt : nullptr,
                                  nxt.n > 0 ? ws->X[(s + 1) & 1] : nullptr, fused ? s - 1 : -1, stream));
     }
@@ -745,9 +795,10 @@ extern "C" int gode_gcn_ode_dopri5_step_adjoint(const gode_gcn_odefunc_t* f, con
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Backprop through a fixed-grid rk4 solve (odeint._OdeintBackprop): a forward solve that keeps every step's y_n and
-// k_1..k_4, and ONE call for the whole reverse sweep over them.  Record r of `save` (step step_begin + r) is
-// [ y_n | k_1 | k_2 | k_3 | k_4 ], five n x d arrays.  Per step, with cotangent abar = dL/dy_{n+1} (3/8 rule):
+// Backprop through a fixed-grid solve (odeint._OdeintBackprop): a forward solve that keeps every step's y_n and
+// k_1..k_S (forward_save), and ONE call for the whole reverse sweep over them (backprop).  Record r of `save` (step
+// step_begin + r) is [ y_n | k_1 | .. | k_S ], S + 1 n x d arrays (rk4: five).  Per step, with cotangent abar = dL/dy_{n+1},
+// kbar_s = h b_s abar + h sum_{q > s} A[q][s] Ybar_q; under the 3/8 rule:
 //   kbar_4 = h/8 abar,  kbar_3 = 3h/8 abar + h Ybar_4,  kbar_2 = 3h/8 abar + h Ybar_3 - h Ybar_4,
 //   kbar_1 = h/8 abar + h/3 Ybar_2 - h/3 Ybar_3 + h Ybar_4;   Ybar_s = J_s^T kbar_s,  theta += (df/dtheta)_s^T kbar_s,
 //   abar_n = abar + sum_s Ybar_s
@@ -805,16 +856,17 @@ int add_stage_parts(float* theta, float* const* kt, int count, int64_t len, void
     return gode_lincomb_f32(theta, &tc, len, stream);
 }
 
-}  // namespace
-
-extern "C" int gode_gcn_ode_rk4_forward_save(const gode_gcn_odefunc_t* f, const float* y0, float* y_end, float* save,
-                                             const gode_rk4_workspace_t* ws, float t0, float t1, int32_t n_steps,
-                                             int32_t step_begin, int32_t step_end, void* stream)
+// Steps step_begin .. step_end - 1 of forward_solve's launches into records (the folded last stage also stores k_S)
+int forward_save(const Tableau* tabp, const gode_gcn_odefunc_t* f, const float* y0, float* y_end, float* save,
+                 const gode_rk4_workspace_t* ws, float t0, float t1, int32_t n_steps, int32_t step_begin, int32_t step_end,
+                 void* stream)
 {
     if (!f || !y0 || !y_end || !save || !ws) return GODE_E_NULLPTR;
+    if (!tabp) return GODE_E_SHAPE;
     if (n_steps <= 0 || f->n <= 0 || f->d <= 0) return GODE_E_SHAPE;
     if (step_begin < 0 || step_end > n_steps || step_begin >= step_end) return GODE_E_SHAPE;
     if (!ws->S) return GODE_E_NULLPTR;
+    const int S = tabp->stages;
     const int64_t nd = f->n * f->d;
     const double h = ((double)t1 - (double)t0) / n_steps;
     const bool fused = fused_small(f);
@@ -824,63 +876,70 @@ extern "C" int gode_gcn_ode_rk4_forward_save(const gode_gcn_odefunc_t* f, const 
         GODE_TRY(gode_lincomb_f32(save, &c, nd, stream));
     }
     for (int i = step_begin; i < step_end; ++i) {
-        float* rec = save + (int64_t)(i - step_begin) * 5 * nd;
-        float* k[4] = {rec + nd, rec + 2 * nd, rec + 3 * nd, rec + 4 * nd};
-        float* ynext = (i + 1 < step_end) ? rec + 5 * nd : y_end;      // the next record's y_n, or the result
-        // the launches of gode_gcn_ode_rk4_forward; the folded last stage also stores k_4
-        GODE_TRY(rk4_forward_step(f, ws, rec, k, ynext, true, (double)t0 + i * h, h, fused, close_once, stream));
+        float* rec = save + (int64_t)(i - step_begin) * (S + 1) * nd;
+        float* k[4] = {};
+        for (int s = 0; s < S; ++s) k[s] = rec + (int64_t)(s + 1) * nd;
+        float* ynext = (i + 1 < step_end) ? rec + (int64_t)(S + 1) * nd : y_end;      // the next record's y_n, or the result
+        GODE_TRY(fixed_forward_step(*tabp, f, ws, rec, k, ynext, true, (double)t0 + i * h, h, fused, close_once, stream));
     }
     return 0;
 }
 
-extern "C" int gode_gcn_ode_rk4_backprop(const gode_gcn_odefunc_t* f, const float* save, float* a, float* theta,
-                                         float** a_result, const gode_rk4_workspace_t* ws, float* cot_colpart,
-                                         float t0, float t1, int32_t n_steps, int32_t step_begin, int32_t step_end,
-                                         void* stream)
+// The reverse sweep over those records
+int backprop(const Tableau* tabp, const gode_gcn_odefunc_t* f, const float* save, float* a, float* theta, float** a_result,
+             const gode_rk4_workspace_t* ws, float* cot_colpart, float t0, float t1, int32_t n_steps, int32_t step_begin,
+             int32_t step_end, void* stream)
 {
     if (!f || !save || !a || !theta || !a_result || !ws) return GODE_E_NULLPTR;
+    if (!tabp) return GODE_E_SHAPE;
     if (n_steps <= 0 || f->n <= 0 || f->d <= 0) return GODE_E_SHAPE;
     if (step_begin < 0 || step_end > n_steps || step_begin >= step_end) return GODE_E_SHAPE;
-    for (int s = 0; s < 4; ++s) if (!ws->ka[s] || !ws->ktheta[s]) return GODE_E_NULLPTR;
+    const Tableau& tab = *tabp;
+    const int S = tab.stages, L = S - 1;
+    for (int s = 0; s < S; ++s) if (!ws->ka[s] || !ws->ktheta[s]) return GODE_E_NULLPTR;
     if (!ws->dZ || !ws->dS || !ws->wpart || !ws->colsum_scratch) return GODE_E_NULLPTR;
     if (f->groups > 0 && (!ws->gpart || !ws->bpart)) return GODE_E_NULLPTR;
     const int64_t n = f->n, d = f->d, nd = n * d;
     const double h = ((double)t1 - (double)t0) / n_steps;
     float* acur = a;
-    float* yb[4] = {ws->ka[0], ws->ka[1], ws->ka[2], ws->ka[3]};   // yb[1..3]: Ybar_2..4; yb[0] receives abar_n
-    auto record = [&](int i) { return save + (int64_t)(i - step_begin) * 5 * nd; };
+    float* yb[4] = {ws->ka[0], ws->ka[1], ws->ka[2], ws->ka[3]};   // yb[1..S-1]: Ybar_2..S; yb[0] receives abar_n
+    auto record = [&](int i) { return save + (int64_t)(i - step_begin) * (S + 1) * nd; };
+    // kbar_S = h b_S abar: b_S is non-zero in every method of the list, so the sweep of a step always opens with one term
+    const float hbl = (float)(h * tab.b[L]);
     const bool fused = fused_small(f) && ws->small_part != nullptr;
     if (fused) {
         // launch-bound graphs: ONE launch per stage - the VJP of stage s (csrc/small.hip) also forms the masked cotangent
-        // of the stage after it in the sweep (s - 1, or stage 4 of the previous step); one launch per step closes theta
+        // of the stage after it in the sweep (s - 1, or stage S of the previous step); one launch per step closes theta
         const int64_t slot = gode_gcn_small_parts(n) * gode_gcn_small_part_len(d);
         float* dz[2] = {ws->dZ, ws->dS};
         int cur = 0;
         {
             const float* r = record(step_end - 1);
-            const gode_lincomb_t c4 = stage_cotangent(TAB38, acur, (float)(h * B38[3]), yb, 3, h);
-            GODE_TRY(gode_masked_cot_f32(&c4, r + 4 * nd, dz[0], n, d, nullptr, stream));
+            const gode_lincomb_t cl = stage_cotangent(tab, acur, hbl, yb, L, h);
+            GODE_TRY(gode_masked_cot_f32(&cl, r + (int64_t)S * nd, dz[0], n, d, nullptr, stream));
         }
         for (int i = step_end - 1; i >= step_begin; --i) {
             const float* y = record(i);
-            float* k[4] = {(float*)y + nd, (float*)y + 2 * nd, (float*)y + 3 * nd, (float*)y + 4 * nd};
+            float* k[4] = {};
+            for (int s = 0; s < S; ++s) k[s] = (float*)y + (int64_t)(s + 1) * nd;
             const double t = (double)t0 + i * h;
-            const gode_lincomb_t pre = sweep_pre(TAB38, acur, 1.f, yb, 1);
-            float stage_t[4];
-            for (int s = 3; s >= 0; --s) {
-                stage_t[s] = (float)(t + C38[s] * h);
-                const gode_lincomb_t yin = stage_terms(y, k, s, h);
+            const gode_lincomb_t pre = sweep_pre(tab, acur, 1.f, yb, 1);
+            float stage_t[4], w1[4];
+            for (int s = L; s >= 0; --s) {
+                stage_t[s] = (float)(t + tab.c[s] * h);
+                w1[s] = 1.f;                                           // h is already inside kbar
+                const gode_lincomb_t yin = tab_stage_terms(tab, y, k, s, h);
                 gode_lincomb_t nxt; nxt.n = 0;
                 const float* knext = nullptr;
                 if (s > 0) {
-                    nxt = stage_cotangent(TAB38, acur, (float)(h * B38[s - 1]), yb, s - 1, h);    // names yb[s]: this launch's rows
+                    nxt = stage_cotangent(tab, acur, (float)(h * tab.b[s - 1]), yb, s - 1, h);   // names yb[s]: this launch's rows
                     knext = k[s - 1];
                 } else if (i > step_begin) {
-                    nxt = one_term(yb[0]); nxt.coef[0] = (float)(h * B38[3]);              // kbar_4 of step i - 1
-                    knext = record(i - 1) + 4 * nd;
+                    nxt = one_term(yb[0]); nxt.coef[0] = hbl;                                  // kbar_S of step i - 1
+                    knext = record(i - 1) + (int64_t)S * nd;
                 }
                 float* part = ws->small_part + s * slot;
-                if (knext) {
+                if (knext && nxt.n > 0) {
                     GODE_TRY(gode_gcn_vjp_small_next_f32(f, &yin, dz[cur], 1.f, s == 0 ? &pre : nullptr, yb[s], part,
                                                          &nxt, knext, dz[cur ^ 1], stream));
                     cur ^= 1;
@@ -888,8 +947,7 @@ extern "C" int gode_gcn_ode_rk4_backprop(const gode_gcn_odefunc_t* f, const floa
                     GODE_TRY(gode_gcn_vjp_small_f32(f, &yin, dz[cur], 1.f, s == 0 ? &pre : nullptr, yb[s], part, stream));
                 }
             }
-            const float w1[4] = {1.f, 1.f, 1.f, 1.f};               // h is already inside kbar
-            GODE_TRY(gode_gcn_small_finish4_f32(f, ws->small_part, theta, w1, stage_t, stream));
+            GODE_TRY(gode_gcn_small_finish_step_f32(f, ws->small_part, S, theta, w1, stage_t, stream));
             float* tmp = acur; acur = yb[0]; yb[0] = tmp;
         }
         *a_result = acur;
@@ -898,51 +956,76 @@ extern "C" int gode_gcn_ode_rk4_backprop(const gode_gcn_odefunc_t* f, const floa
     const SweepRoute route = sweep_route(f, ws, cot_colpart);
     for (int i = step_end - 1; i >= step_begin; --i) {
         const float* y = record(i);
-        float* k[4] = {(float*)y + nd, (float*)y + 2 * nd, (float*)y + 3 * nd, (float*)y + 4 * nd};
+        float* k[4] = {};
+        for (int s = 0; s < S; ++s) k[s] = (float*)y + (int64_t)(s + 1) * nd;
         const double t = (double)t0 + i * h;
-        const gode_lincomb_t pre = sweep_pre(TAB38, acur, 1.f, yb, 1);
-        for (int s = 3; s >= 0; --s) {
-            const gode_lincomb_t cot = stage_cotangent(TAB38, acur, (float)(h * B38[s]), yb, s, h);
-            GODE_TRY(sweep_stage(f, ws, route, cot, k[s], stage_terms(y, k, s, h), s == 0 ? &pre : nullptr, yb[s],
-                                 ws->ktheta[s], (float)(t + C38[s] * h), stream));
+        const gode_lincomb_t pre = sweep_pre(tab, acur, 1.f, yb, 1);
+        for (int s = L; s >= 0; --s) {
+            const gode_lincomb_t cot = stage_cotangent(tab, acur, (float)(h * tab.b[s]), yb, s, h);
+            GODE_TRY(sweep_stage(f, ws, route, cot, k[s], tab_stage_terms(tab, y, k, s, h), s == 0 ? &pre : nullptr, yb[s],
+                                 ws->ktheta[s], (float)(t + tab.c[s] * h), stream));
         }
-        GODE_TRY(add_stage_parts(theta, ws->ktheta, 4, gode_gcn_ode_theta_len(d), stream));
+        GODE_TRY(add_stage_parts(theta, ws->ktheta, S, gode_gcn_ode_theta_len(d), stream));
         float* tmp = acur; acur = yb[0]; yb[0] = tmp;
     }
     *a_result = acur;
     return 0;
 }
 
+}  // namespace
+
+extern "C" int gode_gcn_ode_rk4_forward_save(const gode_gcn_odefunc_t* f, const float* y0, float* y_end, float* save,
+                                             const gode_rk4_workspace_t* ws, float t0, float t1, int32_t n_steps,
+                                             int32_t step_begin, int32_t step_end, void* stream)
+{
+    return forward_save(&TAB38, f, y0, y_end, save, ws, t0, t1, n_steps, step_begin, step_end, stream);
+}
+
+extern "C" int gode_gcn_ode_rk4_backprop(const gode_gcn_odefunc_t* f, const float* save, float* a, float* theta,
+                                         float** a_result, const gode_rk4_workspace_t* ws, float* cot_colpart,
+                                         float t0, float t1, int32_t n_steps, int32_t step_begin, int32_t step_end,
+                                         void* stream)
+{
+    return backprop(&TAB38, f, save, a, theta, a_result, ws, cot_colpart, t0, t1, n_steps, step_begin, step_end, stream);
+}
+
 // ---------------------------------------------------------------------------------------------------------------
-// Backprop through an adaptive dopri5 solve (odeint._OdeintBackpropDopri5): the reverse sweep over ONE accepted step per
+// Backprop through an adaptive solve (odeint._OdeintBackpropDopri5): the reverse sweep over ONE accepted step per
 // call - the controller's record (which steps were accepted, their sizes, the interpolation that ends an interval) stays
-// with the caller, as the controller itself does.  The step went from y_n at t_n with step h through the saved stage
-// derivatives k_1..k_7 (k_1 = f(t_n, y_n) is the step before's k_7, or the interval's opening evaluation); with one
-// cotangent array g and host weights wy, wk[1..7] (stages numbered from 1 in this comment, from 0 in the code):
-//   kbar_s = wk[s] g + h sum_{q > s} DPA[q][s] Ybar_q  (+ kbar7 when s = 7),
-//   Ybar_s = J_s^T kbar_s,  theta += (df/dtheta)_s^T kbar_s   for s = 7..2 (and s = 1 when `first`),
+// with the caller, as the controller itself does.  One body (step_backprop) over an AdaptiveMethod: the dopri5 entry point
+// runs it under ADAPTIVE[GODE_RKA_DOPRI5], the adaptive one under the method of its code.  The step went from y_n at t_n
+// with step h through the saved stage derivatives k_1..k_S (FSAL: k_1 = f(t_n, y_n) is the step before's k_S, or the
+// interval's opening evaluation); with one cotangent array g and host weights wy, wk[1..S] (stages numbered from 1 in this
+// comment, from 0 in the code; A: the method's Butcher matrix):
+//   kbar_s = wk[s] g + h sum_{q > s} A[q][s] Ybar_q  (+ kbar_last when s = S),
+//   Ybar_s = J_s^T kbar_s,  theta += (df/dtheta)_s^T kbar_s   for s = S..2 (and s = 1 when `first`),
 //   ybar_n = wy g + sum_s Ybar_s
-// kbar_1 leaves the call as the kbar7 of the step before, unless `first`: then it is pushed through f at (t_n, y_n) here.
+// kbar_1 leaves the call as the kbar_last of the step before, unless `first`: then it is pushed through f at (t_n, y_n) here.
 // An ordinary step has g = ybar_{n+1}, wy = 1, wk[s] = h b_s; the interpolated last step of an interval folds the
 // interpolation's coefficients into wy and wk.  A stage whose cotangent has no term is skipped.
 // The launches of a stage are the rk4 sweep's (sweep_stage; fused: masked cotangent + one VJP launch); the stages'
 // parameter parts are added to theta by one launch per step.
 // ---------------------------------------------------------------------------------------------------------------
-extern "C" int gode_gcn_ode_dopri5_step_backprop(const gode_gcn_odefunc_t* f, const float* y, float* const* k,
-                                                 const float* g, const float* kbar7, double wy, const double* wk,
-                                                 double t, double h, int32_t first, float* const* ybar, float* ybar_n,
-                                                 float* kbar1, float* theta, float* const* ktheta,
-                                                 const gode_rk4_workspace_t* ws, float* cot_colpart, void* stream)
+namespace {
+
+// am == NULL: a code outside GODE_RKA_*, refused after the null checks
+int step_backprop(const AdaptiveMethod* am, const gode_gcn_odefunc_t* f, const float* y, float* const* k, const float* g,
+                  const float* kbar_last, double wy, const double* wk, double t, double h, int32_t first, float* const* ybar,
+                  float* ybar_n, float* kbar1, float* theta, float* const* ktheta, const gode_rk4_workspace_t* ws,
+                  float* cot_colpart, void* stream)
 {
     if (!f || !y || !k || !g || !wk || !ybar || !ybar_n || !theta || !ktheta || !ws) return GODE_E_NULLPTR;
+    if (!am) return GODE_E_SHAPE;
+    const Tableau& tab = am->tab;
+    const int S = tab.stages;
     if (f->n <= 0 || f->d <= 0) return GODE_E_SHAPE;
     if (!first && !kbar1) return GODE_E_NULLPTR;
-    for (int s = 0; s < 7; ++s) if (!k[s] || !ktheta[s]) return GODE_E_NULLPTR;
-    for (int s = 1; s < 7; ++s) if (!ybar[s]) return GODE_E_NULLPTR;
+    for (int s = 0; s < S; ++s) if (!k[s] || !ktheta[s]) return GODE_E_NULLPTR;
+    for (int s = 1; s < S; ++s) if (!ybar[s]) return GODE_E_NULLPTR;
     if (first && !ybar[0]) return GODE_E_NULLPTR;
-    if (ybar_n == g || ybar_n == kbar7 || (kbar1 && (kbar1 == g || kbar1 == kbar7 || kbar1 == ybar_n))) return GODE_E_SHAPE;
-    for (int s = 0; s < 7; ++s)
-        if (ybar[s] && (ybar[s] == g || ybar[s] == kbar7 || ybar[s] == ybar_n || ybar[s] == kbar1)) return GODE_E_SHAPE;
+    if (ybar_n == g || ybar_n == kbar_last || (kbar1 && (kbar1 == g || kbar1 == kbar_last || kbar1 == ybar_n))) return GODE_E_SHAPE;
+    for (int s = 0; s < S; ++s)
+        if (ybar[s] && (ybar[s] == g || ybar[s] == kbar_last || ybar[s] == ybar_n || ybar[s] == kbar1)) return GODE_E_SHAPE;
     if (!ws->dZ || !ws->dS || !ws->wpart || !ws->colsum_scratch) return GODE_E_NULLPTR;
     if (f->groups > 0 && (!ws->gpart || !ws->bpart)) return GODE_E_NULLPTR;
     const int64_t n = f->n, d = f->d, nd = n * d, P = gode_gcn_ode_theta_len(d);
@@ -954,18 +1037,18 @@ extern "C" int gode_gcn_ode_dopri5_step_backprop(const gode_gcn_odefunc_t* f, co
     float* kt[7]; float kt_time[7];
     int live = 0;
     auto cotangent = [&](int s) {
-        gode_lincomb_t c = stage_cotangent(TABDP, g, (float)wk[s], ybar, s, h, dead);
-        if (s == 6 && kbar7) { c.coef[c.n] = 1.f; c.ptr[c.n] = kbar7; ++c.n; }
+        gode_lincomb_t c = stage_cotangent(tab, g, (float)wk[s], ybar, s, h, dead);
+        if (s == S - 1 && kbar_last) { c.coef[c.n] = 1.f; c.ptr[c.n] = kbar_last; ++c.n; }
         return c;
     };
-    for (int s = 6; s >= last; --s) {
+    for (int s = S - 1; s >= last; --s) {
         const gode_lincomb_t cot = cotangent(s);
         if (cot.n == 0) { dead[s] = true; continue; }
-        const float ts = (float)(t + DPC[s] * h);
-        const gode_lincomb_t yin = dp_terms(y, k, DPA[s], s, h, true);
+        const float ts = (float)(t + tab.c[s] * h);
+        const gode_lincomb_t yin = tab_stage_terms(tab, y, k, s, h);
         // `first`: the launch that forms Ybar_1 adds the rest of ybar_n to it (every later stage is settled by then)
         const bool closes = first && s == 0;
-        const gode_lincomb_t pre = sweep_pre(TABDP, g, (float)wy, ybar, 1, dead);
+        const gode_lincomb_t pre = sweep_pre(tab, g, (float)wy, ybar, 1, dead);
         float* out = closes ? ybar_n : ybar[s];
         if (fused) {
             GODE_TRY(gode_masked_cot_f32(&cot, k[s], ws->dZ, n, d, nullptr, stream));
@@ -979,7 +1062,7 @@ extern "C" int gode_gcn_ode_dopri5_step_backprop(const gode_gcn_odefunc_t* f, co
     if (!first || dead[0]) {
         // ybar_n = wy g + sum Ybar_s, and (not first) kbar_1 for the step before: one launch
         float* outs[2] = {ybar_n, kbar1};
-        gode_lincomb_t lcs[2] = {sweep_pre(TABDP, g, (float)wy, ybar, 1, dead), cotangent(0)};
+        gode_lincomb_t lcs[2] = {sweep_pre(tab, g, (float)wy, ybar, 1, dead), cotangent(0)};
         int64_t lens[2] = {nd, nd};
         int count = first ? 1 : 2;
         if (count == 2 && lcs[1].n == 0) { GODE_TRY(gode_zero_f32(kbar1, nd, stream)); count = 1; }
@@ -990,10 +1073,23 @@ extern "C" int gode_gcn_ode_dopri5_step_backprop(const gode_gcn_odefunc_t* f, co
     return add_stage_parts(theta, kt, live, P, stream);
 }
 
+}  // namespace
+
+extern "C" int gode_gcn_ode_dopri5_step_backprop(const gode_gcn_odefunc_t* f, const float* y, float* const* k,
+                                                 const float* g, const float* kbar7, double wy, const double* wk,
+                                                 double t, double h, int32_t first, float* const* ybar, float* ybar_n,
+                                                 float* kbar1, float* theta, float* const* ktheta,
+                                                 const gode_rk4_workspace_t* ws, float* cot_colpart, void* stream)
+{
+    return step_backprop(&ADAPTIVE[GODE_RKA_DOPRI5], f, y, k, g, kbar7, wy, wk, t, h, first, ybar, ybar_n, kbar1, theta, ktheta, ws,
+                         cot_colpart, stream);
+}
+
 // ---------------------------------------------------------------------------------------------------------------
-// The adaptive step drivers by method (GODE_RKA_*): the three dopri5 step functions above driven by a tableau and its error
+// The adaptive step drivers by method (GODE_RKA_*): the dopri5 step functions above driven by a tableau and its error
 // weights (rk_driver.h: AdaptiveMethod), on the same routes.  The forward and the adjoint step close with the fused
-// launch of rk.hip (gode_rk_close_err_multi_f32): the solution and the error sums from one pass over the stages.
+// launch of rk.hip (gode_rk_close_err_multi_f32): the solution and the error sums from one pass over the stages; the sweep
+// is step_backprop, the body the dopri5 sweep runs.
 // ---------------------------------------------------------------------------------------------------------------
 extern "C" int gode_rka_stages(int32_t method)
 {
@@ -1102,68 +1198,13 @@ extern "C" int gode_gcn_ode_adaptive_step_backprop(int32_t method, const gode_gc
                                                    float* const* ktheta, const gode_rk4_workspace_t* ws,
                                                    float* cot_colpart, void* stream)
 {
-    if (!f || !y || !k || !g || !wk || !ybar || !ybar_n || !theta || !ktheta || !ws) return GODE_E_NULLPTR;
-    const AdaptiveMethod* am = adaptive_method(method);
-    if (!am) return GODE_E_SHAPE;
-    const Tableau& tab = am->tab;
-    const int S = tab.stages;
-    if (f->n <= 0 || f->d <= 0) return GODE_E_SHAPE;
-    if (!first && !kbar1) return GODE_E_NULLPTR;
-    for (int s = 0; s < S; ++s) if (!k[s] || !ktheta[s]) return GODE_E_NULLPTR;
-    for (int s = 1; s < S; ++s) if (!ybar[s]) return GODE_E_NULLPTR;
-    if (first && !ybar[0]) return GODE_E_NULLPTR;
-    if (ybar_n == g || ybar_n == kbar_last || (kbar1 && (kbar1 == g || kbar1 == kbar_last || kbar1 == ybar_n))) return GODE_E_SHAPE;
-    for (int s = 0; s < S; ++s)
-        if (ybar[s] && (ybar[s] == g || ybar[s] == kbar_last || ybar[s] == ybar_n || ybar[s] == kbar1)) return GODE_E_SHAPE;
-    if (!ws->dZ || !ws->dS || !ws->wpart || !ws->colsum_scratch) return GODE_E_NULLPTR;
-    if (f->groups > 0 && (!ws->gpart || !ws->bpart)) return GODE_E_NULLPTR;
-    const int64_t n = f->n, d = f->d, nd = n * d, P = gode_gcn_ode_theta_len(d);
-    const bool fused = fused_small(f) && ws->small_part != nullptr;
-    const SweepRoute route = sweep_route(f, ws, cot_colpart);
-    const int64_t slot = fused ? gode_gcn_small_parts(n) * gode_gcn_small_part_len(d) : 0;
-    const int last = first ? 0 : 1;                // the last stage the sweep pushes through f
-    bool dead[7] = {};
-    float* kt[7]; float kt_time[7];
-    int live = 0;
-    auto cotangent = [&](int s) {
-        gode_lincomb_t c = stage_cotangent(tab, g, (float)wk[s], ybar, s, h, dead);
-        if (s == S - 1 && kbar_last) { c.coef[c.n] = 1.f; c.ptr[c.n] = kbar_last; ++c.n; }
-        return c;
-    };
-    for (int s = S - 1; s >= last; --s) {
-        const gode_lincomb_t cot = cotangent(s);
-        if (cot.n == 0) { dead[s] = true; continue; }
-        const float ts = (float)(t + tab.c[s] * h);
-        const gode_lincomb_t yin = tab_stage_terms(tab, y, k, s, h);
-        const bool closes = first && s == 0;
-        const gode_lincomb_t pre = sweep_pre(tab, g, (float)wy, ybar, 1, dead);
-        float* out = closes ? ybar_n : ybar[s];
-        if (fused) {
-            GODE_TRY(gode_masked_cot_f32(&cot, k[s], ws->dZ, n, d, nullptr, stream));
-            GODE_TRY(gode_gcn_vjp_small_f32(f, &yin, ws->dZ, 1.f, closes ? &pre : nullptr, out, ws->small_part + live * slot, stream));
-        } else {
-            GODE_TRY(sweep_stage(f, ws, route, cot, k[s], yin, closes ? &pre : nullptr, out, ktheta[live], ts, stream));
-        }
-        kt[live] = ktheta[live]; kt_time[live] = ts;
-        ++live;
-    }
-    if (!first || dead[0]) {
-        // ybar_n = wy g + sum Ybar_s, and (not first) kbar_1 for the step before: one launch
-        float* outs[2] = {ybar_n, kbar1};
-        gode_lincomb_t lcs[2] = {sweep_pre(tab, g, (float)wy, ybar, 1, dead), cotangent(0)};
-        int64_t lens[2] = {nd, nd};
-        int count = first ? 1 : 2;
-        if (count == 2 && lcs[1].n == 0) { GODE_TRY(gode_zero_f32(kbar1, nd, stream)); count = 1; }
-        GODE_TRY(gode_lincomb_multi_f32(outs, lcs, lens, count, stream));
-    }
-    if (live == 0) return 0;
-    if (fused) GODE_TRY(gode_gcn_small_finish_multi_f32(f, ws->small_part, live, kt, kt_time, stream));
-    return add_stage_parts(theta, kt, live, P, stream);
+    return step_backprop(adaptive_method(method), f, y, k, g, kbar_last, wy, wk, t, h, first, ybar, ybar_n, kbar1, theta, ktheta,
+                         ws, cot_colpart, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// The fixed-grid drivers by method (GODE_RK_*): the rk4 launch sequences above driven by a tableau (rk_driver.h).  The last
-// stage of a step is the closing one; GODE_RK_RK4_38 calls the rk4 entry point itself.
+// The fixed-grid drivers by method (GODE_RK_*): the bodies the rk4 entry points run, under the tableau of the code
+// (rk_driver.h: fixed_tableau).  The last stage of a step is the closing one.
 // ---------------------------------------------------------------------------------------------------------------
 extern "C" int gode_rk_stages(int32_t method)
 {
@@ -1184,100 +1225,13 @@ extern "C" int gode_rk_tableau(int32_t method, double* c, double* a, double* b)
     return 0;
 }
 
-namespace {
-
-// the closing-combination-once launch needs the last stage's input and the closing combination to name the same arrays in
-// the same order, and saves something only where they are several (the 3/8 rule).  The midpoint rule's differ and explicit
-// Euler's is y alone: both close from their terms - one array, as the once route reads.
-bool same_arrays(const gode_lincomb_t& x, const gode_lincomb_t& p) {
-    if (x.n != p.n || x.n < 2) return false;
-    for (int j = 0; j < x.n; ++j) if (x.ptr[j] != p.ptr[j]) return false;
-    return true;
-}
-
-// rk4_forward_step for any tableau: k_1..k_{S-1} into k[0..S-2], y_{n+1} into ynext (which may be k[S-1]) - or, keep_last,
-// k_S into k[S-1] as well (ynext is then another array)
-int fixed_forward_step(const Tableau& tab, const gode_gcn_odefunc_t* f, const gode_rk4_workspace_t* ws, const float* y,
-                       float* const* k, float* ynext, bool keep_last, double t, double h, bool fused, bool close_once,
-                       void* stream, bool diag_ok = false) {
-    const int S = tab.stages;
-    for (int s = 0; s < S; ++s) {
-        const gode_lincomb_t xin = tab_stage_terms(tab, y, k, s, h);
-        const float ts = (float)(t + tab.c[s] * h);
-        if (s + 1 < S) {
-            if (fused) GODE_TRY(gode_gcn_feval_small_f32(f, &xin, ts, 1.f, nullptr, nullptr, nullptr, k[s], stream));
-            else GODE_TRY(feval_large(f, xin, ts, ws->S, k[s], nullptr, nullptr, stream, diag_ok));
-            continue;
-        }
-        StepClose close = {tab_combine_terms(tab, y, k, h), (float)(h * tab.b[s]), close_once};
-        close.once = close_once && same_arrays(xin, close.pre);
-        float* klast = keep_last ? k[s] : nullptr;
-        if (!fused) GODE_TRY(feval_large(f, xin, ts, ws->S, ynext, &close, klast, stream, diag_ok));
-        else if (keep_last) GODE_TRY(gode_gcn_feval_small_save_f32(f, &xin, ts, close.alpha, &close.pre, ynext, klast, stream));
-        else GODE_TRY(gode_gcn_feval_small_f32(f, &xin, ts, close.alpha, &close.pre, nullptr, nullptr, ynext, stream));
-    }
-    return 0;
-}
-
-// rk4_adjoint_small for any tableau of up to 4 stages
-int fixed_adjoint_small(const Tableau& tab, const gode_gcn_odefunc_t* f, const gode_rk4_workspace_t* ws, float* y, float* a,
-                        float* theta, float** y_result, float** a_result, float t0, double h, int32_t n_steps, void* stream) {
-    const int S = tab.stages, L = S - 1;
-    float* ycur = y; float* acur = a;
-    float* ky[4] = {ws->ky[0], ws->ky[1], ws->ky[2], ws->ky[3]};
-    float* ka[4] = {ws->ka[0], ws->ka[1], ws->ka[2], ws->ka[3]};
-    const int64_t slot = gode_gcn_small_parts(f->n) * gode_gcn_small_part_len(f->d);
-    const float hbl = (float)(h * tab.b[L]);
-    for (int i = 0; i < n_steps; ++i) {
-        float stage_t[4], wb[4];
-        const gode_lincomb_t ypre = tab_combine_terms(tab, ycur, ky, h), apre = tab_combine_terms(tab, acur, ka, h);
-        for (int s = 0; s < S; ++s) {
-            stage_t[s] = (float)((double)t0 + i * h + tab.c[s] * h);
-            wb[s] = (float)(h * tab.b[s]);
-            const gode_lincomb_t yin = tab_stage_terms(tab, ycur, ky, s, h);
-            const gode_lincomb_t cot = negated(tab_stage_terms(tab, acur, ka, s, h));   // cotangent of the VJP is -a
-            GODE_TRY(gode_gcn_feval_small_f32(f, &yin, stage_t[s], s == L ? hbl : 1.f, s == L ? &ypre : nullptr,
-                                              &cot, ws->dZ, ky[s], stream));
-            GODE_TRY(gode_gcn_vjp_small_f32(f, &yin, ws->dZ, s == L ? hbl : 1.f, s == L ? &apre : nullptr,
-                                            ka[s], ws->small_part + s * slot, stream));
-        }
-        GODE_TRY(gode_gcn_small_finish_step_f32(f, ws->small_part, S, theta, wb, stage_t, stream));
-        float* tmp = ycur; ycur = ky[L]; ky[L] = tmp;
-        tmp = acur; acur = ka[L]; ka[L] = tmp;
-    }
-    *y_result = ycur;
-    *a_result = acur;
-    return 0;
-}
-
-}  // namespace
-
 extern "C" int gode_gcn_ode_fixed_forward(int32_t method, const gode_gcn_odefunc_t* f, float* y, float** result,
                                           const gode_rk4_workspace_t* ws, float t0, float t1, int32_t n_steps, void* stream)
 {
-    if (!f || !y || !ws || !result) return GODE_E_NULLPTR;
-    const Tableau* tab = fixed_tableau(method);
-    if (!tab) return GODE_E_SHAPE;
-    if (method == GODE_RK_RK4_38) return gode_gcn_ode_rk4_forward(f, y, result, ws, t0, t1, n_steps, stream);
-    if (n_steps <= 0 || f->n <= 0 || f->d <= 0) return GODE_E_SHAPE;
-    const int S = tab->stages, L = S - 1;
-    if (!ws->S) return GODE_E_NULLPTR;
-    for (int s = 0; s < S; ++s) if (!ws->ky[s]) return GODE_E_NULLPTR;
-    const double h = ((double)t1 - (double)t0) / n_steps;
-    float* cur = y;
-    float* k[4] = {ws->ky[0], ws->ky[1], ws->ky[2], ws->ky[3]};
-    const bool fused = fused_small(f);
-    const bool close_once = close_once_route(f);
-    const bool diag_ok = gode_opt_diag_rows() && !fused && f->n > kMergedFinishMaxRows && f->d == 128 && f->a_core_items &&
-                         f->a_diag && f->at_diag && f->A.items && f->a_n_core > 0 && f->a_n_core <= f->A.n_items;
-    for (int i = 0; i < n_steps; ++i) {
-        GODE_TRY(fixed_forward_step(*tab, f, ws, cur, k, k[L], false, (double)t0 + i * h, h, fused, close_once, stream, diag_ok));
-        float* tmp = cur; cur = k[L]; k[L] = tmp;      // k[L] holds the new solution
-    }
-    *result = cur;
-    return 0;
+    return forward_solve(fixed_tableau(method), f, y, result, ws, t0, t1, n_steps, stream);
 }
 
+// (the rk4 adjoint has routes of its own - the two-chain schedule of large graphs - so that code goes to its entry point)
 extern "C" int gode_gcn_ode_fixed_adjoint(int32_t method, const gode_gcn_odefunc_t* f, float* y, float* a, float* theta,
                                           float** y_result, float** a_result, const gode_rk4_workspace_t* ws,
                                           float t0, float t1, int32_t n_steps, void* stream)
@@ -1298,31 +1252,7 @@ extern "C" int gode_gcn_ode_fixed_forward_save(int32_t method, const gode_gcn_od
                                                float* save, const gode_rk4_workspace_t* ws, float t0, float t1,
                                                int32_t n_steps, int32_t step_begin, int32_t step_end, void* stream)
 {
-    if (!f || !y0 || !y_end || !save || !ws) return GODE_E_NULLPTR;
-    const Tableau* tab = fixed_tableau(method);
-    if (!tab) return GODE_E_SHAPE;
-    if (method == GODE_RK_RK4_38)
-        return gode_gcn_ode_rk4_forward_save(f, y0, y_end, save, ws, t0, t1, n_steps, step_begin, step_end, stream);
-    if (n_steps <= 0 || f->n <= 0 || f->d <= 0) return GODE_E_SHAPE;
-    if (step_begin < 0 || step_end > n_steps || step_begin >= step_end) return GODE_E_SHAPE;
-    if (!ws->S) return GODE_E_NULLPTR;
-    const int S = tab->stages;
-    const int64_t nd = f->n * f->d;
-    const double h = ((double)t1 - (double)t0) / n_steps;
-    const bool fused = fused_small(f);
-    const bool close_once = close_once_route(f);
-    if (y0 != save) {                                            // record 0 starts with a copy of y0
-        const gode_lincomb_t c = one_term(y0);
-        GODE_TRY(gode_lincomb_f32(save, &c, nd, stream));
-    }
-    for (int i = step_begin; i < step_end; ++i) {
-        float* rec = save + (int64_t)(i - step_begin) * (S + 1) * nd;
-        float* k[4] = {};
-        for (int s = 0; s < S; ++s) k[s] = rec + (int64_t)(s + 1) * nd;
-        float* ynext = (i + 1 < step_end) ? rec + (int64_t)(S + 1) * nd : y_end;      // the next record's y_n, or the result
-        GODE_TRY(fixed_forward_step(*tab, f, ws, rec, k, ynext, true, (double)t0 + i * h, h, fused, close_once, stream));
-    }
-    return 0;
+    return forward_save(fixed_tableau(method), f, y0, y_end, save, ws, t0, t1, n_steps, step_begin, step_end, stream);
 }
 
 extern "C" int gode_gcn_ode_fixed_backprop(int32_t method, const gode_gcn_odefunc_t* f, const float* save, float* a,
@@ -1330,93 +1260,13 @@ extern "C" int gode_gcn_ode_fixed_backprop(int32_t method, const gode_gcn_odefun
                                            float* cot_colpart, float t0, float t1, int32_t n_steps, int32_t step_begin,
                                            int32_t step_end, void* stream)
 {
-    if (!f || !save || !a || !theta || !a_result || !ws) return GODE_E_NULLPTR;
-    const Tableau* tabp = fixed_tableau(method);
-    if (!tabp) return GODE_E_SHAPE;
-    if (method == GODE_RK_RK4_38)
-        return gode_gcn_ode_rk4_backprop(f, save, a, theta, a_result, ws, cot_colpart, t0, t1, n_steps, step_begin, step_end, stream);
-    if (n_steps <= 0 || f->n <= 0 || f->d <= 0) return GODE_E_SHAPE;
-    if (step_begin < 0 || step_end > n_steps || step_begin >= step_end) return GODE_E_SHAPE;
-    const Tableau& tab = *tabp;
-    const int S = tab.stages, L = S - 1;
-    for (int s = 0; s < S; ++s) if (!ws->ka[s] || !ws->ktheta[s]) return GODE_E_NULLPTR;
-    if (!ws->dZ || !ws->dS || !ws->wpart || !ws->colsum_scratch) return GODE_E_NULLPTR;
-    if (f->groups > 0 && (!ws->gpart || !ws->bpart)) return GODE_E_NULLPTR;
-    const int64_t n = f->n, d = f->d, nd = n * d;
-    const double h = ((double)t1 - (double)t0) / n_steps;
-    float* acur = a;
-    float* yb[4] = {ws->ka[0], ws->ka[1], ws->ka[2], ws->ka[3]};   // yb[1..S-1]: Ybar_2..S; yb[0] receives abar_n
-    auto record = [&](int i) { return save + (int64_t)(i - step_begin) * (S + 1) * nd; };
-    // kbar_S = h b_S abar: b_S is non-zero in every method of the list, so the sweep of a step always opens with one term
-    const float hbl = (float)(h * tab.b[L]);
-    const bool fused = fused_small(f) && ws->small_part != nullptr;
-    if (fused) {
-        // the rk4 sweep's launches: the VJP of stage s also forms the masked cotangent of the stage after it in the sweep
-        const int64_t slot = gode_gcn_small_parts(n) * gode_gcn_small_part_len(d);
-        float* dz[2] = {ws->dZ, ws->dS};
-        int cur = 0;
-        {
-            const float* r = record(step_end - 1);
-            const gode_lincomb_t cl = stage_cotangent(tab, acur, hbl, yb, L, h);
-            GODE_TRY(gode_masked_cot_f32(&cl, r + (int64_t)S * nd, dz[0], n, d, nullptr, stream));
-        }
-        for (int i = step_end - 1; i >= step_begin; --i) {
-            const float* y = record(i);
-            float* k[4] = {};
-            for (int s = 0; s < S; ++s) k[s] = (float*)y + (int64_t)(s + 1) * nd;
-            const double t = (double)t0 + i * h;
-            const gode_lincomb_t pre = sweep_pre(tab, acur, 1.f, yb, 1);
-            float stage_t[4], w1[4];
-            for (int s = L; s >= 0; --s) {
-                stage_t[s] = (float)(t + tab.c[s] * h);
-                w1[s] = 1.f;                                           // h is already inside kbar
-                const gode_lincomb_t yin = tab_stage_terms(tab, y, k, s, h);
-                gode_lincomb_t nxt; nxt.n = 0;
-                const float* knext = nullptr;
-                if (s > 0) {
-                    nxt = stage_cotangent(tab, acur, (float)(h * tab.b[s - 1]), yb, s - 1, h);   // names yb[s]: this launch's rows
-                    knext = k[s - 1];
-                } else if (i > step_begin) {
-                    nxt = one_term(yb[0]); nxt.coef[0] = hbl;                                  // kbar_S of step i - 1
-                    knext = record(i - 1) + (int64_t)S * nd;
-                }
-                float* part = ws->small_part + s * slot;
-                if (knext && nxt.n > 0) {
-                    GODE_TRY(gode_gcn_vjp_small_next_f32(f, &yin, dz[cur], 1.f, s == 0 ? &pre : nullptr, yb[s], part,
-                                                         &nxt, knext, dz[cur ^ 1], stream));
-                    cur ^= 1;
-                } else {
-                    GODE_TRY(gode_gcn_vjp_small_f32(f, &yin, dz[cur], 1.f, s == 0 ? &pre : nullptr, yb[s], part, stream));
-                }
-            }
-            GODE_TRY(gode_gcn_small_finish_step_f32(f, ws->small_part, S, theta, w1, stage_t, stream));
-            float* tmp = acur; acur = yb[0]; yb[0] = tmp;
-        }
-        *a_result = acur;
-        return 0;
-    }
-    const SweepRoute route = sweep_route(f, ws, cot_colpart);
-    for (int i = step_end - 1; i >= step_begin; --i) {
-        const float* y = record(i);
-        float* k[4] = {};
-        for (int s = 0; s < S; ++s) k[s] = (float*)y + (int64_t)(s + 1) * nd;
-        const double t = (double)t0 + i * h;
-        const gode_lincomb_t pre = sweep_pre(tab, acur, 1.f, yb, 1);
-        for (int s = L; s >= 0; --s) {
-            const gode_lincomb_t cot = stage_cotangent(tab, acur, (float)(h * tab.b[s]), yb, s, h);
-            GODE_TRY(sweep_stage(f, ws, route, cot, k[s], tab_stage_terms(tab, y, k, s, h), s == 0 ? &pre : nullptr, yb[s],
-                                 ws->ktheta[s], (float)(t + tab.c[s] * h), stream));
-        }
-        GODE_TRY(add_stage_parts(theta, ws->ktheta, S, gode_gcn_ode_theta_len(d), stream));
-        float* tmp = acur; acur = yb[0]; yb[0] = tmp;
-    }
-    *a_result = acur;
-    return 0;
+    return backprop(fixed_tableau(method), f, save, a, theta, a_result, ws, cot_colpart, t0, t1, n_steps, step_begin, step_end,
+                    stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// explicit_adams (4th-order Adams-Bashforth on the fixed grid): kAdamsStart 3/8-rule steps - rk4_forward_step /
-// rk4_adjoint_small's launches, whose k_1 = f_i is kept - then ONE evaluation per step.  A multistep step is explicit
+// explicit_adams (4th-order Adams-Bashforth on the fixed grid): kAdamsStart 3/8-rule steps - fixed_forward_step /
+// adjoint_small_step under TAB38, whose k_1 = f_i is kept - then ONE evaluation per step.  A multistep step is explicit
 // Euler's closing stage with more pre terms: the launch that evaluates f_i on y_i stores f_i (the save form) and
 // y_{i+1} = (y_i + h sum_{j>=1} beta_j f_{i-j}) + h beta_0 f_i.  At most kAdamsStart steps: the rk4 entry point itself.
 // Arrays: y, the four ws->ky (ka) and two more per chain from `extra` take turns as the solution, the history and the stage
@@ -1460,12 +1310,11 @@ extern "C" int gode_gcn_ode_adams_forward(const gode_gcn_odefunc_t* f, float* y,
     const double h = ((double)t1 - (double)t0) / n_steps;
     const bool fused = fused_small(f);
     const bool close_once = close_once_route(f);
-    const bool diag_ok = gode_opt_diag_rows() && !fused && f->n > kMergedFinishMaxRows && f->d == 128 && f->a_core_items &&
-                         f->a_diag && f->at_diag && f->A.items && f->a_n_core > 0 && f->a_n_core <= f->A.n_items;
+    const bool diag_ok = diag_rows_route(f, fused);
     // (option local_tail is rk4's alone: the tail rows take the launches of the other rows here)
     AdamsChain c(y, ws->ky, extra[0], extra[1]);
     for (int i = 0; i < kAdamsStart; ++i) {
-        GODE_TRY(rk4_forward_step(f, ws, c.cur, c.k, c.k[3], false, (double)t0 + i * h, h, fused, close_once, stream, diag_ok));
+        GODE_TRY(fixed_forward_step(TAB38, f, ws, c.cur, c.k, c.k[3], false, (double)t0 + i * h, h, fused, close_once, stream, diag_ok));
         c.close_start(i);
     }
     const float hb0 = (float)(h * ADAMS_B[0]);
@@ -1482,7 +1331,7 @@ extern "C" int gode_gcn_ode_adams_forward(const gode_gcn_odefunc_t* f, float* y,
     return 0;
 }
 
-// The adjoint solve on the launch-bound route: rk4_adjoint_small's stages for the start-up (k_1 of y and of a kept), then
+// The adjoint solve on the launch-bound route: adjoint_small_step for the start-up (k_1 of y and of a kept), then
 // two launches and the closing reduction per step - the forward recompute leaves f_i, the masked cotangent and y_{i+1}, the
 // VJP leaves a's derivative for the history and a_{i+1}.  The parameter and a_t components are pure quadratures (no stage
 // input reads them): every evaluation's partials are added ONCE, with the weight the evaluation ends up with (adams_weight;
@@ -1498,23 +1347,10 @@ extern "C" int gode_gcn_ode_adams_adjoint(const gode_gcn_odefunc_t* f, float* y,
     for (int s = 0; s < 4; ++s) if (!ws->ky[s] || !ws->ka[s] || !extra[s]) return GODE_E_NULLPTR;
     if (!ws->dZ) return GODE_E_NULLPTR;
     const double h = ((double)t1 - (double)t0) / n_steps;   // negative: the adjoint runs from t0 (later) to t1 (earlier)
-    const int64_t slot = gode_gcn_small_parts(f->n) * gode_gcn_small_part_len(f->d);
     AdamsChain cy(y, ws->ky, extra[0], extra[1]), ca(a, ws->ka, extra[2], extra[3]);
-    const float hb3 = (float)(h * B38[3]);
     for (int i = 0; i < kAdamsStart; ++i) {
-        float stage_t[4];
-        const gode_lincomb_t ypre = combine_terms(cy.cur, cy.k, h), apre = combine_terms(ca.cur, ca.k, h);
-        for (int s = 0; s < 4; ++s) {
-            stage_t[s] = (float)((double)t0 + i * h + C38[s] * h);
-            const gode_lincomb_t yin = stage_terms(cy.cur, cy.k, s, h);
-            const gode_lincomb_t cot = negated(stage_terms(ca.cur, ca.k, s, h));          // cotangent of the VJP is -a
-            GODE_TRY(gode_gcn_feval_small_f32(f, &yin, stage_t[s], s == 3 ? hb3 : 1.f, s == 3 ? &ypre : nullptr,
-                                              &cot, ws->dZ, cy.k[s], stream));
-            GODE_TRY(gode_gcn_vjp_small_f32(f, &yin, ws->dZ, s == 3 ? hb3 : 1.f, s == 3 ? &apre : nullptr,
-                                            ca.k[s], ws->small_part + s * slot, stream));
-        }
-        const float wb[4] = {(float)(h * B38[0] + adams_weight(i, n_steps, h)), (float)(h * B38[1]), (float)(h * B38[2]), hb3};
-        GODE_TRY(gode_gcn_small_finish_step_f32(f, ws->small_part, 4, theta, wb, stage_t, stream));
+        GODE_TRY(adjoint_small_step(TAB38, f, ws, cy.cur, cy.k, ca.cur, ca.k, theta, (double)t0 + i * h, h,
+                                    adams_weight(i, n_steps, h), stream));
         cy.close_start(i);
         ca.close_start(i);
     }
@@ -1583,7 +1419,7 @@ extern "C" int gode_gcn_ode_adams_forward_save(const gode_gcn_odefunc_t* f, cons
         float* ynext = (i + 1 < step_end) ? record(i + 1) : y_end;       // the next record's y_i, or the result
         if (i < kAdamsStart) {
             float* k[4] = {rec + nd, rec + 2 * nd, rec + 3 * nd, rec + 4 * nd};
-            GODE_TRY(rk4_forward_step(f, ws, rec, k, ynext, true, (double)t0 + i * h, h, fused, close_once, stream));
+            GODE_TRY(fixed_forward_step(TAB38, f, ws, rec, k, ynext, true, (double)t0 + i * h, h, fused, close_once, stream));
             continue;
         }
         const float* fh[3] = {f_of(i - 1), f_of(i - 2), f_of(i - 3)};
@@ -1620,7 +1456,7 @@ gode_lincomb_t adams_fbar(gode_lincomb_t lc, const AdamsPending& p, int i, int n
 
 // save: the records of steps 0 .. n_steps - 1 (gode_adams_record_offset) - or, with `rerun` given (5 n d floats), the
 // start-up steps' y_0, y_1, y_2 alone (3 n d floats) followed by the multistep records: each start-up step is then re-run
-// into `rerun` (rk4_forward_step, the forward's launches) just before its sweep.  work: four n x d arrays; with `a` they
+// into `rerun` (fixed_forward_step, the forward's launches) just before its sweep.  work: four n x d arrays; with `a` they
 // hold the pending cotangents, and *a_result names the one that holds dL/dy_0.
 extern "C" int gode_gcn_ode_adams_backprop(const gode_gcn_odefunc_t* f, const float* save, float* rerun, float* a, float* theta,
                                            float** a_result, const gode_rk4_workspace_t* ws, float* cot_colpart,
@@ -1685,7 +1521,7 @@ extern "C" int gode_gcn_ode_adams_backprop(const gode_gcn_odefunc_t* f, const fl
         float* k[4];
         if (rerun) {
             for (int s = 0; s < 4; ++s) k[s] = rerun + (int64_t)(s + 1) * nd;
-            GODE_TRY(rk4_forward_step(f, ws, y, k, rerun, true, t, h, fused_small(f), close_once, stream));
+            GODE_TRY(fixed_forward_step(TAB38, f, ws, y, k, rerun, true, t, h, fused_small(f), close_once, stream));
         } else {
             for (int s = 0; s < 4; ++s) k[s] = (float*)y + (int64_t)(s + 1) * nd;
         }
@@ -1703,7 +1539,7 @@ extern "C" int gode_gcn_ode_adams_backprop(const gode_gcn_odefunc_t* f, const fl
             float stage_t[4];
             for (int s = 3; s >= 0; --s) {
                 stage_t[s] = (float)(t + C38[s] * h);
-                const gode_lincomb_t yin = stage_terms(y, k, s, h);
+                const gode_lincomb_t yin = tab_stage_terms(TAB38, y, k, s, h);
                 float* part = ws->small_part + s * slot;
                 if (s > 0) {
                     const gode_lincomb_t nxt = kbar(s - 1);                      // names yb[s]: this launch's rows
@@ -1718,7 +1554,7 @@ extern "C" int gode_gcn_ode_adams_backprop(const gode_gcn_odefunc_t* f, const fl
             GODE_TRY(gode_gcn_small_finish4_f32(f, ws->small_part, theta, w1, stage_t, stream));
         } else {
             for (int s = 3; s >= 0; --s)
-                GODE_TRY(sweep_stage(f, ws, route, kbar(s), k[s], stage_terms(y, k, s, h), s == 0 ? &pre : nullptr, yb[s],
+                GODE_TRY(sweep_stage(f, ws, route, kbar(s), k[s], tab_stage_terms(TAB38, y, k, s, h), s == 0 ? &pre : nullptr, yb[s],
                                      ws->ktheta[s], (float)(t + C38[s] * h), stream));
             GODE_TRY(add_stage_parts(theta, ws->ktheta, 4, P, stream));
         }

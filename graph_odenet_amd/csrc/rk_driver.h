@@ -1,6 +1,7 @@
 // rk_driver.h — what the C-level Runge-Kutta drivers (ode_driver.hip, gat_driver.hip) share: the error-propagation macros,
-// the coefficient tables of the two methods and the term lists built from them.  Private to csrc/; everything here has
-// internal linkage, so the header adds nothing to the library's exports.
+// the coefficient tables of every method and the term lists built from them - each list is built by ONE function over a
+// Tableau, whichever method a driver runs.  Private to csrc/; everything here has internal linkage, so the header adds
+// nothing to the library's exports.
 #pragma once
 #include "common.h"
 
@@ -45,19 +46,6 @@ const double DPE[7] = {35.0 / 384 - 1951.0 / 21600, 0, 500.0 / 1113 - 22642.0 / 
 inline gode_lincomb_t one_term(const float* p) { gode_lincomb_t lc; lc.n = 1; lc.coef[0] = 1.f; lc.ptr[0] = p; return lc; }
 inline gode_lincomb_t negated(gode_lincomb_t lc) { for (int j = 0; j < lc.n; ++j) lc.coef[j] = -lc.coef[j]; return lc; }
 
-// terms of  y + h * sum_{j<s} A38[s][j] * k[j]
-inline gode_lincomb_t stage_terms(const float* y, float* const* k, int s, double h) {
-    gode_lincomb_t lc = one_term(y);
-    for (int j = 0; j < s; ++j)
-        if (A38[s][j] != 0.0) { lc.coef[lc.n] = (float)(h * A38[s][j]); lc.ptr[lc.n] = k[j]; ++lc.n; }
-    return lc;
-}
-// terms of  y + h * sum_{j<3} B38[j] * k[j]   (the last stage is folded into the producing launch)
-inline gode_lincomb_t combine_terms(const float* y, float* const* k, double h) {
-    gode_lincomb_t lc = one_term(y);
-    for (int j = 0; j < 3; ++j) { lc.coef[lc.n] = (float)(h * B38[j]); lc.ptr[lc.n] = k[j]; ++lc.n; }
-    return lc;
-}
 // A Butcher matrix as the sweeps read it: a[q * lda + s] = A[q][s] of a method with `stages` stages
 // (b, c: the weights and abscissae)
 struct Tableau { const double* a; int lda; int stages; const double* b; const double* c; };
@@ -118,7 +106,7 @@ inline gode_lincomb_t close_terms(const AdaptiveMethod& am, const float* y, floa
         }
     return lc;
 }
-// terms of  y + h * sum_{j<s} A[s][j] * k[j]  of any tableau (zero coefficients dropped; stage_terms is the 3/8 rule's)
+// terms of  y + h * sum_{j<s} A[s][j] * k[j]  of a tableau (zero coefficients dropped)
 inline gode_lincomb_t tab_stage_terms(const Tableau& tab, const float* y, float* const* k, int s, double h) {
     gode_lincomb_t lc = one_term(y);
     for (int j = 0; j < s; ++j) {

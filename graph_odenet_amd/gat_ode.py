@@ -316,34 +316,22 @@ class GatOdeField(Field):
         return w.sweep
 
     def _rk4_forward_save(self, y0, y_end, save, t0, t1, n_steps, i0, i1):
-        """Steps i0 .. i1-1 with the launches of solver.integrate_rk4 on this field (the same bits); save[r] = [y_n, k_1..k_4]
-        of step i0 + r."""
-        fs, ws = self._structs(True)
-        _lib.check(_lib.load().gode_gat_ode_rk4_forward_save(
-            ctypes.byref(fs), _lib.ptr(y0), _lib.ptr(y_end), _lib.ptr(save), ctypes.byref(ws), float(t0), float(t1), int(n_steps),
-            int(i0), int(i1), _lib.stream_ptr()), "gode_gat_ode_rk4_forward_save")
+        self._fixed_forward_save("rk4", y0, y_end, save, t0, t1, n_steps, i0, i1)
 
     def _rk4_backprop(self, save, a, theta, t0, t1, n_steps, i0, i1):
-        """Reverse sweep over the records of steps i0 .. i1-1; `a` is advanced in place and returned, theta incremented."""
-        fs, ws = self._structs(True)
-        sw = self._sweep_work()
-        ybar = (ctypes.c_void_p * 4)(*[b.data_ptr() for b in sw.ybar[:4]])
-        _lib.check(_lib.load().gode_gat_ode_rk4_backprop(
-            ctypes.byref(fs), _lib.ptr(save), _lib.ptr(a), _lib.ptr(theta), ybar, _lib.ptr(sw.k_scratch), _lib.ptr(sw.parts),
-            ctypes.byref(ws), float(t0), float(t1), int(n_steps), int(i0), int(i1), _lib.stream_ptr()),
-            "gode_gat_ode_rk4_backprop")
-        return a
+        return self._fixed_backprop("rk4", save, a, theta, t0, t1, n_steps, i0, i1)
 
     def _fixed_forward_save(self, method, y0, y_end, save, t0, t1, n_steps, i0, i1):
-        """_rk4_forward_save for any fixed-grid method (the launches of solver.integrate_fixed on this field); save[r] =
-        [y_n, k_1..k_S]."""
+        """Steps i0 .. i1-1 with the launches of solver.integrate_fixed on this field (the same bits; rk4: integrate_rk4's);
+        save[r] = [y_n, k_1..k_S] of step i0 + r."""
         fs, ws = self._structs(True)
         _lib.check(_lib.load().gode_gat_ode_fixed_forward_save(
             method_code(method), ctypes.byref(fs), _lib.ptr(y0), _lib.ptr(y_end), _lib.ptr(save), ctypes.byref(ws), float(t0),
             float(t1), int(n_steps), int(i0), int(i1), _lib.stream_ptr()), "gode_gat_ode_fixed_forward_save")
 
     def _fixed_backprop(self, method, save, a, theta, t0, t1, n_steps, i0, i1):
-        """_rk4_backprop for any fixed-grid method, over the records of _fixed_forward_save."""
+        """Reverse sweep over the records of steps i0 .. i1-1 (_fixed_forward_save); `a` is advanced in place and returned,
+        theta incremented."""
         fs, ws = self._structs(True)
         sw = self._sweep_work()
         ybar = (ctypes.c_void_p * 4)(*[b.data_ptr() for b in sw.ybar[:4]])
@@ -357,41 +345,36 @@ class GatOdeField(Field):
         sw = self._sweep_work()
         return {"ybar": sw.ybar, "pairs": sw.pairs}
 
-    def _dopri5_step_backprop(self, y, k, g, kbar7, wy, wk, t, h, first, work, turn, theta):
-        """Reverse sweep over one accepted step (gode_gat_ode_dopri5_step_backprop).  Returns (ybar_n, kbar_1) in
-        work["pairs"][turn]; kbar_1 is None when `first`."""
+    def _step_backprop(self, export, head, S, y, k, g, kbar_last, wy, wk, t, h, first, work, turn, theta):
+        """Reverse sweep over one accepted step of an S-stage adaptive method (k, wk of S entries; kbar_last arrives on k_S)
+        through `export`, whose leading arguments are `head`.  Returns (ybar_n, kbar_1) in work["pairs"][turn]; kbar_1 is None
+        when `first`."""
         fs, ws = self._structs(True)
         sw = self._sweep_work()
         ybar_n, kbar1 = work["pairs"][turn]
-        kptr = (ctypes.c_void_p * 7)(*[x.data_ptr() for x in k])
-        ybar = (ctypes.c_void_p * 7)(*[b.data_ptr() for b in work["ybar"]])
-        wka = (ctypes.c_double * 7)(*[float(v) for v in wk])
-        _lib.check(_lib.load().gode_gat_ode_dopri5_step_backprop(
-            ctypes.byref(fs), _lib.ptr(y), kptr, _lib.ptr(g), _lib.ptr(kbar7), float(wy), wka, float(t), float(h),
+        kptr = (ctypes.c_void_p * S)(*[x.data_ptr() for x in k])
+        ybar = (ctypes.c_void_p * S)(*[b.data_ptr() for b in work["ybar"][:S]])
+        wka = (ctypes.c_double * S)(*[float(v) for v in wk])
+        _lib.check(getattr(_lib.load(), export)(
+            *head, ctypes.byref(fs), _lib.ptr(y), kptr, _lib.ptr(g), _lib.ptr(kbar_last), float(wy), wka, float(t), float(h),
             1 if first else 0, ybar, _lib.ptr(ybar_n), _lib.ptr(kbar1), _lib.ptr(theta), _lib.ptr(sw.k_scratch),
-            _lib.ptr(sw.parts), ctypes.byref(ws), _lib.stream_ptr()), "gode_gat_ode_dopri5_step_backprop")
+            _lib.ptr(sw.parts), ctypes.byref(ws), _lib.stream_ptr()), export)
         return ybar_n, (None if first else kbar1)
+
+    def _dopri5_step_backprop(self, y, k, g, kbar7, wy, wk, t, h, first, work, turn, theta):
+        """The sweep under dopri5 through its own entry point (same body in C): the member is offered with ADAPTIVE_NATIVE off
+        as well, and a refusal names gode_gat_ode_dopri5_step_backprop."""
+        return self._step_backprop("gode_gat_ode_dopri5_step_backprop", (), 7, y, k, g, kbar7, wy, wk, t, h, first, work, turn,
+                                   theta)
 
     def _adaptive_backprop_work(self, method, like):
         """_dopri5_backprop_work for any adaptive method: _SweepWork's 7 Ybar and 7 slots serve every S."""
         return self._dopri5_backprop_work(like)
 
     def _adaptive_step_backprop(self, method, y, k, g, kbar_last, wy, wk, t, h, first, work, turn, theta):
-        """_dopri5_step_backprop for any adaptive method (k, wk of S entries; kbar_last arrives on k_S):
-        gode_gat_ode_adaptive_step_backprop."""
-        fs, ws = self._structs(True)
-        sw = self._sweep_work()
-        S = adaptive_stages(method)
-        ybar_n, kbar1 = work["pairs"][turn]
-        kptr = (ctypes.c_void_p * S)(*[x.data_ptr() for x in k])
-        ybar = (ctypes.c_void_p * S)(*[b.data_ptr() for b in work["ybar"][:S]])
-        wka = (ctypes.c_double * S)(*[float(v) for v in wk])
-        _lib.check(_lib.load().gode_gat_ode_adaptive_step_backprop(
-            adaptive_code(method), ctypes.byref(fs), _lib.ptr(y), kptr, _lib.ptr(g), _lib.ptr(kbar_last), float(wy), wka,
-            float(t), float(h), 1 if first else 0, ybar, _lib.ptr(ybar_n), _lib.ptr(kbar1), _lib.ptr(theta),
-            _lib.ptr(sw.k_scratch), _lib.ptr(sw.parts), ctypes.byref(ws), _lib.stream_ptr()),
-            "gode_gat_ode_adaptive_step_backprop")
-        return ybar_n, (None if first else kbar1)
+        """The sweep under any adaptive method (k, wk of S entries): gode_gat_ode_adaptive_step_backprop."""
+        return self._step_backprop("gode_gat_ode_adaptive_step_backprop", (adaptive_code(method),), adaptive_stages(method), y, k,
+                                   g, kbar_last, wy, wk, t, h, first, work, turn, theta)
 
     def _project(self, t, y_terms):
         """Ps, Pt, A2 of the stage input; returns the term list later launches of the stage should read."""

@@ -537,8 +537,10 @@ class GcnOdeField(_PackedParams, Field):
                                                    int(n_steps), _lib.stream_ptr()), "gode_gcn_ode_adams_backprop")
         return _by_ptr(res.value, [a] + work + ka)
 
+    # ---- backprop through a fixed-grid solve (odeint._OdeintBackprop; csrc/ode_driver.hip) ---------------------
     def fixed_forward_save(self, method, y0, y_end, save, t0, t1, n_steps, i0, i1):
-        """rk4_forward_save for any fixed-grid method: save[r] = [y_n, k_1..k_S] of step i0 + r."""
+        """Steps i0 .. i1-1 of the n_steps-step solve from t0 to t1, bit for bit fixed_native's launches (rk4: rk4_native's);
+        save[r] = [y_n, k_1..k_S] of step i0 + r (y0 is copied into save[0][0] unless it is that slice)."""
         lib = _lib.load()
         s, w = self.s, self.w
         fs, ws = _func_struct(s), w.workspace_struct(False, s.groups)
@@ -547,7 +549,9 @@ class GcnOdeField(_PackedParams, Field):
                                                        int(i0), int(i1), _lib.stream_ptr()), "gode_gcn_ode_fixed_forward_save")
 
     def fixed_backprop(self, method, save, a, theta, t0, t1, n_steps, i0, i1):
-        """rk4_backprop for any fixed-grid method, over the records of fixed_forward_save."""
+        """Reverse sweep over the records of fixed_forward_save: `a` (dL/dy after step i1-1) is overwritten; returns the
+        tensor holding dL/dy before step i0 (`a` or a workspace buffer); theta (packed [W | b | gamma | beta | .]) is
+        incremented by the parameter gradients."""
         lib = _lib.load()
         s, w = self.s, self.w
         ka = w.stage_buffers(True)[1]
@@ -559,31 +563,11 @@ class GcnOdeField(_PackedParams, Field):
                                                    int(i1), _lib.stream_ptr()), "gode_gcn_ode_fixed_backprop")
         return _by_ptr(res.value, [a] + ka)
 
-    # ---- backprop through a fixed-grid solve (odeint._OdeintBackprop under rk4; csrc/ode_driver.hip) -----------
     def rk4_forward_save(self, y0, y_end, save, t0, t1, n_steps, i0, i1):
-        """Steps i0 .. i1-1 of the n_steps-step rk4 solve from t0 to t1, bit for bit rk4_native's launches; save[r] =
-        [y_n, k_1, k_2, k_3, k_4] of step i0 + r (y0 is copied into save[0][0] unless it is that slice)."""
-        lib = _lib.load()
-        s, w = self.s, self.w
-        fs, ws = _func_struct(s), w.workspace_struct(False, s.groups)
-        _lib.check(lib.gode_gcn_ode_rk4_forward_save(ctypes.byref(fs), _lib.ptr(y0), _lib.ptr(y_end), _lib.ptr(save),
-                                                     ctypes.byref(ws), float(t0), float(t1), int(n_steps), int(i0), int(i1),
-                                                     _lib.stream_ptr()), "gode_gcn_ode_rk4_forward_save")
+        self.fixed_forward_save("rk4", y0, y_end, save, t0, t1, n_steps, i0, i1)
 
     def rk4_backprop(self, save, a, theta, t0, t1, n_steps, i0, i1):
-        """Reverse sweep over the records of rk4_forward_save: `a` (dL/dy after step i1-1) is overwritten; returns the
-        tensor holding dL/dy before step i0 (`a` or a workspace buffer); theta (packed [W | b | gamma | beta | .]) is
-        incremented by the parameter gradients."""
-        lib = _lib.load()
-        s, w = self.s, self.w
-        ka = w.stage_buffers(True)[1]
-        fs, ws = _func_struct(s), w.workspace_struct(True, s.groups)
-        res = ctypes.c_void_p()
-        _lib.check(lib.gode_gcn_ode_rk4_backprop(ctypes.byref(fs), _lib.ptr(save), _lib.ptr(a), _lib.ptr(theta),
-                                                 ctypes.byref(res), ctypes.byref(ws), _lib.ptr(w.cot_colpart()),
-                                                 float(t0), float(t1), int(n_steps), int(i0), int(i1), _lib.stream_ptr()),
-                   "gode_gcn_ode_rk4_backprop")
-        return _by_ptr(res.value, [a] + ka)
+        return self.fixed_backprop("rk4", save, a, theta, t0, t1, n_steps, i0, i1)
 
     def eval_combine(self, t, terms, pre, coef, out):
         """Last RK stage: out[0] = (sum pre[0]) + coef * f(t, sum terms[0]) without materialising f."""
@@ -625,36 +609,16 @@ class GcnOdeField(_PackedParams, Field):
                    "gode_gcn_ode_adaptive_step_forward")
         return sums
 
-    # ---- backprop through an adaptive solve (odeint._OdeintBackprop under dopri5; csrc/ode_driver.hip) -------
+    # ---- backprop through an adaptive solve (odeint._OdeintBackpropDopri5; csrc/ode_driver.hip) ------------------
     def dopri5_backprop_work(self, like):
-        """Work arrays of dopri5_step_backprop for a state like `like`: 7 Ybar, two (ybar_n, kbar_1) pairs that take
-        turns from step to step, 7 packed parameter parts."""
-        lib = _lib.load()
-        P = lib.gode_gcn_ode_theta_len(self.s.d)
-        return {"ybar": [torch.empty_like(like) for _ in range(7)],
-                "pairs": [(torch.empty_like(like), torch.empty_like(like)) for _ in range(2)],
-                "ktheta": [torch.empty(P, dtype=torch.float32, device=like.device) for _ in range(7)]}
+        return self.adaptive_backprop_work("dopri5", like)
 
     def dopri5_step_backprop(self, y, k, g, kbar7, wy, wk, t, h, first, work, turn, theta):
-        """Reverse sweep over one accepted step (y_n, k_1..k_7, t_n, h) with cotangent g, weights wy / wk[7] and the
-        cotangent kbar7 arriving on k_7 (None: none); theta (packed [W | b | gamma | beta | .]) is incremented.
-        Returns (ybar_n, kbar_1) in work["pairs"][turn]; kbar_1 is None when `first` (it went through f here)."""
-        lib = _lib.load()
-        s, w = self.s, self.w
-        w.stage_buffers(True)
-        fs, ws = _func_struct(s), w.workspace_struct(True, s.groups)
-        arr = lambda ts: (ctypes.c_void_p * 7)(*[x.data_ptr() for x in ts])      # noqa: E731
-        ybar_n, kbar1 = work["pairs"][turn]
-        _lib.check(lib.gode_gcn_ode_dopri5_step_backprop(
-            ctypes.byref(fs), _lib.ptr(y), arr(k), _lib.ptr(g), _lib.ptr(kbar7), float(wy),
-            (ctypes.c_double * 7)(*[float(v) for v in wk]), float(t), float(h), int(bool(first)), arr(work["ybar"]),
-            _lib.ptr(ybar_n), _lib.ptr(kbar1), _lib.ptr(theta), arr(work["ktheta"]), ctypes.byref(ws),
-            _lib.ptr(w.cot_colpart()), _lib.stream_ptr()), "gode_gcn_ode_dopri5_step_backprop")
-        return ybar_n, (None if first else kbar1)
-
+        return self.adaptive_step_backprop("dopri5", y, k, g, kbar7, wy, wk, t, h, first, work, turn, theta)
 
     def adaptive_backprop_work(self, method, like):
-        """dopri5_backprop_work for any adaptive method: S Ybar, two (ybar_n, kbar_1) pairs, S packed parameter parts."""
+        """Work arrays of adaptive_step_backprop for a state like `like`: S Ybar, two (ybar_n, kbar_1) pairs that take
+        turns from step to step, S packed parameter parts."""
         lib = _lib.load()
         S = adaptive_stages(method)
         P = lib.gode_gcn_ode_theta_len(self.s.d)
@@ -663,7 +627,9 @@ class GcnOdeField(_PackedParams, Field):
                 "ktheta": [torch.empty(P, dtype=torch.float32, device=like.device) for _ in range(S)]}
 
     def adaptive_step_backprop(self, method, y, k, g, kbar_last, wy, wk, t, h, first, work, turn, theta):
-        """dopri5_step_backprop for any adaptive method (k, wk of S entries; kbar_last arrives on k_S):
+        """Reverse sweep over one accepted step (y_n, k_1..k_S, t_n, h) with cotangent g, weights wy / wk[S] and the
+        cotangent kbar_last arriving on k_S (None: none); theta (packed [W | b | gamma | beta | .]) is incremented.
+        Returns (ybar_n, kbar_1) in work["pairs"][turn]; kbar_1 is None when `first` (it went through f here).
         gode_gcn_ode_adaptive_step_backprop."""
         lib = _lib.load()
         s, w = self.s, self.w

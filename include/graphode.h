@@ -805,7 +805,9 @@ int gode_rk_tableau(int32_t method, double* c, double* a, double* b);
 int gode_gcn_small_finish_step_f32(const gode_gcn_odefunc_t* f, const float* part, int32_t n_stages, float* theta,
                                    const float* wb /* host */, const float* ts /* host */, void* stream);
 
-/* The four rk4 drivers above with the method as an argument (GODE_RK_*); GODE_RK_RK4_38 calls the rk4 entry point itself.
+/* The four rk4 drivers above with the method as an argument (GODE_RK_*).  Forward, forward-save and backprop are one body per
+ * launch sequence over the method's tableau, which the rk4 entry points run under the 3/8 rule's: GODE_RK_RK4_38 returns their
+ * bits.  The adjoint under GODE_RK_RK4_38 is the rk4 entry point itself (its large-graph schedule is the 3/8 rule's alone).
  * h, the stage times and every h * coefficient product are formed in double and rounded once; a term with a zero
  * coefficient is not read (the midpoint rule's closing combination never names k_1).  The last stage of a step is the
  * closing one, and every option of the rk4 drivers applies to it as it does there; explicit Euler's only stage closes the
@@ -956,7 +958,8 @@ int gode_rka_tableau(int32_t method, double* c, double* a, double* b, double* e)
 /* The three dopri5 step drivers above for any adaptive method (GODE_RKA_*): the same arguments after the code, with k /
  * ky / ka / ktheta / ybar of S entries and wk of S; small_part, when given, must hold S slots.  The same routes; the
  * forward and the adjoint step close with gode_rk_close_err_multi_f32 (the adjoint: one call for its three outputs and
- * four error groups), so GODE_RKA_DOPRI5 returns the dopri5 entry points' arrays and sums bit for bit.
+ * four error groups), so GODE_RKA_DOPRI5 returns the dopri5 entry points' arrays and sums bit for bit.  The sweep
+ * (_step_backprop) is one body over the method's tableau; gode_gcn_ode_dopri5_step_backprop runs it under dopri5's.
  * Validation: null pointers, then a method outside the list (GODE_E_SHAPE), then the dopri5 counterpart's checks;
  * err_scratch >= gode_rk_close_err_scratch_bytes(). */
 int gode_gcn_ode_adaptive_step_forward(int32_t method, const gode_gcn_odefunc_t* f, const float* y, float* const* k /* S */,
@@ -1116,7 +1119,8 @@ int gode_gat_ode_rk4_forward_save(const gode_gat_odefunc_t* f, const float* y0, 
 int gode_gat_ode_rk4_backprop(const gode_gat_odefunc_t* f, const float* save, float* a, float* theta,
                               float* const* ybar /* 4 */, float* k_scratch, float* parts, const gode_gat_workspace_t* ws,
                               float t0, float t1, int32_t n_steps, int32_t step_begin, int32_t step_end, void* stream);
-/* The rk4 pair for any fixed-grid method (GODE_RK_*; GODE_RK_RK4_38 calls it): records of (S + 1) n x d floats, ybar and
+/* The rk4 pair for any fixed-grid method (GODE_RK_*; the same bodies, which the rk4 pair runs under the 3/8 rule's tableau,
+ * so GODE_RK_RK4_38 returns its bits): records of (S + 1) n x d floats, ybar and
  * the slots of `parts` counted per stage (S of each), one gode_gat_small_close_stages_f32 launch per swept step.
  * Validation: null pointers, a method outside the list (GODE_E_SHAPE), then the rk4 pair's checks in their order. */
 int gode_gat_ode_fixed_forward_save(int32_t method, const gode_gat_odefunc_t* f, const float* y0, float* y_end, float* save,
